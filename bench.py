@@ -17,8 +17,12 @@ keys and tables are replicated, only the timing is reduced (max over ranks).  Ra
     ckks_n32768_chain      configs[2]: CKKS N=32768 L=14, multiply -> relinearize -> rescale -> rotate(1), chained to depth 3
     bgv_n65536_relin_rot   configs[3]: BGV N=65536, size-3 ciphertexts, relinearize + rotateRows(1)
     ckks_matmul_128        configs[4]: CKKS 128x128 matmul of app/LinearHelperCKKS.cuh (MatmulHelper), one input row per batch item
-Every line carries `roofline` (dominant kernel, algorithmic bytes per SURVEY.md 8d, live HIP-event time), `roofline.per_kernel`
-(every kernel of one step, timed by the library's per-launch HIP events) and -- on one rank -- `cpu_baseline`.
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and the configuration.  With --full the line also
+carries `verified` (items of the last step against the CPU oracle), `roofline` (dominant kernel, algorithmic bytes per SURVEY.md 8d, live
+HIP-event time), `roofline.per_kernel` (every kernel of one step, timed by the library's per-launch HIP events), the clock / power of the
+device over the timed region (`rank_devices[]`) and -- on one rank -- `cpu_baseline`.
+
+--dump-outputs DIR writes what the last timed step computed, as the caller of the step receives it, to DIR/<name>.npy (dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -383,6 +387,47 @@ def verify(w):
             checked.append(str(idx))
         return True, "first and last output block of input rows " + ", ".join(checked)
     return None, "no checker for this workload"
+
+
+# ---------------------------------------------------------------- what the timed path computed (--dump-outputs)
+DUMP_BYTES = 56 << 20  # the sampled data of all files together; the .npy headers add about a hundred bytes each (the limit is 64 MB)
+DUMP_ITEMS = 16        # batch items per output at most: evenly spread, first and last included
+DUMP_COEFFS = 4096     # coefficient positions per limb at most: a seeded random choice, the same for every run at the same N
+
+
+def step_outputs(w):
+    """[(name, batch items, read(item) -> u64 [size][limbs][N])]: the ciphertexts the last step handed its caller"""
+    if w.wl["kind"] == "mul_relin":
+        w.finish_pending()  # odd lanes end a step with a product: relinearize it (the same launch as in the step, untimed)
+        w.sync_all()
+
+        def read(g):  # item g of the rank's batch: the lanes hold consecutive slices of it
+            for ln in w.lanes:
+                Bi, oi = ln[2], ln[5]
+                if g < Bi:
+                    return _item(oi.buf, oi.bstride, g, (oi.capacity, w.L, w.N))[:2]
+                g -= Bi
+        return [("ct_out", w.B, read)]
+    w.sync_all()
+    outs = w.last if w.wl["kind"] == "matmul" else [w.last]
+    names = ["out_block%d" % j for j in range(len(outs))] if w.wl["kind"] == "matmul" else ["ct_out"]
+    return [(name, ct.batch, lambda i, ct=ct: _item(ct.buf, ct.bstride, i, (ct.capacity, ct.limbs, w.N))[:ct.size()]) for name, ct in zip(names, outs)]
+
+
+def dump_outputs(w, outdir):
+    """DIR/<name>.npy for each output of the last step: a fixed sample of it, float64 [item][poly][limb][coefficient][2] holding each u64 residue
+    exactly as its high and low 32 bits.  Items and coefficient positions depend only on the shape of the output, so two builds run with the same arguments
+    on the same (seeded) inputs write arrays that compare element for element."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    outs = step_outputs(w)
+    for name, count, read in outs:
+        items = np.unique(np.linspace(0, count - 1, min(count, DUMP_ITEMS)).round().astype(np.int64))
+        first = read(int(items[0]))
+        n = max(1, min(w.N, DUMP_COEFFS, DUMP_BYTES // len(outs) // (len(items) * first.shape[0] * first.shape[1] * 16)))
+        coeffs = np.sort(np.random.default_rng(0xD0).choice(w.N, n, replace=False))
+        a = np.stack([first[..., coeffs]] + [read(int(i))[..., coeffs] for i in items[1:]])
+        np.save(os.path.join(outdir, name + ".npy"), np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1))
 
 
 # ---------------------------------------------------------------- roofline
@@ -793,10 +838,17 @@ def main():
     ap.add_argument("--ntt-reps", type=int, default=40,
                     help="timed roofline launches (forward / inverse alternating); 40 keeps the two cold launches in front of them below 2 %% of a rocprofv3 average")
     ap.add_argument("--no-roofline", action="store_true", help="skip the roofline launches (PMC passes over the timed step only)")
-    ap.add_argument("--roofline-only", action="store_true", help="skip the timed steps: only the roofline NTT launches run (for the rocprofv3 summary of exactly that kernel)")
+    ap.add_argument("--roofline-only", action="store_true", help="skip the timed steps: only the roofline NTT launches run (for the rocprofv3 summary of exactly that kernel); implies --full")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even for one rank (tests the RCCL path)")
     ap.add_argument("--allow-gloo", action="store_true", help="development only: rendezvous over gloo when fewer GPUs than ranks are visible (never the default)")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: the oracle check of the last step, the roofline launches and per-kernel events, "
+                                                        "the clock / power sampler and the CPU baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (dump_outputs())")
     args = ap.parse_args()
+    if args.roofline_only:
+        args.full = True  # the roofline launches are all that run
+        if args.dump_outputs:
+            ap.error("--dump-outputs needs the timed steps; --roofline-only skips them")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -857,14 +909,16 @@ def main():
     for _ in range(args.warmup):
         w.step()
     barrier()
-    smi = SmiSampler(place.get("pci"))
-    smi.start()
+    smi = SmiSampler(place.get("pci")) if args.full else None
+    if smi:
+        smi.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         w.step()
     w.sync_all()
     dt = max(time.perf_counter() - t0, 1e-9)
-    place.update(smi.stop())  # sclk_mhz / power_w averaged over exactly the timed region (rank_devices[])
+    if smi:
+        place.update(smi.stop())  # sclk_mhz / power_w averaged over exactly the timed region (rank_devices[])
     barrier()
     placements = [place]
     if use_dist:  # after the timed region: every rank's device, NUMA binding, clock and power
@@ -886,9 +940,12 @@ def main():
         world_seen = 1
     value = total_units / dt
 
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(w, args.dump_outputs)
+
     # the bench checks its own work: items 0 and B-1 of the last step against the CPU oracle (every rank checks its own shard)
-    verified, verified_what = None, "skipped (--no-verify / --roofline-only)"
-    if not args.no_verify and not args.roofline_only and args.steps > 0:
+    verified, verified_what = None, "skipped (--no-verify / --roofline-only)" if args.full else "skipped (plain run: --full checks the last step)"
+    if args.full and not args.no_verify and not args.roofline_only and args.steps > 0:
         try:
             verified, verified_what = verify(w)
         except ImportError as e:  # the checker (oracle/libtroy_oracle.so) did not travel
@@ -897,7 +954,7 @@ def main():
             verified = bool(min_over_ranks(1.0 if verified else 0.0, backend) > 0.5) if verified is not None else None
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         if wl["kind"] == "matmul":
             roofline = matmul_roofline(ta, capi, lib, w)
         else:
@@ -941,7 +998,7 @@ def main():
                 roofline["step"] = st
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(w)
         except Exception as e:  # the baseline is informational; never let it kill the bench line
@@ -959,7 +1016,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3) if args.steps else None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u64", "data": "synthetic", "config": cfg, "ranks": world_seen, "per_rank_ops_per_s": [round(v, 2) for v in per_rank],
-            "verified": verified, "verified_what": verified_what, "build_id": capi.build_id(), "rank_devices": placements,
+            "verified": verified, "verified_what": verified_what, "full": args.full, "build_id": capi.build_id(), "rank_devices": placements,
             "roofline": roofline, "cpu_baseline": cpu,
         }
         sys.stdout.flush()

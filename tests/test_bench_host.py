@@ -58,3 +58,51 @@ def test_in_step_roofline_is_time_weighted_over_the_transform_kernels():
     assert r["kernel"] == "ntt2_kernel<0, 0, 9, 0, 1, 0, 1>" and r["share_of_step"] == 0.5 and r["transform_share_of_step"] == round(5000 / 6000, 3)
     assert r["weighted_frac"] == round(14.0e9 / 5000e-6 / 1e9 / 8000.0, 4)
     assert bench.in_step_roofline([k[2]]) is None
+
+
+class _HostBuf:
+    def __init__(self, a):
+        self.a = a.reshape(-1)
+
+    def to_numpy(self, words, offset=0):
+        return self.a[offset:offset + words].copy()
+
+
+class _HostCt:
+    """a batch [batch][capacity][limbs][N] laid out as the library's Ciphertext"""
+
+    def __init__(self, a, size):
+        self.batch, self.capacity, self.limbs, n = a.shape
+        self.buf, self.bstride, self._size = _HostBuf(a), self.capacity * self.limbs * n, size
+
+    def size(self):
+        return self._size
+
+
+def test_dump_outputs_is_an_exact_fixed_sample_under_the_size_limit(tmp_path):
+    """--dump-outputs at the largest output of the workloads (BGV N = 2^16, 14 limbs, 128 ciphertexts): float64, every residue exact as its two
+    32-bit halves, first and last item included, the same positions on every run, at most 64 MB"""
+    import numpy as np
+    import bench
+    N, L, B = 65536, 14, 128
+    a = np.random.default_rng(5).integers(0, 1 << 60, (B, 3, L, N), dtype=np.uint64)
+
+    class W:
+        wl, last = {"kind": "relin_rot"}, _HostCt(a, 2)
+
+        def sync_all(self):
+            pass
+
+    W.N = N
+    for d in ("one", "two"):
+        bench.dump_outputs(W(), str(tmp_path / d))
+    f = tmp_path / "one" / "ct_out.npy"
+    got = np.load(f)
+    assert os.path.getsize(f) <= 64 << 20 and got.dtype == np.float64 and got.shape[:3] == (bench.DUMP_ITEMS, 2, L) and got.shape[-1] == 2
+    assert np.array_equal(got, np.load(tmp_path / "two" / "ct_out.npy"))
+    u = got[..., 0].astype(np.uint64) << np.uint64(32) | got[..., 1].astype(np.uint64)
+    items = np.unique(np.linspace(0, B - 1, bench.DUMP_ITEMS).round().astype(np.int64))
+    assert items[0] == 0 and items[-1] == B - 1
+    for k, i in enumerate(items):  # each sampled row is a row of the item at the recorded positions
+        pos = np.flatnonzero(np.isin(a[i, 0, 0], u[k, 0, 0]))
+        assert len(pos) == u.shape[3] and np.array_equal(a[i, :2, :, pos].transpose(1, 2, 0), u[k])

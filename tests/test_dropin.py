@@ -110,17 +110,29 @@ def _gpu_binary(name):
     return path
 
 
+def _run_gpu(name):
+    """run a prebuilt *_gpu binary against THIS tree's libtroyhip.so.  The binaries record the bare library name; their $ORIGIN runpath finds it only
+    while oracle/_ref really lies inside the tree (a prebuilt oracle/_ref that arrives through a symlink resolves $ORIGIN to where it is stored), so the
+    tree's troy_amd/ goes first on the search path"""
+    lib = os.path.join(ROOT, "troy_amd")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p))
+    r = subprocess.run([_gpu_binary(name)], capture_output=True, text=True, timeout=1500, cwd=OUT, env=env)
+    r.report = "exit %d\n%s\n--- stderr\n%s" % (r.returncode, r.stdout[-3000:], r.stderr[-2000:])
+    return r
+
+
 @pytest.mark.gpu
 def test_reference_gpu_tests_pass_unchanged_on_gpu():
-    r = subprocess.run([_gpu_binary("troytest")], capture_output=True, text=True, timeout=1500, cwd=OUT)
+    r = _run_gpu("troytest")
+    assert re.search(r"\[==========\] \d+ tests ran", r.stdout), r.report
     ran, failed = _summary(r.stdout)
     assert (ran, failed, r.returncode) == (CASES, 0, 0), r.stdout[-4000:] + r.stderr[-2000:]
 
 
 @pytest.mark.gpu
 def test_reference_timetest_runs_unchanged_on_gpu():
-    r = subprocess.run([_gpu_binary("timetest")], capture_output=True, text=True, timeout=1500, cwd=OUT)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    r = _run_gpu("timetest")
+    assert r.returncode == 0, r.report
     for label in ("Encrypt", "Decrypt", "Multiply-inplace", "Relinearize-inplace", "Square-assign", "RotateRows-inplace", "MultiplyPlain-assign"):  # timer labels of its BFV run
         assert re.search(label, r.stdout, re.I), r.stdout[-3000:]
 
@@ -128,14 +140,14 @@ def test_reference_timetest_runs_unchanged_on_gpu():
 @pytest.mark.gpu
 def test_reference_linear_apps_run_unchanged_on_gpu():
     # test/app/linear.cu: BFV 64 x 128 x 256 matmul with ciphertext weights through app/LinearHelper.cuh's interface -- exact arithmetic modulo t
-    r = subprocess.run([_gpu_binary("linear")], capture_output=True, text=True, timeout=1500, cwd=OUT)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    r = _run_gpu("linear")
+    assert r.returncode == 0, r.report
     diffs = re.findall(r"Difference = (\S+)", r.stdout)
     assert diffs and all(float(d) == 0 for d in diffs), r.stdout[-3000:]
     # test/app/linear_ckks.cu: CKKS 1 x 256 x 64 x 56 x 56 convolution of reals in [0, 10) at scale 2^15 -- approximate.  Each of the 256 products per
     # output carries the two encoding roundings, (|x| + |w|) 2^-16 <= 30 * 1.5e-5, so the sum is within 256 * 4.6e-4 = 0.12 of the exact value at worst
     # (a random walk of them: ~0.03, which is what the run prints); the reference itself only prints the number
-    r = subprocess.run([_gpu_binary("linear_ckks")], capture_output=True, text=True, timeout=1500, cwd=OUT)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    r = _run_gpu("linear_ckks")
+    assert r.returncode == 0, r.report
     diffs = re.findall(r"Difference = (\S+)", r.stdout)
     assert diffs and all(float(d) < 0.12 for d in diffs), r.stdout[-3000:]

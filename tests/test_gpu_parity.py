@@ -741,7 +741,7 @@ def test_bench_accounts_for_every_kernel_at_small_batches(batch, gpu):
     """the library picks the single-pass inverse per launch (at least four rows per CU): at a small lane batch the key switch's accumulators take the
     two-pass kernels while the multiply's rows still run single-pass.  bench.py's byte table follows that rule -- every kernel of the step has its
     fraction, the line verifies, and nothing raises (found with `--batch 64` under two ranks)"""
-    line = _run_bench(["--steps", "1", "--warmup", "0", "--batch", str(batch), "--no-cpu-baseline", "--ntt-reps", "1"])
+    line = _run_bench(["--full", "--steps", "1", "--warmup", "0", "--batch", str(batch), "--no-cpu-baseline", "--ntt-reps", "1"])
     assert line["verified"] is True and line["config"]["batch_per_gpu"] == batch
     assert all(k.get("frac") for k in line["roofline"]["per_kernel"]), [k["name"] for k in line["roofline"]["per_kernel"] if not k.get("frac")]
     # round 6: the headline fraction is the in-step one (the standalone pair keeps its numbers beside it), the operation's own HBM rate and the
@@ -758,9 +758,24 @@ def test_bench_accounts_for_every_kernel_at_small_batches(batch, gpu):
 def test_bench_accounts_for_every_kernel_of_one_ciphertext(workload, batch, gpu):
     """one ciphertext (a few small ones) on one stream: the merged small-launch forms -- the byte table names the kernels that ran (a renamed
     instance would raise) and the line verifies"""
-    line = _run_bench(["--steps", "1", "--warmup", "0", "--batch", str(batch), "--streams", "1", "--workload", workload, "--no-cpu-baseline", "--ntt-reps", "1"])
+    line = _run_bench(["--full", "--steps", "1", "--warmup", "0", "--batch", str(batch), "--streams", "1", "--workload", workload, "--no-cpu-baseline", "--ntt-reps", "1"])
     assert line["verified"] is True and line["config"]["batch_per_gpu"] == batch
     assert all(k.get("frac") for k in line["roofline"]["per_kernel"]), [k["name"] for k in line["roofline"]["per_kernel"] if not k.get("frac")]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_full_run_verifies(gpu, tmp_path):
+    """a plain run times exactly --steps steps and carries nothing of --full; --dump-outputs writes the last step's ciphertexts, and a --full run with
+    the same arguments -- whose last step passes the oracle check -- writes the same arrays"""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--batch", "8", "--workload", "bfv_n8192_l4"]
+    plain = _run_bench(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["full"] is False
+    assert plain["verified"] is None and plain["roofline"] is None and plain["cpu_baseline"] is None
+    full = _run_bench(args + ["--full", "--no-cpu-baseline", "--ntt-reps", "1", "--dump-outputs", str(tmp_path / "full")])
+    assert full["verified"] is True and full["roofline"] is not None
+    a, b = np.load(tmp_path / "plain" / "ct_out.npy"), np.load(tmp_path / "full" / "ct_out.npy")
+    assert a.dtype == np.float64 and a.shape[:3] == (8, 2, 4) and np.array_equal(a, b) and a[..., 0].max() > 0
 
 
 @pytest.mark.gpu
@@ -773,7 +788,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--allow-gloo", "--batch", "16", "--workload", "bfv_n8192_l4",
+                        os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--allow-gloo", "--batch", "16", "--workload", "bfv_n8192_l4",
                         "--no-cpu-baseline", "--ntt-reps", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -793,7 +808,7 @@ def test_bench_eight_ranks_share_one_gpu_over_gloo(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", "29547",
-                        os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--allow-gloo", "--batch", "8", "--workload", "bfv_n8192_l4",
+                        os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--allow-gloo", "--batch", "8", "--workload", "bfv_n8192_l4",
                         "--no-cpu-baseline", "--ntt-reps", "1"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

@@ -12,7 +12,7 @@ wl = args.pop(0)
 extra = []
 if args and args[0] == "--no-verify":
     extra.append(args.pop(0))
-r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", wl, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--ntt-reps", "2"] + extra, capture_output=True, text=True)
+r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--workload", wl, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--ntt-reps", "2"] + extra, capture_output=True, text=True)
 lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 if not lines:
     print(r.stdout[-1500:], r.stderr[-1500:])

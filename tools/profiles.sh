@@ -37,10 +37,10 @@ traffic)
 bench)
   for wl in $WLS; do
     extra="--no-cpu-baseline"; case $wl in bfv_n32768_l14|bfv_n8192_l4) extra="";; esac
-    python bench.py --workload $wl $extra > $O/${TAG}_bench_$wl.json 2> $O/bench_$wl.err
+    python bench.py --full --workload $wl $extra > $O/${TAG}_bench_$wl.json 2> $O/bench_$wl.err
   done ;;
 stats)
-  for wl in $WLS; do stats_of $O/${TAG}_${wl}_kernel_stats.csv --workload $wl --steps 5 --warmup 2 --no-cpu-baseline --no-verify; done ;;
+  for wl in $WLS; do stats_of $O/${TAG}_${wl}_kernel_stats.csv --full --workload $wl --steps 5 --warmup 2 --no-cpu-baseline --no-verify; done ;;
 roofline)
   for wl in bfv_n32768_l14 bfv_n32768_l14_p49; do stats_of $O/${TAG}_roofline_${wl}_kernel_stats.csv --workload $wl --roofline-only --no-cpu-baseline; done ;;
 sq)
@@ -75,7 +75,7 @@ small)
     for a in "bfv_n32768_l14 20 1 8 128" "bfv_n8192_l4 50 1 8 128 1024"; do
       set -- $a; wl=$1; steps=$2; shift 2
       for b in "$@"; do
-        python bench.py --workload $wl --batch $b --streams 1 --steps $steps --warmup 3 --no-cpu-baseline --no-roofline --no-per-kernel 2>/dev/null | tail -1 |
+        python bench.py --full --workload $wl --batch $b --streams 1 --steps $steps --warmup 3 --no-cpu-baseline --no-roofline --no-per-kernel 2>/dev/null | tail -1 |
           python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({"workload": d["config"]["workload"], "api": "C ABI (bench.py)", "batch": d["config"]["batch_per_gpu"], "ms_per_step": d["ms_per_step"], "ops_per_s": d["value"], "verified": d["verified"]}))'
       done
     done; } > $O/${TAG}_small_batch.txt 2>&1 ;;

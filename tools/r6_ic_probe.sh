@@ -6,7 +6,7 @@ for b in 2 4 8 32 128; do
   python - $wl $b <<'PY'
 import json, subprocess, sys
 wl, b = sys.argv[1], sys.argv[2]
-r = subprocess.run([sys.executable, "bench.py", "--workload", wl, "--batch", b, "--streams", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--ntt-reps", "2", "--no-verify"], capture_output=True, text=True)
+r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", wl, "--batch", b, "--streams", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--ntt-reps", "2", "--no-verify"], capture_output=True, text=True)
 d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 print(f"{wl} B={int(b):4d}  {d['value']:9.1f} {d['unit']}")
 for k in d["roofline"]["per_kernel"]:
