@@ -262,6 +262,25 @@ int troyhip_divide_by_poly_modulus_degree(troyhip_context *ctx, troyhip_ct *ct, 
 int troyhip_decrypt(troyhip_context *ctx, const troyhip_ct *ct, const uint64_t *secret_key, uint64_t *plain_out, uint64_t plain_batch_stride, uint64_t batch,
                     void *stream);
 
+/* ---- Device encryption, `batch` items per call (Encryptor::encrypt / encryptZero / encryptSymmetric / encryptZeroSymmetric,
+ * src/encryptor_cuda.cuh:170-320, src/utils/rlwe_cuda.cu:23-330).  Item i is BYTE-IDENTICAL to the host form called with item i's seed:
+ * the device draws the same ChaCha20 stream.  seeds: HOST [batch][2] (lo, hi), read before return.  out->data,
+ * out->batch_stride (>= 2 limbs N) and out->limbs (the level) are inputs; size, form, scale and correction factor are set.  Invalid input
+ * returns the status and message of the host form; batch must lie in 1 .. 65535. */
+/* public key [2][K][N] (device, NTT form).  plain != NULL: item i == troyhip_host_encrypt(seeds[i]); the plaintext operands are those of
+ * troyhip_add_plain (plain_batch_stride 0 = one plaintext for every item; BFV/BGV at the first level only; CKKS [limbs][N] NTT form with
+ * plain_scale its scale).  plain == NULL: item i == troyhip_host_encrypt_zero(seeds[i], symmetric = 0) at any data level. */
+int troyhip_encrypt(troyhip_context *ctx, const uint64_t *public_key, const uint64_t *seeds, const uint64_t *plain, uint64_t plain_coeff_count,
+                    uint64_t plain_batch_stride, double plain_scale, troyhip_ct *out, uint64_t batch, void *stream);
+/* secret key [K][N] (device, NTT form).  a_seeds NULL: c1 from the item's own stream, item i == troyhip_host_encrypt_symmetric(seeds[i]) (plain)
+ * or troyhip_host_encrypt_zero(seeds[i], symmetric = 1); else HOST [batch] non-zero seeds, item i ==
+ * troyhip_host_encrypt_symmetric_seeded(seeds[i], a_seeds[i]). */
+int troyhip_encrypt_symmetric(troyhip_context *ctx, const uint64_t *secret_key, const uint64_t *seeds, const uint64_t *a_seeds, const uint64_t *plain,
+                              uint64_t plain_coeff_count, uint64_t plain_batch_stride, double plain_scale, troyhip_ct *out, uint64_t batch, void *stream);
+/* item i of c1_out (device, out_batch_stride words apart) == troyhip_host_expand_seed(a_seeds[i], limbs): the c1 of a seeded ciphertext in the
+ * form the ciphertext stores it.  a_seeds: HOST [batch], non-zero. */
+int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs, uint64_t *c1_out, uint64_t out_batch_stride, uint64_t batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

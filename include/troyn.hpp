@@ -25,6 +25,7 @@
 #include <ostream>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1078,8 +1079,8 @@ public:
     Encryptor(const SEALContext &c, const PublicKey &pk, const SecretKey &sk) : c_(c), pk_(valid(c, pk)), sk_(valid(c, sk)) {}
     // deterministic stream (seed, call counter) for tests ONLY
     Encryptor(const SEALContext &c, const PublicKey &pk, uint64_t seed_lo, uint64_t seed_hi = 0) : c_(c), pk_(valid(c, pk)), seeded_(true), lo_(seed_lo), hi_(seed_hi) {}
-    void setPublicKey(const PublicKey &pk) { pk_ = valid(c_, pk); }
-    void setSecretKey(const SecretKey &sk) { sk_ = valid(c_, sk); }
+    void setPublicKey(const PublicKey &pk) { pk_ = valid(c_, pk); mirror_ = std::make_shared<KeyMirror>(); }
+    void setSecretKey(const SecretKey &sk) { sk_ = valid(c_, sk); mirror_ = std::make_shared<KeyMirror>(); }
     static const PublicKey &valid(const SEALContext &c, const PublicKey &pk) {
         if (pk.parms_id != c.keyParmsID() || pk.data.size() != 2 * c.keyLimbs() * c.polyModulusDegree()) throw std::invalid_argument("public key is not valid for encryption parameters");
         return pk;
@@ -1135,7 +1136,110 @@ public:
     void encryptZeroSymmetric(Ciphertext &dst) const { encryptZeroSymmetric(c_.firstParmsID(), dst); }
     Ciphertext encryptZeroSymmetric(const ParmsID &parms_id) const { Ciphertext d; encryptZeroSymmetric(parms_id, d); return d; }
     Ciphertext encryptZeroSymmetric() const { return encryptZeroSymmetric(c_.firstParmsID()); }
+
+    // ---- batched forms on the device (troyhip_encrypt / troyhip_encrypt_symmetric): the ciphertexts are Ciphertext::allocateBatch members of ONE device
+    // slab.  Item i consumes call number counter_ + 1 + i -- the seed (and a_seed) the (i + 1)-th next single call would take -- and the counter then
+    // advances by the batch size: item i is byte-identical to that single call, so a deterministic encryptor gives the bytes of the loop of single calls.
+    // An encryptor seeded by the operating system draws the 16 B bytes of the item seeds in one troyhip_random_bytes call.  The device copy of the key
+    // is made once, on the context's device.
+    std::vector<Ciphertext> encryptBatch(const std::vector<const Plaintext *> &plains) const {
+        if (pk_.data.empty()) {
+            if (sk_.data.empty()) throw std::logic_error("public key is not set");
+            return batch(1, &plains, plains.size(), 0); // a secret key alone encrypts symmetrically, as encrypt() does
+        }
+        return batch(0, &plains, plains.size(), 0);
+    }
+    std::vector<Ciphertext> encryptSymmetricBatch(const std::vector<const Plaintext *> &plains) const { // seeded: seed() is set per item
+        if (sk_.data.empty()) throw std::logic_error("secret key is not set");
+        return batch(2, &plains, plains.size(), 0);
+    }
+    std::vector<Ciphertext> encryptZeroBatch(size_t count, const ParmsID &parms_id) const {
+        if (pk_.data.empty()) throw std::logic_error("public key is not set");
+        return batch(0, nullptr, count, zero_limbs(parms_id));
+    }
+    std::vector<Ciphertext> encryptZeroSymmetricBatch(size_t count, const ParmsID &parms_id) const {
+        if (sk_.data.empty()) throw std::logic_error("secret key is not set");
+        return batch(2, nullptr, count, zero_limbs(parms_id));
+    }
 private:
+    struct KeyMirror { std::mutex mu; std::shared_ptr<DeviceArray> pk, sk; };
+    int zero_limbs(const ParmsID &id) const {
+        if (!c_.getContextData(id) || id.limbs > (int)c_.firstLimbs()) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        return id.limbs;
+    }
+    // the key on the context's device, uploaded the first time it is needed (one copy per key however many threads encrypt)
+    const uint64_t *device_key(bool secret) const {
+        std::lock_guard<std::mutex> g(mirror_->mu);
+        std::shared_ptr<DeviceArray> &slot = secret ? mirror_->sk : mirror_->pk;
+        if (!slot) {
+            const std::vector<uint64_t> &h = secret ? sk_.data : pk_.data;
+            int cur = 0;
+            check(troyhip_get_device(&cur));
+            const int dev = c_.device();
+            if (dev != cur) check(troyhip_set_device(dev));
+            auto a = std::make_shared<DeviceArray>(h.size());
+            check(troyhip_copy_h2d(a->get(), h.data(), h.size() * 8, nullptr));
+            if (dev != cur) check(troyhip_set_device(cur));
+            slot = std::move(a);
+        }
+        return slot->get();
+    }
+    // kind: 0 public key, 1 symmetric (c1 from the item's stream), 2 seeded symmetric; plains == nullptr: zero at `limbs`
+    std::vector<Ciphertext> batch(int kind, const std::vector<const Plaintext *> *plains, size_t count, int limbs) const {
+        if (!count) return {};
+        const size_t N = c_.polyModulusDegree();
+        const bool ckks = c_.parms().scheme() == SchemeType::ckks;
+        std::vector<uint64_t> slab;
+        size_t n = 0, stride = 0;
+        double scale = 1.0;
+        if (plains) {
+            for (const Plaintext *p : *plains) {
+                if (!p) throw std::invalid_argument("encryptBatch: null plaintext");
+                if (ckks && !p->isNttForm()) throw std::invalid_argument("plain must be in NTT form");
+                if (!ckks && p->isNttForm()) throw std::invalid_argument("plain cannot be in NTT form");
+            }
+            const Plaintext &head = *(*plains)[0];
+            if (ckks) { // one level and one scale for the whole batch
+                for (const Plaintext *p : *plains)
+                    if (p->coeffCount() != head.coeffCount() || p->scale() != head.scale())
+                        throw std::invalid_argument("encryptBatch: CKKS plaintexts of different levels or scales");
+                limbs = (int)(head.coeffCount() / N);
+                n = N;
+                stride = head.coeffCount();
+                scale = head.scale();
+            } else { // coefficient counts may differ: zero-padded to the longest (a zero coefficient adds exactly 0)
+                limbs = (int)c_.firstLimbs();
+                for (const Plaintext *p : *plains) n = std::max(n, p->coeffCount());
+                stride = n;
+            }
+            slab.assign(std::max<size_t>(count * stride, 1), 0);
+            for (size_t i = 0; i < count; i++) std::copy((*plains)[i]->data(), (*plains)[i]->data() + (*plains)[i]->coeffCount(), slab.begin() + (std::ptrdiff_t)(i * stride));
+        }
+        std::vector<uint64_t> seeds(2 * count), a_seeds(kind == 2 ? count : 0);
+        if (seeded_) {
+            for (size_t i = 0; i < count; i++) { seeds[2 * i] = lo_ + counter_ + 1 + i; seeds[2 * i + 1] = hi_; }
+        } else {
+            check(troyhip_random_bytes(seeds.data(), seeds.size() * 8));
+        }
+        for (size_t i = 0; i < a_seeds.size(); i++) a_seeds[i] = fresh_a_seed(counter_ + 1 + i);
+        counter_ += count;
+        Ciphertext like(c_);
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(count, like, 2, (size_t)limbs);
+        troyhip_ct d = *out[0].raw();
+        d.batch_stride = 2 * (uint64_t)limbs * N;
+        DeviceArray dplain(slab.size());
+        if (!slab.empty()) check(troyhip_copy_h2d(dplain.get(), slab.data(), slab.size() * 8, nullptr));
+        const uint64_t *pl = plains ? dplain.get() : nullptr;
+        if (kind == 0) check(troyhip_encrypt(c_.handle(), device_key(false), seeds.data(), pl, n, stride, scale, &d, count, nullptr));
+        else check(troyhip_encrypt_symmetric(c_.handle(), device_key(true), seeds.data(), kind == 2 ? a_seeds.data() : nullptr, pl, n, stride, scale, &d, count, nullptr));
+        check(troyhip_stream_synchronize(nullptr)); // dplain is freed on return
+        for (size_t i = 0; i < count; i++) {
+            troyhip_ct *r = out[i].raw();
+            r->size = d.size; r->is_ntt_form = d.is_ntt_form; r->scale = d.scale; r->correction_factor = d.correction_factor;
+            if (kind == 2) out[i].seed() = a_seeds[i];
+        }
+        return out;
+    }
     void zero(const std::vector<uint64_t> &key, int symmetric, const ParmsID &id, Ciphertext &dst) const {
         if (!c_.getContextData(id) || id.limbs > (int)c_.firstLimbs()) throw std::invalid_argument("parms_id is not valid for encryption parameters");
         const size_t N = c_.polyModulusDegree();
@@ -1169,6 +1273,7 @@ private:
     bool seeded_ = false;
     uint64_t lo_ = 0, hi_ = 0;
     mutable uint64_t counter_ = 0;
+    std::shared_ptr<KeyMirror> mirror_ = std::make_shared<KeyMirror>();
 };
 
 class Decryptor { // src/decryptor_cuda.cuh:13-60: the secret key is uploaded once, decryption runs on the device

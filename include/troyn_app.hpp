@@ -97,10 +97,10 @@ inline Cipher2d encryptGrid(const troyn::Encryptor &encryptor, const Plain2d &pl
     }
     const size_t cols = plain.data[0].size();
     for (size_t i = 0; i < rows; i++) out[i].resize(cols);
-    for (size_t j = 0; j < cols; j++) {
-        std::vector<troyn::Ciphertext> fresh(rows);
-        for (size_t i = 0; i < rows; i++) encryptor.encryptSymmetric(plain[i][j], fresh[i]);
-        std::vector<troyn::Ciphertext> column = troyn::Ciphertext::packBatch(fresh);
+    for (size_t j = 0; j < cols; j++) { // one device encryption per column; the counter order (column j, rows 0 .. rows - 1) is the loop's
+        std::vector<const troyn::Plaintext *> column_plain(rows);
+        for (size_t i = 0; i < rows; i++) column_plain[i] = &plain[i][j];
+        std::vector<troyn::Ciphertext> column = encryptor.encryptSymmetricBatch(column_plain);
         for (size_t i = 0; i < rows; i++) out[i][j] = std::move(column[i]);
     }
     return out;

@@ -914,6 +914,81 @@ class Encryptor:
         return self._zero(self.sk, True, limbs)
 
 
+    # ---- device forms: `batch` ciphertexts per call on the GPU (troyhip_encrypt / troyhip_encrypt_symmetric).  Item i is byte-identical to the
+    # single call that would have come next but i: it takes the seed of call number counter + 1 + i, and the counter advances by the batch size.
+    def _device_key(self, symmetric):
+        key = self.sk if symmetric else self.pk
+        if key is None:
+            raise RuntimeError("secret key is not set" if symmetric else "public key is not set")
+        attr = "_dsk" if symmetric else "_dpk"
+        cached = getattr(self, attr, None)
+        if cached is None or cached[0] is not key:  # one device copy per key array (setSecretKey replaces the array)
+            cached = (key, DeviceBuffer.from_numpy(key))
+            setattr(self, attr, cached)
+        return cached[1]
+
+    def _batch_seeds(self, batch):
+        if self.seed is None:
+            seeds = np.frombuffer(os.urandom(16 * batch), dtype="<u8").reshape(batch, 2)
+        else:
+            seeds = np.array([[(self.seed[0] + self.counter + 1 + i) & (2**64 - 1), self.seed[1]] for i in range(batch)], dtype=np.uint64)
+        self.counter += batch
+        return np.ascontiguousarray(seeds, dtype=np.uint64)
+
+    def _run_batch(self, symmetric, plains, scale, batch=None, limbs=None):
+        ctx = self.context
+        key = self._device_key(symmetric)
+        dplain, n, stride = None, 0, 0
+        if plains is not None:
+            P = np.ascontiguousarray(plains, dtype=np.uint64)
+            if ctx.scheme == CKKS:
+                P = P[None] if P.ndim == 2 else P
+                batch, limbs, n = P.shape[0], P.shape[1], ctx.N
+                stride = limbs * ctx.N
+            else:
+                P = P[None] if P.ndim == 1 else P
+                batch, n = P.shape
+                limbs, stride = ctx.first_limbs, n
+            dplain = DeviceBuffer.from_numpy(P) if P.size else None
+        else:
+            limbs = ctx.first_limbs if limbs is None else int(limbs)
+        batch = int(batch)
+        if batch < 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "batch must lie in 1 .. 65535")
+        seeds = self._batch_seeds(batch)
+        out = Ciphertext(ctx, batch, 2, limbs)
+        st = out.struct()
+        if plains is not None and dplain is None:  # empty plaintexts add nothing: one zero word stands for them
+            dplain = DeviceBuffer.from_numpy(np.zeros(1, dtype=np.uint64))
+        pl = None if dplain is None else C.c_void_p(dplain.ptr)
+        if symmetric:
+            rc = self.lib.troyhip_encrypt_symmetric(ctx.h, C.c_void_p(key.ptr), _u64p(seeds), None, pl, C.c_uint64(n), C.c_uint64(stride), C.c_double(scale),
+                                                    C.byref(st), C.c_uint64(batch), None)
+        else:
+            rc = self.lib.troyhip_encrypt(ctx.h, C.c_void_p(key.ptr), _u64p(seeds), pl, C.c_uint64(n), C.c_uint64(stride), C.c_double(scale), C.byref(st),
+                                          C.c_uint64(batch), None)
+        capi.check(self.lib, rc)
+        out._absorb(st)
+        return out
+
+    def encryptBatch(self, plains, scale=1.0):
+        """encrypt() of every plaintext on the device: plains [B][n] (BFV/BGV coefficients mod t) or [B][limbs][N] (CKKS, NTT form, `scale` its
+        scale) -> a device Ciphertext of B items; item i == the i-th next encrypt() call, byte for byte"""
+        return self._run_batch(False, plains, scale)
+
+    def encryptSymmetricBatch(self, plains, scale=1.0):
+        """encryptSymmetric() of every plaintext on the device (same layouts as encryptBatch)"""
+        return self._run_batch(True, plains, scale)
+
+    def encryptZeroBatch(self, batch, limbs=None):
+        """`batch` x encryptZero(limbs) on the device"""
+        return self._run_batch(False, None, 1.0, batch, limbs)
+
+    def encryptZeroSymmetricBatch(self, batch, limbs=None):
+        """`batch` x encryptZeroSymmetric(limbs) on the device"""
+        return self._run_batch(True, None, 1.0, batch, limbs)
+
+
 class Decryptor:
     """Decryptor::decrypt (src/decryptor.cpp:115-371), on the CPU; deterministic."""
 

@@ -3,6 +3,7 @@
 #include <cerrno>
 #include "../../include/troyhip.h"
 #include "evaluator.h"
+#include "encryptor.h"
 #include "kernels.h"
 #include "build_id.h"
 #include "hostcrypto.h"
@@ -22,7 +23,8 @@ using namespace troyhip;
 struct troyhip_context {
     Context ctx;
     Evaluator ev;
-    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true) : ctx(scheme, N, q, t, device), ev(ctx) {}
+    DeviceEncryptor enc;
+    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true) : ctx(scheme, N, q, t, device), ev(ctx), enc(ctx, ev) {}
 };
 
 namespace {
@@ -599,6 +601,35 @@ int troyhip_host_batch_encode(const troyhip_context *ctx, const uint64_t *values
 }
 int troyhip_host_batch_decode(const troyhip_context *ctx, const uint64_t *plain, uint64_t n_coeffs, uint64_t *values_out) {
     return guard([&] { hostcrypto::batch_decode(need(ctx)->ctx, plain, n_coeffs, values_out); }, false);
+}
+
+// ---- device encryption (encryptor.cpp): the context's device is bound before the stream is announced
+int troyhip_encrypt(troyhip_context *ctx, const uint64_t *public_key, const uint64_t *seeds, const uint64_t *plain, uint64_t plain_coeff_count,
+                    uint64_t plain_batch_stride, double plain_scale, troyhip_ct *out, uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        CtBatch o = view(out);
+        const hipStream_t s = on(stream);
+        x->enc.encrypt(public_key, false, seeds, nullptr, plain, plain_coeff_count, plain_batch_stride, plain_scale, o, batch, s);
+        store(o, out);
+    });
+}
+int troyhip_encrypt_symmetric(troyhip_context *ctx, const uint64_t *secret_key, const uint64_t *seeds, const uint64_t *a_seeds, const uint64_t *plain,
+                              uint64_t plain_coeff_count, uint64_t plain_batch_stride, double plain_scale, troyhip_ct *out, uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        CtBatch o = view(out);
+        const hipStream_t s = on(stream);
+        x->enc.encrypt(secret_key, true, seeds, a_seeds, plain, plain_coeff_count, plain_batch_stride, plain_scale, o, batch, s);
+        store(o, out);
+    });
+}
+int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs, uint64_t *c1_out, uint64_t out_batch_stride, uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->enc.expand_seed(a_seeds, limbs, c1_out, out_batch_stride, batch, s);
+    });
 }
 
 int troyhip_ntt(troyhip_context *ctx, uint64_t *data, uint64_t rows, const uint64_t *row_primes, int period, int inner, int inverse, void *stream) {

@@ -175,6 +175,47 @@ void launch_copy_strided(const u64 *src, u64 src_bstride, u64 *dst, u64 dst_bstr
 void launch_zero_strided(u64 *dst, u64 dst_bstride, u64 count, u64 batch, hipStream_t s);
 void launch_fill_uniform(u64 *out, const PrimeDesc *primes, const LimbMap &map, int logn, u64 seed, u64 row0, u64 rows, hipStream_t s);
 
+// ---- sampler.hip (device encryption: the ChaCha20 stream of hostcrypto.cpp, drawn over a batch of items) ----
+// One rejection sampler over `items` streams: draws [0, draws) of item b take the accepted words (w <= limit) of the stream (seeds[b], stream) from word
+// pos_in[b] on; pos_out[b] receives the word after the last one consumed.  A parallel window of `window` words (a multiple of 8) is counted, ranked and
+// scattered; a window with too few accepted words is finished by a sequential tail (tail_ran[b] = 1).  blocks = window / 8 + 1.
+struct SamplerArgs {
+    const u64 *seeds; // [items][2] (lo, hi)
+    u64 stream;       // nonce: the stream id of hostcrypto's Rng
+    const u64 *pos_in;
+    u64 *pos_out;
+    u64 draws, window, blocks, limit, items;
+    u32 *counts, *offs; // [items][blocks] scratch
+    u64 *total, *tail_ran; // [items]
+    int kind;         // 0 ternary (uniform_below(3)) lifted to limbs [l0, l1); 1 uniform_below(p) of limb l0
+    int l0, l1, logn;
+    u64 *out;         // draw r of item b, limb l -> out[b * out_bstride + l * N + r]
+    u64 out_bstride;
+    const PrimeDesc *primes; // limb l uses primes[l] (the key primes lead the registry)
+};
+void launch_sampler(const SamplerArgs &a, hipStream_t s);
+// CBD draws [0, draws) of item b from word pos[b]: draw r -> out[b * out_bstride + (r / N) * out_pstride + l * N + r % N] for l < limbs, stored or (add)
+// multiplied by ts[l] and added
+struct CbdArgs {
+    const u64 *seeds;
+    u64 stream;
+    const u64 *pos;
+    u64 draws, items;
+    int logn, limbs;
+    bool add;
+    u64 *out;
+    u64 out_bstride, out_pstride;
+    const PrimeDesc *primes;
+    u64 ts[64];
+};
+void launch_sample_cbd(const CbdArgs &a, hipStream_t s);
+struct EncScale { u64 v[64]; }; // per-limb factor of the error (BGV: t mod p_l, else 1)
+// out[b][j][l] = u[b][l] * pk[j][l] (+ e[b][j][l]) mod p_l, j = 0, 1; u [batch][el][N], pk [2][K][N], e / out [batch][2][el][N]
+void launch_enc_pk_product(const u64 *u, const u64 *pk, u64 K, const u64 *e, u64 *out, const PrimeDesc *primes, int logn, u64 el, u64 batch, hipStream_t s);
+// ct[b] = (-(c1 * sk + e * es), c1) in NTT form: c1 = ct[b][1] already holds a; e [batch][limbs][N]
+void launch_enc_sk_combine(u64 *ct, u64 ct_bstride, const u64 *sk, const u64 *e, const EncScale &es, const PrimeDesc *primes, int logn, u64 limbs, u64 batch,
+                           hipStream_t s);
+
 // ---- selftest.hip (test support) ----
 void launch_modarith_probe(int op, const u64 *a, const u64 *b, const u64 *c, u64 p, u64 aux_value, u64 *out, u64 n, hipStream_t s);
 
