@@ -195,6 +195,11 @@ int troyhip_host_decrypt(const troyhip_context *ctx, const uint64_t *secret_key,
  * 2 x (N/2) matrix order <-> the plaintext polynomial [N] in coefficient form.  BFV / BGV with a batching plain modulus (t prime, t = 1 mod 2N). */
 int troyhip_host_batch_encode(const troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t *plain_out);
 int troyhip_host_batch_decode(const troyhip_context *ctx, const uint64_t *plain, uint64_t n_coeffs, uint64_t *values_out);
+/* CKKSEncoder::encode / decode of include/troyn.hpp (N/2 complex slots, the canonical embedding), restated with the host NTT tables; works on a
+ * host-only context.  values: [count][2] (re, im) doubles, count <= N/2;  plain: [limbs][N] NTT form at the level of `limbs` primes;  decode
+ * writes [N/2][2].  Encode refuses "encoded values are too large" (the header's test) and non-finite values * scale. */
+int troyhip_host_ckks_encode(const troyhip_context *ctx, const double *values, uint64_t count, int limbs, double scale, uint64_t *plain_out);
+int troyhip_host_ckks_decode(const troyhip_context *ctx, const uint64_t *plain, int limbs, double scale, double *values_out);
 
 /* ---- kernel_util (src/kernelutils.cuh:562-672) ----
  * rows limb-polynomials of N coefficients at `data`; row r is reduced modulo row_primes[(r / inner) % period].
@@ -280,6 +285,24 @@ int troyhip_encrypt_symmetric(troyhip_context *ctx, const uint64_t *secret_key, 
 /* item i of c1_out (device, out_batch_stride words apart) == troyhip_host_expand_seed(a_seeds[i], limbs): the c1 of a seeded ciphertext in the
  * form the ciphertext stores it.  a_seeds: HOST [batch], non-zero. */
 int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs, uint64_t *c1_out, uint64_t out_batch_stride, uint64_t batch, void *stream);
+
+/* ---- Device encoding, `batch` items per call (BatchEncoder / CKKSEncoder).  Item i is BYTE-IDENTICAL to the host form called with item i
+ * (DESIGN.md section 4.7).  Every buffer is device memory; strides are in words (u64 or double) between consecutive items; batch in 1 .. 65535.
+ * Invalid input returns the host form's status and message.  The outputs feed troyhip_encrypt's `plain` operand directly (BFV [B][N], CKKS
+ * [B][limbs][N] NTT form) and the decoders read troyhip_decrypt's `plain_out` directly. */
+/* item i == troyhip_host_batch_encode(values + i values_stride, count) -> plain_out + i plain_stride (plain_stride >= N) */
+int troyhip_batch_encode(troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t values_stride, uint64_t *plain_out, uint64_t plain_stride,
+                         uint64_t batch, void *stream);
+/* item i == troyhip_host_batch_decode(plain + i plain_stride, n_coeffs) -> values_out + i values_stride (values_stride >= N) */
+int troyhip_batch_decode(troyhip_context *ctx, const uint64_t *plain, uint64_t n_coeffs, uint64_t plain_stride, uint64_t *values_out, uint64_t values_stride,
+                         uint64_t batch, void *stream);
+/* item i == troyhip_host_ckks_encode(values + i values_stride, count, limbs, scale) -> plain_out + i plain_stride (>= limbs N).  The call reads back
+ * one word per item (one synchronisation of `stream`) and refuses the first item that is too large or not finite, naming it, before the NTT runs. */
+int troyhip_ckks_encode(troyhip_context *ctx, const double *values, uint64_t count, uint64_t values_stride, int limbs, double scale, uint64_t *plain_out,
+                        uint64_t plain_stride, uint64_t batch, void *stream);
+/* item i == troyhip_host_ckks_decode(plain + i plain_stride, limbs, scale) -> values_out + i values_stride (values_stride >= N) */
+int troyhip_ckks_decode(troyhip_context *ctx, const uint64_t *plain, int limbs, double scale, uint64_t plain_stride, double *values_out, uint64_t values_stride,
+                        uint64_t batch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1351,6 +1351,42 @@ public:
         destination.assign(slots_, 0);
         for (size_t i = 0; i < std::min(plain.coeffCount(), slots_); i++) destination[i] = plain[i] > half ? (int64_t)(plain[i] - t) : (int64_t)plain[i];
     }
+    // device forms, one call for the whole batch (troyhip_batch_encode / _decode): item i == encode(values[i]) / decode(plains[i]) byte for byte.  The
+    // plaintexts keep their device copy (what encryptBatch reads)
+    void encodeBatch(const std::vector<std::vector<uint64_t>> &values, std::vector<Plaintext> &destination) const {
+        size_t count = 0;
+        for (auto &v : values) count = std::max(count, v.size());
+        if (count > slots_) throw std::invalid_argument("values_matrix size is too large");
+        std::vector<uint64_t> flat(std::max<size_t>(1, values.size() * count), 0); // shorter rows are zero-padded: zero slots encode alike
+        for (size_t b = 0; b < values.size(); b++) std::copy(values[b].begin(), values[b].end(), flat.begin() + (long)(b * count));
+        run_batch(true, flat, count, values.size(), destination, nullptr);
+    }
+    void encodeBatch(const std::vector<std::vector<int64_t>> &values, std::vector<Plaintext> &destination) const {
+        const uint64_t t = c_.parms().plainModulus().value();
+        std::vector<std::vector<uint64_t>> u(values.size());
+        for (size_t b = 0; b < values.size(); b++)
+            for (int64_t v : values[b]) u[b].push_back(v < 0 ? t + (uint64_t)v : (uint64_t)v);
+        encodeBatch(u, destination);
+    }
+    void decodeBatch(const std::vector<Plaintext> &plains, std::vector<std::vector<uint64_t>> &destination) const {
+        size_t n = 0;
+        for (auto &p : plains) {
+            if (p.isNttForm()) throw std::invalid_argument("plain cannot be in NTT form");
+            n = std::max(n, std::min(p.coeffCount(), slots_));
+        }
+        std::vector<uint64_t> flat(std::max<size_t>(1, plains.size() * n), 0);
+        for (size_t b = 0; b < plains.size(); b++) std::copy(plains[b].data(), plains[b].data() + std::min(plains[b].coeffCount(), n), flat.begin() + (long)(b * n));
+        std::vector<Plaintext> unused;
+        run_batch(false, flat, n, plains.size(), unused, &destination);
+    }
+    void decodeBatch(const std::vector<Plaintext> &plains, std::vector<std::vector<int64_t>> &destination) const {
+        std::vector<std::vector<uint64_t>> u;
+        decodeBatch(plains, u);
+        const uint64_t t = c_.parms().plainModulus().value(), half = (t + 1) >> 1;
+        destination.assign(u.size(), std::vector<int64_t>(slots_));
+        for (size_t b = 0; b < u.size(); b++)
+            for (size_t i = 0; i < slots_; i++) destination[b][i] = u[b][i] >= half ? (int64_t)u[b][i] - (int64_t)t : (int64_t)u[b][i];
+    }
     void decode(const Plaintext &plain, std::vector<int64_t> &destination) const { // values above t / 2 come back negative (batchencoder.cpp:215-243)
         std::vector<uint64_t> u;
         decode(plain, u);
@@ -1359,6 +1395,28 @@ public:
         for (size_t i = 0; i < slots_; i++) destination[i] = u[i] >= half ? (int64_t)u[i] - (int64_t)t : (int64_t)u[i];
     }
 private:
+    // encode: flat [batch][n] values -> destination;  decode: flat [batch][n] coefficients -> *values
+    void run_batch(bool encode, const std::vector<uint64_t> &flat, size_t n, size_t batch, std::vector<Plaintext> &destination,
+                   std::vector<std::vector<uint64_t>> *values) const {
+        const size_t N = slots_;
+        DeviceArray src(flat.size());
+        check(troyhip_copy_h2d(src.get(), flat.data(), flat.size() * 8, nullptr));
+        auto out = std::make_shared<DeviceArray>(std::max<size_t>(1, batch) * N);
+        if (encode) check(troyhip_batch_encode(c_.handle(), src.get(), n, n, out->get(), N, batch, nullptr));
+        else check(troyhip_batch_decode(c_.handle(), src.get(), n, n, out->get(), N, batch, nullptr));
+        std::vector<uint64_t> host(batch * N);
+        check(troyhip_copy_d2h(host.data(), out->get(), host.size() * 8, nullptr));
+        if (encode) {
+            destination.assign(batch, Plaintext());
+            for (size_t b = 0; b < batch; b++) {
+                destination[b].resize(N);
+                std::copy(host.begin() + (long)(b * N), host.begin() + (long)((b + 1) * N), destination[b].data());
+            }
+        } else {
+            values->assign(batch, std::vector<uint64_t>());
+            for (size_t b = 0; b < batch; b++) (*values)[b].assign(host.begin() + (long)(b * N), host.begin() + (long)((b + 1) * N));
+        }
+    }
     const SEALContext &c_;
     size_t slots_;
 };
@@ -1447,6 +1505,80 @@ public:
         decode(plain, c);
         destination.resize(c.size());
         for (size_t i = 0; i < c.size(); i++) destination[i] = c[i].real();
+    }
+
+    // device forms, one call for the whole batch (troyhip_ckks_encode / _decode): item i is byte-identical to troyhip_host_ckks_encode / _decode of
+    // item i.  The plaintexts are NTT form at parms_id with the given scale.
+    void encodeBatch(const std::vector<std::vector<std::complex<double>>> &values, const ParmsID &parms_id, double scale, std::vector<Plaintext> &destination) const {
+        auto level = c_.getContextData(parms_id);
+        if (!level) throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        const int limbs = (int)level->parms().coeffModulus().size();
+        const size_t n = slots_ * 2, batch = values.size();
+        size_t count = 0;
+        for (auto &v : values) count = std::max(count, v.size());
+        if (count > slots_) throw std::invalid_argument("values_size is too large");
+        std::vector<double> flat(std::max<size_t>(1, batch * count * 2), 0.0); // shorter items are padded with zero slots, which encode alike
+        for (size_t b = 0; b < batch; b++)
+            for (size_t i = 0; i < values[b].size(); i++) { flat[(b * count + i) * 2] = values[b][i].real(); flat[(b * count + i) * 2 + 1] = values[b][i].imag(); }
+        DeviceArray src(flat.size());
+        check(troyhip_copy_h2d(src.get(), flat.data(), flat.size() * 8, nullptr));
+        const size_t item = (size_t)limbs * n;
+        DeviceArray out(std::max<size_t>(1, batch) * item);
+        check(troyhip_ckks_encode(c_.handle(), (const double *)src.get(), count, 2 * count, limbs, scale, out.get(), item, batch, nullptr));
+        destination.assign(batch, Plaintext());
+        for (size_t b = 0; b < batch; b++) {
+            auto dev = std::make_shared<DeviceArray>(item);
+            check(troyhip_copy_d2d(dev->get(), out.get() + b * item, item * 8, nullptr));
+            destination[b].assignWords(item);
+            check(troyhip_copy_d2h(destination[b].data(), dev->get(), item * 8, nullptr));
+            destination[b].adoptDevice(dev);
+            destination[b].setNttForm(parms_id);
+            destination[b].scale() = scale;
+        }
+    }
+    void encodeBatch(const std::vector<std::vector<std::complex<double>>> &values, double scale, std::vector<Plaintext> &destination) const {
+        encodeBatch(values, c_.firstParmsID(), scale, destination);
+    }
+    void encodeBatch(const std::vector<std::vector<double>> &values, const ParmsID &parms_id, double scale, std::vector<Plaintext> &destination) const {
+        std::vector<std::vector<std::complex<double>>> c(values.size());
+        for (size_t b = 0; b < values.size(); b++) c[b].assign(values[b].begin(), values[b].end());
+        encodeBatch(c, parms_id, scale, destination);
+    }
+    void encodeBatch(const std::vector<std::vector<double>> &values, double scale, std::vector<Plaintext> &destination) const {
+        encodeBatch(values, c_.firstParmsID(), scale, destination);
+    }
+    // plains of one level and one scale
+    void decodeBatch(const std::vector<Plaintext> &plains, std::vector<std::vector<std::complex<double>>> &destination) const {
+        destination.clear();
+        if (plains.empty()) return;
+        const size_t n = slots_ * 2, batch = plains.size();
+        for (auto &p : plains) {
+            if (!p.isNttForm()) throw std::invalid_argument("plain is not in NTT form");
+            if (p.parmsID() != plains[0].parmsID() || p.scale() != plains[0].scale()) throw std::invalid_argument("decodeBatch: plaintexts of different levels or scales");
+        }
+        auto level = c_.getContextData(plains[0].parmsID());
+        if (!level) throw std::invalid_argument("plain is not valid for encryption parameters");
+        const int limbs = (int)level->parms().coeffModulus().size();
+        const size_t item = (size_t)limbs * n;
+        DeviceArray src(batch * item);
+        for (size_t b = 0; b < batch; b++) {
+            if (plains[b].coeffCount() != item) throw std::invalid_argument("plain is not valid for encryption parameters");
+            check(troyhip_copy_d2d(src.get() + b * item, plains[b].device(), item * 8, nullptr));
+        }
+        DeviceArray out(batch * n);
+        check(troyhip_ckks_decode(c_.handle(), src.get(), limbs, plains[0].scale(), item, (double *)out.get(), n, batch, nullptr));
+        std::vector<double> host(batch * n);
+        check(troyhip_copy_d2h(host.data(), out.get(), host.size() * 8, nullptr));
+        destination.assign(batch, std::vector<std::complex<double>>(slots_));
+        for (size_t b = 0; b < batch; b++)
+            for (size_t i = 0; i < slots_; i++) destination[b][i] = {host[b * n + 2 * i], host[b * n + 2 * i + 1]};
+    }
+    void decodeBatch(const std::vector<Plaintext> &plains, std::vector<std::vector<double>> &destination) const {
+        std::vector<std::vector<std::complex<double>>> c;
+        decodeBatch(plains, c);
+        destination.assign(c.size(), std::vector<double>());
+        for (size_t b = 0; b < c.size(); b++)
+            for (auto &z : c[b]) destination[b].push_back(z.real());
     }
 
     // ckks_cuda.cu:455-575 encodePolynomialInternal

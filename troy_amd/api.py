@@ -939,7 +939,18 @@ class Encryptor:
         ctx = self.context
         key = self._device_key(symmetric)
         dplain, n, stride = None, 0, 0
-        if plains is not None:
+        if isinstance(plains, DeviceBuffer):  # already on the device (encodeBatch(device=True)): no copy
+            shape = getattr(plains, "shape", None) or ((plains.words // ctx.N, ctx.N) if ctx.scheme != CKKS else None)
+            if shape is None:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "a CKKS DeviceBuffer plaintext needs its shape (batch, limbs, N)")
+            if ctx.scheme == CKKS:
+                batch, limbs, n = shape[0], shape[1], ctx.N
+                stride = limbs * ctx.N
+            else:
+                batch, n = shape[0], shape[-1]
+                limbs, stride = ctx.first_limbs, n
+            dplain = plains
+        elif plains is not None:
             P = np.ascontiguousarray(plains, dtype=np.uint64)
             if ctx.scheme == CKKS:
                 P = P[None] if P.ndim == 2 else P
@@ -973,7 +984,8 @@ class Encryptor:
 
     def encryptBatch(self, plains, scale=1.0):
         """encrypt() of every plaintext on the device: plains [B][n] (BFV/BGV coefficients mod t) or [B][limbs][N] (CKKS, NTT form, `scale` its
-        scale) -> a device Ciphertext of B items; item i == the i-th next encrypt() call, byte for byte"""
+        scale) -> a device Ciphertext of B items; item i == the i-th next encrypt() call, byte for byte.  `plains` may also be a DeviceBuffer
+        from encodeBatch(device=True) (its `shape` gives the layout; BFV/BGV without one: [words / N][N])"""
         return self._run_batch(False, plains, scale)
 
     def encryptSymmetricBatch(self, plains, scale=1.0):
@@ -1033,6 +1045,52 @@ class BatchEncoder:
         capi.check(self.lib, self.lib.troyhip_host_batch_decode(self.context.h, _u64p(p), C.c_uint64(p.size), _u64p(out)))
         return out
 
+    # ---- device forms: B items per call (troyhip_batch_encode / _decode); item i == encode(values[i]) / decode(plains[i]) byte for byte
+    def encodeBatch(self, values, device=False):
+        """values [B][count] (numpy: unsigned, or signed with encode()'s mapping of negatives; or a DeviceBuffer of B x N words, `count` = N)
+        -> plaintexts [B][N] (numpy; device=True: a DeviceBuffer with shape (B, N), the `plains` operand of Encryptor.encryptBatch)"""
+        ctx = self.context
+        N = ctx.N
+        if isinstance(values, DeviceBuffer):
+            src, (batch, count) = values, (getattr(values, "shape", None) or (values.words // N, N))
+        else:
+            v = np.asarray(values)
+            v = v[None] if v.ndim == 1 else v
+            if v.dtype.kind == "i":
+                v = v.astype(np.int64) % np.int64(ctx.plain_modulus)
+            v = np.ascontiguousarray(v, dtype=np.uint64)
+            batch, count = v.shape
+            src = DeviceBuffer.from_numpy(v) if v.size else DeviceBuffer(1)
+        out = DeviceBuffer(max(1, batch) * N)
+        capi.check(self.lib, self.lib.troyhip_batch_encode(ctx.h, C.c_void_p(src.ptr), C.c_uint64(count), C.c_uint64(count), C.c_void_p(out.ptr), C.c_uint64(N),
+                                                           C.c_uint64(batch), None))
+        out.shape = (batch, N)
+        return out if device else out.to_numpy().reshape(batch, N)
+
+    def decodeBatch(self, plains, device=False, signed=False):
+        """plains [B][n] (numpy, n <= N coefficients, or a DeviceBuffer of B x N words such as Decryptor output) -> slots [B][N] uint64
+        (signed=True: int64 with decode()'s centring; device=True: a DeviceBuffer of unsigned slots)"""
+        ctx = self.context
+        N = ctx.N
+        if isinstance(plains, DeviceBuffer):
+            src, (batch, n) = plains, (getattr(plains, "shape", None) or (plains.words // N, N))
+        else:
+            p = np.ascontiguousarray(plains, dtype=np.uint64)
+            p = p[None] if p.ndim == 1 else p
+            batch, n = p.shape
+            src = DeviceBuffer.from_numpy(p) if p.size else DeviceBuffer(1)
+        out = DeviceBuffer(max(1, batch) * N)
+        capi.check(self.lib, self.lib.troyhip_batch_decode(ctx.h, C.c_void_p(src.ptr), C.c_uint64(n), C.c_uint64(n), C.c_void_p(out.ptr), C.c_uint64(N),
+                                                           C.c_uint64(batch), None))
+        out.shape = (batch, N)
+        if device:
+            return out
+        u = out.to_numpy().reshape(batch, N)
+        if not signed:
+            return u
+        t = np.uint64(ctx.plain_modulus)
+        return np.where(u >= (t + np.uint64(1)) >> np.uint64(1), u.astype(np.int64) - np.int64(t), u.astype(np.int64))
+
     def encodePolynomial(self, values):
         """BatchEncoderCuda::encodePolynomial (src/batchencoder_cuda.cu:124-170): the values ARE the coefficients, modulo t.  Unsigned input keeps
         len(values) coefficients; signed input (any negative value, or a signed dtype) is padded to N, negative v stored as t - |v|"""
@@ -1055,3 +1113,80 @@ class BatchEncoder:
         out = np.zeros(self.context.N, dtype=np.int64)
         out[:p.size] = [int(x) - t if int(x) > t >> 1 else int(x) for x in p]
         return out
+
+
+class CKKSEncoder:
+    """CKKSEncoder::encode / decode of include/troyn.hpp: N/2 complex slots <-> an RNS plaintext [limbs][N] in NTT form (the canonical embedding).
+    encode / decode run on the host (troyhip_host_ckks_*); encodeBatch / decodeBatch run B items per call on the device, item i byte-identical."""
+
+    def __init__(self, context):
+        if context.scheme != CKKS:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "unsupported scheme")
+        self.context, self.lib = context, context.lib
+
+    def slotCount(self):
+        return self.context.N // 2
+
+    @staticmethod
+    def _pairs(values):
+        v = np.asarray(values)
+        if np.iscomplexobj(v):
+            v = np.stack([v.real, v.imag], axis=-1)
+        else:
+            v = np.stack([v.astype(np.float64), np.zeros(v.shape)], axis=-1)
+        return np.ascontiguousarray(v, dtype=np.float64)
+
+    def encode(self, values, scale, limbs=None):
+        """values: up to N/2 complex (or real) slots -> uint64 [limbs][N] (default: the first data level)"""
+        ctx = self.context
+        limbs = ctx.first_limbs if limbs is None else int(limbs)
+        v = self._pairs(values).reshape(-1, 2)
+        out = np.zeros((max(limbs, 0), ctx.N), dtype=np.uint64)
+        capi.check(self.lib, self.lib.troyhip_host_ckks_encode(ctx.h, v.ctypes.data_as(C.c_void_p), C.c_uint64(v.shape[0]), limbs, C.c_double(scale), _u64p(out)))
+        return out
+
+    def decode(self, plain, scale):
+        """plain [limbs][N] NTT form -> complex128 [N/2]"""
+        ctx = self.context
+        p = np.ascontiguousarray(plain, dtype=np.uint64)
+        out = np.zeros((ctx.N // 2, 2), dtype=np.float64)
+        capi.check(self.lib, self.lib.troyhip_host_ckks_decode(ctx.h, _u64p(p), p.shape[0], C.c_double(scale), out.ctypes.data_as(C.c_void_p)))
+        return out[:, 0] + 1j * out[:, 1]
+
+    def encodeBatch(self, values, scale, limbs=None, device=False):
+        """values [B][count] complex or real (numpy) -> uint64 [B][limbs][N] NTT form (device=True: a DeviceBuffer with shape (B, limbs, N), the
+        `plains` operand of Encryptor.encryptBatch).  A DeviceBuffer input holds [B][count][2] doubles and needs a `shape` (B, count)."""
+        ctx = self.context
+        limbs = ctx.first_limbs if limbs is None else int(limbs)
+        if isinstance(values, DeviceBuffer):
+            src, (batch, count) = values, values.shape[:2]
+        else:
+            v = self._pairs(values)
+            v = v[None] if v.ndim == 2 else v
+            batch, count = v.shape[0], v.shape[1]
+            src = DeviceBuffer.from_numpy(v.view(np.uint64)) if v.size else DeviceBuffer(1)
+        out = DeviceBuffer(max(1, batch) * max(1, limbs) * ctx.N)
+        capi.check(self.lib, self.lib.troyhip_ckks_encode(ctx.h, C.c_void_p(src.ptr), C.c_uint64(count), C.c_uint64(2 * count), limbs, C.c_double(scale),
+                                                          C.c_void_p(out.ptr), C.c_uint64(limbs * ctx.N), C.c_uint64(batch), None))
+        out.shape = (batch, limbs, ctx.N)
+        return out if device else out.to_numpy().reshape(batch, limbs, ctx.N)
+
+    def decodeBatch(self, plains, scale, device=False):
+        """plains [B][limbs][N] NTT form (numpy, or a DeviceBuffer with shape (B, limbs, N)) -> complex128 [B][N/2] (device=True: a DeviceBuffer
+        of [B][N/2][2] doubles)"""
+        ctx = self.context
+        if isinstance(plains, DeviceBuffer):
+            src, (batch, limbs) = plains, plains.shape[:2]
+        else:
+            p = np.ascontiguousarray(plains, dtype=np.uint64)
+            p = p[None] if p.ndim == 2 else p
+            batch, limbs = p.shape[0], p.shape[1]
+            src = DeviceBuffer.from_numpy(p)
+        out = DeviceBuffer(max(1, batch) * ctx.N)
+        capi.check(self.lib, self.lib.troyhip_ckks_decode(ctx.h, C.c_void_p(src.ptr), limbs, C.c_double(scale), C.c_uint64(limbs * ctx.N), C.c_void_p(out.ptr),
+                                                          C.c_uint64(ctx.N), C.c_uint64(batch), None))
+        out.shape = (batch, ctx.N // 2, 2)
+        if device:
+            return out
+        d = out.to_numpy().view(np.float64).reshape(batch, ctx.N // 2, 2)
+        return d[..., 0] + 1j * d[..., 1]

@@ -4,6 +4,7 @@
 #include "../../include/troyhip.h"
 #include "evaluator.h"
 #include "encryptor.h"
+#include "encoder.h"
 #include "kernels.h"
 #include "build_id.h"
 #include "hostcrypto.h"
@@ -24,7 +25,8 @@ struct troyhip_context {
     Context ctx;
     Evaluator ev;
     DeviceEncryptor enc;
-    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true) : ctx(scheme, N, q, t, device), ev(ctx), enc(ctx, ev) {}
+    DeviceEncoder encd;
+    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true) : ctx(scheme, N, q, t, device), ev(ctx), enc(ctx, ev), encd(ctx) {}
 };
 
 namespace {
@@ -602,6 +604,18 @@ int troyhip_host_batch_encode(const troyhip_context *ctx, const uint64_t *values
 int troyhip_host_batch_decode(const troyhip_context *ctx, const uint64_t *plain, uint64_t n_coeffs, uint64_t *values_out) {
     return guard([&] { hostcrypto::batch_decode(need(ctx)->ctx, plain, n_coeffs, values_out); }, false);
 }
+int troyhip_host_ckks_encode(const troyhip_context *ctx, const double *values, uint64_t count, int limbs, double scale, uint64_t *plain_out) {
+    return guard([&] {
+        if ((count && !values) || !plain_out) throw Error(ST_INVALID_ARGUMENT, "null buffer");
+        hostcrypto::ckks_encode(need(ctx)->ctx, values, count, limbs, scale, plain_out);
+    }, false);
+}
+int troyhip_host_ckks_decode(const troyhip_context *ctx, const uint64_t *plain, int limbs, double scale, double *values_out) {
+    return guard([&] {
+        if (!plain || !values_out) throw Error(ST_INVALID_ARGUMENT, "null buffer");
+        hostcrypto::ckks_decode(need(ctx)->ctx, plain, limbs, scale, values_out);
+    }, false);
+}
 
 // ---- device encryption (encryptor.cpp): the context's device is bound before the stream is announced
 int troyhip_encrypt(troyhip_context *ctx, const uint64_t *public_key, const uint64_t *seeds, const uint64_t *plain, uint64_t plain_coeff_count,
@@ -629,6 +643,39 @@ int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs
         troyhip_context *x = need(ctx);
         const hipStream_t s = on(stream);
         x->enc.expand_seed(a_seeds, limbs, c1_out, out_batch_stride, batch, s);
+    });
+}
+
+int troyhip_batch_encode(troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t values_stride, uint64_t *plain_out, uint64_t plain_stride,
+                         uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->encd.bfv_encode(values, count, values_stride, plain_out, plain_stride, batch, s);
+    });
+}
+int troyhip_batch_decode(troyhip_context *ctx, const uint64_t *plain, uint64_t n_coeffs, uint64_t plain_stride, uint64_t *values_out, uint64_t values_stride,
+                         uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->encd.bfv_decode(plain, n_coeffs, plain_stride, values_out, values_stride, batch, s);
+    });
+}
+int troyhip_ckks_encode(troyhip_context *ctx, const double *values, uint64_t count, uint64_t values_stride, int limbs, double scale, uint64_t *plain_out,
+                        uint64_t plain_stride, uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->encd.ckks_encode(values, count, values_stride, limbs, scale, plain_out, plain_stride, batch, s);
+    });
+}
+int troyhip_ckks_decode(troyhip_context *ctx, const uint64_t *plain, int limbs, double scale, uint64_t plain_stride, double *values_out, uint64_t values_stride,
+                        uint64_t batch, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->encd.ckks_decode(plain, limbs, scale, plain_stride, values_out, values_stride, batch, s);
     });
 }
 

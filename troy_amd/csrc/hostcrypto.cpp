@@ -9,6 +9,9 @@
 // reference's own Decryptor -- to the same plaintext.  Decryption is deterministic and bit-exact.
 // Nothing here touches the GPU; a host-only context (troyhip_context_create_host) is enough.
 #include "hostcrypto.h"
+#include "encoder_math.h"
+#include <algorithm>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -427,11 +430,6 @@ void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs
 // slot i of the 2 x (N/2) matrix sits at the bit-reversed position of the exponent 3^i (row 0) / -3^i (row 1) of the primitive 2N-th root
 // (populateMatrixRepsIndexMap, batchencoder.cpp:61-81); encode = scatter + inverse negacyclic NTT modulo t, decode = NTT + gather.  The table
 // modulo t is the reference's plainNTTTables: minimal primitive root, SEAL order (host::NttTable).
-namespace {
-struct PlainTables {
-    host::NttTable tb;
-    std::vector<uint32_t> index_map;
-};
 const PlainTables &plain_tables(const Context &c) {
     static std::mutex mu;
     static std::map<std::pair<u64, int>, std::unique_ptr<PlainTables>> cache;
@@ -444,16 +442,17 @@ const PlainTables &plain_tables(const Context &c) {
         slot->tb.build(c.logn, c.t);
         const size_t n = c.N, row = n >> 1, m = n << 1;
         slot->index_map.resize(n);
+        slot->slot_of.resize(n);
         u64 pos = 1;
         for (size_t i = 0; i < row; i++) {
             slot->index_map[i] = host::reverse_bits((uint32_t)((pos - 1) >> 1), c.logn);
             slot->index_map[row | i] = host::reverse_bits((uint32_t)((m - pos - 1) >> 1), c.logn);
             pos = (pos * 3) & (m - 1);
         }
+        for (size_t i = 0; i < n; i++) slot->slot_of[slot->index_map[i]] = (uint32_t)i;
     }
     return *slot;
 }
-} // namespace
 void batch_encode(const Context &c, const u64 *values, size_t count, u64 *plain) {
     const PlainTables &pt = plain_tables(c);
     if (count > c.N) throw Error(ST_INVALID_ARGUMENT, "values_matrix size is too large");
@@ -469,6 +468,150 @@ void batch_decode(const Context &c, const u64 *plain, size_t n_coeffs, u64 *valu
     for (size_t i = 0; i < n_coeffs && i < c.N; i++) tmp[i] = plain[i];
     ntt_forward(tmp.data(), pt.tb);
     for (size_t i = 0; i < c.N; i++) values[i] = tmp[pt.index_map[i]];
+}
+
+// ------------------------------------------------------------------ CKKSEncoder (include/troyn.hpp encode / decode)
+// The host restatement of the header's slot encoder: the same FFT stage order, the same per-element operations (encoder_math.h) and the host NTT
+// tables -- so it runs on a host-only context, and the device forms (encoder.cpp) are checked against it byte for byte.
+const CkksTables &ckks_tables(const Context &c) {
+    static std::mutex mu;
+    static std::map<int, std::unique_ptr<CkksTables>> cache;
+    std::lock_guard<std::mutex> g(mu);
+    auto &slot = cache[c.logn];
+    if (!slot) {
+        slot.reset(new CkksTables);
+        const size_t n = c.N, row = n >> 1, m = n << 1;
+        slot->w.assign(2 * n, 0.0);
+        // root(k, n) = exp(2 pi i k / 2n), the header's expression.  glibc sincos, not cos and sin: g++ (-O1 and above) turns the header's cos / sin
+        // pair of one angle into one sincos call, and the two differ in the last ulp for a few angles (7 of the 8191 twiddles at N = 8192)
+        for (size_t k = 1; k < n; k++) {
+            const double ang = 3.14159265358979323846264338327950288 * (double)host::reverse_bits((uint32_t)k, c.logn) / (double)n;
+            ::sincos(ang, &slot->w[2 * k + 1], &slot->w[2 * k]);
+        }
+        slot->index_map.resize(n);
+        slot->slot_of.resize(n);
+        u64 pos = 1;
+        for (size_t i = 0; i < row; i++) {
+            slot->index_map[i] = host::reverse_bits((uint32_t)((pos - 1) >> 1), c.logn);
+            slot->index_map[row | i] = host::reverse_bits((uint32_t)((m - pos - 1) >> 1), c.logn);
+            pos = (pos * 3) & (m - 1);
+        }
+        for (size_t i = 0; i < n; i++) slot->slot_of[slot->index_map[i]] = (uint32_t)i;
+    }
+    return *slot;
+}
+
+CkksLevelConsts ckks_level_consts(const Context &c, int limbs) {
+    CkksLevelConsts L;
+    std::vector<u64> q(c.primes.begin(), c.primes.begin() + limbs);
+    L.total.assign(limbs, 0);
+    L.total[0] = 1;
+    for (int i = 0; i < limbs; i++) { // Q in base 2^64
+        u128 carry = 0;
+        for (int w = 0; w < limbs; w++) {
+            const u128 t = (u128)L.total[w] * q[i] + carry;
+            L.total[w] = (u64)t;
+            carry = t >> 64;
+        }
+    }
+    L.half = L.total; // upper_half_threshold = (Q + 1) >> 1, as the header forms it
+    for (int w = 0, carry = 1; w < limbs && carry; w++) carry = ++L.half[w] == 0;
+    for (int w = 0; w < limbs; w++) L.half[w] = (L.half[w] >> 1) | (w + 1 < limbs ? L.half[w + 1] << 63 : 0);
+    L.inv.assign((size_t)limbs * limbs, Shoup{0, 0});
+    for (int i = 0; i < limbs; i++)
+        for (int j = 0; j < i; j++) L.inv[(size_t)i * limbs + j] = make_shoup(host::inv_mod_checked(q[j] % q[i], q[i]), q[i]);
+    L.total_bits = host::bit_length_of_product(q);
+    return L;
+}
+
+void ckks_check_encode(const Context &c, size_t count, int limbs) {
+    if (c.scheme != SCHEME_CKKS) throw Error(ST_INVALID_ARGUMENT, "unsupported scheme");
+    if (count > c.N / 2) throw Error(ST_INVALID_ARGUMENT, "values_size is too large");
+    if (!c.has_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "parms_id is not valid for encryption parameters");
+}
+void ckks_check_decode(const Context &c, int limbs, double scale) {
+    if (c.scheme != SCHEME_CKKS) throw Error(ST_INVALID_ARGUMENT, "unsupported scheme");
+    if (!c.has_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "plain is not valid for encryption parameters");
+    std::vector<u64> q(c.primes.begin(), c.primes.begin() + limbs);
+    if (!std::isfinite(scale) || scale <= 0 || (int)std::log2(scale) >= host::bit_length_of_product(q)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+}
+const char *ckks_value_error(u64 largest_bits, int total_bits) {
+    if (largest_bits >= NONFINITE_BITS) return "encoded values are not finite";
+    // one more bit for the sign; nothing below 1.0 goes through log2 (the header's test, host std::log2)
+    const int bits = (int)std::ceil(std::log2(std::max(bits_dbl(largest_bits), 1.0))) + 1;
+    return bits >= total_bits ? "encoded values are too large" : nullptr;
+}
+
+void ckks_encode(const Context &c, const double *values, size_t count, int limbs, double scale, u64 *plain) {
+    TROY_NO_CONTRACT
+    ckks_check_encode(c, count, limbs);
+    const CkksTables &T = ckks_tables(c);
+    const size_t n = c.N, slots = n >> 1;
+    std::vector<Cplx> a(n, Cplx{0.0, 0.0});
+    for (size_t i = 0; i < count; i++) {
+        const Cplx v{values[2 * i], values[2 * i + 1]};
+        a[T.index_map[i]] = v;
+        a[T.index_map[i + slots]] = cconj(v);
+    }
+    for (size_t m = n >> 1, t = 1; m >= 1; m >>= 1, t <<= 1)
+        for (size_t i = 0; i < m; i++) {
+            const Cplx w = cconj(Cplx{T.w[2 * (m + i)], T.w[2 * (m + i) + 1]});
+            for (size_t j = 2 * i * t; j < 2 * i * t + t; j++) {
+                const Cplx x = a[j], y = a[j + t];
+                a[j] = cadd(x, y);
+                a[j + t] = cmul(csub(x, y), w);
+            }
+        }
+    std::vector<double> scaled(n);
+    u64 largest = 0;
+    for (size_t i = 0; i < n; i++) {
+        scaled[i] = ckks_scaled(a[i].re, 1.0 / (double)n, scale);
+        largest = std::max(largest, dbl_bits(std::fabs(scaled[i])));
+    }
+    std::vector<u64> q(c.primes.begin(), c.primes.begin() + limbs);
+    if (const char *e = ckks_value_error(largest, host::bit_length_of_product(q))) throw Error(ST_INVALID_ARGUMENT, e);
+    for (size_t i = 0; i < n; i++) {
+        u64 mant;
+        int shift;
+        bool negative;
+        ckks_split(std::round(scaled[i]), mant, shift, negative);
+        for (int j = 0; j < limbs; j++) plain[(size_t)j * n + i] = ckks_residue(mant, shift, negative, make_mod(q[j]));
+    }
+    for (int j = 0; j < limbs; j++) ntt_forward(plain + (size_t)j * n, c.tables[j]);
+}
+
+void ckks_decode(const Context &c, const u64 *plain, int limbs, double scale, double *values) {
+    TROY_NO_CONTRACT
+    ckks_check_decode(c, limbs, scale);
+    const CkksTables &T = ckks_tables(c);
+    const size_t n = c.N, slots = n >> 1;
+    std::vector<u64> rns(plain, plain + (size_t)limbs * n);
+    for (int j = 0; j < limbs; j++) ntt_inverse(rns.data() + (size_t)j * n, c.tables[j]);
+    const CkksLevelConsts L = ckks_level_consts(c, limbs);
+    std::vector<Mod> mods;
+    for (int j = 0; j < limbs; j++) mods.push_back(make_mod(c.primes[j]));
+    std::vector<u64> digit(limbs), word(limbs);
+    const double inv_scale = 1.0 / scale;
+    std::vector<Cplx> a(n);
+    for (size_t k = 0; k < n; k++) {
+        const double x = ckks_compose(
+            limbs, [&](int i) { return rns[(size_t)i * n + k]; }, [&](int i) -> u64 & { return digit[i]; }, [&](int i) -> u64 & { return word[i]; },
+            L.inv.data(), mods.data(), L.total.data(), L.half.data(), inv_scale);
+        a[k] = Cplx{x, 0.0};
+    }
+    for (size_t m = 1, t = n >> 1; m < n; m <<= 1, t >>= 1)
+        for (size_t i = 0; i < m; i++) {
+            const Cplx w{T.w[2 * (m + i)], T.w[2 * (m + i) + 1]};
+            for (size_t j = 2 * i * t; j < 2 * i * t + t; j++) {
+                const Cplx u = a[j], v = cmul(a[j + t], w);
+                a[j] = cadd(u, v);
+                a[j + t] = csub(u, v);
+            }
+        }
+    for (size_t i = 0; i < slots; i++) {
+        values[2 * i] = a[T.index_map[i]].re;
+        values[2 * i + 1] = a[T.index_map[i]].im;
+    }
 }
 
 } // namespace hostcrypto

@@ -36,6 +36,37 @@ void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs
 // BatchEncoder (src/batchencoder.cpp:61-190): `count` <= N slot values modulo t <-> the plaintext polynomial [N] (coefficient form)
 void batch_encode(const Context &c, const u64 *values, size_t count, u64 *plain);
 void batch_decode(const Context &c, const u64 *plain, size_t n_coeffs, u64 *values);
+// the tables of batch_encode / _decode: index_map[slot] = coefficient position, slot_of = its inverse.  Throws what the encoder throws for a context
+// without batching (ST_LOGIC_ERROR "batching is not enabled ...") or a CKKS context
+struct PlainTables {
+    host::NttTable tb;
+    std::vector<uint32_t> index_map, slot_of;
+};
+const PlainTables &plain_tables(const Context &c);
+
+// CKKSEncoder::encode / decode of include/troyn.hpp (N/2 complex slots, the canonical embedding), restated on the host with the host NTT tables.
+// values: [count][2] (re, im), count <= N/2;  plain: [limbs][N] NTT form at the level of `limbs` primes;  decode writes [N/2][2].
+void ckks_encode(const Context &c, const double *values, size_t count, int limbs, double scale, u64 *plain);
+void ckks_decode(const Context &c, const u64 *plain, int limbs, double scale, double *values);
+// what both forms share: the FFT twiddles w[k] = root(bitrev(k), n) = (cos, sin)(pi bitrev(k) / n) for k in [1, n), glibc sincos of the header's
+// expression on the host; index_map[slot] / slot_of[position] as BatchEncoder's (2N-th roots, n = N);  the level's decode constants
+struct CkksTables {
+    std::vector<double> w; // [n][2]
+    std::vector<uint32_t> index_map, slot_of;
+};
+const CkksTables &ckks_tables(const Context &c);
+struct CkksLevelConsts {
+    std::vector<u64> total, half; // Q and (Q + 1) >> 1, base 2^64, `limbs` words
+    std::vector<Shoup> inv;        // [limbs][limbs]: inv[i][j] = q_j^-1 mod q_i (j < i), Shoup operands
+    int total_bits = 0;
+};
+CkksLevelConsts ckks_level_consts(const Context &c, int limbs);
+// the argument checks of the two forms (the header's messages); the device forms run the same ones
+void ckks_check_encode(const Context &c, size_t count, int limbs);
+void ckks_check_decode(const Context &c, int limbs, double scale);
+// "encoded values are too large": the header's test on the largest |value * scale| of one item, given as its bit pattern (NONFINITE_BITS and
+// above: an infinity or a NaN, refused with its own message).  Returns nullptr when the item passes.
+const char *ckks_value_error(u64 largest_bits, int total_bits);
 
 } // namespace hostcrypto
 } // namespace troyhip

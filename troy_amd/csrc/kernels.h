@@ -285,4 +285,30 @@ void launch_behz_extend(const u64 *in, u64 in_pstride, u64 *out, u64 out_pstride
 void launch_behz_floor_sk(const u64 *dq, u64 dq_pstride, const u64 *db, u64 db_pstride, u64 *out, u64 out_pstride, const PrimeDesc *primes, const BehzDev &c, u64 N,
                           u64 polys, hipStream_t s);
 
+// ---- encoder.hip: BatchEncoder / CKKSEncoder, `batch` items per launch (encoder.cpp) ----
+// BFV / BGV: plain[b][pos] = values[b][slot_of[pos]] mod t (0 past `count`);  decode: the first n_coeffs words of an item, zero-extended to N,
+// into a contiguous [batch][N];  gather: values[b][i] = ntt[b][index_map[i]]
+void launch_bfv_encode_scatter(const u64 *values, u64 count, u64 vstride, u64 *plain, u64 pstride, const uint32_t *slot_of, const Mod &t, int logn, u64 batch,
+                               hipStream_t s);
+void launch_bfv_decode_load(const u64 *plain, u64 n_coeffs, u64 pstride, u64 *out, int logn, u64 batch, hipStream_t s);
+void launch_bfv_decode_gather(const u64 *ntt, u64 *values, u64 vstride, const uint32_t *index_map, int logn, u64 batch, hipStream_t s);
+struct Cplx; // encoder_math.h
+// CKKS encode up to the forward NTT: values [b][count][2] -> plain [b][limbs][N] coefficient-form residues, maxbits[b] = max |value * scale| of item b
+// as a bit pattern (encoder_math.h).  A: scratch [batch][N] complex;  partial: scratch [batch][nparts], nparts = ckks_encode_parts(logn)
+struct CkksEncArgs {
+    const double *values; u64 count, vstride;
+    u64 *plain; u64 pstride; int limbs; const Mod *mods;
+    const uint32_t *slot_of; const double *w; int logn; double inv_n, scale;
+    Cplx *A; u64 *partial; unsigned nparts; u64 *maxbits; u64 batch;
+};
+unsigned ckks_encode_parts(int logn);
+void launch_ckks_encode(const CkksEncArgs &a, hipStream_t s);
+// CKKS decode after the inverse NTT: R [batch][limbs][N] coefficient form -> values [b][N/2][2].  inv [limbs][limbs] Shoup, total / half [limbs]
+struct CkksDecArgs {
+    const u64 *R; int limbs; const Mod *mods; const Shoup *inv; const u64 *total, *half; double inv_scale;
+    const uint32_t *slot_of; const double *w; int logn;
+    Cplx *A; double *values; u64 vstride; u64 batch;
+};
+void launch_ckks_decode(const CkksDecArgs &a, hipStream_t s);
+
 } // namespace troyhip
