@@ -148,7 +148,7 @@ def main():
     ap.add_argument("src")
     ap.add_argument("--kernel", default="", help="only kernels whose demangled name contains this")
     ap.add_argument("--loops", action="store_true", help="per-loop breakdown")
-    ap.add_argument("--flags", default="", help="extra hipcc flags, e.g. -DN2_MAC_WAVES=3")
+    ap.add_argument("--flags", default="", help="extra hipcc flags, e.g. -DTROYHIP_PROBES")
     a = ap.parse_args()
     path = a.src
     if not path.endswith(".s"):

@@ -16,8 +16,6 @@ build() { # name flags...
 for v in "$@"; do
     case $v in
         base) build base ;;
-        exp*) build $v -DN2_EXP=${v#exp} ;;
-        w*) build $v -DN2_MIN_WAVES=${v#w} ;;
         *:*) build ${v%%:*} ${v#*:} ;;   # name:-Dflag -Dflag
     esac
 done

@@ -24,13 +24,6 @@ namespace troyhip {
 
 #define B2_THREADS 256
 #define B2_TILE 64
-#ifndef B2_TPW
-#define B2_TPW 8 // tiles of 64 coefficients per workgroup
-#endif
-// probe hooks for throw-away builds (tools/behz_probe.sh): bit0 no HBM loads, bit1 no MFMA, bit2 no recombine/reduce, bit4 no stores
-#ifndef B2_EXP
-#define B2_EXP 0
-#endif
 
 #ifdef TROYHIP_CPU_EMUL
 #define B2_UNIFORM(x) (x)
@@ -55,12 +48,6 @@ __device__ __forceinline__ void b2_zero(MfmaAcc &a) {
 #pragma unroll
     for (int r = 0; r < 16; r++) a.v[r] = 0;
 }
-#define B2_MFMA(fa, fb, fc)                                                                                               \
-    do {                                                                                                                 \
-        if (B2_EXP & 2) (fc).v[0] += (fb).bytes[0] + (fa).bytes[0];                                                      \
-        else TROY_MFMA_I8(fa, fb, fc);                                                                                   \
-    } while (0)
-#define B2_LOAD(expr, fake) ((B2_EXP & 1) ? (u64)(fake) : (expr))
 
 // V = lo + top 2^64 (top < 2^16): the biased sum of one output
 struct B2Sum { u64 lo; u32 top; };
@@ -94,7 +81,6 @@ __device__ __forceinline__ u64 b2_reduce_slow(const B2Sum v, const B2Slow &k) {
     return s >= k.p ? s - k.p : s;
 }
 template <int BASE> __device__ __forceinline__ u64 b2_finish(const MfmaAcc &acc, u64 addend, const BehzK2 &k) {
-    if (B2_EXP & 4) return (u64)(u32)acc.v[BASE] ^ addend ^ ((u64)(u32)acc.v[BASE + 7] << 32);
     return b2_reduce(b2_recombine<BASE>(acc, addend, k.bias1), k);
 }
 
@@ -162,7 +148,7 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
 #pragma unroll
         for (int i = 0; i < KB; i++) {
             const u32 l = (u32)(w + 4 * i);
-            xr[i] = B2_LOAD(buf_load_u64(rin, (l < (u32)c.L && n < n32) ? (l * n32 + n) * 8u : TROY_BUF_OOB), (lane + n) * 0x9E3779B97F4Aull + l);
+            xr[i] = buf_load_u64(rin, (l < (u32)c.L && n < n32) ? (l * n32 + n) * 8u : TROY_BUF_OOB);
         }
     };
     fetch(0);
@@ -191,7 +177,7 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
             MfmaAcc acc;
             b2_zero(acc);
 #pragma unroll
-            for (int kb = 0; kb < KB; kb++) B2_MFMA(am[kb], bf[kb], acc);
+            for (int kb = 0; kb < KB; kb++) TROY_MFMA_I8(am[kb], bf[kb], acc);
             const u32 rsum = (u32)acc.v[0] + ((u32)acc.v[1] << 8) + ((u32)acc.v[2] << 16) + ((u32)acc.v[3] << 24);
             const u64 r_mt = ((u64)rsum * c.neg_inv_q_mod_mt) & 0xFFFFFFFFull;
             // centred representative of r (rns.cpp:966-975) as one more input: out = (sum + r q) m_tilde^-1
@@ -200,14 +186,14 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
             if (owner) {
                 b2_zero(acc);
 #pragma unroll
-                for (int kb = 0; kb < KB; kb++) B2_MFMA(af[kb], bf[kb], acc);
+                for (int kb = 0; kb < KB; kb++) TROY_MFMA_I8(af[kb], bf[kb], acc);
                 r[0] = b2_finish<0>(acc, k2[0].biaslo, k2[0]);
                 r[1] = b2_finish<8>(acc, k2[1].biaslo, k2[1]);
             }
 #pragma unroll
             for (int j = 0; j < 2; j++) { // the same number of stores on every path keeps the outstanding-store count a constant
                 const u32 o = 4 * (u32)w + 2 * j + half;
-                const bool live = (B2_EXP & 16) ? r[j] == ~0ull : (owner && o < (u32)c.nBsk && n0 + cc < n32);
+                const bool live = owner && o < (u32)c.nBsk && n0 + cc < n32;
                 buf_store_u64(rout, live ? (o * n32 + n0 + cc) * 8u : TROY_BUF_OOB, r[j]);
             }
         }
@@ -267,7 +253,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
 #pragma unroll
         for (int i = 0; i < KB1; i++) {
             const u32 l = (u32)(w + 4 * i);
-            xr[i] = B2_LOAD(buf_load_u64(rq, (l < (u32)c.L && n < n32) ? (l * n32 + n) * 8u : TROY_BUF_OOB), (lane + n) * 0x9E3779B97F4Aull + l);
+            xr[i] = buf_load_u64(rq, (l < (u32)c.L && n < n32) ? (l * n32 + n) * 8u : TROY_BUF_OOB);
         }
 #pragma unroll
         for (int sub = 0; sub < 2; sub++)
@@ -275,7 +261,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
             for (int j = 0; j < 2; j++) {
                 const u32 o = 4 * (u32)w + 2 * j + half;
                 const u32 m = t0 + sub * 32 + cl;
-                dbn[sub][j] = B2_LOAD(buf_load_u64(rb, (o < (u32)c.nBsk && m < n32) ? (o * n32 + m) * 8u : TROY_BUF_OOB), (lane + m) * 0x9E3779B97F4Aull + o);
+                dbn[sub][j] = buf_load_u64(rb, (o < (u32)c.nBsk && m < n32) ? (o * n32 + m) * 8u : TROY_BUF_OOB);
             }
     };
     fetch(0);
@@ -301,7 +287,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
                 MfmaAcc acc;
                 b2_zero(acc);
 #pragma unroll
-                for (int kb = 0; kb < KB1; kb++) B2_MFMA(af1[kb], b2_frag(ydig, (size_t)(2 * kb + half) * B2_TILE + cc), acc);
+                for (int kb = 0; kb < KB1; kb++) TROY_MFMA_I8(af1[kb], b2_frag(ydig, (size_t)(2 * kb + half) * B2_TILE + cc), acc);
                 const u64 r0 = b2_finish<0>(acc, k1[0].biaslo + dbv[sub][0], k1[0]);
                 const u64 r1 = b2_finish<8>(acc, k1[1].biaslo + dbv[sub][1], k1[1]);
 #pragma unroll
@@ -324,7 +310,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
             MfmaAcc acc;
             b2_zero(acc);
 #pragma unroll
-            for (int kb = 0; kb < KB2; kb++) B2_MFMA(amsk[kb], bf[kb], acc);
+            for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(amsk[kb], bf[kb], acc);
             // alpha = (conv_{B->m_sk}(z) - z_sk) B^-1 mod m_sk; above m_sk / 2 it stands for a negative value (rns.cpp:905-930)
             const u64 conv = b2_finish<0>(acc, msk.biaslo, msk);
             const u64 z = zsk[cc];
@@ -335,7 +321,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
             if (owner2) {
                 b2_zero(acc);
 #pragma unroll
-                for (int kb = 0; kb < KB2; kb++) B2_MFMA(af2[kb], bf[kb], acc);
+                for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(af2[kb], bf[kb], acc);
                 if (FAST2) {
                     r[0] = b2_finish<0>(acc, k2[0].biaslo, k2[0]);
                     r[1] = b2_finish<8>(acc, k2[1].biaslo, k2[1]);
@@ -347,7 +333,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const u32 l = 4 * (u32)w + 2 * j + half;
-                const bool live = (B2_EXP & 16) ? r[j] == ~0ull : (owner2 && l < (u32)c.L && n0 + cc < n32);
+                const bool live = owner2 && l < (u32)c.L && n0 + cc < n32;
                 buf_store_u64(rout, live ? (l * n32 + n0 + cc) * 8u : TROY_BUF_OOB, r[j]);
             }
         }
@@ -427,7 +413,7 @@ template <int KB, int RB> __global__ __launch_bounds__(B2_THREADS) void behz2s_e
         MfmaAcc acc;
         b2_zero(acc);
 #pragma unroll
-        for (int kb = 0; kb < KB; kb++) B2_MFMA(am[kb], bf[kb], acc);
+        for (int kb = 0; kb < KB; kb++) TROY_MFMA_I8(am[kb], bf[kb], acc);
         const u32 rsum = (u32)acc.v[0] + ((u32)acc.v[1] << 8) + ((u32)acc.v[2] << 16) + ((u32)acc.v[3] << 24);
         const u64 r_mt = ((u64)rsum * c.neg_inv_q_mod_mt) & 0xFFFFFFFFull;
         b2_patch(bf[KB - 1], where, b2_digits((u64)((long long)r_mt - (long long)((r_mt >> 31) << 32))));
@@ -435,7 +421,7 @@ template <int KB, int RB> __global__ __launch_bounds__(B2_THREADS) void behz2s_e
         for (int rb = 0; rb < RB; rb++) {
             b2_zero(acc);
 #pragma unroll
-            for (int kb = 0; kb < KB; kb++) B2_MFMA(af[rb][kb], bf[kb], acc);
+            for (int kb = 0; kb < KB; kb++) TROY_MFMA_I8(af[rb][kb], bf[kb], acc);
             const u64 r0 = b2_finish<0>(acc, k2[rb][0].biaslo, k2[rb][0]), r1 = b2_finish<8>(acc, k2[rb][1].biaslo, k2[rb][1]);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -526,7 +512,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
         for (int rb = 0; rb < KB2; rb++) {
             b2_zero(acc);
 #pragma unroll
-            for (int kb = 0; kb < KB1; kb++) B2_MFMA(af1[rb][kb], bf1[kb], acc);
+            for (int kb = 0; kb < KB1; kb++) TROY_MFMA_I8(af1[rb][kb], bf1[kb], acc);
             const u64 r0 = b2_finish<0>(acc, k1[rb][0].biaslo + dbv[rb][0], k1[rb][0]), r1 = b2_finish<8>(acc, k1[rb][1].biaslo + dbv[rb][1], k1[rb][1]);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -545,7 +531,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
         // ---- stage 2
         b2_zero(acc);
 #pragma unroll
-        for (int kb = 0; kb < KB2; kb++) B2_MFMA(amsk[kb], bf2[kb], acc);
+        for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(amsk[kb], bf2[kb], acc);
         const u64 conv = b2_finish<0>(acc, msk.biaslo, msk);
         const u64 alpha = conv >= z ? conv - z : conv + msk.p - z;
         const bool neg = alpha > (msk.p >> 1);
@@ -554,7 +540,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
         for (int rb = 0; rb < KB1; rb++) {
             b2_zero(acc);
 #pragma unroll
-            for (int kb = 0; kb < KB2; kb++) B2_MFMA(af2[rb][kb], bf2[kb], acc);
+            for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(af2[rb][kb], bf2[kb], acc);
             u64 r0, r1;
             if (FAST2) {
                 r0 = b2_finish<0>(acc, k2[rb][0].biaslo, k2[rb][0]);
@@ -579,7 +565,8 @@ static bool behz3_enabled() {
     static const bool v = [] { const char *e = probe_env("TROYHIP_BEHZ"); return !(e && e[0] == 'm'); }();
     return v;
 }
-static unsigned b2_tiles_per_wg(u64 tiles, u64 polys) { return plan_per_workgroup(tiles, tiles >= 64 ? B2_TPW : 1, polys); }
+// tiles of 64 coefficients per workgroup: 8 where there are enough of them
+static unsigned b2_tiles_per_wg(u64 tiles, u64 polys) { return plan_per_workgroup(tiles, tiles >= 64 ? 8 : 1, polys); }
 // small-base kernels: a wave takes 32 columns per step, so the per-workgroup setup wants more steps
 static unsigned b2s_tiles_per_wg(u64 tiles, u64 polys) { // 8 / 16 / 32 / 64 at N = 8192 and a large batch: 389 / 352 / 347 / 390 us
     return plan_per_workgroup(tiles, tiles >= 64 ? 16u : (tiles >= 16 ? (unsigned)(tiles / 4) : 1u), polys);

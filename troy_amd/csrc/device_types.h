@@ -76,18 +76,15 @@ __device__ __forceinline__ u64 buf_load_u64(BufRsrc r, u32 off) {
     const troy_v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
     return (u64)v.x | ((u64)v.y << 32);
 }
-#ifndef TROY_BUF_ST_POL
-#define TROY_BUF_ST_POL 0 // probe: cache policy of the buffer stores (BEHZ kernels): 2 = non-temporal
-#endif
 __device__ __forceinline__ void buf_store_u64(BufRsrc r, u32 off, u64 v) {
     troy_v2u d;
     d.x = (u32)v;
     d.y = (u32)(v >> 32);
-    __builtin_amdgcn_raw_buffer_store_b64(d, r, (int)off, 0, TROY_BUF_ST_POL);
+    __builtin_amdgcn_raw_buffer_store_b64(d, r, (int)off, 0, 0);
 }
 #define TROY_GLDS16(gptr, lds_base)                                                                                      \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr), (__attribute__((address_space(3))) void *)(lds_base), 16, 0, 0)
-// the same with a cache-policy immediate (gfx940 encoding: 1 = sc0, 2 = nt, 16 = sc1); probes only (N1_DMA_POL, N2_DMA_POL)
+// the same with a cache-policy immediate (gfx940 encoding: 1 = sc0, 2 = nt, 16 = sc1): ntt2.hip's non-temporal row prefetch
 #define TROY_GLDS16_POL(gptr, lds_base, pol)                                                                             \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr), (__attribute__((address_space(3))) void *)(lds_base), 16, 0, pol)
 #define TROY_WAIT_VMEM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")

@@ -68,21 +68,14 @@ struct Ntt1Args {
     unsigned md_dl;
     unsigned fp_red_mask; // FP64 instances (ntt1_*_fp_kernel, fpmod.h): bit r = reduce the values before round r (forward: A, B, C1, C2; inverse:
                           // D', C', B', A', the last stage of A'); walked on the host (fp_plan / fp_plan_inv)
-    u64 *dbg;             // development builds (-DN1_TIMING): s_memtime stamps of wave 0 of workgroup dbg_block
-    unsigned dbg_block;
 };
 // wave priority by progress: a wave that is ahead of the others in a barrier-to-barrier segment lowers its own priority, so the
 // four waves of a SIMD advance together (the arbiter otherwise serves the oldest wave first and the segment ends with one wave
 // per SIMD running alone)
-#if !defined(N1_PRIO_OFF) && !defined(TROYHIP_CPU_EMUL) // forward kernels only; on since they store lane-linearly (round 4: integer forward -3 %, FP64 -1 %; before that neutral).  The same hints in the inverse kernels: FP64 +4 % SLOWER, integer neutral
+#ifndef TROYHIP_CPU_EMUL // forward kernels only; on since they store lane-linearly (round 4: integer forward -3 %, FP64 -1 %; before that neutral).  The same hints in the inverse kernels: FP64 +4 % SLOWER, integer neutral
 #define N1_PRIO(k) __builtin_amdgcn_s_setprio(k)
 #else
 #define N1_PRIO(k)
-#endif
-#ifdef N1_TIMING
-#define N1_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && blockIdx.x == a.dbg_block) a.dbg[(i) + 16 * (mm - m_begin)] = clock64(); } while (0)
-#else
-#define N1_STAMP(i)
 #endif
 
 // position of element j (0..1023) of a sub-block inside its 8 KiB LDS region.  Involution; keeps bit 0 (16-byte pairs stay
@@ -94,48 +87,18 @@ __device__ __forceinline__ unsigned sw1(unsigned j) { return j ^ (((j >> 6) & 7u
 // SQ_LDS_BANK_CONFLICT = 34 % of the inverse kernel's LDS cycles in round 2, 0 in the forward kernel, which only reads that pattern).  One more
 // term -- bit 2 ^= bit 4 -- separates them and keeps every other pattern conflict-free (tools/lds_banks.py); it is no involution any more
 // (bit 4 is both a source and a target), so the LDS-DMA staging, which needs "which element belongs at position x", uses sw2_inv.
-#ifndef N1_FP_FENCE_B
-#define N1_FP_FENCE_B 2 // FP64 forward kernel, round B (16 values in registers next to the waiting half): butterflies in flight between scheduling fences
-#endif
-#ifndef N1_FWD_STORE_VIA_LDS
-#define N1_FWD_STORE_VIA_LDS 1 // 0 (probe): the forward kernels store each thread's eight consecutive results directly
-#endif
-#ifndef N1_CR_LINEAR
-#define N1_CR_LINEAR 1 // 0 (probe): the divide-and-round epilogue on a thread's eight consecutive coefficients (16-byte loads every 64 bytes)
-#endif
-#ifndef N1_FWD_STORE_UNROLL
-#define N1_FWD_STORE_UNROLL 2
-#endif
-#ifndef N1_FP_ODD_EARLY
-#define N1_FP_ODD_EARLY 0 // 1 (probe): the odd half of a row is converted up front, as before round 4
-#endif
-#ifndef N1_INV_SWZ
-#define N1_INV_SWZ 2
-#endif
-#ifndef N1_INV_EXP
-#define N1_INV_EXP 0 // removal probes of the N = 2^15 inverse body (wrong results; tools/ntt_probe.sh name:-DN1_INV_EXP=k): 1 no global reads, 2 no global writes, 4 no workgroup barriers
-#endif
-#ifndef N1_DMA_POL
-#define N1_DMA_POL 0 // probe: cache policy of the inverse kernels' LDS-DMA staged half (2 = non-temporal)
-#endif
-#ifndef N1_NT_INV
-#define N1_NT_INV 0 // non-temporal stores in the INTEGER N = 2^15 inverse kernels: bit 0 the plain rows, bit 1 the mod-down epilogue's
-#endif
+__device__ __forceinline__ unsigned sw2(unsigned j) { return sw1(j) ^ (((j >> 4) & 1u) << 2); }
+__device__ __forceinline__ unsigned sw2_inv(unsigned x) { // bits 5.. are untouched by sw2: undo bit 4 first, then the term it feeds
+    const unsigned y = sw1(x);
+    return y ^ (((y >> 4) & 1u) << 2);
+}
 // workgroup -> unit of the slot-major list (slot, chunk).  The hardware deals consecutive workgroups to the 8 XCDs in turn; with the flat mapping every XCD
 // therefore works on every prime in flight (2-4 at a time: each a 1 MiB twiddle table competing for that XCD's 4 MiB of L2 with the rows streaming through).
 // XCD-aware: XCD x walks its own contiguous eighth of the list, one prime at a time.
-#ifndef N1_XCD
-#define N1_XCD 1
-#endif
 // xcd_group > 1 (the forms whose rows of DIFFERENT primes read one shared row: the special limb of a mod-down, the dropped limb of a divide-and-round): the
 // list is ordered (group of xcd_group primes, chunk, prime within the group), so the workgroups an XCD starts back to back are the same rows under
-// xcd_group primes and the shared row is fetched into that L2 once for all of them -- at the price of xcd_group twiddle tables in it.
-#ifndef N1_XCD_GROUP_FP
-#define N1_XCD_GROUP_FP 4
-#endif
-#ifndef N1_XCD_GROUP_INT
-#define N1_XCD_GROUP_INT 4
-#endif
+// xcd_group primes and the shared row is fetched into that L2 once for all of them -- at the price of xcd_group twiddle tables in it.  4, for the
+// integer and the FP64 kernels alike (launch_ntt1).
 __device__ __forceinline__ bool n1_unit(const Ntt1Args &a, unsigned &sidx, unsigned &chunk) {
     unsigned q = blockIdx.x;
     if (a.xcd_per) {
@@ -161,31 +124,6 @@ __device__ __forceinline__ bool n1_unit(const Ntt1Args &a, unsigned &sidx, unsig
     }
     return true;
 }
-#ifndef N1_STAGGER
-#define N1_STAGGER 0 // probe: the workgroups of a launch's first round start N1_STAGGER x 3.9 us x ((blockIdx / 8) % 8) late -- are the CUs of an XCD phase-aligned (bursty traffic)?
-#endif
-__device__ __forceinline__ void n1_stagger() {
-#if N1_STAGGER && !defined(TROYHIP_CPU_EMUL)
-    if (blockIdx.x < 256) {
-        const unsigned ph = (blockIdx.x >> 3) & 7;
-        for (unsigned i = 0; i < ph * N1_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
-}
-#ifndef N1_INV_TOP
-#define N1_INV_TOP 0 // where an inverse row waits for its LDS-DMA staged half: 0 at the top of the row (after requesting the second half); probes, all measured
-#endif               // NEUTRAL in round 5 (profiles/r05_inv_probes.txt): 1 drain then request, 2 request then vmcnt(8), 3 wait BEFORE the previous row's stores
-
-__device__ __forceinline__ unsigned sw2(unsigned j) { return N1_INV_SWZ == 2 ? sw1(j) ^ (((j >> 4) & 1u) << 2) : sw1(j); }
-#ifndef N1_FWD_WB_SW1
-#define N1_FWD_WB_SW1 0 // 1 (probe): the forward kernels' write-back for the lane-linear stores under sw1 (2-way conflicted 16-byte writes)
-#endif
-__device__ __forceinline__ unsigned wb_swz(unsigned j) { return N1_FWD_WB_SW1 ? sw1(j) : sw2(j); }
-__device__ __forceinline__ unsigned sw2_inv(unsigned x) { // bits 5.. are untouched by sw2: undo bit 4 first, then the term it feeds
-    if (N1_INV_SWZ != 2) return sw1(x);
-    const unsigned y = sw1(x);
-    return y ^ (((y >> 4) & 1u) << 2);
-}
 
 __device__ __forceinline__ u64 *lds_at(u64 *lds_base, unsigned byte_off) { return reinterpret_cast<u64 *>(reinterpret_cast<char *>(lds_base) + byte_off); }
 
@@ -197,11 +135,7 @@ __device__ __forceinline__ Shoup ld_tw(const Shoup *base, unsigned idx) { return
 __device__ __forceinline__ Shoup ld_tw_uniform(const Shoup *p) { return *p; }
 #else
 typedef unsigned long long troy_v2ull __attribute__((ext_vector_type(2)));
-#ifndef N1_EXP_NOTW
-#define N1_EXP_NOTW 0 // removal probe (wrong results): 1 = the per-lane twiddles are made up from the index instead of loaded -- what their latency costs
-#endif
 __device__ __forceinline__ Shoup ld_tw(const Shoup *base, unsigned idx) { // base is wave-uniform (SGPR pair), idx per lane: saddr + 32-bit offset
-    if (N1_EXP_NOTW) return Shoup{(u64)idx * 0x9E3779B97F4A7C15ull >> 8, (u64)idx * 0xD1B54A32D192ED03ull};
     const troy_v2ull v = ((const __attribute__((address_space(1))) troy_v2ull *)base)[idx];
     return Shoup{v.x, v.y};
 }
@@ -212,13 +146,12 @@ __device__ __forceinline__ Shoup ld_tw_uniform(const Shoup *p) {
 #endif
 // FP64 instances, per-lane twiddles: only the double w is needed -- half the twiddle registers of the sub-block rounds; the quotient then comes from the
 // rounded product and 1 / p (fp_mulmod_pinv).  They come from the compact tables (PrimeDesc::root_w / iroot_w: 8-byte entries): one entry, or 2 / 4 consecutive ones as one / two 16-byte loads (idx a multiple of
-// 2 / 4: the groups are aligned).  Round 5: a removal probe (N1_EXP_NOTW) put the per-lane twiddle loads at 10 % of the FP64 single-pass kernels (1 % of the
+// 2 / 4: the groups are aligned).  Round 5: a removal probe (twiddles made up from the index instead of loaded) put the per-lane twiddle loads at 10 % of the FP64 single-pass kernels (1 % of the
 // integer ones, whose 15-instruction butterflies hide them): from the pair tables a thread's 4 + 2 + 1 twiddles were seven 8-byte loads at a 16-byte stride.
 __device__ __forceinline__ Shoup ld_w1(const u64 *base, unsigned idx) {
 #ifdef TROYHIP_CPU_EMUL
     return Shoup{base[idx], 0};
 #else
-    if (N1_EXP_NOTW) return Shoup{__builtin_bit_cast(u64, (double)(idx | 1u)), 0};
     return Shoup{((const __attribute__((address_space(1))) u64 *)base)[idx], 0};
 #endif
 }
@@ -226,7 +159,6 @@ __device__ __forceinline__ void ld_w2(const u64 *base, unsigned idx, Shoup (&t)[
 #ifdef TROYHIP_CPU_EMUL
     t[0] = Shoup{base[idx], 0}; t[1] = Shoup{base[idx + 1], 0};
 #else
-    if (N1_EXP_NOTW) { t[0] = ld_w1(base, idx); t[1] = ld_w1(base, idx + 1); return; }
     const troy_v2ull v = *(const __attribute__((address_space(1))) troy_v2ull *)((const __attribute__((address_space(1))) u64 *)base + idx);
     t[0] = Shoup{v.x, 0}; t[1] = Shoup{v.y, 0};
 #endif
@@ -235,7 +167,6 @@ __device__ __forceinline__ void ld_w4(const u64 *base, unsigned idx, Shoup (&t)[
 #ifdef TROYHIP_CPU_EMUL
     for (int i = 0; i < 4; i++) t[i] = Shoup{base[idx + i], 0};
 #else
-    if (N1_EXP_NOTW) { for (int i = 0; i < 4; i++) t[i] = ld_w1(base, idx + i); return; }
     const __attribute__((address_space(1))) troy_v2ull *q = (const __attribute__((address_space(1))) troy_v2ull *)((const __attribute__((address_space(1))) u64 *)base + idx);
     const troy_v2ull a = q[0], b = q[1];
     t[0] = Shoup{a.x, 0}; t[1] = Shoup{a.y, 0}; t[2] = Shoup{b.x, 0}; t[3] = Shoup{b.y, 0};
@@ -274,36 +205,17 @@ __device__ __forceinline__ unsigned uniform_u32(unsigned v) {
 // data access with a wave-uniform base and a per-lane 32-bit element offset (global_load/store ... saddr form: no 64-bit address VGPRs)
 #ifdef TROYHIP_CPU_EMUL
 __device__ __forceinline__ u64 ld_g(const u64 *base, unsigned off) { return base[off]; }
-__device__ __forceinline__ u64 ld_g_fwd(const u64 *base, unsigned off) { return base[off]; }
 __device__ __forceinline__ void st_g(u64 *base, unsigned off, u64 v) { base[off] = v; }
-template <bool NT> __device__ __forceinline__ void st_g_inv(u64 *base, unsigned off, u64 v) { base[off] = v; }
 __device__ __forceinline__ ulonglong2 ld_g2(const u64 *base, unsigned off) { return *reinterpret_cast<const ulonglong2 *>(base + off); }
 __device__ __forceinline__ void st_g2(u64 *base, unsigned off, ulonglong2 v) { *reinterpret_cast<ulonglong2 *>(base + off) = v; }
 #else
-#ifndef N1_NT
-#define N1_NT 0 // probe: non-temporal row accesses (bit 0 stores, bit 1 every row load, bit 2 the forward kernels' row loads only).  Same-box A/B
-#endif          // (profiles/r05_inv_probes.txt): standalone, stores -1.5 % on the integer inverse and loads -2 % on the forward kernel (+2 % on the inverse);
-                // inside the steps the consumers of those rows lose what L2 / MALL held for them: headline +0.4 %, 49-bit twin -0.8 %, CKKS chain +-0.5 %.  Off.
-__device__ __forceinline__ u64 ld_g(const u64 *base, unsigned off) {
-    if (N1_NT & 2) return __builtin_nontemporal_load(((const __attribute__((address_space(1))) u64 *)base) + off);
-    return ((const __attribute__((address_space(1))) u64 *)base)[off];
-}
-__device__ __forceinline__ u64 ld_g_fwd(const u64 *base, unsigned off) { // the forward kernels' row loads
-    if (N1_NT & 6) return __builtin_nontemporal_load(((const __attribute__((address_space(1))) u64 *)base) + off);
-    return ((const __attribute__((address_space(1))) u64 *)base)[off];
-}
-__device__ __forceinline__ void st_g(u64 *base, unsigned off, u64 v) {
-    if (N1_NT & 1) { __builtin_nontemporal_store(v, ((__attribute__((address_space(1))) u64 *)base) + off); return; }
-    ((__attribute__((address_space(1))) u64 *)base)[off] = v;
-}
-// the stores of the N = 2^15 inverse kernels; NT: streamed past L2's replacement order (N1_NT_INV below)
-template <bool NT> __device__ __forceinline__ void st_g_inv(u64 *base, unsigned off, u64 v) {
-    if (NT || (N1_NT & 1)) { __builtin_nontemporal_store(v, ((__attribute__((address_space(1))) u64 *)base) + off); return; }
-    ((__attribute__((address_space(1))) u64 *)base)[off] = v;
-}
+// (non-temporal row accesses, same-box A/B, profiles/r05_inv_probes.txt: standalone, stores -1.5 % on the integer inverse and loads -2 % on the forward
+// kernel (+2 % on the inverse); inside the steps the consumers of those rows lose what L2 / MALL held for them: headline +0.4 %, 49-bit twin -0.8 %,
+// CKKS chain +-0.5 %.  Not used.)
+__device__ __forceinline__ u64 ld_g(const u64 *base, unsigned off) { return ((const __attribute__((address_space(1))) u64 *)base)[off]; }
+__device__ __forceinline__ void st_g(u64 *base, unsigned off, u64 v) { ((__attribute__((address_space(1))) u64 *)base)[off] = v; }
 __device__ __forceinline__ ulonglong2 ld_g2(const u64 *base, unsigned off) { // off even: 16 bytes
-    const troy_v2ull v = (N1_NT & 2) ? __builtin_nontemporal_load((const __attribute__((address_space(1))) troy_v2ull *)(((const __attribute__((address_space(1))) u64 *)base) + off))
-                                     : *(const __attribute__((address_space(1))) troy_v2ull *)(((const __attribute__((address_space(1))) u64 *)base) + off);
+    const troy_v2ull v = *(const __attribute__((address_space(1))) troy_v2ull *)(((const __attribute__((address_space(1))) u64 *)base) + off);
     ulonglong2 r;
     r.x = v.x;
     r.y = v.y;
@@ -313,7 +225,6 @@ __device__ __forceinline__ void st_g2(u64 *base, unsigned off, ulonglong2 v) {
     troy_v2ull w;
     w.x = v.x;
     w.y = v.y;
-    if (N1_NT & 1) { __builtin_nontemporal_store(w, (__attribute__((address_space(1))) troy_v2ull *)(((__attribute__((address_space(1))) u64 *)base) + off)); return; }
     *(__attribute__((address_space(1))) troy_v2ull *)(((__attribute__((address_space(1))) u64 *)base) + off) = w;
 }
 #endif
@@ -487,10 +398,10 @@ template <int NV> __device__ __forceinline__ void fp_reduce_all(u64 (&y)[NV], co
 // ntt1s_*_body shift every stage number down, the code is the same: a sub-block is 1024 coefficients at every size)
 // LDS addresses: one per-lane byte offset per round, a literal XOR per access (sw1 and sw2 are linear over GF(2): see inv_subblock)
 template <int LOGN, bool LEAN, bool CR, bool FP> __device__ __forceinline__ void fwd_subblock(u64 *lds_base, const unsigned region_words, const unsigned sb, const unsigned lane_in, const PrimeDesc &pd, const PrimeConst &pc, const Mod &m,
-                                                                  u64 *out, const Ntt1Args &a, const unsigned mm, const unsigned m_begin, const int stamp0, const bool hf_last,
+                                                                  u64 *out, const Ntt1Args &a, const bool hf_last,
                                                                   const FpPrime &fc, const u64 *cr_in = nullptr, const Shoup cr_inv = Shoup{0, 0},
                                                                   const u64 *cr_acc = nullptr) {
-    (void)a; (void)mm; (void)m_begin; (void)stamp0; (void)hf_last; (void)fc;
+    (void)a; (void)hf_last; (void)fc;
     constexpr unsigned A = 1u << (LOGN - 10); // blocks of the first sub-block stage per sub-block row: root index of stage s = 2^s + block
     const unsigned lane = opaque(lane_in);
     const unsigned rb = 8 * region_words;
@@ -502,14 +413,14 @@ template <int LOGN, bool LEAN, bool CR, bool FP> __device__ __forceinline__ void
         for (int r = 0; r < 16; r++) y[r] = *lds_at(lds_base, wb ^ (8 * sw1(64 * r)));
         if constexpr (FP) {
             if (a.fp_red_mask & 2u) fp_reduce_all<16>(y, fc);
-            fp_fwd_stages<1, 4, false, N1_FP_FENCE_B>(y, [&](int st, int, int blk) { return ld_tw_uniform(pd.root + (A << st) + (sb << st) + blk); }, fc);
+            // 16 values in registers next to the waiting half: two butterflies in flight between scheduling fences
+            fp_fwd_stages<1, 4, false, 2>(y, [&](int st, int, int blk) { return ld_tw_uniform(pd.root + (A << st) + (sb << st) + blk); }, fc);
         } else
         fwd_stages<1, 4, LEAN, true>(y, [&](int st, int, int blk) { return ld_tw_uniform(pd.root + (A << st) + (sb << st) + blk); }, pc);
 #pragma unroll
         for (int r = 0; r < 16; r++) *lds_at(lds_base, wb ^ (8 * sw1(64 * r))) = y[r];
     }
     TROY_WAVE_SYNC();
-    N1_STAMP(stamp0);
     N1_SCHED_FENCE(); // the twiddle loads below stay below: hoisted over round B they would not fit the register budget (the FP64 instances, whose seven
                       // twiddles are single doubles, were tried with them in front of round B at N <= 2^14, where they fit: no measurable change)
     N1_PRIO(2);
@@ -545,7 +456,6 @@ template <int LOGN, bool LEAN, bool CR, bool FP> __device__ __forceinline__ void
         }
     }
     TROY_WAVE_SYNC();
-    N1_STAMP(stamp0 + 1);
     N1_SCHED_FENCE();
     if (hf_last) { N1_PRIO(2); } else { N1_PRIO(1); }
     // round C2: stages 12..14 on 8 consecutive coefficients, u = j9..j3 = lane + 64 iteration
@@ -565,7 +475,7 @@ template <int LOGN, bool LEAN, bool CR, bool FP> __device__ __forceinline__ void
 #pragma unroll
         for (int i = 0; i < 4; i++) t14[i] = ld_tw(pd.root, 512 * A + 4 * b12 + i);
         }
-        const unsigned wr2 = rb + 8 * sw1(8 * lane) ^ (it ? 8 * sw1(512) : 0u), ww2 = rb + 8 * wb_swz(8 * lane) ^ (it ? 8 * wb_swz(512) : 0u);
+        const unsigned wr2 = rb + 8 * sw1(8 * lane) ^ (it ? 8 * sw1(512) : 0u), ww2 = rb + 8 * sw2(8 * lane) ^ (it ? 8 * sw2(512) : 0u);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(lds_at(lds_base, wr2 ^ (8 * sw1(2 * q))));
@@ -592,82 +502,51 @@ template <int LOGN, bool LEAN, bool CR, bool FP> __device__ __forceinline__ void
                 for (int i = 0; i < 4; i++) y[4 * q + i] = v[i];
             }
         }
-        if (CR && !(N1_FWD_STORE_VIA_LDS && N1_CR_LINEAR)) { // y = NTT(corr), canonical: out = (in + p - y) * inv mod p, stored or added to what is there (Ntt1Corr)
-            const Shoup iq[4] = {cr_inv, cr_inv, cr_inv, cr_inv};
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                u64 w[4], q[4], r[4];
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const ulonglong2 v = ld_g2(cr_in, 8 * u + 4 * h + 2 * e);
-                    w[2 * e] = v.x + pc.p - y[4 * h + 2 * e];
-                    w[2 * e + 1] = v.y + pc.p - y[4 * h + 2 * e + 1];
-                }
-                mulhi_approx4_u(q, w, iq);
-#pragma unroll
-                for (int i = 0; i < 4; i++) r[i] = mul_acc0_u(w[i], cr_inv.op, q[i], pc.negp); // [0, 3p)
-                if (cr_acc) { // what the result is added to: the output itself, or the base polynomial of a rotation (null: nothing, start from zero)
-#pragma unroll
-                    for (int e = 0; e < 2; e++) {
-                        const ulonglong2 v = ld_g2(cr_acc, 8 * u + 4 * h + 2 * e);
-                        r[2 * e] += v.x;
-                        r[2 * e + 1] += v.y;
-                    }
-                }
-                csub4(r, pc.two_p);
-                csub4(r, pc.p);
-#pragma unroll
-                for (int i = 0; i < 4; i++) y[4 * h + i] = r[i];
-            }
-        }
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             ulonglong2 v;
             v.x = y[2 * q];
             v.y = y[2 * q + 1];
-            if (N1_FWD_STORE_VIA_LDS) *reinterpret_cast<ulonglong2 *>(lds_at(lds_base, ww2 ^ (8 * wb_swz(2 * q)))) = v; // into the eight slots it was read from (sw2: these 16-byte writes are 2-way conflicted under sw1)
-            else st_g2(out, 8 * u + 2 * q, v);
+            *reinterpret_cast<ulonglong2 *>(lds_at(lds_base, ww2 ^ (8 * sw2(2 * q)))) = v; // into the eight slots it was read from (sw2: these 16-byte writes are 2-way conflicted under sw1)
         }
     }
-    if (N1_FWD_STORE_VIA_LDS) {
-        // A thread ends with eight consecutive coefficients: stored from there, an instruction writes 16 bytes per lane every 64 bytes -- 64 partial
-        // lines, four instructions per line.  Through the wave's region (its content is dead now) the same data leaves lane-linearly: eight
-        // instructions of one contiguous KiB each.  (The inverse kernel's loads and stores are lane-linear by construction; this was the forward
-        // kernel's one scattered access.)
-        TROY_WAVE_SYNC();
-        if constexpr (CR && N1_CR_LINEAR) {
-            // the divide-and-round epilogue on the way out, in the same layout: y = NTT(corr), canonical; out = (in + p - y) * inv mod p, stored or added to
-            // what is there (Ntt1Corr) -- `in` and the accumulation target are read a contiguous KiB per instruction like the stores
-            const Shoup iq[4] = {cr_inv, cr_inv, cr_inv, cr_inv};
-            u64 *const R = lds_base + region_words;
-#pragma unroll 1
-            for (unsigned i = 0; i < 8; i += 2) {
-                const unsigned j0 = 128 * i + 2 * lane, j1 = j0 + 128;
-                const ulonglong2 ya = *reinterpret_cast<const ulonglong2 *>(R + wb_swz(j0)), yb = *reinterpret_cast<const ulonglong2 *>(R + wb_swz(j1));
-                const ulonglong2 ia = ld_g2(cr_in, j0), ib = ld_g2(cr_in, j1);
-                u64 w[4] = {ia.x + pc.p - ya.x, ia.y + pc.p - ya.y, ib.x + pc.p - yb.x, ib.y + pc.p - yb.y}, q[4], r[4];
-                mulhi_approx4_u(q, w, iq);
-#pragma unroll
-                for (int e = 0; e < 4; e++) r[e] = mul_acc0_u(w[e], cr_inv.op, q[e], pc.negp); // [0, 3p)
-                if (cr_acc) { // what the result is added to: the output itself, or the base polynomial of a rotation (null: nothing, start from zero)
-                    const ulonglong2 ca = ld_g2(cr_acc, j0), cb = ld_g2(cr_acc, j1);
-                    r[0] += ca.x; r[1] += ca.y; r[2] += cb.x; r[3] += cb.y;
-                }
-                csub4(r, pc.two_p);
-                csub4(r, pc.p);
-                st_g2(out, j0, ulonglong2{r[0], r[1]});
-                st_g2(out, j1, ulonglong2{r[2], r[3]});
-            }
-        } else {
+    // A thread ends with eight consecutive coefficients: stored from there, an instruction writes 16 bytes per lane every 64 bytes -- 64 partial
+    // lines, four instructions per line.  Through the wave's region (its content is dead now) the same data leaves lane-linearly: eight
+    // instructions of one contiguous KiB each.  (The inverse kernel's loads and stores are lane-linear by construction; this was the forward
+    // kernel's one scattered access.)
+    TROY_WAVE_SYNC();
+    if constexpr (CR) {
+        // the divide-and-round epilogue on the way out, in the same layout: y = NTT(corr), canonical; out = (in + p - y) * inv mod p, stored or added to
+        // what is there (Ntt1Corr) -- `in` and the accumulation target are read a contiguous KiB per instruction like the stores
+        const Shoup iq[4] = {cr_inv, cr_inv, cr_inv, cr_inv};
         u64 *const R = lds_base + region_words;
 #pragma unroll 1
-        for (unsigned i = 0; i < 8; i += N1_FWD_STORE_UNROLL) { // a few at a time: the waiting half of the row and the next row's prefetch hold most of the registers
+        for (unsigned i = 0; i < 8; i += 2) {
+            const unsigned j0 = 128 * i + 2 * lane, j1 = j0 + 128;
+            const ulonglong2 ya = *reinterpret_cast<const ulonglong2 *>(R + sw2(j0)), yb = *reinterpret_cast<const ulonglong2 *>(R + sw2(j1));
+            const ulonglong2 ia = ld_g2(cr_in, j0), ib = ld_g2(cr_in, j1);
+            u64 w[4] = {ia.x + pc.p - ya.x, ia.y + pc.p - ya.y, ib.x + pc.p - yb.x, ib.y + pc.p - yb.y}, q[4], r[4];
+            mulhi_approx4_u(q, w, iq);
 #pragma unroll
-            for (unsigned k = 0; k < N1_FWD_STORE_UNROLL; k++) {
-                const unsigned j = 128 * (i + k) + 2 * lane;
-                st_g2(out, j, *reinterpret_cast<const ulonglong2 *>(R + wb_swz(j)));
+            for (int e = 0; e < 4; e++) r[e] = mul_acc0_u(w[e], cr_inv.op, q[e], pc.negp); // [0, 3p)
+            if (cr_acc) { // what the result is added to: the output itself, or the base polynomial of a rotation (null: nothing, start from zero)
+                const ulonglong2 ca = ld_g2(cr_acc, j0), cb = ld_g2(cr_acc, j1);
+                r[0] += ca.x; r[1] += ca.y; r[2] += cb.x; r[3] += cb.y;
             }
+            csub4(r, pc.two_p);
+            csub4(r, pc.p);
+            st_g2(out, j0, ulonglong2{r[0], r[1]});
+            st_g2(out, j1, ulonglong2{r[2], r[3]});
         }
+    } else {
+        u64 *const R = lds_base + region_words;
+#pragma unroll 1
+        for (unsigned i = 0; i < 8; i += 2) { // two at a time: the waiting half of the row and the next row's prefetch hold most of the registers
+#pragma unroll
+            for (unsigned k = 0; k < 2; k++) {
+                const unsigned j = 128 * (i + k) + 2 * lane;
+                st_g2(out, j, *reinterpret_cast<const ulonglong2 *>(R + sw2(j)));
+            }
         }
     }
 }
@@ -704,7 +583,6 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
     const Shoup cr_inv = CR ? Shoup{((const u64 *)(a.cr_inv + slot))[0], ((const u64 *)(a.cr_inv + slot))[1]} : Shoup{0, 0};
     const u64 cr_add = CR ? pd.p - barrett64(a.cr_half, m) : 0; // p - [half]_p
     u64 *const region = lds + 1024 * wv;
-    n1_stagger();
     // registers of round A: xe[r'] = coefficient 1024 (2 r') + tid, xo[r'] = coefficient 1024 (2 r' + 1) + tid
     u64 xe[16], xo[16];
     // loads and stores of round A: ONE wave-uniform base (the limb) plus a 32-bit per-thread offset (one v_add per access; 32
@@ -712,7 +590,7 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
     auto load_half = [&](u64 (&x)[16], const u64 *rowp, unsigned odd) {
         const unsigned t = opaque(tid); // the 16 offsets are formed here, next to the loads, not carried through the kernel
 #pragma unroll
-        for (int r = 0; r < 16; r++) x[r] = ld_g_fwd(rowp, t + 2048 * r + 1024 * odd);
+        for (int r = 0; r < 16; r++) x[r] = ld_g(rowp, t + 2048 * r + 1024 * odd);
     };
     load_half(xe, in_row(m_begin), 0);
     load_half(xo, in_row(m_begin), 1);
@@ -748,18 +626,15 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
             }
         };
         prepare(xe);
-        if constexpr (!FP || N1_FP_ODD_EARLY) prepare(xo);
-        N1_STAMP(0);
+        if constexpr (!FP) prepare(xo);
         // round A: stages 0..3 on the even and on the odd registers (the odd ones were requested last), then stage 4 across
         auto twA = [&](int st, int, int blk) { return ld_tw_uniform((pd.root + (1u << st) + blk)); };
         N1_PRIO(1);
         if constexpr (FP) {
             fp_fwd_stages<1, 4>(xe, twA, fc);
-            if constexpr (!N1_FP_ODD_EARLY) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) order_after(xo[r], xe[r]);
-                prepare(xo);
-            }
+            for (int r = 0; r < 16; r++) order_after(xo[r], xe[r]);
+            prepare(xo);
             fp_fwd_stages<1, 4>(xo, twA, fc);
 #pragma unroll
             for (int r = 0; r < 16; r++) { // stage 4: (xe[r], xo[r]) with the twiddle of block r
@@ -785,12 +660,10 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
             N1_SCHED_FENCE();
         }
         }
-        N1_STAMP(1);
         // sub-block 2 r' (2 r' + 1) = xe[r'] (xo[r']) of all threads; half hf = sub-blocks 16 hf .. 16 hf + 15
 #pragma unroll
         for (int hf = 0; hf < 2; hf++) {
             if (hf == 1 || mm != m_begin) __syncthreads(); // every wave is done with the regions' previous content
-            N1_STAMP(2 + 6 * hf);
             if (hf == 1) {
 #pragma unroll
                 for (int r = 0; r < 2; r++) { xe[14 + r] = park[2048 * r]; xo[14 + r] = park[2048 * r + 1024]; }
@@ -807,7 +680,6 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
                 for (int r = 0; r < 2; r++) { park[2048 * r] = xe[14 + r]; park[2048 * r + 1024] = xo[14 + r]; }
             }
             __syncthreads();
-            N1_STAMP(3 + 6 * hf);
             if (hf == 1) {
                 if (mm + 1 < m_end) load_half(xe, in_row(mm + 1), 0); // all 32 registers are free now: request the next limb's even half
                 else {
@@ -819,13 +691,12 @@ template <bool LEAN, bool CR, bool FP> __device__ __forceinline__ void ntt1_fwd_
             }
             // (the FP64 instances compute faster than the odd half of the next row arrives; requesting it earlier -- after round B of the second half --
             // was measured twice, rounds 3 and 4: the 32 registers it holds through rounds C1 / C2 cost 36-52 B of scratch and 5 % of the kernel)
-            fwd_subblock<N1_LOGN, LEAN, CR, FP>(lds, 1024 * wv, 16 * hf + wv, lane, pd, pc, m, out + 1024 * (16 * hf + wv), a, mm, m_begin, 4 + 6 * hf, hf == 1, fc, CR ? cin + 1024 * (16 * hf + wv) : nullptr,
+            fwd_subblock<N1_LOGN, LEAN, CR, FP>(lds, 1024 * wv, 16 * hf + wv, lane, pd, pc, m, out + 1024 * (16 * hf + wv), a, hf == 1, fc, CR ? cin + 1024 * (16 * hf + wv) : nullptr,
                                        cr_inv, CR && cacc ? cacc + 1024 * (16 * hf + wv) : nullptr);
-            N1_STAMP(7 + 6 * hf);
         }
         if (mm + 1 < m_end) {
             load_half(xo, in_row(mm + 1), 1);
-            if constexpr (FP && !N1_FP_ODD_EARLY) N1_PIN_LOADS();
+            if constexpr (FP) N1_PIN_LOADS();
         } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) xo[r] = 0; // dead after the last row (see xe above)
@@ -965,17 +836,11 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
     // LDS-DMA staging of a sub-block into the wave's region, already in sw1 order: instruction i fills bytes [1024 i, 1024 i + 1024)
     // of the region lane-linearly, so lane l fetches the 16-byte unit that belongs at position 128 i + 2 l (sw1 is an involution)
     auto stage_issue = [&](const u64 *sub) {
-        if (N1_INV_EXP & 1) return;
         const unsigned l = opaque(lane);
 #pragma unroll
-        for (int i = 0; i < 8; i++) TROY_GLDS16_POL(sub + sw2_inv(128 * i + 2 * l), region + 128 * i, N1_DMA_POL);
+        for (int i = 0; i < 8; i++) TROY_GLDS16(sub + sw2_inv(128 * i + 2 * l), region + 128 * i);
     };
     auto load16 = [&](u64 (&y)[16], const u64 *sub) { // y[8 i + r] = coefficient 8 (lane + 64 i) + r
-        if (N1_INV_EXP & 1) {
-#pragma unroll
-            for (int i = 0; i < 16; i++) y[i] = (u64)(opaque(lane) + 64 * i) * 0x9E3779B97F4A7C15ull >> 7;
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -991,11 +856,7 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
         const unsigned o = mm / inner, k = mm - o * inner;
         return a.src + (u64)o * a.src_ostride + ((u64)(slot * inner + k) << N1_LOGN);
     };
-    n1_stagger();
     stage_issue(in_of(m_begin) + 1024 * wv);
-#if N1_INV_TOP == 3
-    TROY_WAIT_VMEM(); // the first row's staged half (every later row's is waited for in front of the previous row's stores, below)
-#endif
     // two base registers for the 32 exchange reads: the immediate offset of a ds_read reaches 64 KiB, so rlo + 8 KiB r and rhi + 8 KiB r need nothing else.
     // (rhi's base is made opaque: the compiler otherwise folds the 64 KiB into EIGHT per-lane addresses it keeps live across the row loop, and spills)
     const u64 *const rlo = lds + sw2(tid), *const rhi = lds_at(lds, opaque(8 * (8 * 1024 + sw2(tid))));
@@ -1003,21 +864,11 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
         u64 *const row = a.data + row_of(mm);
         u64 x[32]; // x[r] = coefficient tid of sub-block r after its 10 stages
         u64 y[16], y1[16];
-#if N1_INV_TOP == 3
-        // probe: the staged half was waited for when nothing younger than it was in flight (before the previous row's stores), so no wait here has a fresh
-        // store in front of it.  Measured neutral: what the removal probe N1_INV_EXP = 2 attributes to the stores (10 % of the integer kernel, a third of the
-        // FP64 one) is their HBM traffic, not a drain at this point.
-        load16(y1, in_of(mm) + 1024 * (16 + wv));
-#elif N1_INV_TOP == 0 || defined(TROYHIP_CPU_EMUL)
         load16(y1, in_of(mm) + 1024 * (16 + wv)); // second half's input: in flight while the first half is transformed
         TROY_WAIT_VMEM();                   // the staged first half has landed (vmcnt counts in order: this also waits for y1)
-#elif N1_INV_TOP == 1 // probe: the second half requested AFTER the wait for the staged first half -- its latency sits under the first half's ten stages
-        TROY_WAIT_VMEM();
-        load16(y1, in_of(mm) + 1024 * (16 + wv));
-#else                 // probe: requested first, but the wait leaves its eight loads in flight (reads return in order: everything older has landed)
-        load16(y1, in_of(mm) + 1024 * (16 + wv));
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#endif
+        // (where a row waits for its staged half was measured NEUTRAL in round 5, profiles/r05_inv_probes.txt: drain then request the second half,
+        // request it and leave its eight loads in flight, or wait before the previous row's stores.  A removal probe without the global writes
+        // attributes 10 % of the integer kernel, a third of the FP64 one, to the stores: their HBM traffic, not a drain at this point.)
         const unsigned ol = opaque(lane);   // recomputed per row: hoisted out of the loop these eight addresses are spilled
         const unsigned ws = 8 * 1024 * wv + 8 * sw2(8 * ol); // as round D' of inv_subblock: one per-lane offset, a literal XOR per access
 #pragma unroll
@@ -1032,10 +883,10 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
 #pragma unroll
         for (int hf = 0; hf < 2; hf++) {
             inv_subblock<N1_LOGN, LEAN, FP>(hf ? y1 : y, lds, 1024 * wv, 16 * hf + wv, lane, pd, pc, fc, a.fp_red_mask);
-            if (N1_INV_EXP & 4) TROY_WAVE_SYNC(); else __syncthreads();
+            __syncthreads();
 #pragma unroll
             for (int r = 0; r < 8; r++) { x[16 * hf + r] = rlo[1024 * r]; x[16 * hf + 8 + r] = rhi[1024 * r]; }
-            if (N1_INV_EXP & 4) TROY_WAVE_SYNC(); else __syncthreads();
+            __syncthreads();
         }
         if (mm + 1 < m_end) stage_issue(in_of(mm + 1) + 1024 * wv); // the regions are free during round A'
         // round A': stages 4..0 across the 32 sub-blocks, N^-1 folded into the last one
@@ -1078,9 +929,6 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
             u64 *dst = a.md_ct + (u64)(mm >> 1) * a.md_ct_bstride + (((u64)(mm & 1) * a.md_dl + slot) << N1_LOGN);
             const u64 *onto = !a.md_base ? dst : ((int)(mm & 1) >= a.md_base_polys) ? nullptr : a.md_base + (u64)(mm >> 1) * a.md_base_bstride + (((u64)(mm & 1) * a.md_dl + slot) << N1_LOGN);
             const Shoup iq[4] = {pd.aux, pd.aux, pd.aux, pd.aux};
-#if N1_INV_TOP == 3
-            TROY_WAIT_VMEM(); // the next row's staged half has landed (issued a round ago): waited for HERE, before this row's first store
-#endif
 #pragma unroll
             for (int g = 0; g < 8; g++) { // four coefficients at a time through the butterfly building blocks (bfly.h); x[] stays in registers
                 u64 tl[4], c[4], q[4];
@@ -1104,17 +952,14 @@ template <bool LEAN, bool MD, bool FP> __device__ __forceinline__ void ntt1_inv_
                 for (int i = 0; i < 4; i++) {
                     // (keeping the 32 results in x[] and storing them after the last operand load -- no load ever waited for behind a store -- spills 200-300 B:
                     // the epilogue's branches on `onto` leave the allocator no room.  The groups' own stores stay between their loads.)
-                    st_g_inv<!FP && (N1_NT_INV & 2)>(dst, t + 1024 * (4 * g + i), c[i]);
+                    st_g(dst, t + 1024 * (4 * g + i), c[i]);
                 }
             }
         } else {
             const unsigned t = opaque(tid);
-#if N1_INV_TOP == 3
-            TROY_WAIT_VMEM(); // the next row's staged half has landed (issued a round ago): waited for HERE, while no store is in flight
-#endif
 #pragma unroll
             for (int r = 0; r < 32; r++)
-                if (!(N1_INV_EXP & 2) || x[r] == 0x123456789abcdefull) st_g_inv<!FP && (N1_NT_INV & 1)>(row, t + 1024 * r, x[r]);
+                st_g(row, t + 1024 * r, x[r]);
         }
     }
 }
@@ -1161,7 +1006,7 @@ template <int LOGN, bool LEAN, bool FP> __device__ __forceinline__ void ntt1s_fw
 #pragma unroll
         for (int g = 0; g < G; g++)
 #pragma unroll
-            for (int h = 0; h < NSUB; h++) y[(g << LOGA) + h] = ld_g_fwd(rowp, t + T * (h * G + g));
+            for (int h = 0; h < NSUB; h++) y[(g << LOGA) + h] = ld_g(rowp, t + T * (h * G + g));
     };
     load_row(in_base + row_of(m_begin));
     const Ntt1Args &args = a;
@@ -1185,7 +1030,7 @@ template <int LOGN, bool LEAN, bool FP> __device__ __forceinline__ void ntt1s_fw
         }
         __syncthreads();
         if (mm + 1 < m_end) load_row(in_base + row_of(mm + 1)); // all sixteen registers are free: the next limb streams in under the sub-block rounds
-        fwd_subblock<LOGN, LEAN, false, FP>(lds, 1024 * wv, wv, lane, pd, pc, m, out + 1024 * wv, args, mm, m_begin, 4, true, fc);
+        fwd_subblock<LOGN, LEAN, false, FP>(lds, 1024 * wv, wv, lane, pd, pc, m, out + 1024 * wv, args, true, fc);
     }
 }
 template <int LOGN, bool LEAN> __global__ __launch_bounds__(64 << (LOGN - 10), 4) void ntt1s_fwd_kernel(Ntt1Args a) { ntt1s_fwd_body<LOGN, LEAN, false>(a); }
@@ -1439,9 +1284,9 @@ void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbM
         // soon as the launch is more than ONE round of workgroups: at the headline's two lanes of 128 the mod-down is 481 workgroups on 256 CUs, and flat order
         // fetched the special limb once per prime (same-box A/B, profiles/r06_xcd_md_ab.txt: that kernel 867 -> 853 us, headline +0.4 %)
         const bool shared_row = a.md_ct || a.cr_last;
-        const bool xcd = forced_xcd >= 0 ? forced_xcd != 0 : (N1_XCD && a.nslots > 1 && a.nslots * a.chunks >= (shared_row ? cus + 1 : 2 * cus));
+        const bool xcd = forced_xcd >= 0 ? forced_xcd != 0 : (a.nslots > 1 && a.nslots * a.chunks >= (shared_row ? cus + 1 : 2 * cus));
         a.xcd_per = xcd ? (a.nslots * a.chunks + 7) / 8 : 0;
-        a.xcd_group = forced_group > 0 ? (unsigned)forced_group : !(a.md_ct || a.cr_last) ? 1u : kind == 2 ? N1_XCD_GROUP_FP : N1_XCD_GROUP_INT;
+        a.xcd_group = forced_group > 0 ? (unsigned)forced_group : !(a.md_ct || a.cr_last) ? 1u : 4u;
         static const bool perturb = probe_env("TROYHIP_NTT1_XCD_PERTURB") != nullptr;
         a.xcd_perturb = perturb ? 1u : 0u;
         cls[ncls].a = a;
@@ -1502,27 +1347,8 @@ void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbM
             else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_kernel<false, false>), grid, dim3(N1_THREADS), 0, st, x);
         }
     };
-#ifdef N1_TIMING // development build: phase stamps of one workgroup of the guard-free forward kernel
-    static u64 *dbg = nullptr;
-    if (!dbg) HIP_CHECK(hipMalloc((void **)&dbg, 16 * 8 * 8));
-    for (int i = 0; i < ncls; i++)
-        if (cls[i].lean && !inverse) { cls[i].a.dbg = dbg; cls[i].a.dbg_block = (cls[i].a.nslots * cls[i].a.chunks) / 2 + 3; }
-#endif
     for (int i = 0; i < ncls; i++) launch(cls[i], stream);
     launch_check("ntt1 kernels");
-#ifdef N1_TIMING
-    if (!inverse && ncls && cls[0].lean) {
-        u64 h[16 * 8];
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-        for (unsigned r = 0; r < cls[0].a.rows_per_wg && r < 8; r++) {
-            fprintf(stderr, "n1 fwd row %u:", r);
-            for (int i = 1; i < 14; i++) fprintf(stderr, " %lld", (long long)(h[16 * r + i] - h[16 * r + i - 1]));
-            if (r + 1 < cls[0].a.rows_per_wg && r + 1 < 8) fprintf(stderr, " | next %lld", (long long)(h[16 * (r + 1)] - h[16 * r + 13]));
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
 }
 
 } // namespace troyhip

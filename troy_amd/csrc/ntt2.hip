@@ -30,56 +30,6 @@
 
 namespace troyhip {
 
-// tools/ntt_probe.sh builds throw-away variants with parts of the kernel removed to see what bounds it (results are
-// wrong by construction): bit0 no HBM traffic, bit1 no LDS exchange, bit2 no butterflies, bit3 the contiguous pass reads an
-// L2-resident window instead of its rows.  Always 0 in the product.
-#ifndef N2_EXP
-#define N2_EXP 0
-#endif
-#ifndef N2_MIN_WAVES
-#define N2_MIN_WAVES 4
-#endif
-#ifndef N2_MAC_WAVES
-#define N2_MAC_WAVES 2 // waves per SIMD of the key-switch fused kernel (16 x 128-bit accumulators per thread)
-#endif
-#ifndef N2_MAC_HOIST
-#define N2_MAC_HOIST 1 // keep the last round's twiddles in registers in that kernel
-#endif
-#ifndef N2_DMA
-#define N2_DMA 1 // contiguous passes prefetch the next row with LDS-DMA
-#endif
-#ifndef N2_DMA_POL
-#define N2_DMA_POL 2 // cache policy of the LDS-DMA row prefetch: 2 = non-temporal -- rows that are read once do not displace the key window (and the staged rows of
-                     // the neighbours) in L2: fetch of the key-switch accumulating pass 15.98 -> 14.25 GB per 256 ciphertexts (1.10x -> 1.00x its rows), of the tensor
-                     // pass 8.06 -> 7.89; -0.8 % / -2 % on the two kernels, +0.3-0.5 % on the 49-bit twin, the CKKS chain and BGV (profiles/r05_inv_probes.txt 5e).  0: default policy
-#endif
-#ifndef N2_MAC_STORE_LINEAR
-#define N2_MAC_STORE_LINEAR 1 // the key-switch sums are stored through the wave's exchange area (contiguous KiB per instruction); 0 (probe): from a thread's eight consecutive coefficients
-#endif
-#ifndef N2_COALESCED_STORE
-#define N2_COALESCED_STORE 1 // forward contiguous pass: transpose the last round through LDS, store 1 KiB per instruction
-#endif
-#ifndef N2_TENSOR_WAVES
-#define N2_TENSOR_WAVES 3 // waves per SIMD of the tensor fused kernel: with the LDS addresses formed per row (N2_FRESH_TENSOR) it fits 168 VGPRs
-#endif                    // (196 with hoisted addresses = 2 waves): 1183 -> 1044 us per step, headline +3 %
-#ifndef N2_TENSOR_HOIST1
-#define N2_TENSOR_HOIST1 1 // tensor fused kernel: keep the per-lane twiddles of round 1 / round 2 in registers (0: re-read them per row)
-#endif
-#ifndef N2_TENSOR_HOIST2
-#define N2_TENSOR_HOIST2 1
-#endif
-#ifndef N2_FRESH_TENSOR
-#define N2_FRESH_TENSOR 15
-#endif
-#ifndef N2_FRESH_MD
-#define N2_FRESH_MD 15
-#endif
-#ifndef N2_FRESH_FP_MAC
-#define N2_FRESH_FP_MAC 15
-#endif
-#ifndef N2_FP_MAC_WAVES
-#define N2_FP_MAC_WAVES 3 // waves per SIMD of the FP64 key-switch fused kernel (16 doubles of accumulators per thread)
-#endif
 #define N2_THREADS 256
 #define N2_LOGT 11
 #define N2_T 2048
@@ -137,31 +87,9 @@ struct Ntt2Args {
     unsigned fp_acc_every = 0; // the key-switch accumulators are reduced every this many rows (0: never)
 };
 
-#ifndef N2_NT
-#define N2_NT 1 // non-temporal accesses.  bit 0 (ON): the stores of the forward STRIDED pass -- rows written once and read back by another kernel: the key switch's
-                // digit-expanding pass -2.5 %, headline +0.6 %, 49-bit twin +2 %, CKKS chain +1.3 %, BGV +0.6 % (profiles/r05_inv_probes.txt 5f).  Probes: bit 1 its loads
-                // (the L + 1 readers of a source digit lose their L2 hits: slower), bit 2 the inverse strided pass's stores, bit 3 the contiguous pass's stores
-                // (store_via_lds: transforms, tensor), bit 4 the key-switch sums
-#endif
-template <bool NT> __device__ __forceinline__ u64 n2_ld(const u64 *p) {
-#ifndef TROYHIP_CPU_EMUL
-    if (NT) return __builtin_nontemporal_load(p);
-#endif
-    return *p;
-}
-template <bool NT> __device__ __forceinline__ void n2_st2(u64 *p, ulonglong2 v) { // 16 bytes
-#ifndef TROYHIP_CPU_EMUL
-    if (NT) {
-        typedef u64 v2 __attribute__((ext_vector_type(2)));
-        v2 w;
-        w.x = v.x;
-        w.y = v.y;
-        __builtin_nontemporal_store(w, reinterpret_cast<v2 *>(p));
-        return;
-    }
-#endif
-    *reinterpret_cast<ulonglong2 *>(p) = v;
-}
+// NT: a non-temporal store.  Used for the stores of the forward STRIDED pass -- rows written once and read back by another kernel: the key switch's
+// digit-expanding pass -2.5 %, headline +0.6 %, 49-bit twin +2 %, CKKS chain +1.3 %, BGV +0.6 % (profiles/r05_inv_probes.txt 5f).  Its loads stay
+// temporal (the L + 1 readers of a source digit would lose their L2 hits: slower).
 template <bool NT> __device__ __forceinline__ void n2_st(u64 *p, u64 v) {
 #ifndef TROYHIP_CPU_EMUL
     if (NT) { __builtin_nontemporal_store(v, p); return; }
@@ -195,7 +123,7 @@ __device__ __forceinline__ Shoup to_sgpr(const Shoup w) {
 #endif
 }
 
-template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = true> struct Round {
+template <int INV, int STRIDED, int NS, int LOGC, int LS, int R> struct Round {
     static constexpr int G = 8 >> R;                       // groups per thread
     static constexpr int THREADS = STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS; // a strided pass owns 2^(NS + LOGC) points: 2048 (256 threads) or, wide, 4096 (512)
     static constexpr int NTW = (1 << R) - 1;               // twiddles per group
@@ -205,9 +133,6 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
     static constexpr int LOGD = INV ? (LS + LOGC) : (LOGG - (R - 1));
     static constexpr bool UNIFORM = LOGD >= 6;             // all lanes of a wave share the twiddles
     static constexpr bool LAST = INV ? (LS + R == NS) : (LS + R == NS);
-    // twiddles that live in SGPRs (wave-uniform) or belong to the last round are loaded once per workgroup; the
-    // few-distinct-values rounds in between are re-read from L1 per row, which frees ~28 VGPRs (one more wave per SIMD)
-    static constexpr bool HOIST = HOISTP; // false: twiddles are re-read (L1/L2) for every row instead of living in 28 VGPRs (the key-switch fused kernel needs them)
 
     __device__ static __forceinline__ unsigned base_of(unsigned q) {
         const unsigned hi = q >> LOGD, lo = q & ((1u << LOGD) - 1);
@@ -274,11 +199,6 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
     // value bound (8p at the input of the first pass + 3p * 17 stages at most = 59p < 2^64); the caller reduces with barrett64
     // FP64 form (fpmod.h): x holds the bit patterns of doubles, tw those of (w, w / p); forward stages only
     __device__ static __forceinline__ void compute_fp(u64 (&x)[8], const Shoup (&tw)[G][NTW], const FpPrime &fc, const Shoup inv_n = Shoup{0, 0}) {
-        if (N2_EXP & 4) { // removal probe (tools/ntt_probe.sh): no butterflies
-#pragma unroll
-            for (int u = 0; u < G; u++) x[u] ^= tw[u][0].op;
-            return;
-        }
         if constexpr (INV) { // Gentleman-Sande: X' = X + Y, Y' = (X - Y) w; the last stage of the transform multiplies both outputs (N^-1 folded in)
 #pragma unroll
             for (int st = 0; st < R; st++) {
@@ -320,11 +240,6 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
         }
     }
     __device__ static __forceinline__ void compute(u64 (&x)[8], const Shoup (&tw)[G][NTW], const PrimeDesc &pd, const bool lean = false) {
-        if (N2_EXP & 4) {
-#pragma unroll
-            for (int u = 0; u < G; u++) x[u] ^= tw[u][0].op;
-            return;
-        }
         const PrimeConst pc = make_prime_const(pd.p);
 #pragma unroll
         for (int st = 0; st < R; st++) {
@@ -373,14 +288,12 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
     // t = threadIdx.x, or an opaque copy of it made inside the row loop: the addresses are then formed next to the access instead of
     // being hoisted out of the loop, where eight of them per exchange would live (or be spilled) across the whole kernel
     __device__ static __forceinline__ void lds_read(u64 (&x)[8], const u64 *lds, const unsigned t) {
-        if (N2_EXP & 2) return;
 #pragma unroll
         for (int u = 0; u < G; u++)
 #pragma unroll
             for (int e = 0; e < (1 << R); e++) x[(u << R) + e] = lds[swz(elem(t + THREADS * u, e))];
     }
     __device__ static __forceinline__ void lds_write(const u64 (&x)[8], u64 *lds, const unsigned t) {
-        if (N2_EXP & 2) return;
 #pragma unroll
         for (int u = 0; u < G; u++)
 #pragma unroll
@@ -399,8 +312,11 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
         static_assert(!STRIDED && NS == 9 && R == 3 && LS == 0, "staging is defined for the first round of the contiguous pass");
         const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         const u64 *src = row + ((size_t)tile << N2_LOGT) + 512 * w + 2 * (INV ? unit_perm(lane) : lane);
+        // cache policy 2 = non-temporal: rows that are read once do not displace the key window (and the staged rows of the neighbours) in L2: fetch of
+        // the key-switch accumulating pass 15.98 -> 14.25 GB per 256 ciphertexts (1.10x -> 1.00x its rows), of the tensor pass 8.06 -> 7.89; -0.8 % / -2 %
+        // on the two kernels, +0.3-0.5 % on the 49-bit twin, the CKKS chain and BGV (profiles/r05_inv_probes.txt 5e)
 #pragma unroll
-        for (int i = 0; i < 4; i++) TROY_GLDS16_POL(src + 128 * i, wave_stage + 128 * i, N2_DMA_POL);
+        for (int i = 0; i < 4; i++) TROY_GLDS16_POL(src + 128 * i, wave_stage + 128 * i, 2);
     }
     __device__ static __forceinline__ void stage_read(u64 (&x)[8], const u64 *wave_stage) {
         const unsigned lane = threadIdx.x & 63;
@@ -421,7 +337,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
     // is four stores of 16 bytes every 64 bytes (each touching all 32 lines of the wave's 4 KiB); instead the wave
     // transposes through its private exchange area with the same unit permutation and issues four stores of one
     // contiguous 1 KiB each.
-    template <bool NT = (N2_NT & 8) != 0> __device__ static __forceinline__ void store_via_lds(const u64 (&x)[8], u64 *row, unsigned tile, u64 *wave_xchg) {
+    __device__ static __forceinline__ void store_via_lds(const u64 (&x)[8], u64 *row, unsigned tile, u64 *wave_xchg) {
         const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         u64 *mine = wave_xchg + 128 * (lane >> 4) + 2 * (lane & 15);
 #pragma unroll
@@ -436,7 +352,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(wave_xchg + 128 * c + 2 * lane);
-            n2_st2<NT>(dst + 128 * c, v);
+            *reinterpret_cast<ulonglong2 *>(dst + 128 * c) = v;
         }
     }
     // MAC = 2 epilogue of the forward contiguous pass: virtual row vr = mm % 4 of (a0, a1, b0, b1); x is the lazy transform
@@ -492,7 +408,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             u64 *orow = out + ((((u64)b * 3 + i) * period + slot) << logn);
-            if (N2_COALESCED_STORE && xchg) { // 1 KiB-contiguous stores through the wave's exchange area, as the plain pass
+            if (xchg) { // 1 KiB-contiguous stores through the wave's exchange area, as the plain pass
                 TROY_WAVE_SYNC();
                 store_via_lds(d[i], orow, tile, xchg + 512 * (threadIdx.x >> 6));
                 continue;
@@ -509,11 +425,6 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
     }
     // global access; consecutive-element runs are moved 16 bytes at a time
     template <int REDUCE> __device__ static __forceinline__ void g_read(u64 (&x)[8], const u64 *row, unsigned tile, int logn, const Mod &m, const unsigned t = threadIdx.x) {
-        if (N2_EXP & 1) {
-#pragma unroll
-            for (int e = 0; e < 8; e++) x[e] = (u64)(uintptr_t)row + t * 8 + e;
-            return;
-        }
 #pragma unroll
         for (int u = 0; u < G; u++) {
             const unsigned q = t + THREADS * u;
@@ -526,7 +437,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
                 }
             } else {
 #pragma unroll
-                for (int e = 0; e < (1 << R); e++) x[(u << R) + e] = n2_ld<STRIDED && !INV && (N2_NT & 2) != 0>(row + g_index<STRIDED, NS, LOGC>(tile, elem(q, e), logn));
+                for (int e = 0; e < (1 << R); e++) x[(u << R) + e] = row[g_index<STRIDED, NS, LOGC>(tile, elem(q, e), logn)];
             }
         }
         (void)m;
@@ -538,13 +449,6 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
         if (FINAL && fc) { // FP64 instance: the doubles become canonical words, then the common store code (which skips its own reduction)
 #pragma unroll
             for (int e = 0; e < 8; e++) x[e] = fp_canonical(fp_of_bits(x[e]), *fc, p);
-        }
-        if (N2_EXP & 1) {
-            u64 acc = 0;
-#pragma unroll
-            for (int e = 0; e < 8; e++) acc ^= x[e];
-            if (acc == 0x123456789abcdefull) row[threadIdx.x] = acc; // never true in practice; keeps the work alive
-            return;
         }
         if (FINAL && fc) {
         } else if (FINAL == 1 && lean) { // guard-free forward transform: values below 59p
@@ -559,7 +463,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
                 for (int i = 0; i < 4; i++) x[4 * h + i] = v[i];
             }
         }
-        if constexpr (N2_COALESCED_STORE && !STRIDED && !INV && NS == 9 && R == 3 && LOGD == 0) {
+        if constexpr (!STRIDED && !INV && NS == 9 && R == 3 && LOGD == 0) {
             if (xchg) {
                 TROY_WAVE_SYNC(); // the exchange area was last read by this round's lds_read
                 store_via_lds(x, row, tile, xchg + 512 * (threadIdx.x >> 6));
@@ -579,7 +483,7 @@ template <int INV, int STRIDED, int NS, int LOGC, int LS, int R, bool HOISTP = t
                 }
             } else {
 #pragma unroll
-                for (int e = 0; e < (1 << R); e++) n2_st<STRIDED && ((!INV && (N2_NT & 1) != 0) || (INV && (N2_NT & 4) != 0))>(row + g_index<STRIDED, NS, LOGC>(tile, elem(q, e), logn), x[(u << R) + e]);
+                for (int e = 0; e < (1 << R); e++) n2_st<STRIDED && !INV>(row + g_index<STRIDED, NS, LOGC>(tile, elem(q, e), logn), x[(u << R) + e]);
             }
         }
     }
@@ -673,13 +577,12 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     constexpr int FRESH = (!STRIDED && !INV && NS == 9 && MAC == 0) ? (FINAL ? 15 : 1)            // plain forward contiguous pass (it spilled)
                           : (STRIDED && !INV && NS == 7)                 ? 1                         // 7-stage strided forward pass (it spilled; more than the first exchange costs 2-6 % there)
                           : (!STRIDED && NS == 10)                       ? 63                        // N = 2^17
-                          : (FINAL >= 3 && NS >= 6)                      ? N2_FRESH_MD               // mod-down epilogues: room for their operands
-                          : MAC == 2                                     ? N2_FRESH_TENSOR           // tensor pass: 168 VGPRs = 3 waves per SIMD
-                          : (FP && MAC)                                  ? N2_FRESH_FP_MAC           // FP64 key-switch pass: 184 -> 168 VGPRs = 3 waves per SIMD
+                          : (FINAL >= 3 && NS >= 6)                      ? 15                        // mod-down epilogues: room for their operands
+                          : MAC == 2                                     ? 15                        // tensor pass: 168 VGPRs = 3 waves per SIMD
+                          : (FP && MAC)                                  ? 15                        // FP64 key-switch pass: 184 -> 168 VGPRs = 3 waves per SIMD
                           : (STRIDED && !INV && !REDUCE && NS >= 4 && NS <= 6) ? 15                  // plain strided forward pass: room for the register prefetch (PF)
                                                                          : 0;
     auto round_sync = [&]() {
-        if (N2_EXP & 2) return;
         if (WAVE_PRIVATE) TROY_WAVE_SYNC(); else __syncthreads();
     };
     // inverse passes run the same round list but with growing gaps, so their local-stage offsets are the same sums
@@ -692,8 +595,8 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     constexpr int Q2 = NR > 2 ? (INV ? P::r[NR - 3] : R2) : 0;
     constexpr int Q3 = NR > 3 ? (INV ? P::r[NR - 4] : R3) : 0;
     using Rd0 = Round<INV, STRIDED, NS, LOGC, 0, Q0>;
-    using Rd1 = Round<INV, STRIDED, NS, LOGC, Q0, Q1 ? Q1 : 1, MAC != 2 || N2_TENSOR_HOIST1>;
-    using Rd2 = Round<INV, STRIDED, NS, LOGC, Q0 + Q1, Q2 ? Q2 : 1, (MAC == 2 ? N2_TENSOR_HOIST2 : (MAC != 1 && MAC != 3) || N2_MAC_HOIST)>;
+    using Rd1 = Round<INV, STRIDED, NS, LOGC, Q0, Q1 ? Q1 : 1>;
+    using Rd2 = Round<INV, STRIDED, NS, LOGC, Q0 + Q1, Q2 ? Q2 : 1>;
     using Rd3 = Round<INV, STRIDED, NS, LOGC, Q0 + Q1 + Q2, Q3 ? Q3 : 1>;
 
     const unsigned tile = blockIdx.x & ((1u << a.tiles_per_row_log) - 1);
@@ -709,24 +612,20 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     const FpPrime *const fcp = FP ? &fc_ : nullptr;
     const Mod m = mod_of(pd);
     const bool need_reduce = !FP && REDUCE && (a.src_bound == 0 || (pd.p >> 61) != 0 || a.src_bound > 8 * pd.p);
-#ifdef N2_CENSUS_LEAN // tools/isa_census.py --flags=-DN2_CENSUS_LEAN: the guard-free path alone, so that a loop's count is one path's count (never shipped)
-    const bool lean = !INV;
-#else
     const bool lean = !INV && ((a.map.lean >> slot) & 1); // wave-uniform: prime below 2^58 -> guard-free forward butterflies (bfly.h)
-#endif
     const int logn = a.logn;
     const int k1 = STRIDED ? NS : logn - NS;
     const int s_first = INV ? (STRIDED ? k1 - 1 : logn - 1) : (STRIDED ? 0 : k1);
 
     Shoup tw0[Rd0::G][Rd0::NTW], tw1[Rd1::G][Rd1::NTW], tw2[Rd2::G][Rd2::NTW], tw3[Rd3::G][Rd3::NTW];
-    if constexpr (Rd0::HOIST) Rd0::load_tw(tw0, pd, tile, logn, s_first);
-    if constexpr (NR > 1 && Rd1::HOIST) Rd1::load_tw(tw1, pd, tile, logn, s_first);
-    if constexpr (NR > 2 && Rd2::HOIST) Rd2::load_tw(tw2, pd, tile, logn, s_first);
-    if constexpr (NR > 3 && Rd3::HOIST) Rd3::load_tw(tw3, pd, tile, logn, s_first);
-    if constexpr (Rd0::HOIST) Rd0::settle_tw(tw0);
-    if constexpr (NR > 1 && Rd1::HOIST) Rd1::settle_tw(tw1);
-    if constexpr (NR > 2 && Rd2::HOIST) Rd2::settle_tw(tw2);
-    if constexpr (NR > 3 && Rd3::HOIST) Rd3::settle_tw(tw3);
+    Rd0::load_tw(tw0, pd, tile, logn, s_first);
+    if constexpr (NR > 1) Rd1::load_tw(tw1, pd, tile, logn, s_first);
+    if constexpr (NR > 2) Rd2::load_tw(tw2, pd, tile, logn, s_first);
+    if constexpr (NR > 3) Rd3::load_tw(tw3, pd, tile, logn, s_first);
+    Rd0::settle_tw(tw0);
+    if constexpr (NR > 1) Rd1::settle_tw(tw1);
+    if constexpr (NR > 2) Rd2::settle_tw(tw2);
+    if constexpr (NR > 3) Rd3::settle_tw(tw3);
 
     const unsigned m_begin = chunk * a.rows_per_wg;
     const unsigned m_end = (m_begin + a.rows_per_wg < a.m_total) ? m_begin + a.rows_per_wg : a.m_total;
@@ -756,14 +655,13 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
             if (a.src_same_layout == 2) // wave-uniform: which buffer this row's prime slot lives in
                 in = slot >= a.src_slots ? row : (o < a.src_split ? a.src + (((u64)o * a.src_slots + slot) << logn) : a.src2 + (((u64)(o - a.src_split) * a.src_slots + slot) << logn));
         }
-        if ((N2_EXP & 8) && !STRIDED) in = a.data + ((r & 63) << logn); // probe: the contiguous pass reads a 16 MB window (L2-resident input)
     };
-    constexpr bool DMA = N2_DMA && WAVE_PRIVATE && !(N2_EXP & 1);
-    static_assert(MAC != 3 || DMA || (N2_EXP & 1), "the CKKS key-switch pass (MAC = 3) takes its rows from the LDS-DMA staging area: build it with N2_DMA = 1 and without the no-HBM probe");
+    constexpr bool DMA = WAVE_PRIVATE; // contiguous passes prefetch the next row with LDS-DMA
+    static_assert(MAC != 3 || DMA, "the CKKS key-switch pass (MAC = 3) takes its rows from the LDS-DMA staging area");
     // plain strided forward passes of two rounds: the next row is requested into a second register set before the last round's butterflies
     // (the registers come from forming the LDS addresses per row, FRESH, so the kernel stays at four waves per SIMD): -2 % on that pass.
     // Not the digit-reducing first pass of key switching, whose L2-resident sources arrive fast enough anyway: +6 % there.
-    constexpr bool PF = STRIDED && !INV && NR == 2 && !REDUCE && !(N2_EXP & 1);
+    constexpr bool PF = STRIDED && !INV && NR == 2 && !REDUCE;
     u64 xn[PF ? 8 : 1];
     static_assert(!MAC || (!INV && !STRIDED && NS == 9), "the inner product is fused into the forward contiguous pass");
     u64 tx[MAC == 2 ? 3 : 1][8]; // MAC = 2: the transforms of a0, a1, b0 while b1 is being computed
@@ -792,8 +690,7 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                     const u64 kword = (e & 1) ? kw[cpt][e >> 1].y : kw[cpt][e >> 1].x;
-                    // N2_EXP & 16 (removal probe, wrong results): the key word taken as a double as it lies -- what storing the key as doubles would save
-                    facc[cpt][e] += fp_mulmod_pinv(fp_of_bits(xr[e]), (N2_EXP & 16) ? fp_of_bits(kword) : fp_from_u64(kword), fc);
+                    facc[cpt][e] += fp_mulmod_pinv(fp_of_bits(xr[e]), fp_from_u64(kword), fc);
                 }
             if (a.fp_acc_every && (row_no + 1) % a.fp_acc_every == 0) { // wave-uniform; the sums stay below 2^53 (launch_ntt2_ks_mac)
 #pragma unroll
@@ -821,7 +718,7 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     // consecutive coefficients they were 16 bytes per lane every 64 bytes -- the access pattern that cost the single-pass forward kernel 9 % (ntt1.hip).
     // Same-box A/B (tools/r4_ab_maclin.sh): accumulating pass -1..-3 % at the headline, -4 % in the CKKS chain, -8 % at configs[1], BGV N = 2^16 unchanged.
     // (The key LOADS in that pattern are harmless: a per-row transposition that made them contiguous as well measured the same or 1-2 % slower.)
-    constexpr bool MAC_STORE_LINEAR = KS && N2_MAC_STORE_LINEAR && WAVE_PRIVATE;
+    constexpr bool MAC_STORE_LINEAR = KS && WAVE_PRIVATE;
     u64 *const wave_stage = lds[1] + 512 * (threadIdx.x >> 6);
     u64 x[8];
     unsigned ro = m_begin / inner, rk = m_begin - ro * inner; // (o, k) of the current row
@@ -879,7 +776,6 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
                 if constexpr (FP) Rd1::compute_fp(x, tw1, fc, pd.inv_n); else Rd1::compute(x, tw1, pd, lean);
                 Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
                 round_sync();
-                if constexpr (!Rd2::HOIST) Rd2::load_tw(tw2, pd, tile, logn, s_first);
                 Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
                 fp_guard(x, 2);
                 if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
@@ -926,7 +822,6 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
 #pragma unroll
             for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
         }
-        if constexpr (!Rd0::HOIST) Rd0::load_tw(tw0, pd, tile, logn, s_first);
         if constexpr (FP && REDUCE) { // the digit's residues become doubles: exact below 2^52; a wide source prime (>= 2^50) is reduced modulo this row's prime first
             if ((a.fp_src_wide >> rk) & 1) {
 #pragma unroll
@@ -946,7 +841,6 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
         } else {
             Rd0::lds_write(x, buf, (FRESH & 1) ? n2_opaque(threadIdx.x) : threadIdx.x);
             round_sync();
-            if constexpr (!Rd1::HOIST) Rd1::load_tw(tw1, pd, tile, logn, s_first);
             Rd1::lds_read(x, buf, (FRESH & 2) ? n2_opaque(threadIdx.x) : threadIdx.x);
             if constexpr (PF) {
                 if (mm + 1 < m_end) {
@@ -963,7 +857,6 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
             } else {
                 Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
                 round_sync();
-                if constexpr (!Rd2::HOIST) Rd2::load_tw(tw2, pd, tile, logn, s_first);
                 Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
                 fp_guard(x, 2);
                 if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
@@ -993,7 +886,6 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
                 } else {
                     Rd2::lds_write(x, buf, (FRESH & 16) ? n2_opaque(threadIdx.x) : threadIdx.x);
                     round_sync();
-                    if constexpr (!Rd3::HOIST) Rd3::load_tw(tw3, pd, tile, logn, s_first);
                     Rd3::lds_read(x, buf, (FRESH & 32) ? n2_opaque(threadIdx.x) : threadIdx.x);
                     fp_guard(x, 3);
                     if constexpr (FP) Rd3::compute_fp(x, tw3, fc, pd.inv_n); else Rd3::compute(x, tw3, pd, lean);
@@ -1040,20 +932,23 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
             }
             if constexpr (MAC_STORE_LINEAR) {
                 TROY_WAVE_SYNC();
-                Rd2::template store_via_lds<(N2_NT & 16) != 0>(lin, a.mac_acc + ((((u64)o * 2 + cpt) * period + slot) << logn), tile, lds[0] + 512 * (threadIdx.x >> 6));
+                Rd2::store_via_lds(lin, a.mac_acc + ((((u64)o * 2 + cpt) * period + slot) << logn), tile, lds[0] + 512 * (threadIdx.x >> 6));
             }
             (void)lin;
         }
     }
 }
 
+// waves per SIMD: 4, the key-switch fused kernel 2 (16 x 128-bit accumulators per thread), the tensor fused kernel 3 (with the LDS addresses formed per
+// row, FRESH, it fits 168 VGPRs; 196 with hoisted addresses = 2 waves: 1183 -> 1044 us per step, headline +3 %)
 template <int INV, int STRIDED, int NS, int LOGC, int FINAL, int REDUCE, int MAC = 0>
-__global__ __launch_bounds__(STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS, MAC == 2 ? N2_TENSOR_WAVES : MAC ? N2_MAC_WAVES : N2_MIN_WAVES) void ntt2_kernel(Ntt2Args a) {
+__global__ __launch_bounds__(STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS, MAC == 2 ? 3 : MAC ? 2 : 4) void ntt2_kernel(Ntt2Args a) {
     ntt2_body<INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC, 0>(a);
 }
-// the FP64 instances (primes below 2^50): a kernel name of their own, so that profiles and bench.py's per-kernel accounting tell the two apart
+// the FP64 instances (primes below 2^50): a kernel name of their own, so that profiles and bench.py's per-kernel accounting tell the two apart.
+// The FP64 key-switch fused kernel runs 3 waves per SIMD (16 doubles of accumulators per thread).
 template <int INV, int STRIDED, int NS, int LOGC, int FINAL, int REDUCE, int MAC = 0>
-__global__ __launch_bounds__(STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS, MAC ? N2_FP_MAC_WAVES : N2_MIN_WAVES) void ntt2_fp_kernel(Ntt2Args a) {
+__global__ __launch_bounds__(STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS, MAC ? 3 : 4) void ntt2_fp_kernel(Ntt2Args a) {
     ntt2_body<INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC, 1>(a);
 }
 
@@ -1068,13 +963,10 @@ bool ntt2_supported(int logn) { return logn >= 12 && logn <= 17; }
 // The forward strided pass is bound by HBM, and the part moves strided rows faster in longer runs: a copy in this pass's pattern reaches 4.9-5.1 TB/s with
 // 256-byte runs and 5.7-6.2 TB/s with 512-byte runs (profiles/r05_microbench_nt.txt).  Wide form (N = 2^15): 512 threads own 64 columns x 64 rows
 // = 4096 points (64 KiB of LDS with the double buffer, two workgroups per CU); taken when the launch still fills the chip twice over.
-#ifndef N2_WIDE
-#define N2_WIDE 1
-#endif
 static bool n2_wide(unsigned narrow_blocks) {
     static const int forced = [] { const char *e = probe_env("TROYHIP_NTT2_WIDE"); return e ? std::atoi(e) : -1; }();
     if (forced >= 0) return forced != 0;
-    return N2_WIDE && (narrow_blocks >> 1) >= 4u * device_cus();
+    return (narrow_blocks >> 1) >= 4u * device_cus();
 }
 template <int INV, int STRIDED, int NS, int LOGC, int FINAL, int REDUCE> static void launch_one(const Ntt2Args &a, unsigned blocks, hipStream_t s, bool fp = false) {
     constexpr unsigned THREADS = STRIDED ? (1u << (NS + LOGC - 3)) : N2_THREADS;

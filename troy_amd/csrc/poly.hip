@@ -112,9 +112,7 @@ void launch_mul_plain(u64 *a, const u64 *plain, const PrimeDesc *primes, const L
 // Grid (x: pairs of coefficients of a row, y: row = polynomial x limb, z: batch item): every index comes from the block id -- no 64-bit division per thread, the
 // prime and its Barrett constants are workgroup-uniform (scalar registers).  The flat form spent ~150 of its ~300 VALU instructions per thread on i / item_words
 // and row % limbs, which made a streaming kernel issue-bound (0.595 of the HBM peak at the 128 x 128 matmul; round 6).
-#ifndef MPA_PAIRS
-#define MPA_PAIRS 2 // pairs of coefficients per thread (the second pair half a row away: both sets of loads are in flight before the first product)
-#endif
+constexpr int MPA_PAIRS = 2; // pairs of coefficients per thread (the second pair half a row away: both sets of loads are in flight before the first product)
 __global__ __launch_bounds__(EW_THREADS) void mul_plain_acc_kernel(MulPlainAccArgs x, u64 *out, u64 out_bstride, const PrimeDesc *primes, LimbMap map, int logn, u32 limbs, u32 batch) {
     const u32 n = (blockIdx.x * EW_THREADS + threadIdx.x) * 2; // two coefficients per pair
     const u32 N = 1u << logn, span = N / MPA_PAIRS < 2 ? 2 : N / MPA_PAIRS; // pair j of this thread: coefficients n + j span, n + j span + 1 (tiny rings: fewer pairs)
@@ -578,9 +576,6 @@ __device__ __forceinline__ void mac4(MacAcc (&a)[4], const u64 (&x)[4], const u6
 // ckks_target != nullptr: operand (i == j) comes from the NTT-form input itself (evaluator.cpp:2424-2427)
 // A thread owns V consecutive coefficients of NB consecutive batch items (NB * V = 4 accumulators per key component):
 // every key word it loads is used NB times.
-#ifndef KS_MAC_NB
-#define KS_MAC_NB 4
-#endif
 template <int NB, int V> __global__ __launch_bounds__(EW_THREADS) void ks_mac_kernel(const u64 *D, const u64 *key, const u64 *ckks_target, u64 t_bstride, u64 *acc, KsArgs a) {
     static_assert(NB * V == 4, "mac4 works on four accumulators");
     // block order: (output prime i, coefficient window, batch group) with the batch group FASTEST, so that the workgroups
@@ -723,7 +718,7 @@ void launch_ks_expand(const u64 *target, u64 t_bstride, u64 *D, const KsArgs &a,
 }
 void launch_ks_mac(const u64 *D, const u64 *key, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, hipStream_t s) {
     if (a.dl >= 64) throw Error(ST_LOGIC_ERROR, "ks_mac: more than 63 digits");
-    constexpr int NB = KS_MAC_NB, V = 4 / KS_MAC_NB;
+    constexpr int NB = 4, V = 4 / NB; // four batch items of one coefficient
     const u64 groups = (a.batch + NB - 1) / NB, per_group = (u64)(a.dl + 1) << (a.logn - (V == 2 ? 1 : 0));
     TROY_LAUNCH(HIP_KERNEL_NAME(ks_mac_kernel<NB, V>), dim3(ceil_div(per_group, EW_THREADS) * groups), dim3(EW_THREADS), 0, s, D, key, ckks_target, t_bstride, acc, a);
     launch_check("ks_mac_kernel");
