@@ -286,6 +286,23 @@ int troyhip_encrypt_symmetric(troyhip_context *ctx, const uint64_t *secret_key, 
  * form the ciphertext stores it.  a_seeds: HOST [batch], non-zero. */
 int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs, uint64_t *c1_out, uint64_t out_batch_stride, uint64_t batch, void *stream);
 
+/* ---- Device key generation (KeyGenerator).  Item i is BYTE-IDENTICAL to the host form called with the same seed, secret key and element
+ * (DESIGN.md section 4.8).  Keys are device memory, NTT form; secret_key and new_key are [K][N], a key-switching key is [K-1][2][K][N].
+ * Invalid input returns the host form's status and message: an even element or one >= 2N "Galois element is not valid", K < 2 "keyswitching
+ * is not supported by the context"; a bad element anywhere in the list is refused before anything runs. */
+/* item i == troyhip_host_keygen(seeds[i]) (seeds HOST [batch][2]); sk [K][N] at sk_out + i sk_bstride; pk_out may be NULL, else [2][K][N] at
+ * pk_out + i pk_bstride */
+int troyhip_keygen(troyhip_context *ctx, const uint64_t *seeds, uint64_t *sk_out, uint64_t sk_bstride, uint64_t *pk_out, uint64_t pk_bstride, uint64_t batch,
+                   void *stream);
+/* keys_out[i] (device, [K-1][2][K][N]) == troyhip_host_galois_key(seed, secret_key, galois_elts[i]); elts and the pointer table are HOST, read before return */
+int troyhip_create_galois_keys(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint32_t *galois_elts,
+                               uint64_t *const *keys_out, uint64_t count, void *stream);
+/* out == troyhip_host_relin_key(seed, secret_key) */
+int troyhip_create_relin_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, uint64_t *out, void *stream);
+/* out == troyhip_host_kswitch_key(seed, secret_key, new_key) */
+int troyhip_create_kswitch_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *new_key, uint64_t *out,
+                               void *stream);
+
 /* ---- Device encoding, `batch` items per call (BatchEncoder / CKKSEncoder).  Item i is BYTE-IDENTICAL to the host form called with item i
  * (DESIGN.md section 4.7).  Every buffer is device memory; strides are in words (u64 or double) between consecutive items; batch in 1 .. 65535.
  * Invalid input returns the host form's status and message.  The outputs feed troyhip_encrypt's `plain` operand directly (BFV [B][N], CKKS

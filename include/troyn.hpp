@@ -870,6 +870,8 @@ public:
         check(troyhip_copy_h2d(a->get(), host.data(), host.size() * 8, nullptr));
         keys_[index] = a;
     }
+    // take a device key that already holds [K - 1][2][K][N] words (KeyGenerator::create*OnDevice): no copy
+    void adopt(size_t index, std::shared_ptr<DeviceArray> key) { keys_[index] = std::move(key); }
     const std::map<size_t, std::shared_ptr<DeviceArray>> &all() const { return keys_; }
     void clear() { keys_.clear(); } // src/kswitchkeys_cuda.cuh
     // the same keys on another device (keys are replicated over the GPUs of a batch shard: BASELINE north_star).  Called with `to_device` current.
@@ -1014,19 +1016,7 @@ public:
     }
     // every key rotate / conjugate can ask for: X -> X^(2N-1) and X -> X^(3^(2^i)), X^(3^-(2^i)) (GaloisTool::getEltsAll,
     // src/utils/galois.cpp:101-126)
-    void createGaloisKeys(GaloisKeys &gk) const {
-        const uint64_t m = 2 * (uint64_t)c_.polyModulusDegree();
-        std::vector<uint32_t> elts{(uint32_t)(m - 1)};
-        uint64_t pos = 3, neg = 1;
-        while (neg * 3 % m != 1) neg += 2; // 3^-1 mod 2N
-        for (uint64_t span = 2; span < m / 2; span <<= 1) {
-            elts.push_back((uint32_t)pos);
-            elts.push_back((uint32_t)neg);
-            pos = pos * pos % m;
-            neg = neg * neg % m;
-        }
-        createGaloisKeys(elts, gk);
-    }
+    void createGaloisKeys(GaloisKeys &gk) const { createGaloisKeys(galoisEltsAll(), gk); }
     GaloisKeys createGaloisKeys() const { GaloisKeys g; createGaloisKeys(g); return g; }
     // createKeySwitchingKeys (src/keygenerator.cpp:360-366): ONE key, which takes a ciphertext under `new_key` to one under this generator's
     // secret key (Evaluator::applyKeySwitchingInplace)
@@ -1041,18 +1031,85 @@ public:
     }
     // the keys of fieldTraceInplace / packLWECiphertexts: X -> X^(N/2^k + 1), k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)
     GaloisKeys createAutomorphismKeys() const {
-        std::vector<uint32_t> elts;
-        for (size_t n = c_.polyModulusDegree(); n >= 2; n >>= 1) elts.push_back((uint32_t)(n + 1));
         GaloisKeys g;
-        createGaloisKeys(elts, g);
+        createGaloisKeys(automorphismElts(), g);
         return g;
     }
-    void createGaloisKeys(const std::vector<int> &steps, GaloisKeys &gk) const {
+    void createGaloisKeys(const std::vector<int> &steps, GaloisKeys &gk) const { createGaloisKeys(eltsOfSteps(steps), gk); }
+
+    // ---- the same keys generated on the device (troyhip_create_relin_key / _galois_keys / _kswitch_key): byte-identical to the members above, with
+    // the same describe() stamp; a whole Galois set is one call.  The secret key is uploaded once per generator.
+    void createRelinKeysOnDevice(RelinKeys &rlk) const {
+        auto key = std::make_shared<DeviceArray>(std::max<size_t>(1, ksk_words()));
+        check(troyhip_create_relin_key(c_.handle(), lo_, hi_, deviceSecretKey(), key->get(), nullptr));
+        rlk.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
+        rlk.adopt(RelinKeys::getIndex(2), key);
+    }
+    RelinKeys createRelinKeysOnDevice() const { RelinKeys r; createRelinKeysOnDevice(r); return r; }
+    void createGaloisKeysOnDevice(const std::vector<uint32_t> &galois_elts, GaloisKeys &gk) const {
+        gk.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
+        if (galois_elts.empty()) return;
+        std::vector<std::shared_ptr<DeviceArray>> keys;
+        std::vector<uint64_t *> table;
+        for (size_t i = 0; i < galois_elts.size(); i++) {
+            keys.push_back(std::make_shared<DeviceArray>(std::max<size_t>(1, ksk_words())));
+            table.push_back(keys.back()->get());
+        }
+        check(troyhip_create_galois_keys(c_.handle(), lo_, hi_, deviceSecretKey(), galois_elts.data(), table.data(), galois_elts.size(), nullptr));
+        for (size_t i = 0; i < galois_elts.size(); i++) gk.adopt(GaloisKeys::getIndex(galois_elts[i]), keys[i]);
+    }
+    void createGaloisKeysOnDevice(const std::vector<int> &steps, GaloisKeys &gk) const { createGaloisKeysOnDevice(eltsOfSteps(steps), gk); }
+    void createGaloisKeysOnDevice(GaloisKeys &gk) const { createGaloisKeysOnDevice(galoisEltsAll(), gk); }
+    GaloisKeys createGaloisKeysOnDevice() const { GaloisKeys g; createGaloisKeysOnDevice(g); return g; }
+    GaloisKeys createAutomorphismKeysOnDevice() const { GaloisKeys g; createGaloisKeysOnDevice(automorphismElts(), g); return g; }
+    KSwitchKeys createKeySwitchingKeysOnDevice(const SecretKey &new_key) const {
+        if (new_key.data.size() != sk_.data.size()) throw std::invalid_argument("new_key is not valid for encryption parameters");
+        DeviceArray dnew(new_key.data.size());
+        check(troyhip_copy_h2d(dnew.get(), new_key.data.data(), new_key.data.size() * 8, nullptr));
+        auto key = std::make_shared<DeviceArray>(std::max<size_t>(1, ksk_words()));
+        check(troyhip_create_kswitch_key(c_.handle(), lo_, hi_, deviceSecretKey(), dnew.get(), key->get(), nullptr));
+        check(troyhip_stream_synchronize(nullptr)); // dnew is freed on return
+        KSwitchKeys k;
+        k.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
+        k.adopt(0, key);
+        return k;
+    }
+
+    // every key rotate / conjugate can ask for: X -> X^(2N-1) and X -> X^(3^(2^i)), X^(3^-(2^i)) (GaloisTool::getEltsAll,
+    // src/utils/galois.cpp:101-126)
+    std::vector<uint32_t> galoisEltsAll() const {
+        const uint64_t m = 2 * (uint64_t)c_.polyModulusDegree();
+        std::vector<uint32_t> elts{(uint32_t)(m - 1)};
+        uint64_t pos = 3, neg = 1;
+        while (neg * 3 % m != 1) neg += 2; // 3^-1 mod 2N
+        for (uint64_t span = 2; span < m / 2; span <<= 1) {
+            elts.push_back((uint32_t)pos);
+            elts.push_back((uint32_t)neg);
+            pos = pos * pos % m;
+            neg = neg * neg % m;
+        }
+        return elts;
+    }
+    // the keys of fieldTraceInplace / packLWECiphertexts: X -> X^(N/2^k + 1), k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)
+    std::vector<uint32_t> automorphismElts() const {
         std::vector<uint32_t> elts;
-        for (int s : steps) { uint32_t e; check(troyhip_galois_elt_from_step(c_.handle(), s, &e)); elts.push_back(e); }
-        createGaloisKeys(elts, gk);
+        for (size_t n = c_.polyModulusDegree(); n >= 2; n >>= 1) elts.push_back((uint32_t)(n + 1));
+        return elts;
     }
 private:
+    std::vector<uint32_t> eltsOfSteps(const std::vector<int> &steps) const {
+        std::vector<uint32_t> elts;
+        for (int s : steps) { uint32_t e; check(troyhip_galois_elt_from_step(c_.handle(), s, &e)); elts.push_back(e); }
+        return elts;
+    }
+    const uint64_t *deviceSecretKey() const {
+        if (!dsk_) {
+            dsk_ = std::make_shared<DeviceArray>(sk_.data.size());
+            check(troyhip_copy_h2d(dsk_->get(), sk_.data.data(), sk_.data.size() * 8, nullptr));
+        }
+        return dsk_->get();
+    }
+    mutable std::shared_ptr<DeviceArray> dsk_;
     void generate() {
         const size_t K = c_.keyLimbs(), N = c_.polyModulusDegree();
         sk_.data.resize(K * N);

@@ -344,6 +344,13 @@ class KSwitchKeys:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters")
         self.keys[index] = DeviceBuffer.from_numpy(a)
 
+    def set_device(self, index, buf):
+        """adopt a DeviceBuffer of (K-1) 2 K N words that already holds a key (KeyGenerator.create*(device=True)); no copy"""
+        K, N = self.context.key_limbs, self.context.N
+        if not isinstance(buf, DeviceBuffer) or buf.words != (K - 1) * 2 * K * N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters")
+        self.keys[index] = buf
+
     def hasKey(self, index):
         return index in self.keys
 
@@ -814,38 +821,105 @@ class KeyGenerator:
         K, N = self.context.key_limbs, self.context.N
         return np.zeros((K - 1, 2, K, N), dtype=np.uint64)
 
-    def createRelinKeys(self):
+    # ---- device forms (troyhip_create_relin_key / _galois_keys / _kswitch_key): the keys are generated on the device, byte-identical to the host
+    # forms, and come back as populated RelinKeys / GaloisKeys / KSwitchKeys.  The secret key is uploaded once.
+    def _device_sk(self):
+        if getattr(self, "_dsk", None) is None:
+            self._dsk = DeviceBuffer.from_numpy(self._sk)
+        return self._dsk
+
+    def _device_ksk(self):
+        K, N = self.context.key_limbs, self.context.N
+        return DeviceBuffer(max(1, (K - 1) * 2 * K * N))
+
+    def _seed_args(self):
+        return C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1])
+
+    def createRelinKeys(self, device=False):
+        """the host key array [K-1][2][K][N]; device=True: a RelinKeys whose key was generated on the device"""
+        if device:
+            out = self._device_ksk()
+            capi.check(self.lib, self.lib.troyhip_create_relin_key(self.context.h, *self._seed_args(), C.c_void_p(self._device_sk().ptr), C.c_void_p(out.ptr), None))
+            keys = RelinKeys(self.context)
+            keys.set_device(RelinKeys.getIndex(2), out)
+            return keys
         out = self._ksk()
         capi.check(self.lib, self.lib.troyhip_host_relin_key(self.context.h, C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1]), _u64p(self._sk), _u64p(out)))
         return out
 
-    def createKeySwitchingKeys(self, new_key):
+    def createKeySwitchingKeys(self, new_key, device=False):
         """KeyGenerator::createKeySwitchingKeys (src/keygenerator.cpp:360-366): the host key array that takes a ciphertext under `new_key`
-        (another generator's secretKey()) to one under this generator's secret key; KSwitchKeys.set(0, .) + applyKeySwitchingInplace use it"""
+        (another generator's secretKey()) to one under this generator's secret key; KSwitchKeys.set(0, .) + applyKeySwitchingInplace use it.
+        device=True: a KSwitchKeys whose key (index 0) was generated on the device"""
         new_key = np.ascontiguousarray(new_key, dtype=np.uint64)
         if new_key.shape != self._sk.shape:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "new_key is not valid for encryption parameters")
+        if device:
+            out, dnew = self._device_ksk(), DeviceBuffer.from_numpy(new_key)
+            capi.check(self.lib, self.lib.troyhip_create_kswitch_key(self.context.h, *self._seed_args(), C.c_void_p(self._device_sk().ptr), C.c_void_p(dnew.ptr),
+                                                                     C.c_void_p(out.ptr), None))
+            keys = KSwitchKeys(self.context)
+            keys.set_device(0, out)
+            return keys
         out = self._ksk()
         capi.check(self.lib, self.lib.troyhip_host_kswitch_key(self.context.h, C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1]), _u64p(self._sk), _u64p(new_key), _u64p(out)))
         return out
 
-    def createAutomorphismKeys(self):
-        """KeyGenerator::createAutomorphismKeys (src/keygenerator.cpp:350-358): the keys of fieldTraceInplace / packLWECiphertexts,
-        X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1; returns {elt: host key array}"""
+    def automorphismElts(self):
+        """X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)"""
         elts, n = [], self.context.N
         while n >= 2:
             elts.append(n + 1)
             n >>= 1
-        return self.createGaloisKeys(elts)
+        return elts
 
-    def createGaloisKeys(self, galois_elts):
-        """returns {elt: host key array}"""
+    def galoisEltsAll(self):
+        """every element rotate / conjugate can ask for: X -> X^(2N-1) and X -> X^(3^(2^i)), X^(3^-(2^i)) (GaloisTool::getEltsAll,
+        src/utils/galois.cpp:101-126; the element list of include/troyn.hpp createGaloisKeys())"""
+        m = 2 * self.context.N
+        elts, pos, neg, span = [m - 1], 3, pow(3, -1, m), 2
+        while span < m // 2:
+            elts += [pos, neg]
+            pos, neg, span = pos * pos % m, neg * neg % m, span << 1
+        return elts
+
+    def createAutomorphismKeys(self, device=False):
+        """KeyGenerator::createAutomorphismKeys (src/keygenerator.cpp:350-358): the keys of fieldTraceInplace / packLWECiphertexts,
+        X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1; returns {elt: host key array}, or with device=True a GaloisKeys generated on the device"""
+        return self.createGaloisKeys(self.automorphismElts(), device=device)
+
+    def createGaloisKeys(self, galois_elts=None, device=False):
+        """returns {elt: host key array}; galois_elts=None: galoisEltsAll().  device=True: a GaloisKeys whose keys were all generated on the
+        device in one call"""
+        galois_elts = self.galoisEltsAll() if galois_elts is None else [int(e) for e in galois_elts]
+        if device:
+            elts = np.ascontiguousarray(galois_elts, dtype=np.uint32)
+            bufs = [self._device_ksk() for _ in galois_elts]
+            table = (C.c_void_p * max(1, len(bufs)))(*[b.ptr for b in bufs])
+            capi.check(self.lib, self.lib.troyhip_create_galois_keys(self.context.h, *self._seed_args(), C.c_void_p(self._device_sk().ptr),
+                                                                     elts.ctypes.data_as(C.c_void_p), table, C.c_uint64(len(bufs)), None))
+            keys = GaloisKeys(self.context)
+            for e, b in zip(galois_elts, bufs):
+                keys.set_device(GaloisKeys.getIndex(e), b)
+            return keys
         keys = {}
         for e in galois_elts:
             out = self._ksk()
             capi.check(self.lib, self.lib.troyhip_host_galois_key(self.context.h, C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1]), _u64p(self._sk), C.c_uint32(e), _u64p(out)))
             keys[int(e)] = out
         return keys
+
+    @staticmethod
+    def keygenBatch(context, seeds):
+        """KeyGenerator(context, seed=seeds[i]) for every row of seeds [B][2], on the device: (sk, pk) DeviceBuffers of shape [B][K][N] and
+        [B][2][K][N] (their `shape` attribute); item i is byte-identical to that generator's secretKey() / createPublicKey()"""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, 2)
+        B, K, N = len(seeds), context.key_limbs, context.N
+        sk, pk = DeviceBuffer(max(1, B * K * N)), DeviceBuffer(max(1, B * 2 * K * N))
+        capi.check(context.lib, context.lib.troyhip_keygen(context.h, _u64p(seeds), C.c_void_p(sk.ptr), C.c_uint64(K * N), C.c_void_p(pk.ptr), C.c_uint64(2 * K * N),
+                                                           C.c_uint64(B), None))
+        sk.shape, pk.shape = (B, K, N), (B, 2, K, N)
+        return sk, pk
 
 
 class Encryptor:

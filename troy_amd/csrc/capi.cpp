@@ -5,6 +5,7 @@
 #include "evaluator.h"
 #include "encryptor.h"
 #include "encoder.h"
+#include "keygen.h"
 #include "kernels.h"
 #include "build_id.h"
 #include "hostcrypto.h"
@@ -26,7 +27,9 @@ struct troyhip_context {
     Evaluator ev;
     DeviceEncryptor enc;
     DeviceEncoder encd;
-    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true) : ctx(scheme, N, q, t, device), ev(ctx), enc(ctx, ev), encd(ctx) {}
+    DeviceKeygen kg;
+    troyhip_context(int scheme, u64 N, const std::vector<u64> &q, u64 t, bool device = true)
+        : ctx(scheme, N, q, t, device), ev(ctx), enc(ctx, ev), encd(ctx), kg(ctx) {}
 };
 
 namespace {
@@ -643,6 +646,43 @@ int troyhip_expand_seed(troyhip_context *ctx, const uint64_t *a_seeds, int limbs
         troyhip_context *x = need(ctx);
         const hipStream_t s = on(stream);
         x->enc.expand_seed(a_seeds, limbs, c1_out, out_batch_stride, batch, s);
+    });
+}
+
+// ---- device key generation (keygen.cpp): stream ids as the host forms above
+int troyhip_keygen(troyhip_context *ctx, const uint64_t *seeds, uint64_t *sk_out, uint64_t sk_bstride, uint64_t *pk_out, uint64_t pk_bstride, uint64_t batch,
+                   void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        x->kg.keygen(seeds, sk_out, sk_bstride, pk_out, pk_bstride, batch, s);
+    });
+}
+int troyhip_create_galois_keys(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint32_t *galois_elts,
+                               uint64_t *const *keys_out, uint64_t count, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        std::vector<u64> streams(galois_elts ? count : 0);
+        for (size_t i = 0; i < streams.size(); i++) streams[i] = ((u64)2 << 32) | galois_elts[i];
+        x->kg.kswitch(seed_lo, seed_hi, secret_key, 2, nullptr, streams.data(), galois_elts, keys_out, count, s);
+    });
+}
+int troyhip_create_relin_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, uint64_t *out, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        const u64 sid = 1;
+        x->kg.kswitch(seed_lo, seed_hi, secret_key, 1, nullptr, &sid, nullptr, &out, 1, s);
+    });
+}
+int troyhip_create_kswitch_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *new_key, uint64_t *out,
+                               void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        const u64 sid = (u64)5 << 32;
+        x->kg.kswitch(seed_lo, seed_hi, secret_key, 3, new_key, &sid, nullptr, &out, 1, s);
     });
 }
 

@@ -6,7 +6,6 @@
 
 namespace troyhip {
 
-namespace {
 // Rng::uniform_below(bound) accepts a word w iff w <= limit
 u64 limit_below(u64 bound) { return ~u64(0) - (~u64(0) % bound + 1) % bound; }
 // words of the parallel window of a sampler: the draws, the expected rejections and eight standard deviations of them, 64 more; a multiple of 8.
@@ -22,6 +21,20 @@ u64 window_for(u64 draws, u64 limit) {
     }
     return (draws + margin + 7) & ~u64(7);
 }
+void run_sampler(const SamplerArgs &a, hipStream_t s) {
+    launch_sampler(a, s);
+#ifdef TROYHIP_PROBES
+    // probe builds count the items whose window came up short (troyhip_stat "enc_tail_items"); the product never reads back
+    std::vector<u64> ran(a.items);
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipMemcpy(ran.data(), a.tail_ran, a.items * sizeof(u64), hipMemcpyDeviceToHost));
+    u64 n = 0;
+    for (u64 v : ran) n += v;
+    stats::counter(stats::ENC_TAIL_ITEMS) += n;
+#endif
+}
+
+namespace {
 inline size_t rounded(size_t words) { return (words + 31) & ~size_t(31); } // what Arena::take carves
 u64 item_stream(bool symmetric, bool with_plain) { return (u64)(symmetric ? (with_plain ? 4 : 7) : (with_plain ? 3 : 6)) << 32; } // capi.cpp host forms
 } // namespace
@@ -53,18 +66,7 @@ SamplerArgs DeviceEncryptor::sampler(u64 batch, u64 draws, u64 bound, size_t &bl
     return a;
 }
 
-void DeviceEncryptor::sample(SamplerArgs a, hipStream_t s) {
-    launch_sampler(a, s);
-#ifdef TROYHIP_PROBES
-    // probe builds count the items whose window came up short (troyhip_stat "enc_tail_items"); the product never reads back
-    std::vector<u64> ran(a.items);
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipMemcpy(ran.data(), a.tail_ran, a.items * sizeof(u64), hipMemcpyDeviceToHost));
-    u64 n = 0;
-    for (u64 v : ran) n += v;
-    stats::counter(stats::ENC_TAIL_ITEMS) += n;
-#endif
-}
+void DeviceEncryptor::sample(SamplerArgs a, hipStream_t s) { run_sampler(a, s); }
 
 void DeviceEncryptor::encrypt(const u64 *key, bool symmetric, const u64 *seeds, const u64 *a_seeds, const u64 *plain, u64 n_coeffs, u64 plain_bstride,
                               double plain_scale, CtBatch &out, u64 batch, hipStream_t s) {

@@ -9,6 +9,12 @@
 
 namespace troyhip {
 
+// the sampler rules shared with key generation (keygen.cpp): Rng::uniform_below(bound) accepts a word w iff w <= limit_below(bound); the parallel window
+// of `draws` draws (TROYHIP_ENC_MARGIN=<words> replaces its margin in probe builds); run_sampler = launch_sampler + the probe builds' tail count
+u64 limit_below(u64 bound);
+u64 window_for(u64 draws, u64 limit);
+void run_sampler(const SamplerArgs &a, hipStream_t s);
+
 class DeviceEncryptor {
 public:
     DeviceEncryptor(Context &ctx, Evaluator &ev) : c(ctx), ev_(ev) {}

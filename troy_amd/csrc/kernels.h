@@ -192,9 +192,12 @@ struct SamplerArgs {
     u64 *out;         // draw r of item b, limb l -> out[b * out_bstride + l * N + r]
     u64 out_bstride;
     const PrimeDesc *primes; // limb l uses primes[l] (the key primes lead the registry)
+    const u64 *streams;      // nullptr: every item uses `stream`; else item b uses streams[b]
+    u64 *const *out_tab;     // nullptr: item b writes at out + b * out_bstride; else at out_tab[b] + out_off (device table)
+    u64 out_off;
 };
 void launch_sampler(const SamplerArgs &a, hipStream_t s);
-// CBD draws [0, draws) of item b from word pos[b]: draw r -> out[b * out_bstride + (r / N) * out_pstride + l * N + r % N] for l < limbs, stored or (add)
+// CBD draws [0, draws) of item b from word pos[b]: draw r -> out[b * out_bstride (or out_tab[b] + out_off) + (r / N) * out_pstride + l * N + r % N] for l < limbs, stored or (add)
 // multiplied by ts[l] and added
 struct CbdArgs {
     const u64 *seeds;
@@ -207,6 +210,10 @@ struct CbdArgs {
     u64 out_bstride, out_pstride;
     const PrimeDesc *primes;
     u64 ts[64];
+    const u64 *streams;      // as SamplerArgs
+    u64 *const *out_tab;
+    u64 out_off;
+    u64 *pos_out;            // nullptr, or pos_out[b] = pos[b] + draws (must not alias pos)
 };
 void launch_sample_cbd(const CbdArgs &a, hipStream_t s);
 struct EncScale { u64 v[64]; }; // per-limb factor of the error (BGV: t mod p_l, else 1)
@@ -215,6 +222,29 @@ void launch_enc_pk_product(const u64 *u, const u64 *pk, u64 K, const u64 *e, u64
 // ct[b] = (-(c1 * sk + e * es), c1) in NTT form: c1 = ct[b][1] already holds a; e [batch][limbs][N]
 void launch_enc_sk_combine(u64 *ct, u64 ct_bstride, const u64 *sk, const u64 *e, const EncScale &es, const PrimeDesc *primes, int logn, u64 limbs, u64 batch,
                            hipStream_t s);
+
+// ---- keygen.hip (device key generation, keygen.cpp) ----
+// one digit j of a batch of keys: c0 = -(c1 s + e es_l) + [l == j] factor src_j over limbs l < K, c1 = c0 + K N already holds the uniform draws.
+// Item b's key at out_tab[b] (device table) or out + b * out_bstride; its c0 at + c0_off.  src_kind: 0 none (public key), 1 s^2 (relin),
+// 2 sigma_elts[b](s) in NTT form (Galois), 3 src [K][N] (key switching)
+struct KeyCombineArgs {
+    u64 *const *out_tab;
+    u64 *out;
+    u64 out_bstride, c0_off;
+    const u64 *sk;       // [K][N] NTT form; item b's at sk + b * sk_bstride (0: one key for all)
+    u64 sk_bstride;
+    const u64 *e;        // [items][K][N] NTT form
+    int src_kind, j;
+    const u64 *src;
+    const u64 *elts;     // [items] Galois elements (src_kind 2)
+    u64 factor;          // q_special mod p_j
+    EncScale es;
+    const PrimeDesc *primes;
+    int logn;
+    u32 K;
+    u64 items;
+};
+void launch_key_combine(const KeyCombineArgs &a, hipStream_t s);
 
 // ---- selftest.hip (test support) ----
 void launch_modarith_probe(int op, const u64 *a, const u64 *b, const u64 *c, u64 p, u64 aux_value, u64 *out, u64 n, hipStream_t s);

@@ -39,10 +39,14 @@ __device__ __forceinline__ void chacha_block(u64 lo, u64 hi, u64 stream, u64 ctr
 // word i (0..7) of a block: Rng::next64 = (next32 << 32) | next32
 __device__ __forceinline__ u64 block_word(const u32 x[16], int i) { return ((u64)x[2 * i] << 32) | x[2 * i + 1]; }
 
+// item b's stream id and output base: one id / a dense batch unless the per-item tables are given (key generation: one stream and one allocation per key)
+template <class A> __device__ __forceinline__ u64 stream_of(const A &a, u64 b) { return a.streams ? a.streams[b] : a.stream; }
+template <class A> __device__ __forceinline__ u64 *out_of(const A &a, u64 b) { return a.out_tab ? a.out_tab[b] + a.out_off : a.out + b * a.out_bstride; }
+
 // draw `rank` of item b takes the accepted word w
 __device__ __forceinline__ void sample_store(const SamplerArgs &a, u64 b, u64 rank, u64 w) {
     const u64 N = u64(1) << a.logn;
-    u64 *o = a.out + b * a.out_bstride + rank;
+    u64 *o = out_of(a, b) + rank;
     if (a.kind == 0) { // sample_ternary: 0, 1, 2 -> -1, 0, 1 in every limb
         const u64 r = w % 3;
         for (int l = a.l0; l < a.l1; l++) o[(u64)l * N] = r == 0 ? a.primes[l].p - 1 : r - 1;
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_count_kernel(SamplerArgs a
     if (t >= a.blocks) return;
     const u64 s = a.pos_in[b], blk = s / 8 + t;
     u32 x[16];
-    chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], a.stream, blk, x);
+    chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], stream_of(a, b), blk, x);
     u32 c = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_scatter_kernel(SamplerArgs
         const u64 s = a.pos_in[b], blk = s / 8 + t;
         u64 rank = off[t];
         u32 x[16];
-        chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], a.stream, blk, x);
+        chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], stream_of(a, b), blk, x);
         for (int i = 0; i < 8; i++) {
             const u64 k = blk * 8 + i, w = block_word(x, i);
             if (k < s || k >= s + a.window || w > a.limit) continue;
@@ -121,9 +125,9 @@ __global__ __launch_bounds__(64) void sample_tail_kernel(SamplerArgs a) {
     if (rank >= a.draws) return;
     u64 k = a.pos_in[b] + a.window;
     u32 x[16];
-    chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], a.stream, k / 8, x);
+    chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], stream_of(a, b), k / 8, x);
     for (;; k++) {
-        if (k % 8 == 0) chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], a.stream, k / 8, x);
+        if (k % 8 == 0) chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], stream_of(a, b), k / 8, x);
         const u64 w = block_word(x, (int)(k % 8));
         if (w > a.limit) continue;
         sample_store(a, b, rank, w);
@@ -152,9 +156,10 @@ void launch_sampler(const SamplerArgs &a, hipStream_t s) {
 __global__ __launch_bounds__(SMP_THREADS) void sample_cbd_kernel(CbdArgs a) {
     __shared__ int8_t noise[CBD_WORDS];
     const u64 b = blockIdx.y, s = a.pos[b], blk0 = s / 8 + (u64)blockIdx.x * SMP_THREADS, kbase = blk0 * 8, N = u64(1) << a.logn;
+    if (a.pos_out && blockIdx.x == 0 && threadIdx.x == 0) a.pos_out[b] = s + a.draws; // CBD never rejects: the next sampler starts `draws` words on
     {
         u32 x[16];
-        chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], a.stream, blk0 + threadIdx.x, x);
+        chacha_block(a.seeds[2 * b], a.seeds[2 * b + 1], stream_of(a, b), blk0 + threadIdx.x, x);
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const u64 w = block_word(x, i);
@@ -167,7 +172,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_cbd_kernel(CbdArgs a) {
         if (k < s || k >= s + a.draws) continue;
         const u64 r = k - s;
         const int nz = noise[idx];
-        u64 *o = a.out + b * a.out_bstride + (r >> a.logn) * a.out_pstride + (r & (N - 1));
+        u64 *o = out_of(a, b) + (r >> a.logn) * a.out_pstride + (r & (N - 1));
         for (int l = 0; l < a.limbs; l++, o += N) {
             const Mod m = mod_of(a.primes[l]);
             u64 v = nz < 0 ? m.p - (u64)(-nz) : (u64)nz;
