@@ -170,7 +170,10 @@ int troyhip_host_galois_key(const troyhip_context *ctx, uint64_t seed_lo, uint64
  * for CKKS and coefficient form otherwise, scale 1, correction factor 1 */
 int troyhip_host_encrypt_zero(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *key, int symmetric, int limbs, uint64_t *ct_out);
 /* KeyGenerator::createKeySwitchingKeys(new_key) (src/keygenerator.cpp:294-329, 360-366): the key that takes a ciphertext under `new_key`
- * ([key_limbs][N], NTT form, as troyhip_host_keygen writes a secret key) to one under `secret_key`; layout of `out` as troyhip_host_relin_key */
+ * ([key_limbs][N], NTT form, as troyhip_host_keygen writes a secret key) to one under `secret_key`; layout of `out` as troyhip_host_relin_key.
+ * (a, e) are a function of the seed alone (stream 5 << 32), so ONE SEED MUST NOT SERVE TWO DIFFERENT new_keys: the two results would differ only by
+ * (q_special mod p_j) (new_key - new_key') and publish the difference of the two secret keys.  troyn::KeyGenerator and the Python KeyGenerator pass
+ * (lo + k, hi) on their k-th call. */
 int troyhip_host_kswitch_key(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *new_key, uint64_t *out);
 /* Encryptor::encrypt (public key).  BFV/BGV: plain = n_coeffs coefficients mod t -> ct [2][first_limbs][N];  CKKS: plain = [limbs][N] NTT-form RNS
  * polynomial -> ct [2][limbs][N] NTT form */
@@ -184,7 +187,10 @@ int troyhip_host_encrypt_symmetric(const troyhip_context *ctx, uint64_t seed_lo,
  * :145-190 load(stream, context) regenerates c1): c1 is a function of the public 64-bit `a_seed` (non-zero) alone.  plain == NULL: an encryption of zero
  * at the level of `limbs` primes (encryptZeroSymmetric); otherwise operands and result as troyhip_host_encrypt_symmetric.  troyhip_host_expand_seed
  * writes c1 [limbs][N] in the form the ciphertext stores it (NTT form for CKKS, coefficient form otherwise).  The wire format is the reference's; the
- * seed -> c1 expansion is this library's (ChaCha20; the reference's is curand's XORWOW, which exists only inside that library). */
+ * seed -> c1 expansion is this library's (ChaCha20; the reference's is curand's XORWOW, which exists only inside that library).
+ * The noise e starts at word 0 of the stream 4 << 32 (7 << 32 for zero) of (seed_lo, seed_hi), the very words whose residues
+ * troyhip_host_encrypt_symmetric / _encrypt_zero publish as c1: ONE SEED MUST NOT SERVE BOTH THE SEEDED AND THE UNSEEDED FORM.  The Encryptor wrappers
+ * advance one call counter on every call of any form, so they never do. */
 int troyhip_host_encrypt_symmetric_seeded(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, uint64_t a_seed, const uint64_t *secret_key,
                                           const uint64_t *plain, uint64_t n_coeffs, int limbs, uint64_t *ct_out);
 int troyhip_host_expand_seed(const troyhip_context *ctx, uint64_t a_seed, int limbs, uint64_t *c1_out);
@@ -299,7 +305,7 @@ int troyhip_create_galois_keys(troyhip_context *ctx, uint64_t seed_lo, uint64_t 
                                uint64_t *const *keys_out, uint64_t count, void *stream);
 /* out == troyhip_host_relin_key(seed, secret_key) */
 int troyhip_create_relin_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, uint64_t *out, void *stream);
-/* out == troyhip_host_kswitch_key(seed, secret_key, new_key) */
+/* out == troyhip_host_kswitch_key(seed, secret_key, new_key); as there, one seed must not serve two different new_keys */
 int troyhip_create_kswitch_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *new_key, uint64_t *out,
                                void *stream);
 

@@ -1019,11 +1019,13 @@ public:
     void createGaloisKeys(GaloisKeys &gk) const { createGaloisKeys(galoisEltsAll(), gk); }
     GaloisKeys createGaloisKeys() const { GaloisKeys g; createGaloisKeys(g); return g; }
     // createKeySwitchingKeys (src/keygenerator.cpp:360-366): ONE key, which takes a ciphertext under `new_key` to one under this generator's
-    // secret key (Evaluator::applyKeySwitchingInplace)
+    // secret key (Evaluator::applyKeySwitchingInplace).  Call number k of a generator (k = 0, 1, ..; this member and its OnDevice form count together)
+    // draws its (a, e) from the seed (lo + k, hi): two keys made with one seed differ only by (q_special mod p_j) (new_key - new_key') and would give
+    // away the difference of the two secret keys.
     KSwitchKeys createKeySwitchingKeys(const SecretKey &new_key) const {
         if (new_key.data.size() != sk_.data.size()) throw std::invalid_argument("new_key is not valid for encryption parameters");
         std::vector<uint64_t> h(ksk_words());
-        check(troyhip_host_kswitch_key(c_.handle(), lo_, hi_, sk_.data.data(), new_key.data.data(), h.data()));
+        check(troyhip_host_kswitch_key(c_.handle(), lo_ + kswitch_calls_++, hi_, sk_.data.data(), new_key.data.data(), h.data()));
         KSwitchKeys k;
         k.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
         k.upload(0, h);
@@ -1067,7 +1069,7 @@ public:
         DeviceArray dnew(new_key.data.size());
         check(troyhip_copy_h2d(dnew.get(), new_key.data.data(), new_key.data.size() * 8, nullptr));
         auto key = std::make_shared<DeviceArray>(std::max<size_t>(1, ksk_words()));
-        check(troyhip_create_kswitch_key(c_.handle(), lo_, hi_, deviceSecretKey(), dnew.get(), key->get(), nullptr));
+        check(troyhip_create_kswitch_key(c_.handle(), lo_ + kswitch_calls_++, hi_, deviceSecretKey(), dnew.get(), key->get(), nullptr));
         check(troyhip_stream_synchronize(nullptr)); // dnew is freed on return
         KSwitchKeys k;
         k.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
@@ -1122,6 +1124,7 @@ private:
     size_t ksk_words() const { const size_t K = c_.keyLimbs(); return (K - 1) * 2 * K * c_.polyModulusDegree(); }
     const SEALContext &c_;
     uint64_t lo_, hi_;
+    mutable uint64_t kswitch_calls_ = 0;
     SecretKey sk_;
     PublicKey pk_;
 };

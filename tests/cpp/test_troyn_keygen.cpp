@@ -68,9 +68,13 @@ static void run(SchemeType scheme, size_t n, const vector<int> &bits, const char
 
     EXPECT(same(keygen.createAutomorphismKeys(), keygen.createAutomorphismKeysOnDevice()), "createAutomorphismKeysOnDevice");
 
-    KeyGenerator other(context, 99, 1);
-    EXPECT(same(keygen.createKeySwitchingKeys(other.secretKey()), keygen.createKeySwitchingKeysOnDevice(other.secretKey())),
-           "createKeySwitchingKeysOnDevice");
+    // every createKeySwitchingKeys call of a generator draws from a seed of its own (call number k: lo + k), so the host and the device form are
+    // compared at equal call numbers, on two generators of one seed
+    KeyGenerator other(context, 99, 1), third(context, 98, 2), twin(context, 0x5EED, 7);
+    KSwitchKeys h0 = keygen.createKeySwitchingKeys(other.secretKey()), h1 = keygen.createKeySwitchingKeys(third.secretKey());
+    EXPECT(same(h0, twin.createKeySwitchingKeysOnDevice(other.secretKey())), "createKeySwitchingKeysOnDevice (call 0)");
+    EXPECT(same(h1, twin.createKeySwitchingKeysOnDevice(third.secretKey())), "createKeySwitchingKeysOnDevice (call 1, another new_key)");
+    EXPECT(!same(h0, keygen.createKeySwitchingKeys(other.secretKey())), "a later call with the same new_key draws afresh");
 
     bool threw = false;
     try {

@@ -238,9 +238,12 @@ def test_python_device_forms(name, emul_api):
     assert sorted(ak.keys) == sorted(api.GaloisKeys.getIndex(e) for e in kg.automorphismElts())
     e = kg.automorphismElts()[-1]
     assert np.array_equal(ak.keys[api.GaloisKeys.getIndex(e)].to_numpy().reshape(S.ksk_shape()), kg.createAutomorphismKeys()[e])
-    other = api.KeyGenerator(S.ctx, seed=(3, 4)).secretKey()
-    ks = kg.createKeySwitchingKeys(other, device=True)
-    assert np.array_equal(ks.keys[0].to_numpy().reshape(S.ksk_shape()), kg.createKeySwitchingKeys(other))
+    # every createKeySwitchingKeys call of a generator draws from a seed of its own: the forms are compared at equal call numbers of two generators
+    other, third = api.KeyGenerator(S.ctx, seed=(3, 4)).secretKey(), api.KeyGenerator(S.ctx, seed=(4, 3)).secretKey()
+    twin = api.KeyGenerator(S.ctx, seed=S.seed)
+    for new_key in (other, third, other):
+        ks = kg.createKeySwitchingKeys(new_key, device=True)
+        assert np.array_equal(ks.keys[0].to_numpy().reshape(S.ksk_shape()), twin.createKeySwitchingKeys(new_key))
     with pytest.raises(ValueError):
         ks.set_device(1, api.DeviceBuffer(5))
     seeds = G.seeds_for(3)

@@ -1,10 +1,12 @@
 """Device encryption on the MI355X: item i of a batch is byte-identical to the host form with item i's seed (small shapes, every form and level;
-the bench shapes on a few items), and a headline batch encrypted on the device multiplies, relinearizes and decrypts to the slot products."""
+the bench shapes on a few items), and a headline batch encrypted on the device multiplies, relinearizes and decrypts to the slot products.  At the bench shapes the symmetric forms are also compared with the independent model of the
+streams (tests/sampler_model.py)."""
 import numpy as np
 import pytest
 
 import cases
 import enc_cases as E
+import sampler_model as M
 from troy_amd.capi import BFV, BGV, CKKS
 
 pytestmark = pytest.mark.gpu
@@ -91,3 +93,48 @@ def test_headline_batch_multiply_relin_decrypt(gpu_api):
     for b in range(B):
         got = enc.decode(plain[b])
         assert np.array_equal(np.asarray(got, dtype=np.uint64), (x[b].astype(object) * y[b].astype(object) % t).astype(np.uint64)), b
+
+
+# ---- the device against the independent model of the streams (tests/sampler_model.py) at the bench shapes: c1 and the recovered noise, with
+# Python integers and the oracle's NTT; nothing here goes through the host forms.
+EDGE_SEEDS = {0: (0x5EED, 7), 63: (0x8000000000000123, 0), 127: (0xFFFFFFFFFFFFFFF0, 0x9000000000000001)}
+
+
+def symmetric_b128(S, limbs, seeded, rng):
+    """troyhip_encrypt_symmetric at B = 128, one plaintext for every item: items 0, 63 and 127 against the model, in the first and the last limb"""
+    import ctypes as C
+    from troy_amd import api, capi
+    N, P, B = S.N, S.primes, 128
+    seeds = E.seeds_for(B, base=limbs)
+    for i, seed in EDGE_SEEDS.items():
+        seeds[i] = seed
+    a_seeds = E.a_seeds_for(B, base=limbs) if seeded else None
+    plain = S.plains(1, limbs, rng)
+    dplain = api.DeviceBuffer.from_numpy(np.ascontiguousarray(plain, dtype=np.uint64))
+    stride = 2 * limbs * N
+    out = api.DeviceBuffer(B * stride)
+    st = capi.CtStruct(out.ptr, stride, 0, limbs, 0, 0.0, 0)
+    rc = S.lib.troyhip_encrypt_symmetric(S.ctx.h, C.c_void_p(S.dsk.ptr), E._p(seeds), None if a_seeds is None else E._p(a_seeds), C.c_void_p(dplain.ptr),
+                                         C.c_uint64(N if S.scheme == CKKS else plain.shape[1]), C.c_uint64(0), C.c_double(2.0**20 if S.scheme == CKKS else 1.0),
+                                         C.byref(st), C.c_uint64(B), None)
+    assert rc == capi.OK, S.lib.troyhip_last_error().decode()
+    for i, seed in EDGE_SEEDS.items():
+        ct = out.to_numpy(stride, offset=i * stride).reshape(2, limbs, N)
+        if seeded:
+            a, e = M.symmetric_seeded(*seed, int(a_seeds[i]), N, P[:limbs])
+        else:
+            a, e, _ = M.symmetric(*seed, N, P[:limbs])
+        for l in (0, limbs - 1):
+            c1 = ct[1, l] if S.scheme == CKKS else M.ntt(N, P[l], ct[1, l])
+            assert np.array_equal(c1, a[l]), (seeded, limbs, i, l)
+            assert np.array_equal(M.symmetric_noise(S.scheme, ct, S.sk, l, limbs, P, S.t, N, plain[0]), e), (seeded, limbs, i, l)
+
+
+@pytest.mark.parametrize("name", sorted(BENCH))
+def test_symmetric_b128_matches_model(name, gpu_api):
+    """seeded and unseeded, at the first level, and for CKKS also at the last"""
+    S = E.Setup.from_cfg(BENCH[name])
+    rng = np.random.default_rng(12)
+    for limbs in ([S.ctx.first_limbs, S.ctx.last_limbs] if S.scheme == CKKS else [S.ctx.first_limbs]):
+        for seeded in (False, True):
+            symmetric_b128(S, limbs, seeded, rng)

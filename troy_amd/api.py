@@ -806,6 +806,7 @@ class KeyGenerator:
         if seed is None:
             seed = struct.unpack("<QQ", os.urandom(16))
         self.context, self.lib, self.seed = context, context.lib, (int(seed[0]), int(seed[1]))
+        self.kswitch_calls = 0  # createKeySwitchingKeys calls so far: each one draws from a seed of its own
         K, N = context.key_limbs, context.N
         self._sk = np.zeros((K, N), dtype=np.uint64)
         self._pk = np.zeros((2, K, N), dtype=np.uint64)
@@ -850,19 +851,23 @@ class KeyGenerator:
     def createKeySwitchingKeys(self, new_key, device=False):
         """KeyGenerator::createKeySwitchingKeys (src/keygenerator.cpp:360-366): the host key array that takes a ciphertext under `new_key`
         (another generator's secretKey()) to one under this generator's secret key; KSwitchKeys.set(0, .) + applyKeySwitchingInplace use it.
-        device=True: a KSwitchKeys whose key (index 0) was generated on the device"""
+        device=True: a KSwitchKeys whose key (index 0) was generated on the device.
+        Call number k of a generator (k = 0, 1, ..; host and device forms count together) draws its (a, e) from the seed (lo + k, hi): two keys made
+        with one seed differ only by (q_special mod p_j) (new_key - new_key') and would give away the difference of the two secret keys."""
         new_key = np.ascontiguousarray(new_key, dtype=np.uint64)
         if new_key.shape != self._sk.shape:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "new_key is not valid for encryption parameters")
+        lo, hi = C.c_uint64((self.seed[0] + self.kswitch_calls) & (2**64 - 1)), C.c_uint64(self.seed[1])
+        self.kswitch_calls += 1
         if device:
             out, dnew = self._device_ksk(), DeviceBuffer.from_numpy(new_key)
-            capi.check(self.lib, self.lib.troyhip_create_kswitch_key(self.context.h, *self._seed_args(), C.c_void_p(self._device_sk().ptr), C.c_void_p(dnew.ptr),
+            capi.check(self.lib, self.lib.troyhip_create_kswitch_key(self.context.h, lo, hi, C.c_void_p(self._device_sk().ptr), C.c_void_p(dnew.ptr),
                                                                      C.c_void_p(out.ptr), None))
             keys = KSwitchKeys(self.context)
             keys.set_device(0, out)
             return keys
         out = self._ksk()
-        capi.check(self.lib, self.lib.troyhip_host_kswitch_key(self.context.h, C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1]), _u64p(self._sk), _u64p(new_key), _u64p(out)))
+        capi.check(self.lib, self.lib.troyhip_host_kswitch_key(self.context.h, lo, hi, _u64p(self._sk), _u64p(new_key), _u64p(out)))
         return out
 
     def automorphismElts(self):
