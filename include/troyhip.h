@@ -197,6 +197,13 @@ int troyhip_host_expand_seed(const troyhip_context *ctx, uint64_t a_seed, int li
 /* Decryptor::decrypt.  BFV/BGV: N plaintext coefficients;  CKKS: the [limbs][N] RNS plaintext (NTT form) */
 int troyhip_host_decrypt(const troyhip_context *ctx, const uint64_t *secret_key, const uint64_t *ct, int size, int limbs, int is_ntt_form,
                          uint64_t correction_factor, uint64_t *plain_out);
+/* Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441), BFV / BGV in coefficient form, any size >= 2, any data level; all HOST memory, works
+ * on a host-only context.  noise = c_0 + c_1 s + .. (times t for BFV; BGV: the correction factor is not used) mod q, norm = the largest
+ * |centred coefficient|, *budget_out = max(0, bitlength(q) - bitlength(norm) - 1).  norm_out: NULL, or `limbs` words, base 2^64, least significant
+ * first (the reference's `norm`).  Refuses as the reference does: size < 2 "encrypted is empty", CKKS "unsupported scheme" (LOGIC_ERROR),
+ * "encrypted cannot be in NTT form". */
+int troyhip_host_noise_budget(const troyhip_context *ctx, const uint64_t *secret_key, const uint64_t *ct, int size, int limbs, int is_ntt_form,
+                              int *budget_out, uint64_t *norm_out);
 /* BatchEncoder::encode / decode (src/batchencoder.cpp:84-190; CUDA twin src/batchencoder_cuda.cu): `count` <= N slot values modulo t in the reference's
  * 2 x (N/2) matrix order <-> the plaintext polynomial [N] in coefficient form.  BFV / BGV with a batching plain modulus (t prime, t = 1 mod 2N). */
 int troyhip_host_batch_encode(const troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t *plain_out);
@@ -272,6 +279,12 @@ int troyhip_divide_by_poly_modulus_degree(troyhip_context *ctx, troyhip_ct *ct, 
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */
 int troyhip_decrypt(troyhip_context *ctx, const troyhip_ct *ct, const uint64_t *secret_key, uint64_t *plain_out, uint64_t plain_batch_stride, uint64_t batch,
                     void *stream);
+/* ---- Decryptor::invariantNoiseBudget over a batch (src/decryptor.cpp:373-441; the body of the CUDA twin is commented out,
+ * src/decryptor_cuda.cu:330-395): item i equals troyhip_host_noise_budget on item i.  All DEVICE memory: secret_key [K][N] (NTT form);
+ * budget_out[i] one word per item; norm_out NULL, or `limbs` words per item (base 2^64, least significant first), items norm_batch_stride words
+ * apart.  Stream-ordered like troyhip_decrypt: no synchronisation, nothing read back; scratch comes from the context's arena. */
+int troyhip_noise_budget(troyhip_context *ctx, const troyhip_ct *ct, const uint64_t *secret_key, uint64_t *budget_out, uint64_t *norm_out,
+                         uint64_t norm_batch_stride, uint64_t batch, void *stream);
 
 /* ---- Device encryption, `batch` items per call (Encryptor::encrypt / encryptZero / encryptSymmetric / encryptZeroSymmetric,
  * src/encryptor_cuda.cuh:170-320, src/utils/rlwe_cuda.cu:23-330).  Item i is BYTE-IDENTICAL to the host form called with item i's seed:

@@ -1352,6 +1352,29 @@ public:
         dst.setNttForm(ckks ? ct.parmsID() : parmsIDZero);
         if (ckks) dst.scale() = ct.scale();
     }
+    // Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441; the reference's CUDA twin has it commented out, src/decryptor_cuda.cu:330-395): the bits
+    // of noise budget left in a BFV / BGV ciphertext in coefficient form, on the device (troyhip_noise_budget).  Throws what the reference throws:
+    // invalid_argument "encrypted is empty" (size < 2), logic_error "unsupported scheme" (CKKS), invalid_argument "encrypted cannot be in NTT form".
+    int invariantNoiseBudget(const Ciphertext &ct) const { return invariantNoiseBudgetBatch(std::vector<const Ciphertext *>{&ct})[0]; }
+    // ... of every ciphertext of a batch in ONE library call: consecutive members of one slab (Ciphertext::allocateBatch, the result of a ...Batch
+    // call) are read where they lie, anything else is packed into a slab first.  The ciphertexts must agree in shape.
+    std::vector<int> invariantNoiseBudgetBatch(const std::vector<const Ciphertext *> &items) const {
+        if (items.empty()) return {};
+        for (const Ciphertext *c : items)
+            if (!c->sameShape(*items[0])) throw std::invalid_argument("batch: ciphertexts of different shape");
+        std::vector<Ciphertext> packed;
+        const troyhip_ct *view = items[0]->raw();
+        if (items.size() > 1 && !Ciphertext::isRun(items)) {
+            packed = Ciphertext::packBatch(items);
+            view = static_cast<const Ciphertext &>(packed[0]).raw();
+        }
+        DeviceArray out(items.size());
+        check(troyhip_noise_budget(c_.handle(), view, sk_.get(), out.get(), nullptr, 0, items.size(), nullptr));
+        std::vector<uint64_t> words(items.size());
+        check(troyhip_copy_d2h(words.data(), out.get(), words.size() * 8, nullptr));
+        return std::vector<int>(words.begin(), words.end());
+    }
+    std::vector<int> invariantNoiseBudgetBatch(const std::vector<Ciphertext> &items) const { return invariantNoiseBudgetBatch(Ciphertext::pointers(items)); }
 private:
     const SEALContext &c_;
     DeviceArray sk_;

@@ -786,6 +786,21 @@ class Evaluator:
         r = out.to_numpy()
         return r.reshape(a.batch, a.limbs, N) if self.context.scheme == capi.CKKS else r.reshape(a.batch, N)
 
+    def invariantNoiseBudget(self, a, secret_key, with_norm=False):
+        """Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441) over the batch `a` (BFV / BGV, coefficient form) on the device:
+        secret_key = DeviceBuffer [K][N] (NTT form).  Returns a numpy array of `batch` budgets in bits; with_norm: also the infinity norms of
+        the noise polynomials, uint64 [batch][limbs], base 2^64, least significant word first."""
+        if secret_key.words != self.context.key_limbs * self.context.N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "secret key must hold [K][N] words")
+        out = DeviceBuffer(a.batch * (1 + (a.limbs if with_norm else 0)))
+        st = a.struct()
+        norm = C.c_void_p(out.ptr + 8 * a.batch) if with_norm else None
+        self._chk(self.lib.troyhip_noise_budget(self.context.h, C.byref(st), C.c_void_p(secret_key.ptr), C.c_void_p(out.ptr), norm, C.c_uint64(a.limbs),
+                                                C.c_uint64(a.batch), self.stream))
+        r = out.to_numpy()
+        budgets = r[:a.batch].astype(np.int64)
+        return (budgets, r[a.batch:].reshape(a.batch, a.limbs)) if with_norm else budgets
+
     def transformPlainToNtt(self, plain, limbs, n_coeffs=None, count=1):
         """transformToNttInplace(Plaintext, parms_id): returns a DeviceBuffer [count][limbs][N]."""
         n = self.context.N if n_coeffs is None else int(n_coeffs)
@@ -1096,6 +1111,21 @@ class Decryptor:
         out = np.zeros(limbs * N if ctx.scheme == CKKS else N, dtype=np.uint64)
         capi.check(self.lib, self.lib.troyhip_host_decrypt(ctx.h, _u64p(self.sk), _u64p(ct), size, limbs, int(is_ntt_form), C.c_uint64(correction_factor), _u64p(out)))
         return out.reshape(limbs, N) if ctx.scheme == CKKS else out
+
+    def invariantNoiseBudget(self, ct, is_ntt_form=False, with_norm=False):
+        """Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441), on the CPU: the bits of noise budget left in the BFV / BGV ciphertext
+        ct [size][limbs][N] (coefficient form).  with_norm: also the infinity norm of the noise polynomial as a Python integer."""
+        ctx = self.context
+        ct = np.ascontiguousarray(ct, dtype=np.uint64)
+        if ct.ndim != 3 or ct.shape[2] != ctx.N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "encrypted is not valid for encryption parameters")
+        if self.sk.size != ctx.key_limbs * ctx.N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "secret key must hold [K][N] words")
+        size, limbs, N = ct.shape
+        budget = C.c_int(0)
+        norm = np.zeros(max(limbs, 1), dtype=np.uint64)
+        capi.check(self.lib, self.lib.troyhip_host_noise_budget(ctx.h, _u64p(self.sk), _u64p(ct), size, limbs, int(is_ntt_form), C.byref(budget), _u64p(norm)))
+        return (budget.value, sum(int(w) << (64 * i) for i, w in enumerate(norm))) if with_norm else budget.value
 
 
 class BatchEncoder:

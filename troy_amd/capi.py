@@ -66,6 +66,7 @@ SYMBOLS = [
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",
+    "troyhip_host_noise_budget", "troyhip_noise_budget",
 ]
 
 _lib = None

@@ -600,6 +600,10 @@ int troyhip_host_decrypt(const troyhip_context *ctx, const uint64_t *secret_key,
                          uint64_t correction_factor, uint64_t *plain_out) {
     return guard([&] { hostcrypto::decrypt(need(ctx)->ctx, secret_key, ct, size, limbs, is_ntt_form != 0, correction_factor, plain_out); }, false);
 }
+int troyhip_host_noise_budget(const troyhip_context *ctx, const uint64_t *secret_key, const uint64_t *ct, int size, int limbs, int is_ntt_form, int *budget_out,
+                              uint64_t *norm_out) {
+    return guard([&] { hostcrypto::noise_budget(need(ctx)->ctx, secret_key, ct, size, limbs, is_ntt_form != 0, budget_out, norm_out); }, false);
+}
 
 int troyhip_host_batch_encode(const troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t *plain_out) {
     return guard([&] { hostcrypto::batch_encode(need(ctx)->ctx, values, count, plain_out); }, false);
@@ -888,6 +892,10 @@ int troyhip_context_parms_id(const troyhip_context *ctx, int limbs, uint64_t out
 int troyhip_decrypt(troyhip_context *ctx, const troyhip_ct *ct, const uint64_t *secret_key, uint64_t *plain_out, uint64_t plain_batch_stride, uint64_t batch,
                     void *stream) {
     return guard([&] { CtBatch x = view(ct); need(ctx)->ev.decrypt(x, secret_key, plain_out, plain_batch_stride, batch, on(stream)); });
+}
+int troyhip_noise_budget(troyhip_context *ctx, const troyhip_ct *ct, const uint64_t *secret_key, uint64_t *budget_out, uint64_t *norm_out, uint64_t norm_batch_stride,
+                         uint64_t batch, void *stream) {
+    return guard([&] { troyhip_context *x = need(ctx); CtBatch v = view(ct); x->ev.noise_budget(v, secret_key, budget_out, norm_out, norm_batch_stride, batch, on(stream)); });
 }
 
 } // extern "C"

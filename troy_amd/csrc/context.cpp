@@ -1,6 +1,7 @@
 // context.cpp -- see context.h.
 #include "context.h"
 #include "fpmod.h"
+#include "hostcrypto.h"
 #include "kernels.h"
 #include <algorithm>
 #include <cstdlib>
@@ -167,6 +168,19 @@ bool Context::small_launch(u64 rows, unsigned per_cu) const { return has_device 
 Context::~Context() {
     for (void *p : dev_allocs_) (void)hipFree(p);
     for (auto &kv : levels) for (void *p : kv.second.dev_blocks) (void)hipFree(p);
+}
+
+const NoiseDev &Context::noise_level(int limbs) {
+    auto it = noise_levels_.find(limbs);
+    if (it != noise_levels_.end()) return it->second;
+    const hostcrypto::NoiseLevelConsts L = hostcrypto::noise_level_consts(*this, limbs);
+    NoiseDev d;
+    d.mods = upload(L.mods, dev_allocs_);
+    d.inv = upload(L.inv, dev_allocs_);
+    if (scheme == SCHEME_BFV) d.t_factor = upload(L.t_factor, dev_allocs_);
+    d.half_digits = upload(L.half_digits, dev_allocs_);
+    d.total_bits = L.total_bits;
+    return noise_levels_[limbs] = d;
 }
 
 const Level &Context::level(int limbs) const {

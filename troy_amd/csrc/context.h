@@ -53,6 +53,14 @@ struct Level {
     std::vector<void *> dev_blocks;
 };
 
+// the constants of Decryptor::invariantNoiseBudget at one level, on the device (hostcrypto::NoiseLevelConsts; kernels.h NoiseArgs)
+struct NoiseDev {
+    const Mod *mods = nullptr;
+    const Shoup *inv = nullptr, *t_factor = nullptr;
+    const u64 *half_digits = nullptr;
+    int total_bits = 0;
+};
+
 class Context {
 public:
     // with_device = false builds the host tables only (no HIP call): enough for hostcrypto (config A plumbing)
@@ -91,12 +99,15 @@ public:
     LimbMap ct_map(int limbs) const;            // rows cycle through key primes 0..limbs-1
     LimbMap ids_map(const std::vector<uint8_t> &ids, uint32_t inner = 1) const;
     LimbMap single_map(int id) const;
+    // BFV / BGV: built on the first use of a level and kept for the lifetime of the context (the calling thread's current device must be `device`)
+    const NoiseDev &noise_level(int limbs);
 
 private:
     int register_prime(u64 p);
     void upload_tables();
     void build_level(int limbs);
     std::vector<void *> dev_allocs_;
+    std::map<int, NoiseDev> noise_levels_;
     template <class T> T *upload(const std::vector<T> &v, std::vector<void *> &owner);
 };
 

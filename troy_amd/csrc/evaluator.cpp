@@ -1,5 +1,6 @@
 // evaluator.cpp -- see evaluator.h.  Host-side orchestration only; all arithmetic is in the kernels.
 #include "evaluator.h"
+#include "hostcrypto.h"
 #include "kernels.h"
 #include <algorithm>
 #include <cmath>
@@ -802,19 +803,13 @@ void Evaluator::divide_by_degree(CtBatch &ct, u64 mul, u64 batch, hipStream_t s)
 }
 
 // ---- decryption ----
-void Evaluator::decrypt(const CtBatch &ct, const u64 *sk, u64 *out, u64 out_bstride, u64 batch, hipStream_t s) {
-    check_ct(ct);
-    if (!sk || !out) throw Error(ST_INVALID_ARGUMENT, "secret key / destination");
-    if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
-    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    const u64 N = c.N, limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;
-    const host::RnsLevel &r = c.level(ct.limbs).rns;
-    DecryptArgs a;
+u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
+    const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;
     std::memset(&a, 0, sizeof(a));
     a.primes = c.d_desc; a.map = c.ct_map(ct.limbs); a.logn = c.logn;
-    a.limbs = limbs; a.size = ct.size; a.batch = batch; a.ct_bstride = ct.bstride; a.out_bstride = out_bstride;
+    a.limbs = limbs; a.size = ct.size; a.batch = batch; a.ct_bstride = ct.bstride;
     c.arena.begin(s);
-    c.arena.reserve(batch * np * pw + np * pw + batch * pw + 512);
+    c.arena.reserve(batch * np * pw + np * pw + batch * pw + 512 + extra);
     u64 *x = c.arena.take(batch * np * pw), *spow = c.arena.take(np * pw), *acc = c.arena.take(batch * pw);
     // c_1 .. c_{size-1} in NTT form
     launch_copy_strided(ct.data + pw, ct.bstride, x, np * pw, np * pw, batch, s);
@@ -825,6 +820,19 @@ void Evaluator::decrypt(const CtBatch &ct, const u64 *sk, u64 *out, u64 out_bstr
     launch_dot_sk(x, spow, acc, a, s);
     if (!ct.ntt) launch_ntt(acc, c.d_desc, a.map, batch * limbs, c.logn, true, s);
     launch_add_c0(ct.data, acc, a, s);
+    return acc;
+}
+
+void Evaluator::decrypt(const CtBatch &ct, const u64 *sk, u64 *out, u64 out_bstride, u64 batch, hipStream_t s) {
+    check_ct(ct);
+    if (!sk || !out) throw Error(ST_INVALID_ARGUMENT, "secret key / destination");
+    if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
+    const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs);
+    const host::RnsLevel &r = c.level(ct.limbs).rns;
+    DecryptArgs a;
+    u64 *acc = dot_ct_sk(ct, sk, batch, 0, a, s);
+    a.out_bstride = out_bstride;
     if (c.scheme == SCHEME_CKKS) {
         launch_copy_strided(acc, pw, out, out_bstride, pw, batch, s);
         return;
@@ -852,6 +860,27 @@ void Evaluator::decrypt(const CtBatch &ct, const u64 *sk, u64 *out, u64 out_bstr
         if (ct.cf != 1 && !host::inv_mod(ct.cf, c.t, a.inv_cf)) throw Error(ST_LOGIC_ERROR, "invalid correction factor");
     }
     launch_decrypt_final(c.scheme, acc, out, a, s);
+}
+
+// ---- Decryptor::invariantNoiseBudget (decryptor.cpp:373-441) ----
+void Evaluator::noise_budget(const CtBatch &ct, const u64 *sk, u64 *budget, u64 *norm, u64 norm_bstride, u64 batch, hipStream_t s) {
+    check_ct(ct);
+    hostcrypto::noise_check(c, ct.size, ct.limbs, ct.ntt);
+    if (!sk || !budget) throw Error(ST_INVALID_ARGUMENT, "secret key / destination");
+    if (!batch || batch > 65535) throw Error(ST_INVALID_ARGUMENT, "batch must lie in 1 .. 65535"); // the batch is a grid dimension
+    if (norm && norm_bstride < (u64)ct.limbs) throw Error(ST_INVALID_ARGUMENT, "norm_batch_stride is smaller than the norm");
+    const NoiseDev &lv = c.noise_level(ct.limbs);
+    NoiseArgs n;
+    std::memset(&n, 0, sizeof(n));
+    n.nparts = noise_parts(c.logn);
+    const size_t partial_words = (size_t)batch * n.nparts * ct.limbs;
+    DecryptArgs a;
+    n.acc = dot_ct_sk(ct, sk, batch, partial_words + 32, a, s);
+    n.partial = c.arena.take(partial_words);
+    n.limbs = ct.limbs; n.logn = c.logn;
+    n.mods = lv.mods; n.inv = lv.inv; n.t_factor = lv.t_factor; n.half_digits = lv.half_digits; n.total_bits = lv.total_bits;
+    n.budget = budget; n.norm = norm; n.norm_bstride = norm_bstride; n.batch = batch;
+    launch_noise_budget(n, s);
 }
 
 } // namespace troyhip

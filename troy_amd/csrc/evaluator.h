@@ -38,6 +38,10 @@ public:
     // DecryptorCuda::decrypt (decryptor_cuda.cu:61-330): sk [K][N] NTT form (device); out: BFV/BGV N coefficients mod t per item
     // (stride out_bstride), CKKS the RNS plaintext [limbs][N] (NTT form)
     void decrypt(const CtBatch &ct, const u64 *sk, u64 *out, u64 out_bstride, u64 batch, hipStream_t s);
+    // Decryptor::invariantNoiseBudget (decryptor.cpp:373-441; the reference's CUDA twin has none) over a batch of BFV / BGV ciphertexts in
+    // coefficient form: budget[b] one word per item, norm (optional) `limbs` words per item, base 2^64, least significant first, norm_bstride
+    // apart.  All device memory, stream-ordered, nothing read back.
+    void noise_budget(const CtBatch &ct, const u64 *sk, u64 *budget, u64 *norm, u64 norm_bstride, u64 batch, hipStream_t s);
     // applyKeySwitchingInplace (evaluator_cuda.cu:1365-1378) and negacyclicShift (evaluator_cuda.cu:2342-2351)
     void apply_key_switching(CtBatch &ct, const KsKey &key, u64 batch, hipStream_t s);
     void negacyclic_shift(CtBatch &ct, u64 shift, u64 batch, hipStream_t s);
@@ -68,6 +72,9 @@ public:
 
 private:
     void check_ct(const CtBatch &a) const;
+    // dotProductCtSkArray: acc [batch][limbs][N] = c_0 + c_1 s + .. in the form the ciphertext is in, carved from the arena together with
+    // `extra` more words for the caller (what decrypt and noise_budget share)
+    u64 *dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, struct DecryptArgs &a, hipStream_t s);
     bool scale_ok(double scale, int limbs) const;
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void balance_correction(u64 f1, u64 f2, u64 &f, u64 &e1, u64 &e2) const;

@@ -9,6 +9,7 @@
 // reference's own Decryptor -- to the same plaintext.  Decryption is deterministic and bit-exact.
 // Nothing here touches the GPU; a host-only context (troyhip_context_create_host) is enough.
 #include "hostcrypto.h"
+#include "noise_math.h"
 #include "encoder_math.h"
 #include <algorithm>
 #include <cmath>
@@ -356,10 +357,10 @@ void encrypt_symmetric_seeded(const Context &c, Rng &rng, u64 a_seed, const u64 
     if (plain) add_message(c, P, plain, n_coeffs, limbs, ct);
 }
 
-// decryptor.cpp:115-371.  ct [size][limbs][N]; BFV/BGV: N plaintext coefficients; CKKS: [limbs][N] RNS plaintext (NTT form)
-void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt, u64 correction_factor, u64 *out) {
+// dotProductCtSkArray (decryptor.cpp:281-371): c_0 + c_1 s + .. + c_{size-1} s^{size-1} as [limbs][N], in the form the ciphertext is in -- what decrypt and
+// noise_budget share
+static std::vector<u64> dot_ct_sk(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt) {
     const size_t N = c.N;
-    if (!c.is_data_level(limbs) || size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
     std::vector<u64> acc((size_t)limbs * N, 0), tmp(N), spow(sk, sk + (size_t)limbs * N);
     for (int i = 1; i < size; i++) {
         for (int l = 0; l < limbs; l++) {
@@ -375,6 +376,14 @@ void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs
         if (!is_ntt) ntt_inverse(&acc[l * N], c.tables[l]);
         for (size_t k = 0; k < N; k++) acc[l * N + k] = addmod(acc[l * N + k], ct[l * N + k], c.primes[l]);
     }
+    return acc;
+}
+
+// decryptor.cpp:115-371.  ct [size][limbs][N]; BFV/BGV: N plaintext coefficients; CKKS: [limbs][N] RNS plaintext (NTT form)
+void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt, u64 correction_factor, u64 *out) {
+    const size_t N = c.N;
+    if (!c.is_data_level(limbs) || size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    const std::vector<u64> acc = dot_ct_sk(c, sk, ct, size, limbs, is_ntt);
     const host::RnsLevel &r = c.level(limbs).rns;
     if (c.scheme == SCHEME_CKKS) {
         std::memcpy(out, acc.data(), sizeof(u64) * limbs * N);
@@ -424,6 +433,71 @@ void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs
             out[k] = d;
         }
     }
+}
+
+// ------------------------------------------------------------------ Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441)
+NoiseLevelConsts noise_level_consts(const Context &c, int limbs) {
+    const CkksLevelConsts L = ckks_level_consts(c, limbs); // q, (q + 1) >> 1 and the Garner inverses: nothing in them is specific to CKKS
+    NoiseLevelConsts n;
+    n.total = L.total;
+    n.half = L.half;
+    n.inv = L.inv;
+    n.total_bits = L.total_bits;
+    std::vector<u64> h = L.half; // the mixed-radix digits of half: divide by q_0, q_1, .. and keep the remainders
+    for (int i = 0; i < limbs; i++) {
+        const u64 p = c.primes[i];
+        n.mods.push_back(make_mod(p));
+        n.t_factor.push_back(c.scheme == SCHEME_BFV ? make_shoup(c.t % p, p) : make_shoup(1, p));
+        u64 rem = 0;
+        for (int w = limbs; w-- > 0;) {
+            const u128 cur = ((u128)rem << 64) | h[w];
+            h[w] = (u64)(cur / p);
+            rem = (u64)(cur % p);
+        }
+        n.half_digits.push_back(rem);
+    }
+    return n;
+}
+
+void noise_check(const Context &c, int size, int limbs, bool is_ntt) {
+    if (!c.is_data_level(limbs) || size < 1) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted is empty");
+    if (c.scheme != SCHEME_BFV && c.scheme != SCHEME_BGV) throw Error(ST_LOGIC_ERROR, "unsupported scheme");
+    if (is_ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted cannot be in NTT form");
+}
+
+// The specification of the device path (noise.hip): per coefficient the factor t (BFV), the Garner digits and the base-2^64 composition, then
+// polyInftyNormCoeffmod word by word -- where the kernels stay in mixed radix and compose the maximum alone.
+void noise_budget(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt, int *budget, u64 *norm) {
+    if (!ct) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    noise_check(c, size, limbs, is_ntt);
+    if (!sk || !budget) throw Error(ST_INVALID_ARGUMENT, "secret key / destination");
+    const size_t N = c.N;
+    const std::vector<u64> acc = dot_ct_sk(c, sk, ct, size, limbs, false);
+    const NoiseLevelConsts L = noise_level_consts(c, limbs);
+    const bool bfv = c.scheme == SCHEME_BFV;
+    std::vector<u64> digit(limbs), word(limbs), best(limbs, 0);
+    auto greater_eq = [&](const std::vector<u64> &a, const std::vector<u64> &b) { // isGreaterThanOrEqualUint
+        for (int w = limbs; w-- > 0;)
+            if (a[w] != b[w]) return a[w] > b[w];
+        return true;
+    };
+    for (size_t k = 0; k < N; k++) {
+        noise_garner(limbs, [&](int i) { return bfv ? mul_shoup(acc[i * N + k], L.t_factor[i], L.mods[i].p) : acc[i * N + k]; },
+                     [&](int i) -> u64 & { return digit[i]; }, L.inv.data(), L.mods.data());
+        noise_compose(limbs, [&](int i) { return digit[i]; }, [&](int w) -> u64 & { return word[w]; }, L.mods.data());
+        if (greater_eq(word, L.half)) { // q - x
+            u64 borrow = 0;
+            for (int w = 0; w < limbs; w++) {
+                const u64 a = L.total[w], b = word[w], d = a - b - borrow;
+                borrow = (a < b) || (a == b && borrow);
+                word[w] = d;
+            }
+        }
+        if (!greater_eq(best, word)) best = word;
+    }
+    *budget = noise_budget_of(L.total_bits, noise_bit_length(limbs, [&](int w) { return best[w]; }));
+    if (norm) std::memcpy(norm, best.data(), sizeof(u64) * limbs);
 }
 
 // ------------------------------------------------------------------ BatchEncoder (src/batchencoder.cpp)

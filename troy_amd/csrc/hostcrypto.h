@@ -33,6 +33,20 @@ void encrypt_zero_symmetric(const Context &c, Rng &rng, const u64 *sk, int limbs
 void expand_seed(const Context &c, u64 a_seed, int limbs, u64 *c1);
 void encrypt_symmetric_seeded(const Context &c, Rng &rng, u64 a_seed, const u64 *sk, const u64 *plain, size_t n_coeffs, int limbs, u64 *ct); // plain == nullptr: zero
 void decrypt(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt, u64 correction_factor, u64 *out);
+// Decryptor::invariantNoiseBudget (src/decryptor.cpp:373-441), BFV / BGV in coefficient form: noise = c_0 + c_1 s + .. (times t for BFV) mod q,
+// norm = max |centred coefficient|, *budget = max(0, bitlength(q) - bitlength(norm) - 1); norm (optional): `limbs` words, base 2^64, least
+// significant first.  Refuses as the reference does: size < 2 "encrypted is empty", CKKS "unsupported scheme" (logic error), NTT form.
+void noise_budget(const Context &c, const u64 *sk, const u64 *ct, int size, int limbs, bool is_ntt, int *budget, u64 *norm);
+void noise_check(const Context &c, int size, int limbs, bool is_ntt); // those refusals alone (the device form runs the same ones)
+// per-level constants of both forms: q and (q + 1) >> 1 in base 2^64, the primes with their Barrett constants, inv[i][j] = q_j^-1 mod q_i (j < i),
+// t mod q_i (BFV; 1 for BGV) as Shoup operands, and the mixed-radix digits of (q + 1) >> 1 (noise_math.h)
+struct NoiseLevelConsts {
+    std::vector<u64> total, half, half_digits;
+    std::vector<Mod> mods;
+    std::vector<Shoup> inv, t_factor;
+    int total_bits = 0;
+};
+NoiseLevelConsts noise_level_consts(const Context &c, int limbs);
 // BatchEncoder (src/batchencoder.cpp:61-190): `count` <= N slot values modulo t <-> the plaintext polynomial [N] (coefficient form)
 void batch_encode(const Context &c, const u64 *values, size_t count, u64 *plain);
 void batch_decode(const Context &c, const u64 *plain, size_t n_coeffs, u64 *values);

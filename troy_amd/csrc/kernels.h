@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (ntt.hip, poly.hip, behz.hip).
+// kernels.h -- launch interface of the gfx950 kernels (ntt.hip, poly.hip, behz.hip, ...).
 #pragma once
 #include "device_types.h"
 
@@ -340,5 +340,18 @@ struct CkksDecArgs {
     Cplx *A; double *values; u64 vstride; u64 batch;
 };
 void launch_ckks_decode(const CkksDecArgs &a, hipStream_t s);
+
+// ---- noise.hip: Decryptor::invariantNoiseBudget over a batch (Evaluator::noise_budget; hostcrypto::noise_budget is the specification) ----
+// acc [batch][limbs][N] coefficient form, canonical residues (the front half of decryption) -> budget[b], norm[b * norm_bstride + w] (norm may be
+// nullptr; `limbs` words, base 2^64, least significant first).  mods / inv / t_factor / half_digits: the level's constants on the device
+// (hostcrypto::NoiseLevelConsts; t_factor == nullptr: no factor, BGV);  partial: scratch [batch][nparts][limbs], nparts = noise_parts(logn)
+struct NoiseArgs {
+    const u64 *acc; int limbs, logn;
+    const Mod *mods; const Shoup *inv, *t_factor; const u64 *half_digits; int total_bits;
+    u64 *partial; unsigned nparts;
+    u64 *budget, *norm; u64 norm_bstride, batch;
+};
+unsigned noise_parts(int logn);
+void launch_noise_budget(const NoiseArgs &a, hipStream_t s);
 
 } // namespace troyhip
