@@ -35,12 +35,26 @@ CONFIGS = {
     "ckks_n16384_k4": dict(scheme=CKKS, N=16384, bits=[50, 40, 40, 50], tbits=0),
     "bfv_n131072_k3": dict(scheme=BFV, N=131072, bits=[50, 50, 50], tbits=20),       # largest N: 10-stage contiguous pass, unfused paths
     "cfgD_bgv_n65536_k15": dict(scheme=BGV, N=65536, bits=[60] + [50] * 13 + [60], tbits=20),  # relinearize + rotateRows
+    # coefficient primes below 2^33 at real ring sizes (every kernel family branches there: guarded butterflies in the single-pass transform, the FP64
+    # instances with a wide source / narrow output ratio, BEHZ on the matrix cores with the two-word q-side reduction instead of the one-step estimate, the element-wise rescale / mod-down)
+    "nar_bfv_n4096_k3": dict(scheme=BFV, N=4096, bits=[30, 25, 32], tbits=20),            # all narrow
+    "nar_bgv_n4096_k4": dict(scheme=BGV, N=4096, bits=[27, 31, 20, 33], tbits=17),        # all narrow (the 20-bit batching prime IS the 20-bit coefficient prime: t of 17 bits)
+    "nar_bgv_n8192_k4": dict(scheme=BGV, N=8192, bits=[60, 22, 24, 60], tbits=20),        # narrow data primes under 60-bit ends
+    "nar_bfv_n8192_k4": dict(scheme=BFV, N=8192, bits=[50, 58, 45, 22], tbits=20),        # narrow special prime: the mod-down divides by a P below every q_i
+    "nar_ckks_n16384_k5": dict(scheme=CKKS, N=16384, bits=[32, 25, 28, 30, 31], tbits=0),  # all narrow
+    "nar_ckks_n32768_k5": dict(scheme=CKKS, N=32768, bits=[60, 30, 28, 26, 60], tbits=0),  # narrow data primes under 60-bit ends
+    "nar_bfv_n32768_k4": dict(scheme=BFV, N=32768, bits=[32, 33, 34, 33], tbits=20),      # straddles 2^33: a 33-bit prime lies below it, a 34-bit one above
+    "nar_bgv_n65536_k4": dict(scheme=BGV, N=65536, bits=[30, 30, 30, 60], tbits=20),      # a two-pass size
 }
+NARROW = ["nar_bfv_n4096_k3", "nar_bgv_n4096_k4", "nar_bgv_n8192_k4", "nar_bfv_n8192_k4", "nar_ckks_n16384_k5", "nar_ckks_n32768_k5", "nar_bfv_n32768_k4",
+          "nar_bgv_n65536_k4"]
 SMALL = ["bfv_n64_k3", "bfv_n128_k4", "bfv_n128_k5_60", "ckks_n128_k6", "bgv_n128_k4"]
-MEDIUM = ["cfgA_bfv_n4096_k3", "cfgB_bfv_n8192_k5", "ckks_n4096_k4", "bgv_n4096_k3"]
-LARGE = ["cfgNS_bfv_n32768_k15", "cfgC_ckks_n32768_k15", "cfgD_bgv_n65536_k15"]
-CHAIN = ["ckks_n128_k6", "ckks_n4096_k4", "cfgC_ckks_n32768_k15"]  # scenario_chain (depth 3; ckks_n4096_k4 has 3 data levels: depth 2 there)
-SIZES = ["bfv_n64_k3", "bfv_n128_k5_60", "ckks_n128_k6", "bgv_n128_k4", "cfgA_bfv_n4096_k3", "ckks_n4096_k4", "bgv_n4096_k3"]  # scenario_sizes
+MEDIUM = ["cfgA_bfv_n4096_k3", "cfgB_bfv_n8192_k5", "ckks_n4096_k4", "bgv_n4096_k3"] + [n for n in NARROW if CONFIGS[n]["N"] <= 8192]
+LARGE = ["cfgNS_bfv_n32768_k15", "cfgC_ckks_n32768_k15", "cfgD_bgv_n65536_k15"] + [n for n in NARROW if CONFIGS[n]["N"] > 8192]
+CHAIN = ["ckks_n128_k6", "ckks_n4096_k4", "cfgC_ckks_n32768_k15",  # scenario_chain (depth 3; ckks_n4096_k4 has 3 data levels: depth 2 there)
+         "nar_ckks_n16384_k5", "nar_ckks_n32768_k5"]
+SIZES = ["bfv_n64_k3", "bfv_n128_k5_60", "ckks_n128_k6", "bgv_n128_k4", "cfgA_bfv_n4096_k3", "ckks_n4096_k4", "bgv_n4096_k3",  # scenario_sizes
+         "nar_bfv_n4096_k3", "nar_bgv_n4096_k4"]
 
 KEY_STEPS = (1, -1, 4)  # Galois keys present; rotations by 5 = naf [1, 4] and 3 = naf [-1, 4] exercise the NAF path
 SEED = 0x5EED
@@ -219,14 +233,14 @@ class _EvalBackend:
 
 def ref_backend(cfg):
     from oracle import ref
-    primes = ref.coeff_modulus_create(cfg["N"], cfg["bits"])
+    primes = cfg.get("primes") or ref.coeff_modulus_create(cfg["N"], cfg["bits"])
     t = ref.plain_batching(cfg["N"], cfg["tbits"]) if cfg["scheme"] != CKKS else 0
     return _EvalBackend(ref, cfg, primes, t)
 
 
 def oracle_backend(cfg):
     from oracle import oracle
-    primes = oracle.coeff_modulus_create(cfg["N"], cfg["bits"])
+    primes = cfg.get("primes") or oracle.coeff_modulus_create(cfg["N"], cfg["bits"])  # "primes": an explicit list instead of CoeffModulus.Create(bits)
     t = oracle.plain_batching(cfg["N"], cfg["tbits"]) if cfg["scheme"] != CKKS else 0
     return _EvalBackend(oracle, cfg, primes, t)
 
@@ -237,7 +251,7 @@ class GpuBackend:
     def __init__(self, cfg, batch=1):
         from troy_amd import api
         self.api, self.cfg, self.batch = api, cfg, batch
-        self.primes = api.CoeffModulus.Create(cfg["N"], cfg["bits"])
+        self.primes = cfg.get("primes") or api.CoeffModulus.Create(cfg["N"], cfg["bits"])
         self.t = api.PlainModulus.Batching(cfg["N"], cfg["tbits"]) if cfg["scheme"] != CKKS else 0
         self.ctx = api.SEALContext(cfg["scheme"], cfg["N"], self.primes, self.t)
         self.ev = api.Evaluator(self.ctx)
@@ -559,14 +573,15 @@ def check_ckks_conv2d_helper(N=4096, bits=(40, 30, 30, 40), batch=2, image=(12, 
     return h
 
 
-def check_bfv_multiply_limb_count(K, N=256, batch=2, seed=900, big=False):
+def check_bfv_multiply_limb_count(K, N=256, batch=2, seed=900, big=False, tbits=14):
     """BFV multiply (both BEHZ kernels) at L = K - 1 limbs against the oracle: L runs over every k-block count of the matrix-core
     kernels and, past 15 limbs, over the VALU kernels.  big=False: 40/45-bit primes (6 digit rows per q-side output), big=True:
     55/60-bit primes (the headline's case), big="small": 30/32-bit primes (below 2^33 the q side of Shenoy-Kumaresan takes the
-    two-word reduction).  The last batch items are extreme inputs: every residue p - 1, and a 0 / 1 pattern."""
+    two-word reduction), big="narrow": 22/25-bit primes.  The last batch items are extreme inputs: every residue p - 1, and a 0 / 1 pattern."""
     from troy_amd import api, synth
-    bits = {True: [60] + [55] * (K - 2) + [60], False: [45] + [40] * (K - 2) + [45], "small": [32] + [30] * (K - 2) + [32]}[big]
-    cfg = dict(scheme=BFV, N=N, bits=bits, tbits=14)
+    bits = {True: [60] + [55] * (K - 2) + [60], False: [45] + [40] * (K - 2) + [45], "small": [32] + [30] * (K - 2) + [32],
+            "narrow": [25] + [22] * (K - 2) + [25]}[big]
+    cfg = dict(scheme=BFV, N=N, bits=bits, tbits=tbits)  # (no batching prime of 14 bits from N = 4096 on: the larger sizes pass 17)
     be, ob = GpuBackend(cfg), oracle_backend(cfg)
     L = K - 1
     xa, xb = synth.uniform_ct(seed + K, be.primes[:L], 2, N, batch + 2), synth.uniform_ct(seed + 50 + K, be.primes[:L], 2, N, batch + 2)
@@ -616,7 +631,7 @@ def check_multiply_plain_accumulate(N=256, batch=3):
             raise AssertionError("multiplyPlainAccumulate accepted a bad argument")
 
 
-def random_config(seed, sizes=(256, 1024, 4096), pool=None):
+def random_config(seed, sizes=(256, 1024, 4096), pool=None, clamp_ckks=True):
     """a seeded random parameter set: scheme, N, 2..6 primes whose sizes sit on the thresholds the kernels branch on (2^33: BEHZ one-step
     reduction and guard-free butterflies start; 2^50: Bsk-sized; 2^58: guard-free butterflies end; 60 bits: largest allowed)"""
     rng = np.random.default_rng(seed)
@@ -625,16 +640,16 @@ def random_config(seed, sizes=(256, 1024, 4096), pool=None):
     K = int(rng.integers(2, 7))
     pool = pool or [33, 34, 36, 40, 45, 49, 50, 51, 55, 57, 58, 59, 60]
     bits = [int(rng.choice(pool)) for _ in range(K)]
-    if scheme == CKKS:  # rescaling divides by the last data prime: keep the primes at least as large as a sensible scale
-        bits = [max(b, 36) for b in bits]
+    if scheme == CKKS and clamp_ckks:  # rescaling divides by the last data prime: keep the primes at least as large as a sensible scale
+        bits = [max(b, 36) for b in bits]  # (clamp_ckks=False: the widths as drawn -- the arithmetic is exact at any width)
     return dict(scheme=scheme, N=N, bits=bits, tbits=int(rng.integers(14, 21)))
 
 
-def check_random_config(seed, sizes=(256, 1024, 4096), batch=2, light=False, pool=None):
+def check_random_config(seed, sizes=(256, 1024, 4096), batch=2, light=False, pool=None, clamp_ckks=True):
     """the whole op list of `scenario` (every level, every op) on a random parameter set: product vs CPU oracle, limb for limb"""
     from oracle import oracle
     from troy_amd import api
-    cfg = random_config(seed, sizes, pool)
+    cfg = random_config(seed, sizes, pool, clamp_ckks)
     if cfg["scheme"] != CKKS:  # not every size has a batching prime (N = 4096: none of 14 or 15 bits): both sides must say so, then move up
         while True:
             ours = theirs = None

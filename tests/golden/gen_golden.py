@@ -3,6 +3,7 @@
 /root/reference by oracle/Makefile).  Run in the build container only:
 
     python tests/golden/gen_golden.py
+    python tests/golden/gen_golden.py --add    # only the configurations the JSON files do not hold yet: existing entries stay byte-identical
 
 Outputs (data only -- inputs are regenerated from seeds by troy_amd.synth, see tests/cases.py):
   golden_full_<cfg>.npz   every scenario output limb-for-limb (small N)
@@ -31,6 +32,45 @@ def meta_dict(m):
     return dict(sha256=cases.sha(m.data), shape=list(m.data.shape), is_ntt=m.is_ntt, scale=m.scale, cf=m.cf)
 
 
+def params_of(be):
+    R = be.impl
+    K = len(be.primes)
+    p = dict(primes=[str(x) for x in be.primes], plain_modulus=str(R.t), chain=list(R.chain()), levels={}, tables={})
+    for limbs in range(R.chain()[2], K + 1):
+        bsk, gamma = R.behz_bases(limbs)
+        p["levels"][str(limbs)] = dict(bsk=[str(x) for x in bsk], gamma=str(gamma))
+    for i in range(K):
+        t = R.ntt_tables(i)
+        p["tables"][str(be.primes[i])] = dict(root=str(t["root"]), inv_degree=[str(x) for x in t["inv_degree"]],
+                                              root_op=cases.sha(t["root_op"]), root_quo=cases.sha(t["root_quo"]),
+                                              inv_op=cases.sha(t["inv_op"]), inv_quo=cases.sha(t["inv_quo"]),
+                                              head=[str(x) for x in t["root_op"][:4]])
+    return p
+
+
+def add_missing():
+    """hashes / params / sizes / chain of the configurations of tests/cases.py that the files do not hold yet; nothing else is rewritten"""
+    def merge(fname, names, make):
+        path = os.path.join(HERE, fname)
+        cur = json.load(open(path))
+        new = [n for n in names if n not in cur]
+        for name in new:
+            cur[name] = make(name)
+            print(fname, "+", name)
+        if new:
+            json.dump(cur, open(path, "w"), indent=1, sort_keys=True)
+
+    def hashes(name):
+        cfg = cases.CONFIGS[name]
+        return {k: meta_dict(v) for k, v in cases.scenario(cases.ref_backend(cfg), cfg, light=name in cases.LARGE).items()}
+
+    every = cases.SMALL + cases.MEDIUM + cases.LARGE
+    merge("golden_hashes.json", every, hashes)
+    merge("golden_params.json", every, lambda n: params_of(cases.ref_backend(cases.CONFIGS[n])))
+    merge("golden_sizes.json", cases.SIZES, lambda n: {k: meta_dict(v) for k, v in cases.scenario_sizes(cases.ref_backend(cases.CONFIGS[n]), cases.CONFIGS[n]).items()})
+    merge("golden_chain.json", cases.CHAIN, lambda n: {k: meta_dict(v) for k, v in cases.scenario_chain(cases.ref_backend(cases.CONFIGS[n]), cases.CONFIGS[n]).items()})
+
+
 def sizes_only():
     sizes = {}
     for name in cases.SIZES:
@@ -55,28 +95,18 @@ def main():
         return sizes_only()
     if "--chain-only" in sys.argv:  # ... golden_chain.json
         return chain_only()
+    if "--add" in sys.argv:
+        return add_missing()
     hashes, params, sizes = {}, {}, {}
     for name in cases.SMALL + cases.MEDIUM + cases.LARGE:
         cfg = cases.CONFIGS[name]
         be = cases.ref_backend(cfg)
-        R = be.impl
         light = name in cases.LARGE
         out = cases.scenario(be, cfg, light=light)
         hashes[name] = {k: meta_dict(v) for k, v in out.items()}
         if name in cases.SIZES:
             sizes[name] = {k: meta_dict(v) for k, v in cases.scenario_sizes(cases.ref_backend(cfg), cfg).items()}
-        K = len(be.primes)
-        p = dict(primes=[str(x) for x in be.primes], plain_modulus=str(R.t), chain=list(R.chain()), levels={}, tables={})
-        for limbs in range(R.chain()[2], K + 1):
-            bsk, gamma = R.behz_bases(limbs)
-            p["levels"][str(limbs)] = dict(bsk=[str(x) for x in bsk], gamma=str(gamma))
-        for i in range(K):
-            t = R.ntt_tables(i)
-            p["tables"][str(be.primes[i])] = dict(root=str(t["root"]), inv_degree=[str(x) for x in t["inv_degree"]],
-                                                  root_op=cases.sha(t["root_op"]), root_quo=cases.sha(t["root_quo"]),
-                                                  inv_op=cases.sha(t["inv_op"]), inv_quo=cases.sha(t["inv_quo"]),
-                                                  head=[str(x) for x in t["root_op"][:4]])
-        params[name] = p
+        params[name] = params_of(be)
         if name == "bfv_n64_k3":
             np.savez_compressed(os.path.join(HERE, f"golden_full_{name}.npz"), **{k: v.data for k, v in out.items()})
         print("done", name, len(out), "outputs")

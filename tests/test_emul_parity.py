@@ -117,7 +117,7 @@ def test_emulated_moddown_shared_first_pass_fp_bounds(scheme, emul_api, oracle_l
     cases.check_moddown_shared_first_pass(scheme, N=4096, bits=(44, 45, 49))
 
 
-@pytest.mark.parametrize("name", ["bfv_n64_k3", "ckks_n128_k6", "cfgA_bfv_n4096_k3", "bgv_n4096_k3", "ckks_n4096_k4"])
+@pytest.mark.parametrize("name", ["bfv_n64_k3", "ckks_n128_k6", "cfgA_bfv_n4096_k3", "bgv_n4096_k3", "ckks_n4096_k4", "nar_bfv_n4096_k3", "nar_bgv_n4096_k4"])
 def test_emulated_relinearize_out_of_place(name, emul_api):
     cases.check_relinearize_out_of_place(name, batch=2)
 
@@ -402,3 +402,51 @@ def test_emulated_single_pass_ntt_small_sizes(oracle_lib, tmp_path):
     assert got["single"][:3] == got["twopass"][:3] == got["xcd2"][:3] == got["xcd3"][:3]
     assert int(got["single"][3]) >= 12 and int(got["twopass"][3]) == 0  # the single-pass kernels really ran (plain inverse, special limb, mod-down epilogue)
     assert int(got["xcd2"][3]) >= 12 and int(got["xcd3"][3]) >= 12
+
+
+# ------------------------------------------------------------------ coefficient primes below 2^33 (tests/narrow_cases.py; the GPU claim is tests/test_gpu_narrow_primes.py)
+@pytest.mark.parametrize("name", [n for n in cases.NARROW if cases.CONFIGS[n]["N"] <= 4096])
+def test_emulated_narrow_named_sets(name, emul_api, oracle_lib, golden_hashes):
+    """the all-narrow sets at N = 4096: every op at every level against the oracle (which test_oracle_golden pins to the reference's hashes), then the
+    batched op list of the large-plan check at a batch of three"""
+    import narrow_cases as NP
+    assert NP.check_named_small_plan(name) == len(golden_hashes[name])
+    NP.check_named_large_plan(name, batch=3)
+
+
+@pytest.mark.parametrize("logn", [6, 12])
+def test_emulated_ntt_width_matrix(logn, emul_api, oracle_lib):
+    """the smallest NTT prime, 20 .. 34-bit primes and a 60-bit one in one call; uniform, zero, p - 1, alternating and delta rows; the path counters"""
+    import narrow_cases as NP
+    NP.check_ntt_widths(emul_api, oracle_lib, logn, "ragged", "generic")
+    NP.check_ntt_widths(emul_api, oracle_lib, logn, "even", "ntt2" if logn >= 12 else "generic")
+    if logn >= 12:
+        NP.check_ntt_convolution(emul_api, logn)
+
+
+@pytest.mark.parametrize("env,fp64", [({"TROYHIP_NTT": "single"}, True), ({"TROYHIP_NTT": "single", "TROYHIP_FP64": "off"}, False), ({"TROYHIP_FP64": "off"}, False)])
+def test_emulated_ntt_width_matrix_under_switches(env, fp64, oracle_lib, tmp_path):
+    """the same at N = 2^12 in child processes: the single-pass kernels forced (guarded butterflies below 2^33), the integer kernels for every prime"""
+    import sys
+    script = tmp_path / "w.py"
+    script.write_text(
+        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from troy_amd import api, capi\n"
+        "from oracle import oracle\n"
+        "api.KernelProvider.initialize(0, _lib=capi.load(%r))\n"
+        "import narrow_cases as NP\n"
+        "NP.check_ntt_widths(api, oracle, 12, 'even', %r, fp64=%r)\n"
+        "print('ok')\n" % (ROOT, os.path.join(ROOT, "tests"), EMUL, "ntt1" if "TROYHIP_NTT" in env else "ntt2", fp64))
+    out = subprocess.run([sys.executable, str(script)], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
+NARROW_SEEDS = [401, 402, 403, 404, 405, 406, 407, 408]
+
+
+@pytest.mark.parametrize("seed", NARROW_SEEDS)
+def test_emulated_random_narrow_parameter_sets(seed, emul_api, oracle_lib):
+    """the whole op list on seeded sets of 18 .. 60-bit primes, the CKKS widths as drawn; a set both sides reject is no pass"""
+    import narrow_cases as NP
+    cfg, n = NP.check_narrow_random(seed, (64, 128, 256))
+    assert n is not None and n > 10, cfg

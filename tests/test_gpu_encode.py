@@ -17,6 +17,9 @@ BENCH = {  # bench.py's workload parameters
 SMALL = cases.SMALL + ["cfgA_bfv_n4096_k3", "ckks_n4096_k4", "bgv_n4096_k3"]
 
 
+NARROW = ["nar_bgv_n8192_k4", "nar_bfv_n4096_k3"]  # narrow data primes under 60-bit ends, and an all-narrow set (primes of 22 .. 32 bits)
+
+
 @pytest.fixture(scope="module")
 def gpu_api():
     from troy_amd import api
@@ -39,6 +42,25 @@ def test_small_configs_match_host(name, gpu_api):
         for batch in (1, 3, 17):
             for count in (0, ctx.N // 3, ctx.N):
                 E.check_bfv(ctx, batch, count, rng, pad=5 if batch == 3 else 0)
+
+
+@pytest.mark.parametrize("name", NARROW)
+def test_narrow_primes_match_host(name, gpu_api):
+    """BFV / BGV batch encoding under primes of 22 .. 32 bits (the plaintext side is t alone; the context tables are the narrow set's)"""
+    ctx = E.context(cases.CONFIGS[name])
+    rng = np.random.default_rng(ctx.N + 1)
+    for batch in (1, 3, 17):
+        for count in (0, ctx.N // 3, ctx.N):
+            E.check_bfv(ctx, batch, count, rng, pad=5 if batch == 3 else 0)
+
+
+def test_narrow_ckks_primes_match_host(gpu_api):
+    """CKKS encoding into residues of 25 .. 32-bit primes at every level: the Garner digits / base-2^64 composition over narrow moduli"""
+    ctx = E.context(cases.CONFIGS["nar_ckks_n16384_k5"])
+    rng = np.random.default_rng(ctx.N + 2)
+    for limbs in E.levels(ctx):
+        for scale in (2.0**20, 2.0**40, 2.0**80):
+            E.check_ckks(ctx, 3, ctx.N // 2, limbs, scale, rng, complex_=True, pad=7)
 
 
 @pytest.mark.parametrize("name", sorted(BENCH))

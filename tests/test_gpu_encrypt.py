@@ -18,6 +18,9 @@ BENCH = {  # bench.py's workload parameters
 }
 
 
+NARROW = ["nar_bgv_n8192_k4", "nar_bfv_n4096_k3"]  # narrow data primes under 60-bit ends, and an all-narrow set (primes of 22 .. 32 bits)
+
+
 @pytest.fixture(scope="module")
 def gpu_api():
     from troy_amd import api
@@ -34,6 +37,16 @@ def test_small_shapes_match_host(name, gpu_api):
             for batch in (1, 3, 17):
                 E.check_form(S, form, limbs, batch)
             E.check_form(S, form, limbs, 3, per_item=False, pad=S.N)
+
+
+@pytest.mark.parametrize("name", NARROW)
+def test_narrow_primes_match_host(name, gpu_api):
+    """primes of 22 .. 32 bits: the uniform sampler rejects against tiny moduli; every form at the first level, encryptions of zero at every level"""
+    S = E.Setup.from_cfg(cases.CONFIGS[name])
+    for form in E.FORMS:
+        for limbs in (S.data_levels() if form.endswith("0") else [S.ctx.first_limbs]):
+            E.check_form(S, form, limbs, 5)
+        E.check_form(S, form, S.ctx.first_limbs, 3, per_item=False, pad=S.N)
 
 
 def test_rejecting_primes_match_host(gpu_api):

@@ -22,6 +22,9 @@ BENCH = {  # bench.py's workload parameters
 }
 
 
+NARROW = ["nar_bgv_n8192_k4", "nar_bfv_n4096_k3"]  # narrow data primes under 60-bit ends, and an all-narrow set (primes of 22 .. 32 bits)
+
+
 @pytest.fixture(scope="module")
 def gpu_api():
     from troy_amd import api
@@ -39,6 +42,18 @@ def test_small_shapes_match_host(name, gpu_api):
     G.check_relin(S)
     G.check_kswitch(S)
     G.check_galois(S, S.kg.galoisEltsAll() + S.kg.automorphismElts() + [3])
+
+
+@pytest.mark.parametrize("name", NARROW)
+def test_narrow_primes_match_host(name, gpu_api):
+    """primes of 22 .. 32 bits: secret / public key, relin key, a key-switch key and Galois keys byte-identical to the host KeyGenerator"""
+    S = G.Setup.from_cfg(cases.CONFIGS[name])
+    G.check_keygen(S, 3, with_pk=True)
+    G.check_keygen(S, 3, with_pk=False, pad=S.N + 5)
+    G.check_relin(S)
+    G.check_kswitch(S)
+    elts = S.kg.galoisEltsAll()
+    G.check_galois(S, elts, items=[0, len(elts) // 2, len(elts) - 1])
 
 
 def test_rejecting_primes_n4096(gpu_api):

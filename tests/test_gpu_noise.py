@@ -11,6 +11,9 @@ from troy_amd import capi
 pytestmark = pytest.mark.gpu
 
 
+NARROW = ["nar_bgv_n8192_k4", "nar_bfv_n4096_k3"]  # narrow data primes under 60-bit ends, and an all-narrow set (primes of 22 .. 32 bits)
+
+
 @pytest.fixture(scope="module")
 def gpu_api():
     from troy_amd import api
@@ -23,7 +26,7 @@ _setups = {}
 
 def setup_of(name):
     if name not in _setups:
-        _setups[name] = NC.Setup(NC.CONFIGS[name], relin=name not in NC.BENCH)
+        _setups[name] = NC.Setup(NC.CONFIGS[name] if name in NC.CONFIGS else cases.CONFIGS[name], relin=name not in NC.BENCH)
     return _setups[name]
 
 
@@ -73,6 +76,19 @@ def test_device_matches_host(name, gpu_api):
         for size in (2, 3):
             for batch, pad in (((1, 0), (3, 5), (17, 0)) if small else ((3, 5),)):
                 NC.check_device_matches_host(S, batch, size, limbs, pad, ref=ref)
+
+
+@pytest.mark.parametrize("name", NARROW)
+def test_narrow_primes_device_matches_host(name, gpu_api):
+    """primes of 22 .. 32 bits: the Garner digits and the base-2^64 composition of the noise norm over narrow moduli -- budgets and norms of real
+    ciphertexts of size 2 and 3 at every level equal the host form's, and every boundary target at the first and the last level"""
+    S = setup_of(name)
+    ref = NC.make_ref(S)
+    for limbs in S.levels():
+        for size in (2, 3):
+            NC.check_device_matches_host(S, 3, size, limbs, 5, ref=ref)
+    for limbs in (S.ctx.first_limbs, S.ctx.last_limbs):
+        NC.check_boundaries_device(S, limbs)
 
 
 @pytest.mark.parametrize("name", ["cfgB_bfv_n8192_k5"] + sorted(NC.BENCH))

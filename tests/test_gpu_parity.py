@@ -178,20 +178,25 @@ def test_single_pass_ntt_vs_oracle_incl_extremes(gpu, oracle_lib):
 
 
 def test_single_pass_ntt_xcd_order_vs_oracle(gpu, oracle_lib):
-    """a single-pass launch large enough for the XCD-aware workgroup order (ntt1.hip n1_unit: 15 primes x 200 rows -> more than two rounds of workgroups,
-    a list length that is not a multiple of 8: the padded last eighth) against the oracle, EVERY row, forward and inverse"""
-    from troy_amd import synth
+    """single-pass launches on both sides of the XCD-aware workgroup order (ntt1.hip n1_unit) against the oracle, EVERY row, forward and inverse: 15 primes x
+    201 and x 401 rows.  At 401 the planner gives the thirteen 58-bit primes 7 rows per workgroup: 13 x 58 = 754 workgroups, more than two rounds of the
+    chip and not a multiple of 8 (the padded last eighth), and the counter says the order ran.  At 201 -- the only count this test had at first -- it
+    gives them 11 rows: ONE round of 247 workgroups, flat order, counter unchanged: the threshold on record (docs/LAB_NOTEBOOK.md, narrow primes)."""
+    from troy_amd import capi, synth
     N = 32768
     kp = gpu.CoeffModulus.Create(N, [60] + [58] * 13 + [60])
     ctx = gpu.SEALContext(gpu.BFV, N, kp, gpu.PlainModulus.Batching(N, 20))
-    rows = 15 * 201
-    x = synth.uniform_rows(78, kp, rows, N)
-    for mode, inverse in ((1, False), (3, True)):
-        buf = gpu.DeviceBuffer.from_numpy(x)
-        ctx.ntt(buf, rows, kp, inverse=inverse)
-        y = buf.to_numpy().reshape(rows, N)
-        for r in range(rows):
-            assert np.array_equal(y[r], oracle_lib.ntt_standalone(N, kp[r % 15], x[r], mode)), (mode, r)
+    for per_prime, xcd in ((201, 0), (401, 1)):
+        rows = 15 * per_prime
+        x = synth.uniform_rows(78, kp, rows, N)
+        x0 = capi.stat("ntt1_xcd_launches")
+        for mode, inverse in ((1, False), (3, True)):
+            buf = gpu.DeviceBuffer.from_numpy(x)
+            ctx.ntt(buf, rows, kp, inverse=inverse)
+            y = buf.to_numpy().reshape(rows, N)
+            for r in range(rows):
+                assert np.array_equal(y[r], oracle_lib.ntt_standalone(N, kp[r % 15], x[r], mode)), (per_prime, mode, r)
+        assert capi.stat("ntt1_xcd_launches") == x0 + 2 * xcd, (per_prime, "the XCD-aware workgroup order: taken from two rounds of workgroups on, not below")
 
 
 def test_wide_strided_pass_at_a_large_batch(gpu):
@@ -338,6 +343,40 @@ def test_error_conventions(gpu):
         gpu.SEALContext(gpu.BFV, 128, [be.primes[0], be.primes[0]], be.t)  # duplicate primes
     with pytest.raises(capi.InvalidArgument):
         gpu.SEALContext(gpu.BFV, 100, be.primes, be.t)       # N not a power of two
+
+
+def test_end_to_end_own_keys_narrow_primes(gpu):
+    """own keys on a narrow set (BGV N = 8192, [60, 22, 24, 60]): encrypt, add, rotate, add, rotate -- host decrypt equals the plaintext result, and the
+    host invariantNoiseBudget is still positive at the end (additions and two key switches leave most of the fresh budget)"""
+    from oracle import oracle
+    cfg = cases.CONFIGS["nar_bgv_n8192_k4"]
+    N = cfg["N"]
+    primes = gpu.CoeffModulus.Create(N, cfg["bits"])
+    t = gpu.PlainModulus.Batching(N, cfg["tbits"])
+    ctx = gpu.SEALContext(cfg["scheme"], N, primes, t)
+    kg = gpu.KeyGenerator(ctx, seed=(23, 24))
+    enc, dec = gpu.Encryptor(ctx, kg.createPublicKey()), gpu.Decryptor(ctx, kg.secretKey())
+    gk = gpu.GaloisKeys(ctx)
+    g = ctx.galois_elt_from_step(1)
+    gk.set_elt(g, kg.createGaloisKeys([g])[g])
+    rng = np.random.default_rng(10)
+    B = 2
+    m1 = rng.integers(0, t, (B, N), dtype=np.uint64)
+    m2 = rng.integers(0, t, (B, N), dtype=np.uint64)
+    a = gpu.Ciphertext.from_numpy(ctx, np.stack([enc.encrypt(m1[b]) for b in range(B)]))
+    b = gpu.Ciphertext.from_numpy(ctx, np.stack([enc.encrypt(m2[b]) for b in range(B)]))
+    ev = gpu.Evaluator(ctx)
+    ev.addInplace(a, b)
+    ev.applyGaloisInplace(a, g, gk)
+    ev.addInplace(a, b)
+    ev.applyGaloisInplace(a, g, gk)
+    out = a.cpu()
+    budgets = ev.invariantNoiseBudget(a, gpu.DeviceBuffer.from_numpy(kg.secretKey()))
+    for i in range(B):
+        s = (m1[i] + m2[i]) % np.uint64(t)
+        s = (oracle.apply_galois(N, g, t, s) + m2[i]) % np.uint64(t)
+        assert np.array_equal(dec.decrypt(out[i], correction_factor=a.correction_factor), oracle.apply_galois(N, g, t, s)), i
+        assert dec.invariantNoiseBudget(out[i]) > 0 and int(budgets[i]) == dec.invariantNoiseBudget(out[i]), i
 
 
 @pytest.mark.parametrize("scheme,bits,tbits", [(1, [40, 40, 40, 40], 10), (3, [40, 36, 36, 40], 10)])
@@ -539,14 +578,15 @@ def test_random_parameter_sets(seed, gpu, oracle_lib):
 
 
 @pytest.mark.parametrize("scheme", [1, 3])
-@pytest.mark.parametrize("N,bits", [(8192, (46, 46, 46, 48)), (4096, (44, 45, 49)), (16384, (40, 46, 46, 46, 49))])
+@pytest.mark.parametrize("N,bits", [(8192, (46, 46, 46, 48)), (4096, (44, 45, 49)), (16384, (40, 46, 46, 46, 49)), (8192, (25, 22, 30, 32))])
 def test_moddown_shared_first_pass_fp_bounds(scheme, N, bits, gpu, oracle_lib):
     """one ciphertext, FP64-class special prime above the FP64-class data primes: the mod-down's separately launched last passes plan from the
     bound of the shared first pass (uniform and extreme rows and keys vs the oracle; the FP64 two-pass kernels must have run)"""
     cases.check_moddown_shared_first_pass(scheme, N=N, bits=bits)
 
 
-@pytest.mark.parametrize("name", ["cfgA_bfv_n4096_k3", "cfgB_bfv_n8192_k5", "bgv_n4096_k3", "ckks_n4096_k4", "cfgNS_bfv_n32768_k15", "cfgC_ckks_n32768_k15"])
+@pytest.mark.parametrize("name", ["cfgA_bfv_n4096_k3", "cfgB_bfv_n8192_k5", "bgv_n4096_k3", "ckks_n4096_k4", "cfgNS_bfv_n32768_k15", "cfgC_ckks_n32768_k15",
+                                  "nar_bfv_n4096_k3", "nar_bgv_n8192_k4", "nar_bfv_n8192_k4", "nar_ckks_n32768_k5"])
 def test_relinearize_out_of_place(name, gpu):
     """the destination form of relinearize (operand read in place from size 3, every mod-down epilogue accumulating onto (c0, c1) of the
     operand) == copy + relinearizeInplace"""
@@ -585,12 +625,53 @@ def test_bfv_multiply_every_limb_count(K, big, gpu, oracle_lib):
     cases.check_bfv_multiply_limb_count(K, big=big)
 
 
+BEHZ_COUNTERS = ("behz_fp_launches", "behz_mfma_launches", "behz_valu_launches")
+
+
+def _behz_family_check(K, run):
+    """runs `run` (a BFV multiply at K - 1 limbs with every q prime below 2^33) and asserts the BEHZ family through the path counters: matrix cores up to
+    15 limbs, VALU beyond, nothing else"""
+    from troy_amd import capi
+    before = [capi.stat(n) for n in BEHZ_COUNTERS]
+    run()
+    delta = [capi.stat(n) - b for n, b in zip(BEHZ_COUNTERS, before)]
+    expect = 1 if K - 1 <= 15 else 2
+    assert delta[expect] >= 2 and sum(delta) == delta[expect], (K, dict(zip(BEHZ_COUNTERS, delta)))
+
+
+@pytest.mark.parametrize("K", list(range(2, 19)))
+def test_bfv_multiply_every_limb_count_narrow(K, gpu, oracle_lib):
+    """the same with 22/25-bit primes: every q prime far below 2^33 (N = 256 has primes enough of 22 bits for every limb count).  The auxiliary primes are
+    the library's own 50- or 58-bit class, so up to 15 limbs the base keeps the matrix-core kernels (behz2.hip) with the two-word q-side reduction
+    (f2_fast = 0); past 15 limbs the VALU kernels; never the register-resident FP64 form, which needs q primes of at least 2^33 -- the counters say so"""
+    _behz_family_check(K, lambda: cases.check_bfv_multiply_limb_count(K, big="narrow"))
+
+
+# 22-bit primes that are 1 mod 2N: about seventeen at N = 8192, four at N = 32768 -- the narrow column stops where CoeffModulus.Create runs out
+@pytest.mark.parametrize("N,K,big", [(N, K, "small") for N in (8192, 32768) for K in (2, 3, 7, 15, 16, 18)]
+                         + [(8192, K, "narrow") for K in (2, 3, 7, 15, 16)] + [(32768, K, "narrow") for K in (2, 3, 5)])
+def test_bfv_multiply_limb_counts_narrow_primes_at_size(N, K, big, gpu, oracle_lib):
+    """30/32-bit and 22/25-bit q primes at N = 2^13 and 2^15, extreme residues included, behind the two-pass tensor of real ring sizes: up to 15 limbs
+    the matrix-core kernels (behz2.hip) with the two-word q-side reduction, at K = 18 the VALU kernels -- asserted through the counters"""
+    _behz_family_check(K, lambda: cases.check_bfv_multiply_limb_count(K, N=N, batch=1, big=big, tbits=17))
+
+
+def test_bfv_narrow_column_ends_where_the_primes_do(gpu, oracle_lib):
+    """past the last case above both CoeffModulus.Create implementations fail alike (not enough 22-bit primes that are 1 mod 2N)"""
+    for N, K in ((8192, 22), (32768, 8)):
+        for create in (gpu.CoeffModulus.Create, oracle_lib.coeff_modulus_create):
+            with pytest.raises(Exception):
+                create(N, [25] + [22] * (K - 2) + [25])
+
+
 def test_behz_kernel_family_by_base(gpu, oracle_lib):
     """which BEHZ kernels a base gets (path counters, troyhip_stat): small bases of narrow primes the register-resident FP64 form (behz3.hip), up to
     15 limbs the matrix cores (behz2.hip), beyond that the VALU kernels (behz.hip) -- each against the oracle in check_bfv_multiply_limb_count"""
     from troy_amd import capi
     names = ("behz_fp_launches", "behz_mfma_launches", "behz_valu_launches")
-    for K, big, expect in ((3, False, 0), (5, False, 0), (7, False, 0), (5, True, 1), (9, False, 1), (16, True, 1), (18, False, 2)):
+    # q primes below 2^33 ("small": 30/32 bits, "narrow": 22/25 bits) never take the FP64 form, however small the base: matrix cores, then VALU
+    for K, big, expect in ((3, False, 0), (5, False, 0), (7, False, 0), (5, True, 1), (9, False, 1), (16, True, 1), (18, False, 2),
+                           (3, "small", 1), (5, "narrow", 1), (7, "narrow", 1), (16, "small", 1), (18, "narrow", 2)):
         before = [capi.stat(n) for n in names]
         cases.check_bfv_multiply_limb_count(K, big=big)
         delta = [capi.stat(n) - b for n, b in zip(names, before)]
@@ -993,7 +1074,10 @@ def test_fp64_key_switch_prime_widths(N, width, gpu):
     assert capi.stat("ks_fp_launches") > before, "the FP64 key-switch instances did not run"
 
 
-@pytest.mark.parametrize("bits", [[50, 50, 50, 50, 50, 50, 50, 60], [40] * 7 + [60], [50, 30, 50, 30, 45, 60]])
+@pytest.mark.parametrize("bits", [[50, 50, 50, 50, 50, 50, 50, 60], [40] * 7 + [60], [50, 30, 50, 30, 45, 60],
+                                  # source digits of 49 bits into output primes of 18 / 20 / 17 bits: the ratio src_narrow_max / pmin the first round's bound starts from
+                                  # is 2^29 .. 2^32 ("min": the smallest NTT-friendly prime of this ring size, 65537)
+                                  [49, 20, 49, 18, 45, 60], [49, 49, 49, "min", 60]])
 def test_fp64_key_switch_extreme_residues(bits, gpu):
     """worst-case operands for the FP64 value bounds: every ciphertext and key residue at p - 1 (largest magnitude through every stage and
     the largest accumulator sums), at (p - 1) / 2 and alternating p - 1 / 0, relinearize and rotate at the top level against the oracle"""
@@ -1001,6 +1085,13 @@ def test_fp64_key_switch_extreme_residues(bits, gpu):
     from troy_amd import capi
     N = 8192
     cfg = dict(scheme=cases.BGV, N=N, bits=bits, tbits=20)
+    if 20 in bits:
+        cfg["tbits"] = 17  # the 20-bit batching prime is the 20-bit coefficient prime
+    if "min" in bits:
+        import narrow_cases
+        found = iter(gpu.CoeffModulus.Create(N, [b for b in bits if b != "min"]))
+        cfg["primes"] = [narrow_cases.smallest_ntt_prime(N) if b == "min" else next(found) for b in bits]
+        assert min(cfg["primes"]) == 65537
     be, orc = cases.GpuBackend(cfg, batch=3), cases.oracle_backend(cfg)
     primes = be.primes
     L, K = len(primes) - 1, len(primes)

@@ -1286,6 +1286,7 @@ void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbM
         const bool shared_row = a.md_ct || a.cr_last;
         const bool xcd = forced_xcd >= 0 ? forced_xcd != 0 : (a.nslots > 1 && a.nslots * a.chunks >= (shared_row ? cus + 1 : 2 * cus));
         a.xcd_per = xcd ? (a.nslots * a.chunks + 7) / 8 : 0;
+        if (xcd) stats::counter(stats::NTT1_XCD_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
         a.xcd_group = forced_group > 0 ? (unsigned)forced_group : !(a.md_ct || a.cr_last) ? 1u : 4u;
         static const bool perturb = probe_env("TROYHIP_NTT1_XCD_PERTURB") != nullptr;
         a.xcd_perturb = perturb ? 1u : 0u;
