@@ -163,7 +163,8 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
 #pragma unroll
         for (int i = 0; i < KB; i++) {
             const int l = w + 4 * i;
-            yd[(((l >> 1) * B2_TILE) + lane) * 2 + (l & 1)] = b2_digits(mul_shoup(xr[i], qpre[i].op, qpre[i].quo, qp[i]));
+            // a padding slot (wave-uniform; only the last k-block has any) skips the multiplication: its residue was loaded as 0, whose digits are 0
+            yd[(((l >> 1) * B2_TILE) + lane) * 2 + (l & 1)] = l < c.L ? b2_digits(mul_shoup(xr[i], qpre[i].op, qpre[i].quo, qp[i])) : 0;
         }
         fetch(t + 1 < tiles_per_wg ? t + 1 : 0x7FFFFFu); // past the last tile: out of range
         __syncthreads();

@@ -85,6 +85,9 @@ struct Ntt2Args {
     u64 fp_src_wide = 0;       // bit k: the residues of source digit k do not fit a double exactly (prime >= 2^50): integer Barrett step before the conversion
     unsigned fp_red_mask = 0;  // bit r: the values are reduced before round r of this pass (fp_plan)
     unsigned fp_acc_every = 0; // the key-switch accumulators are reduced every this many rows (0: never)
+    // integer key-switch accumulating pass and tensor pass: a workgroup takes mac_units consecutive groups (ciphertexts) of its (slot, tile), of mac_groups
+    // = m_total / rows_per_wg in all; `chunks` then counts the workgroups per (slot, tile)
+    unsigned mac_units = 0, mac_groups = 0; // (0, 0: one group per workgroup, `chunks` of them)
 };
 
 // NT: a non-temporal store.  Used for the stores of the forward STRIDED pass -- rows written once and read back by another kernel: the key switch's
@@ -627,9 +630,9 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     if constexpr (NR > 2) Rd2::settle_tw(tw2);
     if constexpr (NR > 3) Rd3::settle_tw(tw3);
 
-    const unsigned m_begin = chunk * a.rows_per_wg;
-    const unsigned m_end = (m_begin + a.rows_per_wg < a.m_total) ? m_begin + a.rows_per_wg : a.m_total;
     const unsigned inner = a.map.inner, period = a.map.period;
+    // read once: indexing the argument block with `slot` is a memory load, and inside the row loop it sat, with its wait, in front of the key loads
+    const unsigned key_limb = (MAC == 1 || MAC == 3) ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.mac_key_limb[slot]) : 0;
     // FP64 instances: reduce the eight values before round r where the host's bound walk says so (fp_plan, fpmod.h; wave-uniform)
     auto fp_guard = [&](u64 (&v)[8], int r) {
         if constexpr (FP) {
@@ -666,23 +669,9 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
     static_assert(!MAC || (!INV && !STRIDED && NS == 9), "the inner product is fused into the forward contiguous pass");
     u64 tx[MAC == 2 ? 3 : 1][8]; // MAC = 2: the transforms of a0, a1, b0 while b1 is being computed
     Acc128 macc[2][2][4]; // [key component][group of four coefficients][coefficient]
-    if (KS) {
-#pragma unroll
-        for (int cpt = 0; cpt < 2; cpt++)
-#pragma unroll
-            for (int g = 0; g < 2; g++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) macc[cpt][g][e] = Acc128{0, 0, 0, 0};
-    }
     // FP64 instances: one double per accumulator (the products are reduced modulo p as they are formed: 6 + 1 instructions per term and two
     // for the key word's conversion, against 10 for the 128-bit integer form -- and 32 VGPRs of accumulators instead of 64)
     double facc[2][FP ? 8 : 1];
-    if constexpr (FP) {
-#pragma unroll
-        for (int cpt = 0; cpt < 2; cpt++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) facc[cpt][e] = 0.0;
-    }
     auto mac_row = [&](const u64 (&xr)[8], const ulonglong2 (&kw)[2][KS ? 4 : 1], unsigned row_no) {
         if constexpr (FP && KS) {
 #pragma unroll
@@ -712,159 +701,100 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
         }
         (void)row_no;
     };
-    // read once: indexing the argument block with `slot` is a memory load, and inside the row loop it sat, with its wait, in front of the key loads
-    const unsigned key_limb = KS ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.mac_key_limb[slot]) : 0;
     // the sums leave through the wave's exchange area, one contiguous KiB per wave and instruction (Rd2::store_via_lds): written from a thread's eight
     // consecutive coefficients they were 16 bytes per lane every 64 bytes -- the access pattern that cost the single-pass forward kernel 9 % (ntt1.hip).
     // Same-box A/B (tools/r4_ab_maclin.sh): accumulating pass -1..-3 % at the headline, -4 % in the CKKS chain, -8 % at configs[1], BGV N = 2^16 unchanged.
     // (The key LOADS in that pattern are harmless: a per-row transposition that made them contiguous as well measured the same or 1-2 % slower.)
     constexpr bool MAC_STORE_LINEAR = KS && WAVE_PRIVATE;
     u64 *const wave_stage = lds[1] + 512 * (threadIdx.x >> 6);
-    u64 x[8];
-    unsigned ro = m_begin / inner, rk = m_begin - ro * inner; // (o, k) of the current row
-    unsigned parity = 0;
-    // CKKS key switch: the row whose digit index equals the output slot is the NTT-form input itself (evaluator.cpp:2424-2427): the first
-    // pass does not expand it and the fused second pass neither stages nor transforms it (one row in L + 1 of both passes)
-    auto is_diag = [&](unsigned k) { return (MAC == 3 || REDUCE == 2) && k == slot; };
-    {
-        u64 *row0; const u64 *in0;
-        row_ptrs(m_begin, ro, rk, row0, in0);
-        if (!is_diag(rk)) {
-            if constexpr (DMA) Rd0::stage_issue(in0, tile, wave_stage);
-            else Rd0::template g_read<REDUCE>(x, in0, tile, logn, m);
+    // Key-switch accumulating pass and tensor pass: the workgroup keeps its (prime slot, tile) for mac_units consecutive groups (ciphertexts), so the argument
+    // decode and the twiddle prologue above -- about 200 vector instructions -- are paid once per mac_units groups instead of once per group; the last
+    // workgroup of a (slot, tile) may hold fewer.  Every other instance, the FP64 twins included, runs the body once (the loop folds away).
+    constexpr bool KSU = MAC != 0 && !FP; // (the FP64 twins sit at their register limit of three waves per SIMD: one group per workgroup there)
+    const unsigned units = KSU ? (a.mac_units ? a.mac_units : 1u) : 1u; // (an argument block that never set it means one group per workgroup)
+    const unsigned groups = KSU && a.mac_groups ? a.mac_groups : a.chunks * units;
+    // the staged-row pipeline runs on across the workgroup's groups (their rows are consecutive): the first row of the next group streams in
+    // while this group's sums are reduced and stored
+    const unsigned last_group = chunk * units + units < groups ? chunk * units + units : groups;
+    const unsigned stage_end = KSU ? last_group * a.rows_per_wg : 0;
+    for (unsigned un = 0; un < units; un++) {
+        const unsigned uchunk = KSU ? chunk * units + un : chunk;
+        if (KSU && uchunk >= groups) break;
+        const unsigned m_begin = uchunk * a.rows_per_wg;
+        const unsigned m_end = (m_begin + a.rows_per_wg < a.m_total) ? m_begin + a.rows_per_wg : a.m_total;
+        if (KS) {
+#pragma unroll
+            for (int cpt = 0; cpt < 2; cpt++)
+#pragma unroll
+                for (int g = 0; g < 2; g++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) macc[cpt][g][e] = Acc128{0, 0, 0, 0};
         }
-    }
-    for (unsigned mm = m_begin; mm < m_end; mm++) {
-        u64 *row; const u64 *in;
-        row_ptrs(mm, ro, rk, row, in);
-        const unsigned no = rk + 1 == inner ? ro + 1 : ro, nk = rk + 1 == inner ? 0 : rk + 1; // (o, k) of row mm + 1
-        const bool next_wanted = mm + 1 < m_end && !is_diag(nk);
-        const bool skip_row = REDUCE == 2 && is_diag(rk); // nothing to expand: the body below is skipped as a whole, the software pipeline goes on
-        if constexpr (DMA) TROY_WAIT_VMEM(); // this wave's staged row has landed (and its previous stores are out)
-        ulonglong2 kv[2][KS ? 4 : 1]; // MAC: this row's key words, requested now -- BEFORE the next row's staging loads, so that the wait for them (vmcnt counts in
-        // order) does not include the staging loads' HBM latency -- and used after the three rounds
-        auto load_keys = [&]() {
-            const unsigned kk = rk;
-            const u64 *kp = a.mac_key + ((((u64)kk * 2) * a.mac_K + key_limb) << logn) + ((u64)tile << N2_LOGT) + 8 * threadIdx.x;
+        if constexpr (FP) {
 #pragma unroll
-            for (int cpt = 0; cpt < 2; cpt++) {
-                const ulonglong2 *kq = reinterpret_cast<const ulonglong2 *>(kp + ((u64)cpt * a.mac_K << logn));
+            for (int cpt = 0; cpt < 2; cpt++)
 #pragma unroll
-                for (int e = 0; e < 4; e++) kv[cpt][KS ? e : 0] = kq[e];
+                for (int e = 0; e < 8; e++) facc[cpt][e] = 0.0;
+        }
+        u64 x[8];
+        unsigned ro = m_begin / inner, rk = m_begin - ro * inner; // (o, k) of the current row
+        unsigned parity = 0;
+        // CKKS key switch: the row whose digit index equals the output slot is the NTT-form input itself (evaluator.cpp:2424-2427): the first
+        // pass does not expand it and the fused second pass neither stages nor transforms it (one row in L + 1 of both passes)
+        auto is_diag = [&](unsigned k) { return (MAC == 3 || REDUCE == 2) && k == slot; };
+        {
+            u64 *row0; const u64 *in0;
+            row_ptrs(m_begin, ro, rk, row0, in0);
+            if (!is_diag(rk)) {
+                if constexpr (DMA) { if (!KSU || un == 0) Rd0::stage_issue(in0, tile, wave_stage); } // (later groups: issued by the row before)
+                else Rd0::template g_read<REDUCE>(x, in0, tile, logn, m);
             }
-        };
-        if constexpr (KS) load_keys();
-        if constexpr (MAC == 3) { // CKKS key switch: one code path for both kinds of rows, so that the accumulate code exists once
-            const bool diag = is_diag(rk);
-            if (!diag) {
-                Rd0::stage_read(x, wave_stage);
-                TROY_WAIT_LDS();
-            }
-            if (next_wanted) {
-                u64 *nrow; const u64 *nin;
-                row_ptrs(mm + 1, no, nk, nrow, nin);
-                Rd0::stage_issue(nin, tile, wave_stage);
-            }
-            if (!diag) {
-                u64 *buf = lds[0];
-                fp_guard(x, 0);
-                if constexpr (FP) Rd0::compute_fp(x, tw0, fc, pd.inv_n); else Rd0::compute(x, tw0, pd, lean);
-                Rd0::lds_write(x, buf, (FRESH & 1) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                round_sync();
-                Rd1::lds_read(x, buf, (FRESH & 2) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                fp_guard(x, 1);
-                if constexpr (FP) Rd1::compute_fp(x, tw1, fc, pd.inv_n); else Rd1::compute(x, tw1, pd, lean);
-                Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                round_sync();
-                Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                fp_guard(x, 2);
-                if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
-                if constexpr (FP) {
-                } else if (!a.mac_lazy && lean) {
+        }
+        for (unsigned mm = m_begin; mm < m_end; mm++) {
+            u64 *row; const u64 *in;
+            row_ptrs(mm, ro, rk, row, in);
+            const unsigned no = rk + 1 == inner ? ro + 1 : ro, nk = rk + 1 == inner ? 0 : rk + 1; // (o, k) of row mm + 1
+            const bool next_wanted = mm + 1 < (KSU ? stage_end : m_end) && !is_diag(nk);
+            const bool skip_row = REDUCE == 2 && is_diag(rk); // nothing to expand: the body below is skipped as a whole, the software pipeline goes on
+            if constexpr (DMA) TROY_WAIT_VMEM(); // this wave's staged row has landed (and its previous stores are out)
+            ulonglong2 kv[2][KS ? 4 : 1]; // MAC: this row's key words, requested now -- BEFORE the next row's staging loads, so that the wait for them (vmcnt counts in
+            // order) does not include the staging loads' HBM latency -- and used after the three rounds
+            auto load_keys = [&]() {
+                const unsigned kk = rk;
+                const u64 *kp = a.mac_key + ((((u64)kk * 2) * a.mac_K + key_limb) << logn) + ((u64)tile << N2_LOGT) + 8 * threadIdx.x;
 #pragma unroll
-                    for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
-                } else if (!a.mac_lazy) {
-                    const PrimeConst pc = make_prime_const(pd.p);
+                for (int cpt = 0; cpt < 2; cpt++) {
+                    const ulonglong2 *kq = reinterpret_cast<const ulonglong2 *>(kp + ((u64)cpt * a.mac_K << logn));
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        u64 v[4] = {x[4 * h], x[4 * h + 1], x[4 * h + 2], x[4 * h + 3]};
-                        reduce4_from_8p(v, pc);
-#pragma unroll
-                        for (int i = 0; i < 4; i++) x[4 * h + i] = v[i];
-                    }
+                    for (int e = 0; e < 4; e++) kv[cpt][KS ? e : 0] = kq[e];
                 }
-            } else { // the operand is the NTT-form input limb: no staged row, no transform
-                const ulonglong2 *tp = reinterpret_cast<const ulonglong2 *>(a.mac_target + (u64)ro * a.mac_tstride + ((u64)rk << logn) + ((u64)tile << N2_LOGT) + 8 * threadIdx.x);
-#pragma unroll
-                for (int e = 0; e < 4; e++) { const ulonglong2 v = tp[e]; x[2 * e] = v.x; x[2 * e + 1] = v.y; }
-                if constexpr (FP) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
+            };
+            if constexpr (KS) load_keys();
+            if constexpr (MAC == 3) { // CKKS key switch: one code path for both kinds of rows, so that the accumulate code exists once
+                const bool diag = is_diag(rk);
+                if (!diag) {
+                    Rd0::stage_read(x, wave_stage);
+                    TROY_WAIT_LDS();
                 }
-            }
-            mac_row(x, kv, mm - m_begin);
-            ro = no;
-            rk = nk;
-            continue;
-        }
-        if constexpr (DMA) {
-            Rd0::stage_read(x, wave_stage);
-            TROY_WAIT_LDS();             // ... and has been read before the next row overwrites it
-            if (next_wanted) {
-                u64 *nrow; const u64 *nin;
-                row_ptrs(mm + 1, no, nk, nrow, nin);
-                Rd0::stage_issue(nin, tile, wave_stage);
-            }
-        }
-        if (!skip_row) {
-        u64 *buf = DMA ? lds[0] : lds[parity]; // the exchange buffers alternate over the rows that are actually processed (skipped rows have no barriers)
-        if (REDUCE && need_reduce) { // wave-uniform: the butterflies take any input below 8p (ct_bfly4), most prime sets never need this
-#pragma unroll
-            for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
-        }
-        if constexpr (FP && REDUCE) { // the digit's residues become doubles: exact below 2^52; a wide source prime (>= 2^50) is reduced modulo this row's prime first
-            if ((a.fp_src_wide >> rk) & 1) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
-        } else if constexpr (FP && ((!INV && STRIDED) || (INV && !STRIDED))) { // first pass of a plain transform: canonical residues of this row's own prime
-#pragma unroll
-            for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
-        }
-        fp_guard(x, 0);
-        if constexpr (FP) Rd0::compute_fp(x, tw0, fc, pd.inv_n); else Rd0::compute(x, tw0, pd, lean);
-        if constexpr (NR == 1) {
-            if constexpr (FINAL >= 3) Rd0::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
-            else Rd0::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
-        } else {
-            Rd0::lds_write(x, buf, (FRESH & 1) ? n2_opaque(threadIdx.x) : threadIdx.x);
-            round_sync();
-            Rd1::lds_read(x, buf, (FRESH & 2) ? n2_opaque(threadIdx.x) : threadIdx.x);
-            if constexpr (PF) {
-                if (mm + 1 < m_end) {
+                if (next_wanted) {
                     u64 *nrow; const u64 *nin;
                     row_ptrs(mm + 1, no, nk, nrow, nin);
-                    Rd0::template g_read<REDUCE>(xn, nin, tile, logn, m, n2_opaque(threadIdx.x));
+                    Rd0::stage_issue(nin, tile, wave_stage);
                 }
-            }
-            fp_guard(x, 1);
-            if constexpr (FP) Rd1::compute_fp(x, tw1, fc, pd.inv_n); else Rd1::compute(x, tw1, pd, lean);
-            if constexpr (NR == 2) {
-                if constexpr (FINAL >= 3) Rd1::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
-                else Rd1::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
-            } else {
-                Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                round_sync();
-                Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                fp_guard(x, 2);
-                if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
-                if constexpr (NR == 3 && MAC == 2) {
-                    Rd2::tensor_epilogue(x, tx, mm, a.tensor_out, period, slot, tile, logn, m, WAVE_PRIVATE ? buf : nullptr, lean, fcp);
-                } else if constexpr (NR == 3 && KS) {
-                    // the transform of digit k of (o, slot) stays in registers: acc_c += x (.) key[k][c][limb(slot)].  x is lazy, in
-                    // [0, 8p); it is only normalised when dl * 8p * p could overflow the 128-bit accumulator (mac_lazy == 0)
+                if (!diag) {
+                    u64 *buf = lds[0];
+                    fp_guard(x, 0);
+                    if constexpr (FP) Rd0::compute_fp(x, tw0, fc, pd.inv_n); else Rd0::compute(x, tw0, pd, lean);
+                    Rd0::lds_write(x, buf, (FRESH & 1) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    round_sync();
+                    Rd1::lds_read(x, buf, (FRESH & 2) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    fp_guard(x, 1);
+                    if constexpr (FP) Rd1::compute_fp(x, tw1, fc, pd.inv_n); else Rd1::compute(x, tw1, pd, lean);
+                    Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    round_sync();
+                    Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    fp_guard(x, 2);
+                    if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
                     if constexpr (FP) {
                     } else if (!a.mac_lazy && lean) {
 #pragma unroll
@@ -879,62 +809,171 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
                             for (int i = 0; i < 4; i++) x[4 * h + i] = v[i];
                         }
                     }
-                        mac_row(x, kv, mm - m_begin);
-                } else if constexpr (NR == 3) {
-                    if constexpr (FINAL >= 3) Rd2::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
-                    else Rd2::template g_write<FINAL>(x, row, tile, logn, m, lean, WAVE_PRIVATE ? buf : nullptr, fcp);
+                } else { // the operand is the NTT-form input limb: no staged row, no transform
+                    const ulonglong2 *tp = reinterpret_cast<const ulonglong2 *>(a.mac_target + (u64)ro * a.mac_tstride + ((u64)rk << logn) + ((u64)tile << N2_LOGT) + 8 * threadIdx.x);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) { const ulonglong2 v = tp[e]; x[2 * e] = v.x; x[2 * e + 1] = v.y; }
+                    if constexpr (FP) {
+#pragma unroll
+                        for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
+                    }
+                }
+                mac_row(x, kv, mm - m_begin);
+                ro = no;
+                rk = nk;
+                continue;
+            }
+            if constexpr (DMA) {
+                Rd0::stage_read(x, wave_stage);
+                TROY_WAIT_LDS();             // ... and has been read before the next row overwrites it
+                if (next_wanted) {
+                    u64 *nrow; const u64 *nin;
+                    row_ptrs(mm + 1, no, nk, nrow, nin);
+                    Rd0::stage_issue(nin, tile, wave_stage);
+                }
+            }
+            if (!skip_row) {
+            u64 *buf = DMA ? lds[0] : lds[parity]; // the exchange buffers alternate over the rows that are actually processed (skipped rows have no barriers)
+            if (REDUCE && need_reduce) { // wave-uniform: the butterflies take any input below 8p (ct_bfly4), most prime sets never need this
+#pragma unroll
+                for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
+            }
+            if constexpr (FP && REDUCE) { // the digit's residues become doubles: exact below 2^52; a wide source prime (>= 2^50) is reduced modulo this row's prime first
+                if ((a.fp_src_wide >> rk) & 1) {
+#pragma unroll
+                    for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
+                }
+#pragma unroll
+                for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
+            } else if constexpr (FP && ((!INV && STRIDED) || (INV && !STRIDED))) { // first pass of a plain transform: canonical residues of this row's own prime
+#pragma unroll
+                for (int e = 0; e < 8; e++) x[e] = fp_bits(fp_from_u64(x[e]));
+            }
+            fp_guard(x, 0);
+            if constexpr (FP) Rd0::compute_fp(x, tw0, fc, pd.inv_n); else Rd0::compute(x, tw0, pd, lean);
+            if constexpr (NR == 1) {
+                if constexpr (FINAL >= 3) Rd0::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
+                else Rd0::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
+            } else {
+                Rd0::lds_write(x, buf, (FRESH & 1) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                round_sync();
+                Rd1::lds_read(x, buf, (FRESH & 2) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                if constexpr (PF) {
+                    if (mm + 1 < m_end) {
+                        u64 *nrow; const u64 *nin;
+                        row_ptrs(mm + 1, no, nk, nrow, nin);
+                        Rd0::template g_read<REDUCE>(xn, nin, tile, logn, m, n2_opaque(threadIdx.x));
+                    }
+                }
+                fp_guard(x, 1);
+                if constexpr (FP) Rd1::compute_fp(x, tw1, fc, pd.inv_n); else Rd1::compute(x, tw1, pd, lean);
+                if constexpr (NR == 2) {
+                    if constexpr (FINAL >= 3) Rd1::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
+                    else Rd1::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
                 } else {
-                    Rd2::lds_write(x, buf, (FRESH & 16) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    Rd1::lds_write(x, buf, (FRESH & 4) ? n2_opaque(threadIdx.x) : threadIdx.x);
                     round_sync();
-                    Rd3::lds_read(x, buf, (FRESH & 32) ? n2_opaque(threadIdx.x) : threadIdx.x);
-                    fp_guard(x, 3);
-                    if constexpr (FP) Rd3::compute_fp(x, tw3, fc, pd.inv_n); else Rd3::compute(x, tw3, pd, lean);
-                    Rd3::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
+                    Rd2::lds_read(x, buf, (FRESH & 8) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                    fp_guard(x, 2);
+                    if constexpr (FP) Rd2::compute_fp(x, tw2, fc, pd.inv_n); else Rd2::compute(x, tw2, pd, lean);
+                    if constexpr (NR == 3 && MAC == 2) {
+                        Rd2::tensor_epilogue(x, tx, mm, a.tensor_out, period, slot, tile, logn, m, WAVE_PRIVATE ? buf : nullptr, lean, fcp);
+                    } else if constexpr (NR == 3 && KS) {
+                        // the transform of digit k of (o, slot) stays in registers: acc_c += x (.) key[k][c][limb(slot)].  x is lazy, in
+                        // [0, 8p); it is only normalised when dl * 8p * p could overflow the 128-bit accumulator (mac_lazy == 0)
+                        if constexpr (FP) {
+                        } else if (!a.mac_lazy && lean) {
+#pragma unroll
+                            for (int e = 0; e < 8; e++) x[e] = barrett64(x[e], m);
+                        } else if (!a.mac_lazy) {
+                            const PrimeConst pc = make_prime_const(pd.p);
+#pragma unroll
+                            for (int h = 0; h < 2; h++) {
+                                u64 v[4] = {x[4 * h], x[4 * h + 1], x[4 * h + 2], x[4 * h + 3]};
+                                reduce4_from_8p(v, pc);
+#pragma unroll
+                                for (int i = 0; i < 4; i++) x[4 * h + i] = v[i];
+                            }
+                        }
+                            mac_row(x, kv, mm - m_begin);
+                    } else if constexpr (NR == 3) {
+                        if constexpr (FINAL >= 3) Rd2::template md_write<FINAL>(x, a, mm, slot, tile, logn, m, pd, fcp);
+                        else Rd2::template g_write<FINAL>(x, row, tile, logn, m, lean, WAVE_PRIVATE ? buf : nullptr, fcp);
+                    } else {
+                        Rd2::lds_write(x, buf, (FRESH & 16) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                        round_sync();
+                        Rd3::lds_read(x, buf, (FRESH & 32) ? n2_opaque(threadIdx.x) : threadIdx.x);
+                        fp_guard(x, 3);
+                        if constexpr (FP) Rd3::compute_fp(x, tw3, fc, pd.inv_n); else Rd3::compute(x, tw3, pd, lean);
+                        Rd3::template g_write<FINAL>(x, row, tile, logn, m, lean, nullptr, fcp);
+                    }
                 }
             }
-        }
-        } // !skip_row
-        if constexpr (PF) {
+            } // !skip_row
+            if constexpr (PF) {
 #pragma unroll
-            for (int e = 0; e < 8; e++) x[e] = xn[PF ? e : 0];
-        } else if constexpr (!DMA) {
-            if (next_wanted) {
-                u64 *nrow; const u64 *nin;
-                row_ptrs(mm + 1, no, nk, nrow, nin);
-                if constexpr (FINAL >= 3) Rd0::template g_read<REDUCE>(x, nin, tile, logn, m, n2_opaque(threadIdx.x)); // offsets formed here, not carried across the epilogue
-                else Rd0::template g_read<REDUCE>(x, nin, tile, logn, m);
+                for (int e = 0; e < 8; e++) x[e] = xn[PF ? e : 0];
+            } else if constexpr (!DMA) {
+                if (next_wanted) {
+                    u64 *nrow; const u64 *nin;
+                    row_ptrs(mm + 1, no, nk, nrow, nin);
+                    if constexpr (FINAL >= 3) Rd0::template g_read<REDUCE>(x, nin, tile, logn, m, n2_opaque(threadIdx.x)); // offsets formed here, not carried across the epilogue
+                    else Rd0::template g_read<REDUCE>(x, nin, tile, logn, m);
+                }
             }
+            ro = no;
+            rk = nk;
+            if (!skip_row) parity ^= 1u;
         }
-        ro = no;
-        rk = nk;
-        if (!skip_row) parity ^= 1u;
-    }
-    if constexpr (KS) { // one reduction per output coefficient; acc[o][c][slot][N]
-        const unsigned o = m_begin / inner;
-        const u64 pos = ((u64)tile << N2_LOGT) + 8 * threadIdx.x;
+        if constexpr (KS) { // one reduction per output coefficient; acc[o][c][slot][N]
+            const unsigned o = m_begin / inner;
+            static_assert(!KS || MAC_STORE_LINEAR, "the sums leave through the wave's exchange area");
 #pragma unroll
-        for (int cpt = 0; cpt < 2; cpt++) {
-            ulonglong2 *op = reinterpret_cast<ulonglong2 *>(a.mac_acc + ((((u64)o * 2 + cpt) * period + slot) << logn) + pos);
-            u64 lin[8];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                ulonglong2 v;
+            for (int cpt = 0; cpt < 2; cpt++) {
+                u64 lin[8];
                 if constexpr (FP) {
-                    v.x = fp_canonical(facc[cpt][2 * e], fc, m.p);
-                    v.y = fp_canonical(facc[cpt][2 * e + 1], fc, m.p);
+#pragma unroll
+                    for (int e = 0; e < 8; e++) lin[e] = fp_canonical(facc[cpt][e], fc, m.p);
+                } else if (pd.p >> 33) {
+                    // Primes of 34 bits and more (wave-uniform): the generic two-word Barrett step (three high and three low 64-bit products per sum, about 70
+                    // instructions) gives way to a fold of the sum hi 2^64 + lo, whatever its 128 bits:  lo -> below 3.5p by a 32-bit quotient estimate
+                    // (lite_reduce4);  hi 2^64 = hi r64 mod p, r64 = 2^64 mod p with its Shoup quotient, lazily in [0, 3p) (the butterflies' multiply, operand in
+                    // scalar registers), added onto lo by the multiply's own addend: below 6.5p, which fits 64 bits because every prime the context
+                    // registers is below 2^61 (the butterflies' 8p needs the same);  then lean_final4 (anything below 64p, primes below 2^58) or three
+                    // conditional subtractions.  27-30 instructions per sum, the same residue, the same stored words.
+                    const PrimeConst pc = make_prime_const(pd.p);
+                    const LeanFinal lf = lean ? make_lean_final(pd.p, pd.cr1) : LeanFinal{0, 0};
+                    const Shoup r64 = to_sgpr(pd.r64);
+                    const Shoup w4[4] = {r64, r64, r64, r64};
+#pragma unroll
+                    for (int g = 0; g < 2; g++) {
+                        u64 lo[4], hi[4], q[4];
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const Acc128 &sum = macc[cpt][g][i];
+                            lo[i] = mk64(sum.a0, sum.a1);
+                            hi[i] = mk64(sum.a2, sum.a3);
+                        }
+                        lite_reduce4(lo, (u32)pd.cr1, pc);
+                        mulhi_approx4_u(q, hi, w4);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) lo[i] = mul_acc_u(lo[i], hi[i], r64.op, q[i], pc.negp);
+                        if (lean) lean_final4(lo, lf, pc); else reduce4_from_8p(lo, pc);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) lin[4 * g + i] = lo[i];
+                    }
                 } else {
-                    const Acc128 &p0 = macc[cpt][e >> 1][2 * (e & 1)], &p1 = macc[cpt][e >> 1][2 * (e & 1) + 1];
-                    v.x = barrett128(mk64(p0.a0, p0.a1), mk64(p0.a2, p0.a3), m);
-                    v.y = barrett128(mk64(p1.a0, p1.a1), mk64(p1.a2, p1.a3), m);
+#pragma unroll
+                    for (int e = 0; e < 8; e++) {
+                        const Acc128 &sum = macc[cpt][e >> 2][e & 3];
+                        lin[e] = barrett128(mk64(sum.a0, sum.a1), mk64(sum.a2, sum.a3), m);
+                    }
                 }
-                if constexpr (MAC_STORE_LINEAR) { lin[2 * e] = v.x; lin[2 * e + 1] = v.y; }
-                else op[e] = v;
+                if constexpr (MAC_STORE_LINEAR) {
+                    TROY_WAVE_SYNC();
+                    Rd2::store_via_lds(lin, a.mac_acc + ((((u64)o * 2 + cpt) * period + slot) << logn), tile, lds[0] + 512 * (threadIdx.x >> 6));
+                }
             }
-            if constexpr (MAC_STORE_LINEAR) {
-                TROY_WAVE_SYNC();
-                Rd2::store_via_lds(lin, a.mac_acc + ((((u64)o * 2 + cpt) * period + slot) << logn), tile, lds[0] + 512 * (threadIdx.x >> 6));
-            }
-            (void)lin;
         }
     }
 }
@@ -1189,7 +1228,6 @@ void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const PrimeDesc
         if (!a.nsel) continue;
         const bool fp = cls == 1;
         stats::counter(fp ? stats::KS_FP_LAUNCHES : stats::KS_INT_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
-        const unsigned blocks = (unsigned)((a.nsel * a.chunks) << a.tiles_per_row_log);
         a.fp_src_wide = 0; a.fp_red_mask = 0; a.fp_acc_every = 0;
         unsigned mask2 = 0;
         if (fp) { // walk the value bound through both passes (fpmod.h): where to reduce, how often the accumulators must be
@@ -1235,19 +1273,28 @@ void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const PrimeDesc
         }
         Ntt2Args second = a;
         second.fp_red_mask = mask2;
+        // groups per workgroup of the accumulating pass: 4 where the grid then still covers the resident workgroups (two per compute unit at this kernel's
+        // register count) four times over, else 2, else 1 -- a single ciphertext keeps one group per workgroup and spreads over the chip as before
+        second.mac_groups = a.chunks;
+        second.mac_units = fp ? 1 : 4;
+        while (second.mac_units > 1 && (size_t)((a.chunks + second.mac_units - 1) / second.mac_units) * ((size_t)a.nsel << a.tiles_per_row_log) < 8 * (size_t)device_cus())
+            second.mac_units >>= 1;
+        second.chunks = (a.chunks + second.mac_units - 1) / second.mac_units;
+        if (!fp) stats::counter(stats::KS_INT_GROUPS_PER_WG).fetch_add(second.mac_units, std::memory_order_relaxed); // (summed over the launches: the tests read the choice)
+        const unsigned blocks2 = (unsigned)((a.nsel * second.chunks) << a.tiles_per_row_log);
         second.mac_key = key; second.mac_acc = acc; second.mac_target = ckks_target; second.mac_tstride = t_bstride; second.mac_K = K;
         second.mac_lazy = lazy;
         std::memcpy(second.mac_key_limb, key_limb, map.period);
         if (fp) {
             N2_KTAG("ntt2_fp_kernel<0, 0, 9, 0, 1, 0, %d>", skip_diag ? 3 : 1);
-            if (skip_diag) TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks), dim3(N2_THREADS), 0, stream, second);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks), dim3(N2_THREADS), 0, stream, second);
+            if (skip_diag) TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
+            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
         } else if (skip_diag) {
             N2_KTAG("ntt2_kernel<0, 0, 9, 0, 1, 0, 3>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks), dim3(N2_THREADS), 0, stream, second);
+            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
         } else {
             N2_KTAG("ntt2_kernel<0, 0, 9, 0, 1, 0, 1>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks), dim3(N2_THREADS), 0, stream, second);
+            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
         }
         launch_check("ntt2_kernel(ks_mac)");
     }
@@ -1325,7 +1372,11 @@ void launch_ntt2_tensor(u64 *xa, const u64 *src_a, u64 *xb, const u64 *src_b, u6
         std::memcpy(a.sel, sel, sizeof(sel));
         a.fp_red_mask = mask2;
         a.rows_per_wg = 4;
-        a.chunks = (unsigned)batch;
+        // integer instances: up to four ciphertexts per workgroup, as the key-switch accumulating pass (three resident workgroups per compute unit here)
+        a.mac_groups = (unsigned)batch;
+        a.mac_units = fp ? 1 : 4;
+        while (a.mac_units > 1 && (size_t)((a.mac_groups + a.mac_units - 1) / a.mac_units) * ((size_t)nsel << a.tiles_per_row_log) < 12 * (size_t)device_cus()) a.mac_units >>= 1;
+        a.chunks = (a.mac_groups + a.mac_units - 1) / a.mac_units;
         const unsigned blocks = (unsigned)((nsel * a.chunks) << a.tiles_per_row_log);
         if (fp) {
             N2_KTAG("ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 2>");
