@@ -108,7 +108,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -248,6 +248,19 @@ int troyhip_apply_galois(troyhip_context *ctx, troyhip_ct *ct, uint32_t galois_e
  * (evaluator_cuda.cu:2119-2176). */
 int troyhip_rotate(troyhip_context *ctx, troyhip_ct *ct, int steps, int conjugate, const uint32_t *key_elts, const uint64_t *const *keys,
                    int n_keys, uint64_t batch, void *stream);
+/* Hoisted rotations (Halevi-Shoup; no reference counterpart): n_elts Galois automorphisms of ONE batch of size-2 ciphertexts for roughly the price of
+ * one key switch -- c1 is decomposed, extended and transformed once per item, each element then costs a gathered inner product with its key and the
+ * mod-down.  out item r * batch + b = element galois_elts[r] of in item b: n_elts dense batches back to back at out->data, out->batch_stride words
+ * apart (both are INPUTS; out must not overlap in; the call sets the other fields of *out).  galois_keys[r]: the key of galois_elts[r] (device); element 1
+ * is a copy and its key is not read (may be null).  A null key for any other element is refused ("Galois key not present"): there is no NAF
+ * decomposition here, it would undo the hoisting.  Duplicate elements are allowed.  The result is a valid rotation that decrypts to what
+ * troyhip_apply_galois decrypts to under the same noise bound; its limbs are NOT those of troyhip_apply_galois, and they
+ * do not depend on n_elts, the order of the elements, the batch size or the scratch limit.
+ * scratch_limit_words: upper bound of the scratch arena request of this call (the expanded digits take batch (limbs + 1) limbs N words); the call works
+ * in slabs of rotations and / or items under it.  0: the library default, 2^28 words (2 GiB).  A limit below one rotation of one item is refused.
+ * Counter "hoist_slabs" (troyhip_stat): slabs run so far. */
+int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                 int n_elts, uint64_t scratch_limit_words, uint64_t batch, void *stream);
 int troyhip_transform_to_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);            /* transformToNttInplace(Ciphertext) */
 int troyhip_transform_from_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);          /* transformFromNttInplace */
 int troyhip_multiply_plain_ntt(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *plain, double plain_scale, uint64_t batch, void *stream); /* multiplyPlainInplace, NTT-form operands */

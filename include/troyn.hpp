@@ -1939,6 +1939,46 @@ public:
     void rotateColumns(const Ciphertext &a, const GaloisKeys &gk, Ciphertext &d) const { d = a; rotateColumnsInplace(d, gk); }
     void rotateVector(const Ciphertext &a, int steps, const GaloisKeys &gk, Ciphertext &d) const { d = a; rotateVectorInplace(d, steps, gk); }
     void complexConjugate(const Ciphertext &a, const GaloisKeys &gk, Ciphertext &d) const { d = a; complexConjugateInplace(d, gk); }
+    // Hoisted rotations (troyhip_apply_galois_hoisted; the reference has no such call): every element of `elts` applied to ONE ciphertext for roughly the
+    // price of one key switch -- the digits of c1 are expanded once.  Result r decrypts to what applyGalois(a, elts[r]) decrypts to under the same noise
+    // bound; its limbs differ.  Element 1 / step 0 is a copy and needs no key; a missing key is refused (no NAF decomposition).
+    std::vector<Ciphertext> applyGaloisHoisted(const Ciphertext &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const {
+        std::vector<std::vector<Ciphertext>> r = applyGaloisHoistedBatch(std::vector<const Ciphertext *>{&a}, elts, gk);
+        std::vector<Ciphertext> out;
+        for (auto &v : r) out.push_back(std::move(v[0]));
+        return out;
+    }
+    std::vector<Ciphertext> rotateRowsHoisted(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoisted(a, eltsOfSteps(steps), gk); }
+    std::vector<Ciphertext> rotateVectorHoisted(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoisted(a, eltsOfSteps(steps), gk); }
+    // over a batch: result[r][b] = element r of item b; the R x batch results are members of one slab (R dense batches back to back)
+    std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const {
+        if (elts.empty()) throw std::invalid_argument("hoisted rotations take at least one Galois element");
+        if (a.empty()) return std::vector<std::vector<Ciphertext>>(elts.size());
+        std::vector<const uint64_t *> keys(elts.size(), nullptr);
+        for (size_t r = 0; r < elts.size(); r++) {
+            if (elts[r] == 1) continue;
+            if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
+            if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
+            keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+        }
+        if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
+        std::vector<Ciphertext> pa;
+        const troyhip_ct va = runOf(a, pa);
+        const size_t batch = a.size(), R = elts.size();
+        std::vector<Ciphertext> flat = Ciphertext::allocateBatch(R * batch, *a[0], 2, a[0]->coeffModulusSize());
+        troyhip_ct t = *flat[0].raw();
+        check(troyhip_apply_galois_hoisted(h(), &va, &t, elts.data(), keys.data(), (int)R, 0, batch, nullptr));
+        std::vector<std::vector<Ciphertext>> out(R);
+        for (size_t r = 0; r < R; r++)
+            for (size_t b = 0; b < batch; b++) {
+                flat[r * batch + b].copyMeta(t);
+                out[r].push_back(std::move(flat[r * batch + b]));
+            }
+        return out;
+    }
+    std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return applyGaloisHoistedBatch(Ciphertext::pointers(a), elts, gk); }
+    std::vector<std::vector<Ciphertext>> rotateRowsHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
+    std::vector<std::vector<Ciphertext>> rotateVectorHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
     void transformToNttInplace(Ciphertext &a) const { check(troyhip_transform_to_ntt(h(), a.raw(), 1, nullptr)); }
     void transformFromNttInplace(Ciphertext &a) const { check(troyhip_transform_from_ntt(h(), a.raw(), 1, nullptr)); }
     void transformToNtt(const Ciphertext &a, Ciphertext &d) const { d = a; transformToNttInplace(d); }     // :246-250
@@ -2335,6 +2375,11 @@ private:
                          [&](troyhip_ct *v, size_t count, const Ciphertext &) { check((sub ? troyhip_sub : troyhip_add)(h(), v, &vx, count, nullptr)); });
             i = j;
         }
+    }
+    std::vector<uint32_t> eltsOfSteps(const std::vector<int> &steps) const { // step 0: element 1, a copy
+        std::vector<uint32_t> elts;
+        for (int s : steps) { uint32_t e = 1; if (s) check(troyhip_galois_elt_from_step(h(), s, &e)); elts.push_back(e); }
+        return elts;
     }
     void rotate(Ciphertext &a, int steps, int conj, const GaloisKeys &gk) const {
         std::vector<uint32_t> elts;

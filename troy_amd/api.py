@@ -80,6 +80,17 @@ class DeviceBuffer:
             self.ptr = None
 
 
+class _BufferWindow(DeviceBuffer):
+    """`words` u64 of another DeviceBuffer from `offset_words` on; keeps the owner alive and frees nothing itself"""
+
+    def __init__(self, owner, offset_words, words):
+        self.lib, self.owner, self.words = owner.lib, owner, int(words)
+        self.ptr = owner.ptr + 8 * int(offset_words)
+
+    def __del__(self):
+        self.ptr = self.owner = None
+
+
 def synchronize(stream=None):
     lib = KernelProvider.lib()
     capi.check(lib, lib.troyhip_stream_synchronize(stream))
@@ -667,6 +678,42 @@ class Evaluator:
         st = a.struct()
         self._chk(self.lib.troyhip_apply_galois(self.context.h, C.byref(st), C.c_uint32(galois_elt), C.c_void_p(galois_keys.keys[idx].ptr), C.c_uint64(a.batch), self.stream))
         a._absorb(st)
+
+    # -- hoisted rotations (troyhip_apply_galois_hoisted: no reference counterpart, DESIGN.md section 4.10)
+    def applyGaloisHoisted(self, a, galois_elts, galois_keys, scratch_limit_words=0):
+        """[applyGalois(a, g) for g in galois_elts] for roughly the price of one key switch: the digits of c1 are expanded once.  Every result decrypts to
+        what applyGalois gives; its limbs differ.  Element 1 is a copy.  Returns a list of len(galois_elts) Ciphertext batches."""
+        elts = [int(g) for g in galois_elts]
+        if not elts:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "hoisted rotations take at least one Galois element")
+        ptrs = []
+        for g in elts:
+            idx = GaloisKeys.getIndex(g)
+            if g != 1 and not galois_keys.hasKey(idx):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Galois key not present")
+            ptrs.append(galois_keys.keys[idx].ptr if g != 1 else None)
+        R, item = len(elts), 2 * a.limbs * self.context.N
+        buf = DeviceBuffer(R * a.batch * item)
+        so = CtStruct(buf.ptr, item, 2, a.limbs, int(a.is_ntt_form), a.scale, a.correction_factor)
+        si = a.struct()
+        self._chk(self.lib.troyhip_apply_galois_hoisted(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), R,
+                                                        C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        out = []
+        for r in range(R):  # the results are windows of the one allocation the call filled: no copies; it is freed with the last of them
+            ct = Ciphertext(self.context, a.batch, 2, a.limbs, buf=_BufferWindow(buf, r * a.batch * item, a.batch * item))
+            ct._absorb(so)
+            out.append(ct)
+        return out
+
+    def rotateRowsHoisted(self, a, steps, galois_keys, scratch_limit_words=0):
+        if self.context.scheme not in (BFV, BGV):
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        return self.applyGaloisHoisted(a, [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps], galois_keys, scratch_limit_words)
+
+    def rotateVectorHoisted(self, a, steps, galois_keys, scratch_limit_words=0):
+        if self.context.scheme != CKKS:
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        return self.applyGaloisHoisted(a, [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps], galois_keys, scratch_limit_words)
 
     def _rotate(self, a, steps, conjugate, galois_keys):
         elts = [2 * i + 1 for i in galois_keys.keys]

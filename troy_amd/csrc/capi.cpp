@@ -791,6 +791,17 @@ int troyhip_rescale_to_next(troyhip_context *ctx, const troyhip_ct *in, troyhip_
 int troyhip_apply_galois(troyhip_context *ctx, troyhip_ct *ct, uint32_t galois_elt, const uint64_t *galois_key, uint64_t batch, void *stream) {
     return guard([&] { CtBatch x = view(ct); need(ctx)->ev.apply_galois(x, galois_elt, KsKey{galois_key}, batch, on(stream)); store(x, ct); });
 }
+int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
+                                 uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_elts < 1 || !galois_elts || !galois_keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+        std::vector<KsKey> keys((size_t)n_elts);
+        for (int i = 0; i < n_elts; i++) keys[(size_t)i] = KsKey{galois_keys[i]};
+        CtBatch o = view(out);
+        need(ctx)->ev.apply_galois_hoisted(view(in), o, galois_elts, keys.data(), n_elts, batch, scratch_limit_words, on(stream));
+        store(o, out);
+    });
+}
 
 static void rotate_internal(troyhip_context *ctx, CtBatch &x, int steps, const uint32_t *elts, const uint64_t *const *keys, int n_keys, u64 batch, hipStream_t s) {
     if (steps == 0) return; // evaluator_cuda.cu:2140-2143

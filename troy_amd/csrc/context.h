@@ -23,6 +23,9 @@ public:
     // carve `count` u64 from the arena for the current op; valid until reset()
     u64 *take(size_t count);
     void reset() { used_ = 0; }
+    // an op that runs the same carving several times (slabs) rewinds to a mark instead of growing
+    size_t mark() const { return used_; }
+    void rewind(size_t m) { used_ = m; }
     // every operation that carves scratch opens with begin(stream): the arena (and with it the context) belongs to ONE stream at
     // a time -- two streams on one context would silently overwrite each other's scratch, so the second one is refused until the
     // owner is released (troyhip_context_release_stream, after the caller has synchronised the first stream)

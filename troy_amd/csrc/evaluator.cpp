@@ -315,17 +315,9 @@ size_t Evaluator::scratch_switch_key(int limbs, u64 batch) const {
     return batch * N * (dl /*t_target*/ + rl * dl /*D*/ + 2 * rl /*acc*/ + 2 * dl /*corr*/ + 2 /*last*/) + 512;
 }
 
-// switchKeyInplace (evaluator_cuda.cu:1163-1362; CPU src/evaluator.cpp:2310-2653)
-void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys) {
-    check_ct(ct);
-    if (!target) throw Error(ST_INVALID_ARGUMENT, "target_iter");
-    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
-    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters");
-    if (c.scheme == SCHEME_BFV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
-    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    if (c.scheme == SCHEME_BGV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
-    if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be at least 2");
-    const u64 N = c.N, dl = ct.limbs, rl = dl + 1, K = c.K;
+// the constants of one key switch at `limbs` data limbs over `batch` items (what every kernel of both halves reads)
+KsArgs Evaluator::ks_args(int limbs, u64 batch) const {
+    const u64 dl = limbs, K = c.K;
     const host::RnsLevel &key_rns = c.level((int)K).rns;
     KsArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -342,13 +334,13 @@ void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const 
         a.inv_qk_mod_t = key_rns.inv_q_last_mod_t;
     }
     a.logn = c.logn; a.dl = dl; a.K = K; a.batch = batch;
+    return a;
+}
 
-    c.arena.begin(s);
-    c.arena.reserve(scratch_switch_key((int)dl, batch));
-    u64 *D = c.arena.take(batch * rl * dl * N);
-    u64 *acc = c.arena.take(batch * 2 * rl * N);
+// first half of the key switch, target -> acc: decompose + extend the target to every output prime, transform, inner product with the key
+void Evaluator::ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsArgs &a, hipStream_t s) {
+    const u64 N = c.N, dl = a.dl, rl = dl + 1, K = a.K, batch = a.batch;
     std::vector<uint8_t> out_ids(a.key_id, a.key_id + rl);
-
     const u64 *coeff_target = target;
     u64 ct_tb = t_bstride;
     if (c.scheme == SCHEME_CKKS) { // bring the target to coefficient form (evaluator_cuda.cu:1215-1216)
@@ -392,7 +384,12 @@ void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const 
         // inner products with the key (128-bit lazy accumulation, one reduction per output)
         launch_ks_mac(D, key.data, mac_target, t_bstride, acc, a, s);
     }
+}
 
+// second half, acc (+ base) -> ct: the CKKS correction or one of the three mod-down routes of BFV / BGV, accumulated onto what ct holds or onto (base, 0)
+void Evaluator::ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys) {
+    const u64 N = c.N, dl = a.dl, rl = dl + 1, K = a.K, batch = a.batch, qk = c.primes[K - 1];
+    std::vector<uint8_t> out_ids(a.key_id, a.key_id + rl);
     const LimbMap amap_md = c.ids_map(out_ids);
     bool md_primes33 = true; // the single-pass epilogue's lazy reduction (lite_reduce4) wants primes of at least 33 bits
     for (u64 j = 0; j < dl; j++) md_primes33 = md_primes33 && c.primes[j] >= (u64(1) << 33);
@@ -462,6 +459,26 @@ void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const 
             launch_ks_moddown(c.scheme == SCHEME_BFV ? 0 : 2, acc, ct.data, ct.bstride, a, s);
         }
     }
+}
+
+// switchKeyInplace (evaluator_cuda.cu:1163-1362; CPU src/evaluator.cpp:2310-2653)
+void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys) {
+    check_ct(ct);
+    if (!target) throw Error(ST_INVALID_ARGUMENT, "target_iter");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters");
+    if (c.scheme == SCHEME_BFV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
+    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
+    if (c.scheme == SCHEME_BGV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be at least 2");
+    const u64 N = c.N, dl = ct.limbs, rl = dl + 1;
+    const KsArgs a = ks_args(ct.limbs, batch);
+    c.arena.begin(s);
+    c.arena.reserve(scratch_switch_key((int)dl, batch));
+    u64 *D = c.arena.take(batch * rl * dl * N);
+    u64 *acc = c.arena.take(batch * 2 * rl * N);
+    ks_target_to_acc(target, t_bstride, key, D, acc, a, s);
+    ks_acc_to_ct(ct, acc, a, s, base, base_bstride, base_polys);
 }
 
 // relinearizeInternal (evaluator_cuda.cu:703-744), destination size 2, from any size up to SEAL_CIPHERTEXT_SIZE_MAX.  Exactly as
@@ -637,6 +654,106 @@ void Evaluator::apply_galois(CtBatch &ct, uint32_t elt, const KsKey &key, u64 ba
     launch_galois(ntt_form, ct.data + pw, ct.bstride, t1, pw, c.d_desc, map, c.logn, elt, L, batch, s);
     // switch_key resets the arena but never grows it now, so t0 and t1 (beyond its working set) stay intact; it takes ct as (t0, 0)
     switch_key(ct, t1, pw, key, batch, s, t0, pw);
+}
+
+// Hoisted rotations (Halevi-Shoup; no reference counterpart): the digits of c1 are decomposed, extended and transformed ONCE
+// per item; every Galois element then costs a gathered inner product over them (the automorphism is a permutation in NTT form), sigma(c0) and the
+// second half of the key switch.  Scratch per slab of `bs` items and `rs` rotations:
+//   bs N (rl dl [D] + dl [CKKS: c1 in coefficient form]) + rs bs N (2 rl [acc] + dl [sigma(c0)] + 2 dl + 4 [what the second half carves])
+// A slab is the whole batch times as many consecutive rotations as fit (HOIST_MAX_ROT at the most), or -- where one rotation of the whole batch does
+// not fit -- a run of items times one rotation; the digits of a run of items are made once for all its rotations either way.
+static const u64 HOIST_DEFAULT_SCRATCH_WORDS = u64(1) << 28; // 2 GiB: troyhip.h documents it
+void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+    for (int r = 0; r < R; r++) {
+        if (!(elts[r] & 1) || elts[r] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+        if (elts[r] != 1 && !keys[r].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    }
+    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    if (c.scheme == SCHEME_BFV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
+    if (c.scheme == SCHEME_CKKS && !in.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
+    if (c.scheme == SCHEME_BGV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
+    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "hoisted rotations: more than 63 digits");
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = in.scale; out.cf = in.cf;
+    if (!batch) return;
+    {   // the destination holds R batches back to back and must not share a word with the operand, which every rotation reads
+        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + ((u64)R * batch - 1) * out.bstride + 2 * pw;
+        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations: destination must be a distinct buffer");
+    }
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
+    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
+    const u64 per_item = N * (rl * dl + (ckks ? dl : 0)), per_rot_item = N * (2 * rl + dl + 2 * dl + 4);
+    if (per_item + per_rot_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one rotation of one ciphertext");
+    u64 bs = batch, rs = 1;
+    if (batch * (per_item + per_rot_item) + slack <= limit) rs = std::min<u64>({(u64)R, (u64)HOIST_MAX_ROT, (limit - slack - batch * per_item) / (batch * per_rot_item)});
+    else bs = (limit - slack) / (per_item + per_rot_item);
+
+    c.arena.begin(s);
+    c.arena.reserve(bs * per_item + rs * bs * per_rot_item + slack);
+    u64 *D = c.arena.take(bs * rl * dl * N);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
+    const size_t mark = c.arena.mark();
+    const LimbMap map = c.ct_map(L);
+    u64 src_bound = 0;
+    for (u64 j = 0; j < dl; j++) src_bound = std::max(src_bound, c.primes[j]);
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        KsArgs a = ks_args(L, nb);
+        // the digits of this run of items, once: D[b][i][j] = NTT_{p_i}(d_j mod p_i)
+        const u64 *coeff = c1;
+        u64 coeff_bs = in.bstride;
+        if (ckks) {
+            if (ntt1_supported(c.logn, map, nb * dl, 3)) launch_ntt1(tt, c1, c.d_desc, map, nb * dl, c.logn, true, s, ~0ull, nullptr, nullptr, in.bstride);
+            else {
+                launch_copy_strided(c1, in.bstride, tt, pw, pw, nb, s);
+                launch_ntt(tt, c.d_desc, map, nb * dl, c.logn, true, s);
+            }
+            coeff = tt;
+            coeff_bs = pw;
+        }
+        const LimbMap dmap = c.ids_map(std::vector<uint8_t>(a.key_id, a.key_id + rl), (uint32_t)dl);
+        if (ntt2_supported(c.logn)) launch_ntt2(D, coeff, coeff_bs, true, c.d_desc, dmap, nb * rl * dl, c.logn, false, s, false, src_bound);
+        else {
+            launch_ks_expand(coeff, coeff_bs, D, a, s);
+            launch_ntt(D, c.d_desc, dmap, nb * rl * dl, c.logn, false, s);
+        }
+        for (int r0 = 0; r0 < R;) {
+            if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
+                launch_copy_strided(c0, in.bstride, out.data + ((u64)r0 * batch + b0) * out.bstride, out.bstride, 2 * pw, nb, s);
+                r0++;
+                continue;
+            }
+            HoistArgs h;
+            std::memset(&h, 0, sizeof(h));
+            while (r0 + (int)h.rots < R && h.rots < rs && elts[r0 + h.rots] != 1) {
+                h.elt[h.rots] = elts[r0 + h.rots];
+                h.key[h.rots] = keys[r0 + h.rots].data;
+                h.rots++;
+            }
+            for (u32 r = 0; r < h.rots; r++) launch_galois(ckks, c0, in.bstride, sig0 + (u64)r * nb * pw, pw, c.d_desc, map, c.logn, h.elt[r], dl, nb, s);
+            launch_hoist_mac(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
+            // the second half of the key switch over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
+            CtBatch o = out;
+            o.data = out.data + ((u64)r0 * batch + b0) * out.bstride;
+            o.size = 2; o.limbs = L; o.ntt = in.ntt;
+            a.batch = (u64)h.rots * nb;
+            c.arena.rewind(mark);
+            if (h.rots == 1 || nb == batch) ks_acc_to_ct(o, acc, a, s, sig0, pw, 1);
+            else throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch");
+            a.batch = nb;
+            stats::counter(stats::HOIST_SLABS)++;
+            r0 += (int)h.rots;
+        }
+    }
+    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = in.scale; out.cf = in.cf;
 }
 
 void Evaluator::transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s) { // evaluator_cuda.cu:1950-1985

@@ -25,6 +25,8 @@ struct KsKey {
     const u64 *data = nullptr;
 };
 
+struct KsArgs; // kernels.h
+
 class Evaluator {
 public:
     explicit Evaluator(Context &ctx) : c(ctx) {}
@@ -60,6 +62,11 @@ public:
     void mod_switch_to_next(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void rescale_to_next(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void apply_galois(CtBatch &ct, uint32_t elt, const KsKey &key, u64 batch, hipStream_t s);
+    // Hoisted rotations: out item r * batch + b = the Galois automorphism elts[r] of in item b, key-switched with keys[r] (R dense batches back to
+    // back; out.data / out.bstride are the caller's, room for R * batch size-2 items, distinct from in).  The digits of c1 are expanded once per
+    // item; element 1 is a copy and reads no key.  The arena request stays under scratch_limit_words (0: 2^28 words), in slabs where needed.
+    // The limbs are NOT those of apply_galois; the decryption is.
+    void apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s);
     void transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void transform_from_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void multiply_plain_ntt(CtBatch &ct, const u64 *plain, double plain_scale, u64 batch, hipStream_t s);
@@ -75,6 +82,10 @@ private:
     // dotProductCtSkArray: acc [batch][limbs][N] = c_0 + c_1 s + .. in the form the ciphertext is in, carved from the arena together with
     // `extra` more words for the caller (what decrypt and noise_budget share)
     u64 *dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, struct DecryptArgs &a, hipStream_t s);
+    // the two halves of switch_key: target -> acc (D, acc: scratch of batch (limbs + 1) limbs N and batch 2 (limbs + 1) N words), acc (+ base) -> ct
+    KsArgs ks_args(int limbs, u64 batch) const;
+    void ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsArgs &a, hipStream_t s);
+    void ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys);
     bool scale_ok(double scale, int limbs) const;
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void balance_correction(u64 f1, u64 f2, u64 &f, u64 &e1, u64 &e2) const;

@@ -145,6 +145,11 @@ struct KsArgs {
 };
 void launch_ks_expand(const u64 *target, u64 t_bstride, u64 *D, const KsArgs &a, hipStream_t s);
 void launch_ks_mac(const u64 *D, const u64 *key, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, hipStream_t s);
+// hoisted rotations: acc[(r * batch + b) * 2 + k][i][n] = sum_j opnd(b,i,j)[pi_r(n)] * key[r][j][k][limb(i)][n] mod p_i over the materialised digits D
+// (the operands of launch_ks_mac, read through the NTT-form Galois index map pi_r of element elt[r]; the key is not permuted)
+enum { HOIST_MAX_ROT = 16 };
+struct HoistArgs { const u64 *key[HOIST_MAX_ROT]; uint32_t elt[HOIST_MAX_ROT]; u32 rots; };
+void launch_hoist_mac(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistArgs &h, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

@@ -639,6 +639,69 @@ template <int NB, int V> __global__ __launch_bounds__(EW_THREADS) void ks_mac_ke
         }
     }
 }
+// Hoisted rotations: the inner product of ks_mac_kernel with its operands read through the NTT-form Galois index map of galois_ntt_kernel,
+//   acc[(r * batch + b) * 2 + k][i][n] = sum_j opnd(b,i,j)[pi_r(n)] * key_r[j][k][limb(i)][n] mod p_i.
+// The map costs two bit reversals and a multiply per (rotation, coefficient), outside the loop over j; the gathered 8-byte reads fall into one row of D
+// (N words), which the L2 holds; the key is streamed in order.  Four accumulators per key component and thread:
+//   ROT4 == false: four batch items of ONE rotation -- every key word is used four times (the batched caller);
+//   ROT4 == true:  four rotations of ONE item -- nothing is shared, nothing is recomputed (one or two ciphertexts, where the other form idles 3/4 or 1/2).
+// Block order: (rotation or group of four, output prime and coefficient window, batch group) with the batch group fastest, as ks_mac_kernel: the
+// workgroups in flight share a narrow window of one key (of four keys).
+__device__ __forceinline__ u32 galois_ntt_index(u32 n, uint32_t elt, int logn) {
+    const u32 N = 1u << logn;
+    const uint32_t rev = __brev((uint32_t)(n + N)) >> (32 - (logn + 1));
+    const u64 raw = (((u64)elt * rev) >> 1) & (N - 1);
+    return logn ? (__brev((uint32_t)raw) >> (32 - logn)) : 0;
+}
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void hoist_mac_kernel(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, KsArgs a, HoistArgs h) {
+    const u64 N = u64(1) << a.logn, rl = a.dl + 1;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4), windows = (u32)(((rl << a.logn) + EW_THREADS - 1) / EW_THREADS);
+    const u32 g = blockIdx.x % groups, rest = blockIdx.x / groups, wi = rest % windows, rg = rest / windows;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over (dl + 1) * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 i = idx >> a.logn;
+    const Mod m = mod_of(a.primes[a.key_id[i]]);
+    const u64 kl = a.key_limb[i];
+    // accumulator t: (rotation rr[t], item bb[t]); a ragged last group recomputes its last member and stores nothing for it
+    u32 rr[4], src[4];
+    u64 bb[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u32 r = ROT4 ? rg * 4 + t : rg;
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        rr[t] = r < h.rots ? r : h.rots - 1;
+        bb[t] = b < a.batch ? b : a.batch - 1;
+        if (ROT4 || t == 0) src[t] = galois_ntt_index(n, h.elt[rr[t]], a.logn);
+        else src[t] = src[0];
+    }
+    MacAcc s0[4], s1[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); }
+    for (u64 j = 0; j < a.dl; j++) {
+        const u64 koff = ((j * 2) * a.K + kl) * N + n;
+        u64 k0[4], k1[4], x[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (ROT4 || t == 0) { const u64 *kp = h.key[rr[t]] + koff; k0[t] = kp[0]; k1[t] = kp[a.K * N]; }
+            else { k0[t] = k0[0]; k1[t] = k1[0]; }
+            const u64 *xp = (ckks_target && i == j) ? ckks_target + bb[t] * t_bstride + j * N : D + ((bb[t] * rl + i) * a.dl + j) * N;
+            x[t] = xp[src[t]];
+        }
+        mac4(s0, x, k0);
+        mac4(s1, x, k1);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u32 r = ROT4 ? rg * 4 + t : rg;
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (r >= h.rots || b >= a.batch) break;
+        const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+        const u64 o = (u64)r * a.batch + b;
+        acc[((o * 2 + 0) * rl + i) * N + n] = barrett128(v0.lo, v0.hi, m);
+        acc[((o * 2 + 1) * rl + i) * N + n] = barrett128(v1.lo, v1.hi, m);
+    }
+}
 // BFV (kind 0) / BGV (kind 2) mod-down, everything in coefficient form (evaluator.cpp:2528-2648):
 //   ct[b][k][j][n] += (acc_j - [t']_{q_j} + [half]_{q_j}) * qk^-1 mod q_j, t' = (acc_last + half) mod qk       (BFV)
 //   ct[b][k][j][n] += (acc_j - [acc_last]_{q_j} - [k_t]_{q_j} * qk) * qk^-1,  k_t = -acc_last * qk^-1 mod t     (BGV)
@@ -722,6 +785,18 @@ void launch_ks_mac(const u64 *D, const u64 *key, const u64 *ckks_target, u64 t_b
     const u64 groups = (a.batch + NB - 1) / NB, per_group = (u64)(a.dl + 1) << (a.logn - (V == 2 ? 1 : 0));
     TROY_LAUNCH(HIP_KERNEL_NAME(ks_mac_kernel<NB, V>), dim3(ceil_div(per_group, EW_THREADS) * groups), dim3(EW_THREADS), 0, s, D, key, ckks_target, t_bstride, acc, a);
     launch_check("ks_mac_kernel");
+}
+void launch_hoist_mac(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistArgs &h, hipStream_t s) {
+    if (a.dl >= 64) throw Error(ST_LOGIC_ERROR, "hoist_mac: more than 63 digits");
+    if (!h.rots || h.rots > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "hoist_mac: 1 .. 16 rotations of a non-empty batch per launch");
+    // one or two ciphertexts: four rotations per thread, every accumulator useful; a batch: four items per thread share each key word
+    const bool rot4 = a.batch <= 2 && h.rots > 1;
+    const u64 windows = ((a.dl + 1) << a.logn) / EW_THREADS + ((((a.dl + 1) << a.logn) % EW_THREADS) ? 1 : 0);
+    const u64 blocks = rot4 ? (u64)((h.rots + 3) / 4) * windows * a.batch : (u64)h.rots * windows * ((a.batch + 3) / 4);
+    if (blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, "hoist_mac: batch too large for one launch");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(hoist_mac_kernel<true>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(hoist_mac_kernel<false>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    launch_check("hoist_mac_kernel");
 }
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s) {
     u64 total = a.batch * 2 * a.dl << a.logn;
