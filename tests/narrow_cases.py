@@ -27,7 +27,7 @@ def smallest_ntt_prime(N):
 
 def width_primes(api, N):
     """the primes of one standalone launch at ring size N: the smallest NTT-friendly prime, one each of about 20 .. 34 bits where one exists, one
-    60-bit prime -- every butterfly class in one launch (select_class / the class loop of launch_ntt1)"""
+    60-bit prime -- every butterfly class in one launch (plan_classes of ntt2.hip / the class loop of launch_ntt1)"""
     out = [smallest_ntt_prime(N)]
     for b in WIDTHS + (60,):
         if (1 << b) <= 2 * N:

@@ -259,7 +259,7 @@ void Evaluator::multiply(const CtBatch &a, const CtBatch &b, CtBatch &out, u64 b
         if (!all_done) {
             const PrimeDesc *idesc = behz_floor_prescaled(*lv.behz) ? lv.behz->floor_desc : c.d_desc;
             launch_ntt(dq, idesc, qmap, batch * ds * L, c.logn, true, s);
-            launch_ntt(db, idesc, c.ids_map(lv.bsk_ids), batch * ds * nb, c.logn, true, s);
+            launch_ntt(db, idesc, bmap, batch * ds * nb, c.logn, true, s);
         }
         // (6)-(8) multiply by t, floor, Shenoy-Kumaresan back to base q
         if (all_done) {
@@ -315,11 +315,12 @@ size_t Evaluator::scratch_switch_key(int limbs, u64 batch) const {
     return batch * N * (dl /*t_target*/ + rl * dl /*D*/ + 2 * rl /*acc*/ + 2 * dl /*corr*/ + 2 /*last*/) + 512;
 }
 
-// the constants of one key switch at `limbs` data limbs over `batch` items (what every kernel of both halves reads)
-KsArgs Evaluator::ks_args(int limbs, u64 batch) const {
+// one key switch at `limbs` data limbs over `batch` items
+KsPlan Evaluator::ks_plan(int limbs, u64 batch) const {
     const u64 dl = limbs, K = c.K;
     const host::RnsLevel &key_rns = c.level((int)K).rns;
-    KsArgs a;
+    KsPlan k;
+    KsArgs &a = k.a;
     std::memset(&a, 0, sizeof(a));
     a.primes = c.d_desc;
     for (u64 i = 0; i < dl; i++) { a.key_id[i] = (uint8_t)i; a.key_limb[i] = (uint8_t)i; }
@@ -334,30 +335,58 @@ KsArgs Evaluator::ks_args(int limbs, u64 batch) const {
         a.inv_qk_mod_t = key_rns.inv_q_last_mod_t;
     }
     a.logn = c.logn; a.dl = dl; a.K = K; a.batch = batch;
-    return a;
+    const std::vector<uint8_t> out_ids(a.key_id, a.key_id + dl + 1);
+    k.digit_map = c.ids_map(out_ids, (uint32_t)dl);
+    k.acc_map = c.ids_map(out_ids);
+    return k;
+}
+void Evaluator::check_ks_form(bool ntt) const {
+    if (c.scheme == SCHEME_BFV && ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
+    if (c.scheme == SCHEME_CKKS && !ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
+    if (c.scheme == SCHEME_BGV && ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+}
+// bring a CKKS target to coefficient form (evaluator_cuda.cu:1215-1216)
+const u64 *Evaluator::ks_coeff_target(const u64 *target, u64 &t_bstride, u64 *tt, const KsPlan &k, hipStream_t s) {
+    const u64 dl = k.a.dl, batch = k.a.batch, pw = dl * c.N;
+    const LimbMap tmap = c.ct_map((int)dl);
+    if (ntt1_supported(c.logn, tmap, batch * dl, Ntt1Feature::STRIDED_INVERSE)) { // out of place: the single-pass inverse reads the strided target itself
+        Ntt1Request q{c.d_desc, tmap, batch * dl, c.logn};
+        q.data = tt;
+        q.inverse = true;
+        q.src = target;
+        q.src_ostride = t_bstride;
+        launch_ntt1(q, s);
+    } else {
+        launch_copy_strided(target, t_bstride, tt, pw, pw, batch, s);
+        launch_ntt(tt, c.d_desc, tmap, batch * dl, c.logn, true, s);
+    }
+    t_bstride = pw;
+    return tt;
+}
+// the digits are canonical residues of the ciphertext primes: an output prime p with 8p above the largest of them needs no reduction
+static u64 ks_src_bound(const Context &c, u64 dl) { return *std::max_element(c.primes.begin(), c.primes.begin() + dl); }
+void Evaluator::ks_expand_digits(const u64 *coeff, u64 coeff_bstride, u64 *D, const KsPlan &k, hipStream_t s) {
+    const u64 rows = k.a.batch * (k.a.dl + 1) * k.a.dl;
+    if (ntt2_supported(c.logn)) {
+        Ntt2Request q{D, c.d_desc, k.digit_map, rows, c.logn};
+        q.src.ptr = coeff;
+        q.src.kind = Ntt2Source::KS_DIGITS;
+        q.src.ostride = coeff_bstride;
+        q.src.bound = ks_src_bound(c, k.a.dl);
+        launch_ntt2(q, s);
+    } else {
+        launch_ks_expand(coeff, coeff_bstride, D, k.a, s);
+        launch_ntt(D, c.d_desc, k.digit_map, rows, c.logn, false, s);
+    }
 }
 
 // first half of the key switch, target -> acc: decompose + extend the target to every output prime, transform, inner product with the key
-void Evaluator::ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsArgs &a, hipStream_t s) {
-    const u64 N = c.N, dl = a.dl, rl = dl + 1, K = a.K, batch = a.batch;
-    std::vector<uint8_t> out_ids(a.key_id, a.key_id + rl);
+void Evaluator::ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsPlan &k, hipStream_t s) {
+    const KsArgs &a = k.a;
+    const u64 N = c.N, dl = a.dl, rl = dl + 1, batch = a.batch;
     const u64 *coeff_target = target;
     u64 ct_tb = t_bstride;
-    if (c.scheme == SCHEME_CKKS) { // bring the target to coefficient form (evaluator_cuda.cu:1215-1216)
-        u64 *tt = c.arena.take(batch * dl * N);
-        const LimbMap tmap = c.ct_map((int)dl);
-        if (ntt1_supported(c.logn, tmap, batch * dl, 3)) { // out of place: the single-pass inverse reads the strided target itself
-            launch_ntt1(tt, target, c.d_desc, tmap, batch * dl, c.logn, true, s, ~0ull, nullptr, nullptr, t_bstride);
-        } else {
-            launch_copy_strided(target, t_bstride, tt, dl * N, dl * N, batch, s);
-            launch_ntt(tt, c.d_desc, tmap, batch * dl, c.logn, true, s);
-        }
-        coeff_target = tt;
-        ct_tb = dl * N;
-    }
-    // the digits are canonical residues of the ciphertext primes: an output prime p with 8p above the largest of them needs no reduction
-    u64 src_bound = 0;
-    for (u64 j = 0; j < dl; j++) src_bound = std::max(src_bound, c.primes[j]);
+    if (c.scheme == SCHEME_CKKS) coeff_target = ks_coeff_target(target, ct_tb, c.arena.take(batch * dl * N), k, s);
     // decompose + extend every limb to every output prime, ONE batched NTT over all (L+1)*L rows, inner product with the key
     const u64 *mac_target = c.scheme == SCHEME_CKKS ? target : nullptr;
     if (ntt2_ks_mac_supported(c.logn) && ks_fused()) {
@@ -365,42 +394,34 @@ void Evaluator::ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &
         // the transforms in registers and accumulates them against the key -- the expanded digits are never written back
         // lazy accumulation is exact while dl * (bound of the lazy transform) * p < 2^128 for every output prime (CKKS replaces one
         // operand by a canonical value): the bound is 8p with guarded butterflies, 59p with the guard-free ones (primes below 2^58)
-        const LimbMap ks_map = c.ids_map(out_ids, (uint32_t)dl);
         bool lazy = true;
         for (u64 i = 0; i < rl; i++) {
-            const long double p = (long double)c.primes[out_ids[i]];
-            const long double bound = ((ks_map.lean >> i) & 1) ? 59.0L : 8.0L;
+            const long double p = (long double)c.primes[a.key_id[i]];
+            const long double bound = ((k.digit_map.lean >> i) & 1) ? 59.0L : 8.0L;
             lazy = lazy && (long double)dl * bound * p * p < 3.0e38L; // 2^128 = 3.4e38
         }
-        launch_ntt2_ks_mac(D, coeff_target, ct_tb, c.d_desc, ks_map, batch * rl * dl, c.logn, key.data, acc, a.key_limb, (unsigned)K,
-                           mac_target, t_bstride, lazy, src_bound, s);
+        launch_ntt2_ks_mac(D, coeff_target, ct_tb, k.digit_map, batch * rl * dl, key.data, acc, mac_target, t_bstride, lazy, ks_src_bound(c, dl), a, s);
     } else {
-        if (ntt2_supported(c.logn)) {
-            launch_ntt2(D, coeff_target, ct_tb, true, c.d_desc, c.ids_map(out_ids, (uint32_t)dl), batch * rl * dl, c.logn, false, s, false, src_bound);
-        } else {
-            launch_ks_expand(coeff_target, ct_tb, D, a, s);
-            launch_ntt(D, c.d_desc, c.ids_map(out_ids, (uint32_t)dl), batch * rl * dl, c.logn, false, s);
-        }
+        ks_expand_digits(coeff_target, ct_tb, D, k, s);
         // inner products with the key (128-bit lazy accumulation, one reduction per output)
         launch_ks_mac(D, key.data, mac_target, t_bstride, acc, a, s);
     }
 }
 
 // second half, acc (+ base) -> ct: the CKKS correction or one of the three mod-down routes of BFV / BGV, accumulated onto what ct holds or onto (base, 0)
-void Evaluator::ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys) {
+void Evaluator::ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsPlan &k, hipStream_t s, KsBase base) {
+    const KsArgs &a = k.a;
     const u64 N = c.N, dl = a.dl, rl = dl + 1, K = a.K, batch = a.batch, qk = c.primes[K - 1];
-    std::vector<uint8_t> out_ids(a.key_id, a.key_id + rl);
-    const LimbMap amap_md = c.ids_map(out_ids);
-    bool md_primes33 = true; // the single-pass epilogue's lazy reduction (lite_reduce4) wants primes of at least 33 bits
-    for (u64 j = 0; j < dl; j++) md_primes33 = md_primes33 && c.primes[j] >= (u64(1) << 33);
-    const bool md_single = c.scheme == SCHEME_BFV && c.d_desc_md && md_primes33 && ntt1_supported(c.logn, amap_md, batch * 2 * rl, 1) && ks_moddown_fused();
+    const LimbMap &amap = k.acc_map;
+    const bool md_single = c.scheme == SCHEME_BFV && c.d_desc_md && primes_at_least_33_bits(c, (int)dl) &&
+                           ntt1_supported(c.logn, amap, batch * 2 * rl, Ntt1Feature::MOD_DOWN) && ks_moddown_fused();
     const bool md_two_pass = c.scheme != SCHEME_CKKS && !md_single && c.d_desc_md && ntt2_supported(c.logn) && ks_moddown_fused();
     const bool ckks_single = c.scheme == SCHEME_CKKS && c.d_inv_qk && corr_fused() && primes_at_least_33_bits(c, (int)dl) &&
-                             ntt1_supported(c.logn, c.ct_map((int)dl), batch * 2 * dl, 2);
-    if (base && !md_two_pass && !md_single && !ckks_single) { // the fused epilogues take (base, 0) directly; the element-wise forms accumulate onto what ct holds
-        if (base != ct.data) launch_copy_strided(base, base_bstride, ct.data, ct.bstride, (u64)base_polys * dl * N, batch, s);
-        if (base_polys < 2) launch_zero_strided(ct.data + dl * N, ct.bstride, dl * N, batch, s);
-        base = nullptr;
+                             ntt1_supported(c.logn, c.ct_map((int)dl), batch * 2 * dl, Ntt1Feature::CORRECTION);
+    if (base.ptr && !md_two_pass && !md_single && !ckks_single) { // the fused epilogues take the base directly; the element-wise forms accumulate onto what ct holds
+        if (base.ptr != ct.data) launch_copy_strided(base.ptr, base.bstride, ct.data, ct.bstride, (u64)base.polys * dl * N, batch, s);
+        if (base.polys < 2) launch_zero_strided(ct.data + dl * N, ct.bstride, dl * N, batch, s);
+        base = KsBase{};
     }
     if (c.scheme == SCHEME_CKKS) {
         // special-prime limb -> coefficient form, correction polynomial -> NTT form, combine
@@ -412,48 +433,56 @@ void Evaluator::ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t
             // the correction is built, transformed and combined by ONE single-pass transform (Ntt1Corr): no corr buffer, no element-wise kernels
             Ntt1Corr cr{last, acc, rl * N, ct.data, ct.bstride, dl * N, 2, c.d_inv_qk, qk, a.half, true};
             cr.base = base;
-            cr.base_gstride = base_bstride;
-            cr.base_polys = base_polys;
-            launch_ntt1(nullptr, nullptr, c.d_desc, cmap, batch * 2 * dl, c.logn, false, s, ~0ull, nullptr, &cr);
+            Ntt1Request q{c.d_desc, cmap, batch * 2 * dl, c.logn};
+            q.cr = &cr;
+            launch_ntt1(q, s);
         } else {
             launch_ks_ckks_corr(last, corr, a, s);
             launch_ntt(corr, c.d_desc, cmap, batch * 2 * dl, c.logn, false, s);
             launch_ks_ckks_combine(acc, corr, ct.data, ct.bstride, a, s);
         }
     } else {
-        const LimbMap &amap = amap_md;
         if (md_single) {
             // single-pass inverse: the special limb first, then the data limbs with the mod-down as their store epilogue (no acc round trip,
             // no separate memory-bound kernel)
-            launch_ntt1(acc, nullptr, c.d_desc, amap, batch * 2 * rl, c.logn, true, s, u64(1) << dl);
-            Ntt1ModDown md{ct.data, ct.bstride, dl, qk, a.half};
-            md.base = base;
-            md.base_bstride = base_bstride;
-            md.base_polys = base_polys;
-            launch_ntt1(acc, nullptr, c.d_desc_md, amap, batch * 2 * rl, c.logn, true, s, (u64(1) << dl) - 1, &md);
+            Ntt1Request q{c.d_desc, amap, batch * 2 * rl, c.logn};
+            q.data = acc;
+            q.inverse = true;
+            q.slot_mask = u64(1) << dl;
+            launch_ntt1(q, s);
+            const Ntt1ModDown md{ct.data, ct.bstride, dl, qk, a.half, base};
+            q.primes = c.d_desc_md;
+            q.slot_mask = (u64(1) << dl) - 1;
+            q.md = &md;
+            launch_ntt1(q, s);
         } else if (md_two_pass) {
             // two-pass inverse, same shape: the special limb first, then the data limbs with the mod-down (BFV or BGV) as the last pass's epilogue
             // the first pass is the same for every slot (N^-1 and qk^-1 ride on the last inverse stage): a small launch runs it over the special limb
             // and the data limbs at once, then the two last passes -- three kernels instead of four, the tiny special-limb launch (2 batch rows) half gone
             const bool one_first_pass = take_merged(c, batch * 2 * rl);
+            Ntt2Request q{acc, c.d_desc, amap, batch * 2 * rl, c.logn};
+            q.inverse = true;
             if (one_first_pass) {
-                launch_ntt2_slots(acc, nullptr, 0, false, c.d_desc, amap, batch * 2 * rl, c.logn, true, s, false, 0, 0, (unsigned)rl, nullptr, 1);
+                q.passes = Ntt2Passes::FIRST;
+                launch_ntt2(q, s);
                 // the second passes plan their FP64 reductions from the bound the SHARED first pass left: the largest prime of slots 0 .. rl, not of their own range
-                launch_ntt2_slots(acc, nullptr, 0, false, c.d_desc, amap, batch * 2 * rl, c.logn, true, s, false, 0, (unsigned)dl, 1, nullptr, 2, 0, (unsigned)rl);
-            } else {
-                launch_ntt2_slots(acc, nullptr, 0, false, c.d_desc, amap, batch * 2 * rl, c.logn, true, s, false, 0, (unsigned)dl, 1, nullptr);
+                q.passes = Ntt2Passes::SECOND;
+                q.plan_count = (unsigned)rl;
             }
+            q.slot_begin = (unsigned)dl;
+            q.slot_count = 1;
+            launch_ntt2(q, s);
             u64 *share = nullptr;
             if (c.scheme == SCHEME_BGV) { // what the special limb takes out of every data limb, once per coefficient (the CKKS part of the reservation is free)
                 share = c.arena.take(batch * 4 * N);
                 launch_ks_bgv_share(acc, share, a, s);
             }
-            Ntt2ModDown md{c.scheme == SCHEME_BFV ? 0 : 2, ct.data, ct.bstride, (unsigned)dl, qk, a.half, share};
-            md.base = base;
-            md.base_bstride = base_bstride;
-            md.base_polys = base_polys;
-            launch_ntt2_slots(acc, nullptr, 0, false, c.d_desc_md, amap, batch * 2 * rl, c.logn, true, s, false, 0, 0, (unsigned)dl, &md, one_first_pass ? 2u : 3u, 0,
-                              one_first_pass ? (unsigned)rl : 0u);
+            const Ntt2ModDown md{c.scheme == SCHEME_BFV ? 0 : 2, ct.data, ct.bstride, (unsigned)dl, qk, a.half, share, base};
+            q.primes = c.d_desc_md;
+            q.slot_begin = 0;
+            q.slot_count = (unsigned)dl;
+            q.md = &md;
+            launch_ntt2(q, s);
         } else {
             launch_ntt(acc, c.d_desc, amap, batch * 2 * rl, c.logn, true, s);
             launch_ks_moddown(c.scheme == SCHEME_BFV ? 0 : 2, acc, ct.data, ct.bstride, a, s);
@@ -462,23 +491,21 @@ void Evaluator::ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t
 }
 
 // switchKeyInplace (evaluator_cuda.cu:1163-1362; CPU src/evaluator.cpp:2310-2653)
-void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys) {
+void Evaluator::switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const KsBase &base) {
     check_ct(ct);
     if (!target) throw Error(ST_INVALID_ARGUMENT, "target_iter");
     if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
     if (!key.data) throw Error(ST_INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters");
-    if (c.scheme == SCHEME_BFV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
-    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    if (c.scheme == SCHEME_BGV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    check_ks_form(ct.ntt);
     if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be at least 2");
     const u64 N = c.N, dl = ct.limbs, rl = dl + 1;
-    const KsArgs a = ks_args(ct.limbs, batch);
+    const KsPlan k = ks_plan(ct.limbs, batch);
     c.arena.begin(s);
     c.arena.reserve(scratch_switch_key((int)dl, batch));
     u64 *D = c.arena.take(batch * rl * dl * N);
     u64 *acc = c.arena.take(batch * 2 * rl * N);
-    ks_target_to_acc(target, t_bstride, key, D, acc, a, s);
-    ks_acc_to_ct(ct, acc, a, s, base, base_bstride, base_polys);
+    ks_target_to_acc(target, t_bstride, key, D, acc, k, s);
+    ks_acc_to_ct(ct, acc, k, s, base);
 }
 
 // relinearizeInternal (evaluator_cuda.cu:703-744), destination size 2, from any size up to SEAL_CIPHERTEXT_SIZE_MAX.  Exactly as
@@ -523,7 +550,7 @@ void Evaluator::relinearize_to(const CtBatch &in, CtBatch &out, const KsKey *key
     out.data = d;
     out.bstride = bs;
     out.size = 2;
-    switch_key(out, in.data + 2 * pw, in.bstride, keys[0], batch, s, in.data, in.bstride, 2);
+    switch_key(out, in.data + 2 * pw, in.bstride, keys[0], batch, s, KsBase{in.data, in.bstride, 2});
 }
 void Evaluator::relinearize(CtBatch &ct, const KsKey &key, u64 batch, hipStream_t s) { relinearize(ct, &key, 1, batch, s); }
 
@@ -532,9 +559,7 @@ void Evaluator::mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hip
     check_ct(in);
     const int L = in.limbs, nl = L - 1;
     if (L < 2 || !c.is_data_level(nl)) throw Error(ST_INVALID_ARGUMENT, "end of modulus switching chain reached");
-    if (c.scheme == SCHEME_BFV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
-    if (c.scheme == SCHEME_CKKS && !in.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    if (c.scheme == SCHEME_BGV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    check_ks_form(in.ntt);
     const u64 N = c.N, pw = poly_words(c, L), npw = poly_words(c, nl);
     if (!out.data || out.bstride < (u64)in.size * npw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
     const host::RnsLevel &r = c.level(L).rns;
@@ -564,7 +589,7 @@ void Evaluator::mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hip
     const u64 *src = in.data;
     // CKKS through the fused correction transform reads a strided batch (a relinearized ciphertext keeps its three-polynomial stride) as it lies
     const bool ckks_fused = c.scheme == SCHEME_CKKS && c.level(L).d_inv_qlast && corr_fused() && primes_at_least_33_bits(c, nl) &&
-                            ntt1_supported(c.logn, c.ct_map(nl), batch * in.size * nl, 2);
+                            ntt1_supported(c.logn, c.ct_map(nl), batch * in.size * nl, Ntt1Feature::CORRECTION);
     // the output ranges [out.data + b out.bstride, + size npw) must not overlap what a later row still reads: when the two batches share memory
     // (a direct C-ABI caller rescaling a strided batch onto itself) the input is staged first, as every strided input was before the fused path
     bool overlaps = false;
@@ -591,7 +616,9 @@ void Evaluator::mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hip
         if (ckks_fused) {
             Ntt1Corr cr{last, src, (u64)pw, dst, (u64)in.size * npw, (u64)npw, (unsigned)in.size, lvl.d_inv_qlast, c.primes[L - 1], a.half, false};
             if (!dense_in && !staged) cr.in_gstride = in.bstride;
-            launch_ntt1(nullptr, nullptr, c.d_desc, cmap, batch * in.size * nl, c.logn, false, s, ~0ull, nullptr, &cr);
+            Ntt1Request q{c.d_desc, cmap, batch * in.size * nl, c.logn};
+            q.cr = &cr;
+            launch_ntt1(q, s);
         } else {
             launch_rescale_stepA(last, N, corr, a, s);
             launch_ntt(corr, c.d_desc, cmap, batch * in.size * nl, c.logn, false, s);
@@ -653,7 +680,7 @@ void Evaluator::apply_galois(CtBatch &ct, uint32_t elt, const KsKey &key, u64 ba
     launch_galois(ntt_form, ct.data, ct.bstride, t0, pw, c.d_desc, map, c.logn, elt, L, batch, s);
     launch_galois(ntt_form, ct.data + pw, ct.bstride, t1, pw, c.d_desc, map, c.logn, elt, L, batch, s);
     // switch_key resets the arena but never grows it now, so t0 and t1 (beyond its working set) stay intact; it takes ct as (t0, 0)
-    switch_key(ct, t1, pw, key, batch, s, t0, pw);
+    switch_key(ct, t1, pw, key, batch, s, KsBase{t0, pw});
 }
 
 // Hoisted rotations (Halevi-Shoup; no reference counterpart): the digits of c1 are decomposed, extended and transformed ONCE
@@ -672,9 +699,7 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
     }
     if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
     if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
-    if (c.scheme == SCHEME_BFV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
-    if (c.scheme == SCHEME_CKKS && !in.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    if (c.scheme == SCHEME_BGV && in.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    check_ks_form(in.ntt);
     const int L = in.limbs;
     const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
     if (dl >= 64) throw Error(ST_LOGIC_ERROR, "hoisted rotations: more than 63 digits");
@@ -701,30 +726,16 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
     u64 *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
     const size_t mark = c.arena.mark();
     const LimbMap map = c.ct_map(L);
-    u64 src_bound = 0;
-    for (u64 j = 0; j < dl; j++) src_bound = std::max(src_bound, c.primes[j]);
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
         const u64 nb = std::min(bs, batch - b0);
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
-        KsArgs a = ks_args(L, nb);
+        KsPlan k = ks_plan(L, nb);
+        KsArgs &a = k.a;
         // the digits of this run of items, once: D[b][i][j] = NTT_{p_i}(d_j mod p_i)
         const u64 *coeff = c1;
         u64 coeff_bs = in.bstride;
-        if (ckks) {
-            if (ntt1_supported(c.logn, map, nb * dl, 3)) launch_ntt1(tt, c1, c.d_desc, map, nb * dl, c.logn, true, s, ~0ull, nullptr, nullptr, in.bstride);
-            else {
-                launch_copy_strided(c1, in.bstride, tt, pw, pw, nb, s);
-                launch_ntt(tt, c.d_desc, map, nb * dl, c.logn, true, s);
-            }
-            coeff = tt;
-            coeff_bs = pw;
-        }
-        const LimbMap dmap = c.ids_map(std::vector<uint8_t>(a.key_id, a.key_id + rl), (uint32_t)dl);
-        if (ntt2_supported(c.logn)) launch_ntt2(D, coeff, coeff_bs, true, c.d_desc, dmap, nb * rl * dl, c.logn, false, s, false, src_bound);
-        else {
-            launch_ks_expand(coeff, coeff_bs, D, a, s);
-            launch_ntt(D, c.d_desc, dmap, nb * rl * dl, c.logn, false, s);
-        }
+        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
+        ks_expand_digits(coeff, coeff_bs, D, k, s);
         for (int r0 = 0; r0 < R;) {
             if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
                 launch_copy_strided(c0, in.bstride, out.data + ((u64)r0 * batch + b0) * out.bstride, out.bstride, 2 * pw, nb, s);
@@ -746,7 +757,7 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
             o.size = 2; o.limbs = L; o.ntt = in.ntt;
             a.batch = (u64)h.rots * nb;
             c.arena.rewind(mark);
-            if (h.rots == 1 || nb == batch) ks_acc_to_ct(o, acc, a, s, sig0, pw, 1);
+            if (h.rots == 1 || nb == batch) ks_acc_to_ct(o, acc, k, s, KsBase{sig0, pw});
             else throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch");
             a.batch = nb;
             stats::counter(stats::HOIST_SLABS)++;
@@ -890,7 +901,7 @@ void Evaluator::apply_key_switching(CtBatch &ct, const KsKey &key, u64 batch, hi
     const u64 pw = poly_words(c, ct.limbs);
     // c1 is read as the target by the first stages of the key switch and written only by its last one (the mod-down), which takes the
     // ciphertext as (c0, 0): no copy of c1, no zero fill
-    switch_key(ct, ct.data + pw, ct.bstride, key, batch, s, ct.data, ct.bstride, 1);
+    switch_key(ct, ct.data + pw, ct.bstride, key, batch, s, KsBase{ct.data, ct.bstride});
 }
 // negacyclicShift (evaluator_cuda.cu:2342-2351): every limb of every polynomial is multiplied by x^shift
 void Evaluator::negacyclic_shift(CtBatch &ct, u64 shift, u64 batch, hipStream_t s) {

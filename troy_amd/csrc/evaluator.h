@@ -4,6 +4,7 @@
 // to the caller's stream; nothing here synchronises.
 #pragma once
 #include "context.h"
+#include "kernels.h"
 
 namespace troyhip {
 
@@ -25,7 +26,12 @@ struct KsKey {
     const u64 *data = nullptr;
 };
 
-struct KsArgs; // kernels.h
+// One key switch at a level: the constants every kernel of both halves reads, and the row patterns of its scratch -- the output primes (the data
+// limbs, then the special prime) with the digits of a (item, prime) group as inner rows (D), and with one row per (item, prime) (acc)
+struct KsPlan {
+    KsArgs a;
+    LimbMap digit_map, acc_map;
+};
 
 class Evaluator {
 public:
@@ -52,9 +58,8 @@ public:
     void negate(CtBatch &a, u64 batch, hipStream_t s);
     // out may alias a or b; out.size/limbs/... are set; out.data/out.bstride are the caller's
     void multiply(const CtBatch &a, const CtBatch &b, CtBatch &out, u64 batch, hipStream_t s);
-    // base != nullptr: ct is to be taken as (base, 0) -- polynomial 0 from base[b * base_bstride ..], polynomial 1 zero -- whatever it holds;
-    // base_polys == 2: as (base[b][0], base[b][1])
-    void switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const u64 *base = nullptr, u64 base_bstride = 0, int base_polys = 1);
+    // base.ptr != nullptr: ct is to be taken as the base (KsBase, kernels.h), whatever it holds
+    void switch_key(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, u64 batch, hipStream_t s, const KsBase &base = {});
     // relinearize (not in place): size 3 -> 2 reads the operand where it lies and writes out; larger sizes copy and run in place
     void relinearize_to(const CtBatch &in, CtBatch &out, const KsKey *keys, int n_keys, u64 batch, hipStream_t s);
     void relinearize(CtBatch &ct, const KsKey &key, u64 batch, hipStream_t s);
@@ -83,9 +88,14 @@ private:
     // `extra` more words for the caller (what decrypt and noise_budget share)
     u64 *dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, struct DecryptArgs &a, hipStream_t s);
     // the two halves of switch_key: target -> acc (D, acc: scratch of batch (limbs + 1) limbs N and batch 2 (limbs + 1) N words), acc (+ base) -> ct
-    KsArgs ks_args(int limbs, u64 batch) const;
-    void ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsArgs &a, hipStream_t s);
-    void ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsArgs &a, hipStream_t s, const u64 *base, u64 base_bstride, int base_polys);
+    KsPlan ks_plan(int limbs, u64 batch) const;
+    void check_ks_form(bool ntt) const; // the form every key switch and modulus switch of the scheme takes its ciphertext in
+    // a CKKS target (stride t_bstride) in coefficient form: into tt ([batch][limbs][N]); returns where it lies now and sets its stride
+    const u64 *ks_coeff_target(const u64 *target, u64 &t_bstride, u64 *tt, const KsPlan &k, hipStream_t s);
+    // the unfused digit expansion: D[b][i][j] = NTT_{p_i}(d_j mod p_i) of the coefficient-form target
+    void ks_expand_digits(const u64 *coeff, u64 coeff_bstride, u64 *D, const KsPlan &k, hipStream_t s);
+    void ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsPlan &k, hipStream_t s);
+    void ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsPlan &k, hipStream_t s, KsBase base);
     bool scale_ok(double scale, int limbs) const;
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void balance_correction(u64 f1, u64 f2, u64 &f, u64 &e1, u64 &e2) const;

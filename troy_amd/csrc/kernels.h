@@ -17,9 +17,6 @@ inline unsigned plan_per_workgroup(size_t units, unsigned cap, size_t groups) {
 
 // ---- ntt.hip ----
 void launch_ntt(u64 *data, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, bool inverse, hipStream_t stream);
-// key switching: transforms of all (digit, output prime) pairs + inner product with the key in one pair of launches (ntt2.hip)
-void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, const u64 *key, u64 *acc,
-                        const uint8_t *key_limb, unsigned K, const u64 *ckks_target, u64 t_bstride, bool lazy, u64 src_bound, hipStream_t stream);
 // BEHZ multiply: forward transforms of two size-2 operands + ciphertext tensor in one pass pair (ntt2.hip)
 bool ntt2_tensor_supported(int logn);
 bool ntt2_ks_mac_supported(int logn);
@@ -30,6 +27,11 @@ void launch_ntt2_tensor(u64 *xa, const u64 *src_a, u64 *xb, const u64 *src_b, u6
 // forward transform of `src` (same row layout, left untouched) into `data`
 void launch_ntt_from(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, hipStream_t stream);
 
+// What a key switch accumulates onto instead of what ct holds.  ptr != nullptr: the ciphertext is taken as (ptr[b * bstride ..], 0) (rotations: sigma(c0)
+// in a temporary; spares the copy into ct[b][0] and the zero fill of ct[b][1]);  polys == 2: as (ptr[b][0], ptr[b][1]) -- relinearize out of place.
+// The correction form (Ntt1Corr) reads bstride as the stride between its groups, member 1 of a group at ptr + out_ostride.
+struct KsBase { const u64 *ptr = nullptr; u64 bstride = 0; int polys = 1; };
+
 // ---- ntt2.hip (N >= 4096) ----
 bool ntt2_supported(int logn);
 // Mod-down of BFV (kind 0) / BGV (kind 2) key switching as the store epilogue of the two-pass inverse transform (every size the
@@ -37,28 +39,55 @@ bool ntt2_supported(int logn);
 // (N^-1 constants carry qk^-1, aux = qk^-1); the data slots are transformed and  ct[b][k][j] += (acc_j - share of the special limb) qk^-1
 // is applied instead of storing them (evaluator.cpp:2528-2648).
 // BGV: `share` = the 128-bit integers al + k_t qk per (item, coefficient) from launch_ks_bgv_share (poly.hip).
-// base != nullptr: the ciphertext being accumulated into is (base, 0), i.e. ct[b][0] = base[b] + ..., ct[b][1] = ... (rotations: base = sigma(c0) in a
-// temporary; spares the copy into ct[b][0] and the zero fill of ct[b][1])
-struct Ntt2ModDown { int kind; u64 *ct; u64 ct_bstride; unsigned dl; u64 qk, half; const u64 *share; const u64 *base = nullptr; u64 base_bstride = 0; int base_polys = 1; };
-// passes: bit 0 = the first pass of the transform, bit 1 = the second (a caller that runs the first pass of several slot ranges as ONE launch and the second
-// passes separately: the key-switch mod-down of a small launch, whose special limb and data limbs differ only in the last pass).
-// plan_begin / plan_count (with passes == 2): the slot range the shared FIRST pass ran over -- the FP64 bound walk of this launch assumes the largest
-// prime of that range, because that is the bound the lazy doubles it reads were left with
-void launch_ntt2_slots(u64 *data, const u64 *src, u64 src_ostride, bool src_reduce, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn,
-                       bool inverse, hipStream_t stream, bool src_same_layout, u64 src_bound, unsigned slot_begin, unsigned slot_count, const Ntt2ModDown *md,
-                       unsigned passes = 3, unsigned plan_begin = 0, unsigned plan_count = 0);
-void launch_ntt2(u64 *data, const u64 *src, u64 src_ostride, bool src_reduce, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn,
-                 bool inverse, hipStream_t stream, bool src_same_layout = false, u64 src_bound = 0);
+struct Ntt2ModDown { int kind; u64 *ct; u64 ct_bstride; unsigned dl; u64 qk, half; const u64 *share; KsBase base; };
+enum class Ntt2Source {
+    SAME_LAYOUT, // the rows of `data`, read from elsewhere and left untouched
+    KS_DIGITS    // key switching: item o, digit k at ptr + o * ostride + k * N, a residue of another prime, reduced modulo the row's prime on the fly
+};
+enum class Ntt2Passes { BOTH, FIRST, SECOND };
+enum : unsigned { NTT_ALL_SLOTS = ~0u };
+// One two-pass transform.  Rows are laid out r = (o * period + i) * inner + k with prime map.id[i]; a caller sets what differs from the in-place
+// forward transform of every slot.
+struct Ntt2Request {
+    u64 *data;
+    const PrimeDesc *primes;
+    LimbMap map; // with map.host_primes (the context's registry, indexed by map.id) the slots in map.fp take the FP64 instances
+    size_t rows;
+    int logn;
+    bool inverse = false;
+    struct {
+        const u64 *ptr = nullptr; // forward only
+        Ntt2Source kind = Ntt2Source::SAME_LAYOUT;
+        u64 ostride = 0;          // KS_DIGITS: words between the items of the source
+        u64 bound = 0;            // KS_DIGITS: exclusive upper bound of the source values (largest source prime): rows whose prime p has 8p > bound skip the reduction
+    } src;
+    // only the prime slots [slot_begin, slot_begin + slot_count) of the pattern (in-place inverse)
+    unsigned slot_begin = 0, slot_count = NTT_ALL_SLOTS;
+    // one pass only (in-place inverse): a caller that runs the first pass of several slot ranges as ONE launch and the second passes separately -- the
+    // key-switch mod-down of a small launch, whose special limb and data limbs differ only in the last pass
+    Ntt2Passes passes = Ntt2Passes::BOTH;
+    // with passes == SECOND: the slot range the shared FIRST pass ran over -- the FP64 bound walk of this launch assumes the largest prime of that
+    // range, because that is the bound the lazy doubles it reads were left with
+    unsigned plan_begin = 0, plan_count = 0;
+    const Ntt2ModDown *md = nullptr; // inverse, inner == 1: the last pass ends in the key-switch mod-down instead of storing
+};
+void launch_ntt2(const Ntt2Request &r, hipStream_t stream);
+struct KsArgs;
+// key switching: transforms of all (digit, output prime) pairs + inner product with the key in one pair of launches.  D receives only the first
+// pass; src as Ntt2Source::KS_DIGITS; ckks_target (stride t_bstride): the NTT-form input that supplies the (digit == output slot) operand, else nullptr;
+// lazy: the transforms are accumulated unreduced (the caller checked the bound)
+void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const LimbMap &map, size_t rows, const u64 *key, u64 *acc, const u64 *ckks_target, u64 t_bstride,
+                        bool lazy, u64 src_bound, const KsArgs &a, hipStream_t stream);
 
 // ---- ntt1.hip (N = 2^12 .. 2^15: one HBM round trip per limb-transform) ----
-// feature: 0 plain transform, 1 the BFV mod-down epilogue (Ntt1ModDown), 2 the CKKS correction form (Ntt1Corr), 3 the inverse from a strided source
-bool ntt1_supported(int logn, const LimbMap &map, size_t rows, int feature = 0);
+// N = 2^15 has every form, the smaller sizes (ntt1s_*) the first two
+enum class Ntt1Feature { PLAIN /* in place, or forward from a source of the same layout */, MOD_DOWN /* Ntt1ModDown */, CORRECTION /* Ntt1Corr */, STRIDED_INVERSE };
+bool ntt1_supported(int logn, const LimbMap &map, size_t rows, Ntt1Feature feature = Ntt1Feature::PLAIN);
 // BFV mod-down by the special prime (ks_moddown_kernel<0>, evaluator.cpp:2528-2648) fused into the inverse transform of the key-switch
 // accumulators acc[o = 2 b + cpt][slot][N]: the slots below `dl` leave the kernel as  ct[b][cpt][slot] += (acc - [t']_q + [half]_q) qk^-1
 // instead of being stored; slot `dl` (the special limb) must already be in coefficient form.  `primes` is then Context::d_desc_md,
 // whose N^-1 constants carry qk^-1 and whose `aux` is qk^-1 itself.
-// base != nullptr: accumulate onto (base[b], 0) instead of onto what ct holds (rotations)
-struct Ntt1ModDown { u64 *ct; u64 ct_bstride; u64 dl, qk, half; const u64 *base = nullptr; u64 base_bstride = 0; int base_polys = 1; }; // base_polys == 2: onto (base[b][0], base[b][1]) -- relinearize out of place
+struct Ntt1ModDown { u64 *ct; u64 ct_bstride; u64 dl, qk, half; KsBase base; };
 // CKKS divide-and-round by a prime qx in NTT form (divideAndRoundqLastNttInplace, rns.cpp:832-877; the mod-down of the CKKS key switch,
 // evaluator.cpp:2600-2648): the correction polynomial corr_slot = [(last + half) mod qx]_p + (p - [half]_p) is BUILT on load from the
 // coefficient-form residues `last` of qx (one row per outer index), transformed, and COMBINED on store:
@@ -76,16 +105,24 @@ struct Ntt1Corr {
     u64 qx, half;
     bool accumulate;
     u64 in_gstride = 0;
-    // accumulate with base != nullptr: what is added to is (base, 0, 0, ..) per group instead of what out holds -- member 0 of group g reads
-    // base[g * base_gstride + slot * N ..], the other members start from zero (rotations: base = sigma(c0) in a temporary)
-    const u64 *base = nullptr;
-    u64 base_gstride = 0;
-    int base_polys = 1; // 2: members 0 and 1 of a group read base[g * base_gstride + {0, 1} * out_ostride ..] (relinearize out of place)
+    KsBase base; // accumulate: what is added to is the base per group instead of what out holds -- members from `polys` on start from zero
 };
-// slot_mask: only these prime slots of the row pattern are transformed
+// One single-pass transform; a caller sets what differs from the in-place forward transform of every slot.
 // logn is mandatory (round-4 advisor): a caller at N = 2^12 .. 2^14 that forgot it would run the 2^15 kernel over rows 2 .. 8 times shorter
-void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, bool inverse, hipStream_t stream, u64 slot_mask = ~0ull,
-                 const Ntt1ModDown *md = nullptr, const Ntt1Corr *cr = nullptr, u64 src_ostride = 0);
+struct Ntt1Request {
+    const PrimeDesc *primes;
+    LimbMap map;
+    size_t rows;
+    int logn;
+    u64 *data = nullptr;      // transformed in place, or the destination of src; unused by the correction form (cr->in, cr->out)
+    bool inverse = false;
+    const u64 *src = nullptr; // forward: the same row layout as data;  inverse (N = 2^15): item o at src + o * src_ostride, read where it lies
+    u64 src_ostride = 0;
+    u64 slot_mask = ~0ull;    // only these prime slots of the row pattern are transformed
+    const Ntt1ModDown *md = nullptr;
+    const Ntt1Corr *cr = nullptr;
+};
+void launch_ntt1(const Ntt1Request &r, hipStream_t stream);
 
 // ---- poly.hip ----
 void launch_ew(int op, const u64 *a, const u64 *b, u64 *out, const PrimeDesc *primes, const LimbMap &map, int logn, u64 rows, hipStream_t s);

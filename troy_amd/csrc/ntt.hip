@@ -186,23 +186,31 @@ static void plan(int logn, int &k1, int &k2) {
     k1 = logn - k2;
 }
 
-void launch_ntt_from(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, hipStream_t stream) {
-    if (rows == 0) return;
-    if (ntt1_supported(logn, map, rows)) { launch_ntt1(data, src, primes, map, rows, logn, false, stream); return; }
-    if (ntt2_supported(logn) && rows % ((size_t)map.period * map.inner) == 0) { // the first pass reads src, no copy
-        launch_ntt2(data, src, 0, false, primes, map, rows, logn, false, stream, true);
-        return;
+// the production forms -- the single pass at N = 2^12 .. 2^15 where the launch fills the chip, else the two-pass kernels (N >= 4096); false: not taken.
+// src (forward only, may be nullptr): the rows are read from there, no copy
+static bool launch_production(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, bool inverse, hipStream_t stream) {
+    if (ntt1_supported(logn, map, rows)) {
+        Ntt1Request q{primes, map, rows, logn};
+        q.data = data;
+        q.src = src;
+        q.inverse = inverse;
+        launch_ntt1(q, stream);
+        return true;
     }
+    if (!ntt2_supported(logn) || rows % ((size_t)map.period * map.inner)) return false;
+    Ntt2Request q{data, primes, map, rows, logn};
+    q.src.ptr = src;
+    q.inverse = inverse;
+    launch_ntt2(q, stream);
+    return true;
+}
+void launch_ntt_from(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, hipStream_t stream) {
+    if (rows == 0 || launch_production(data, src, primes, map, rows, logn, false, stream)) return;
     HIP_CHECK(hipMemcpyAsync(data, src, (rows << logn) * sizeof(u64), hipMemcpyDeviceToDevice, stream));
     launch_ntt(data, primes, map, rows, logn, false, stream);
 }
 void launch_ntt(u64 *data, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, bool inverse, hipStream_t stream) {
-    if (rows == 0) return;
-    if (ntt1_supported(logn, map, rows)) { launch_ntt1(data, nullptr, primes, map, rows, logn, inverse, stream); return; } // N = 2^12 .. 2^15: single pass
-    if (ntt2_supported(logn) && rows % ((size_t)map.period * map.inner) == 0) { // production path for N >= 4096
-        launch_ntt2(data, nullptr, 0, false, primes, map, rows, logn, inverse, stream);
-        return;
-    }
+    if (rows == 0 || launch_production(data, nullptr, primes, map, rows, logn, inverse, stream)) return;
     int k1, k2;
     plan(logn, k1, k2);
     NttArgs a;

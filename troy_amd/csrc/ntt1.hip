@@ -1189,42 +1189,59 @@ static int ntt1_mode() {
 }
 // workgroups of the single-pass kernels that share a compute unit: one at N = 2^15 / 2^14 (LDS), two at 2^13, four at 2^12 (16 waves)
 static unsigned ntt1_wgs_per_cu(int logn) { return logn >= 14 ? 1u : (logn == 13 ? 2u : 4u); }
-// feature: 0 the plain transform (in place, or forward from a source of the same layout), 1 the BFV mod-down epilogue, 2 the CKKS correction form,
-// 3 the inverse from a strided source.  N = 2^15 has them all, the smaller sizes (ntt1s_*) the first two.
-bool ntt1_supported(int logn, const LimbMap &map, size_t rows, int feature) {
+bool ntt1_supported(int logn, const LimbMap &map, size_t rows, Ntt1Feature feature) {
     if (ntt1_mode() == 1 || logn < 12 || logn > N1_LOGN || !rows || rows % ((size_t)map.period * map.inner)) return false;
-    if (logn != N1_LOGN && feature > 1) return false;
+    if (logn != N1_LOGN && (feature == Ntt1Feature::CORRECTION || feature == Ntt1Feature::STRIDED_INVERSE)) return false;
     // the launch must give every workgroup slot of the chip about four rows: below that the per-row latency of a whole-limb workgroup shows and the
     // two-pass kernels, which spread a row over N / 2048 small workgroups, are the better grain
     return ntt1_mode() == 2 || rows >= 4 * (size_t)device_cus() * ntt1_wgs_per_cu(logn);
 }
+template <class F> static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// the instance of a launch: EP = the epilogue, the mod-down of an inverse or the correction form of a forward transform (N = 2^15 only, as the caller checked)
+template <int LOGN, bool FP, bool LEAN, bool INV, bool EP> static auto ntt1_instance() -> void (*)(Ntt1Args) {
+    if constexpr (LOGN == N1_LOGN) {
+        if constexpr (FP && INV) return ntt1_inv_fp_kernel<EP>;
+        else if constexpr (FP) return ntt1_fwd_fp_kernel<EP>;
+        else if constexpr (INV) return ntt1_inv_kernel<LEAN, EP>;
+        else return ntt1_fwd_kernel<LEAN, EP>;
+    } else {
+        if constexpr (FP && INV) return ntt1s_inv_fp_kernel<LOGN, EP>;
+        else if constexpr (FP) return ntt1s_fwd_fp_kernel<LOGN>;
+        else if constexpr (INV) return ntt1s_inv_kernel<LOGN, LEAN, EP>;
+        else return ntt1s_fwd_kernel<LOGN, LEAN>;
+    }
+}
 // rows laid out r = (o * period + i) * inner + k, prime map.id[i].  The forward transform is launched once per prime class:
 // guard-free butterflies for the slots in map.lean, guarded ones for the rest.
-void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, bool inverse, hipStream_t stream, u64 slot_mask,
-                 const Ntt1ModDown *md, const Ntt1Corr *cr, u64 src_ostride) {
-    if (rows == 0) return;
+void launch_ntt1(const Ntt1Request &r, hipStream_t stream) {
+    const LimbMap &map = r.map;
+    const int logn = r.logn;
+    const bool inverse = r.inverse;
+    const Ntt1ModDown *md = r.md;
+    const Ntt1Corr *cr = r.cr;
+    if (r.rows == 0) return;
     if (logn < 12 || logn > N1_LOGN) throw Error(ST_LOGIC_ERROR, "ntt1: unsupported size");
-    if (logn != N1_LOGN && (cr || (src && inverse))) throw Error(ST_LOGIC_ERROR, "ntt1: the correction form and the strided source belong to N = 2^15");
+    if (logn != N1_LOGN && (cr || (r.src && inverse))) throw Error(ST_LOGIC_ERROR, "ntt1: the correction form and the strided source belong to N = 2^15");
     const size_t per_outer = (size_t)map.period * map.inner;
-    if (rows % per_outer) throw Error(ST_INVALID_ARGUMENT, "ntt1: row count must be a multiple of the limb pattern");
+    if (r.rows % per_outer) throw Error(ST_INVALID_ARGUMENT, "ntt1: row count must be a multiple of the limb pattern");
     if (md && (!inverse || map.inner != 1 || md->dl >= map.period)) throw Error(ST_LOGIC_ERROR, "ntt1: the mod-down epilogue belongs to the inverse transform of [..][slot][N] accumulators");
     Ntt1Args a;
     std::memset(&a, 0, sizeof(a));
-    a.data = data;
-    a.src = src;
-    a.src_ostride = src_ostride;
-    if (src && inverse && !src_ostride) throw Error(ST_LOGIC_ERROR, "ntt1: the out-of-place inverse takes a strided source");
-    a.primes = primes;
+    a.data = r.data;
+    a.src = r.src;
+    a.src_ostride = r.src_ostride;
+    if (r.src && inverse && !r.src_ostride) throw Error(ST_LOGIC_ERROR, "ntt1: the out-of-place inverse takes a strided source");
+    a.primes = r.primes;
     a.map = map;
-    a.m_total = (unsigned)(rows / per_outer * map.inner);
+    a.m_total = (unsigned)(r.rows / per_outer * map.inner);
     if (cr) {
-        if (inverse || map.inner != 1 || src) throw Error(ST_LOGIC_ERROR, "ntt1: the correction form belongs to the forward transform of [outer][slot][N] rows");
+        if (inverse || map.inner != 1 || r.src) throw Error(ST_LOGIC_ERROR, "ntt1: the correction form belongs to the forward transform of [outer][slot][N] rows");
         a.cr_last = cr->last; a.cr_in = cr->in; a.cr_out = cr->out; a.cr_inv = cr->inv;
         a.cr_in_ostride = cr->in_ostride; a.cr_in_gstride = cr->in_gstride; a.cr_out_gstride = cr->out_gstride; a.cr_out_ostride = cr->out_ostride;
         a.cr_qx = cr->qx; a.cr_half = cr->half; a.cr_group = cr->group ? cr->group : 1; a.cr_accumulate = cr->accumulate ? 1 : 0;
-        a.cr_base = cr->base; a.cr_base_gstride = cr->base_gstride; a.cr_base_polys = cr->base_polys;
+        a.cr_base = cr->base.ptr; a.cr_base_gstride = cr->base.bstride; a.cr_base_polys = cr->base.polys;
     }
-    if (md) { a.md_ct = md->ct; a.md_ct_bstride = md->ct_bstride; a.md_qk = md->qk; a.md_half = md->half; a.md_dl = (unsigned)md->dl; a.md_base = md->base; a.md_base_bstride = md->base_bstride; a.md_base_polys = md->base_polys; }
+    if (md) { a.md_ct = md->ct; a.md_ct_bstride = md->ct_bstride; a.md_qk = md->qk; a.md_half = md->half; a.md_dl = (unsigned)md->dl; a.md_base = md->base.ptr; a.md_base_bstride = md->base.bstride; a.md_base_polys = md->base.polys; }
     // One workgroup fills a CU, so a launch runs in rounds of `cus` workgroups and a round lasts as long as a workgroup's rows (plus
     // the un-overlapped first load and last store, about a third of a row): pick the rows per workgroup (they share the prime) that
     // minimises rounds x (rows + 1/3), with a small penalty for spreading the CUs over many primes at once.  A fixed "three workgroups
@@ -1260,7 +1277,7 @@ void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbM
         a.nslots = 0;
         u64 pmax = 0;
         for (unsigned i = 0; i < map.period; i++) {
-            if (!((slot_mask >> i) & 1)) continue;
+            if (!((r.slot_mask >> i) & 1)) continue;
             const int k = ((fp_slots >> i) & 1) ? 2 : (int)((map.lean >> i) & 1);
             if (k != kind) continue;
             a.slots[a.nslots++] = (uint8_t)i;
@@ -1294,61 +1311,36 @@ void launch_ntt1(u64 *data, const u64 *src, const PrimeDesc *primes, const LimbM
         cls[ncls].lean = kind != 0;
         cls[ncls++].fp = kind == 2;
     }
-    auto launch_small = [&](const Cls &k, hipStream_t st, auto logn_tag) { // N = 2^12 .. 2^14 (ntt1s_*)
+    // (logn, FP64, guard-free, direction, epilogue) -> the instance; timed runs name it as rocprofv3 prints it
+    auto launch = [&](const Cls &k, auto logn_tag) {
         constexpr int LN = decltype(logn_tag)::value;
         const Ntt1Args &x = k.a;
-        const dim3 grid(x.xcd_per ? 8 * x.xcd_per : x.nslots * x.chunks), block(64u << (LN - 10));
+        const bool ep = inverse ? x.md_ct != nullptr : x.cr_last != nullptr;
+        const dim3 grid(x.xcd_per ? 8 * x.xcd_per : x.nslots * x.chunks), block(LN == N1_LOGN ? N1_THREADS : 64u << (LN - 10));
 #ifndef TROYHIP_CPU_EMUL
-        if (ktime::enabled) { // the instance's name as rocprofv3 prints it (the launch macro would say "LN")
+        if (ktime::enabled) {
             static thread_local char tagbuf[64];
-            if (k.fp) std::snprintf(tagbuf, sizeof(tagbuf), inverse ? "ntt1s_inv_fp_kernel<%d, %s>" : "ntt1s_fwd_fp_kernel<%d>", LN, x.md_ct ? "true" : "false");
-            else if (inverse) std::snprintf(tagbuf, sizeof(tagbuf), "ntt1s_inv_kernel<%d, %s, %s>", LN, k.lean ? "true" : "false", x.md_ct ? "true" : "false");
+            const char *lean = k.fp ? "" : (k.lean ? "true, " : "false, "), *epilogue = ep ? "true" : "false";
+            if (LN == N1_LOGN) std::snprintf(tagbuf, sizeof(tagbuf), "HIP_KERNEL_NAME(ntt1_%s%s_kernel<%s%s>)", inverse ? "inv" : "fwd", k.fp ? "_fp" : "", lean, epilogue);
+            else if (k.fp) std::snprintf(tagbuf, sizeof(tagbuf), inverse ? "ntt1s_inv_fp_kernel<%d, %s>" : "ntt1s_fwd_fp_kernel<%d>", LN, epilogue);
+            else if (inverse) std::snprintf(tagbuf, sizeof(tagbuf), "ntt1s_inv_kernel<%d, %s, %s>", LN, k.lean ? "true" : "false", epilogue);
             else std::snprintf(tagbuf, sizeof(tagbuf), "ntt1s_fwd_kernel<%d, %s>", LN, k.lean ? "true" : "false");
             ktime::tag = tagbuf;
         }
 #endif
-        if (k.fp) {
-            if (!inverse) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_fwd_fp_kernel<LN>), grid, block, 0, st, x);
-            else if (x.md_ct) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_fp_kernel<LN, true>), grid, block, 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_fp_kernel<LN, false>), grid, block, 0, st, x);
-        } else if (!inverse) {
-            if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_fwd_kernel<LN, true>), grid, block, 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_fwd_kernel<LN, false>), grid, block, 0, st, x);
-        } else if (x.md_ct) {
-            if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_kernel<LN, true, true>), grid, block, 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_kernel<LN, false, true>), grid, block, 0, st, x);
-        } else if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_kernel<LN, true, false>), grid, block, 0, st, x);
-        else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1s_inv_kernel<LN, false, false>), grid, block, 0, st, x);
+        with_bool(k.fp, [&](auto fp) { with_bool(k.lean, [&](auto lean) { with_bool(inverse, [&](auto inv) { with_bool(ep, [&](auto e) {
+            const auto kernel = ntt1_instance<LN, decltype(fp)::value, decltype(lean)::value, decltype(inv)::value, decltype(e)::value>();
+            TROY_LAUNCH(kernel, grid, block, 0, stream, x);
+        }); }); }); });
     };
-    auto launch = [&](const Cls &k, hipStream_t st) {
-        if (logn == 14) { launch_small(k, st, std::integral_constant<int, 14>{}); return; }
-        if (logn == 13) { launch_small(k, st, std::integral_constant<int, 13>{}); return; }
-        if (logn == 12) { launch_small(k, st, std::integral_constant<int, 12>{}); return; }
-        const Ntt1Args &x = k.a;
-        const dim3 grid(x.xcd_per ? 8 * x.xcd_per : x.nslots * x.chunks);
-        if (k.fp) {
-            if (inverse) {
-                if (x.md_ct) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_fp_kernel<true>), grid, dim3(N1_THREADS), 0, st, x);
-                else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_fp_kernel<false>), grid, dim3(N1_THREADS), 0, st, x);
-            } else if (x.cr_last) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_fp_kernel<true>), grid, dim3(N1_THREADS), 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_fp_kernel<false>), grid, dim3(N1_THREADS), 0, st, x);
-            return;
+    for (int i = 0; i < ncls; i++) {
+        switch (logn) {
+        case 12: launch(cls[i], std::integral_constant<int, 12>{}); break;
+        case 13: launch(cls[i], std::integral_constant<int, 13>{}); break;
+        case 14: launch(cls[i], std::integral_constant<int, 14>{}); break;
+        default: launch(cls[i], std::integral_constant<int, N1_LOGN>{}); break;
         }
-        if (inverse) {
-            if (x.md_ct) {
-                if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_kernel<true, true>), grid, dim3(N1_THREADS), 0, st, x);
-                else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_kernel<false, true>), grid, dim3(N1_THREADS), 0, st, x);
-            } else if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_kernel<true, false>), grid, dim3(N1_THREADS), 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_inv_kernel<false, false>), grid, dim3(N1_THREADS), 0, st, x);
-        } else {
-            if (x.cr_last) {
-                if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_kernel<true, true>), grid, dim3(N1_THREADS), 0, st, x);
-                else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_kernel<false, true>), grid, dim3(N1_THREADS), 0, st, x);
-            } else if (k.lean) TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_kernel<true, false>), grid, dim3(N1_THREADS), 0, st, x);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt1_fwd_kernel<false, false>), grid, dim3(N1_THREADS), 0, st, x);
-        }
-    };
-    for (int i = 0; i < ncls; i++) launch(cls[i], stream);
+    }
     launch_check("ntt1 kernels");
 }
 

@@ -991,6 +991,7 @@ __global__ __launch_bounds__(STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS, MAC 
     ntt2_body<INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC, 1>(a);
 }
 
+
 // ---- host side ----
 bool ntt2_supported(int logn) { return logn >= 12 && logn <= 17; }
 
@@ -1007,45 +1008,64 @@ static bool n2_wide(unsigned narrow_blocks) {
     if (forced >= 0) return forced != 0;
     return (narrow_blocks >> 1) >= 4u * device_cus();
 }
-template <int INV, int STRIDED, int NS, int LOGC, int FINAL, int REDUCE> static void launch_one(const Ntt2Args &a, unsigned blocks, hipStream_t s, bool fp = false) {
+// names (as rocprofv3 prints the instance) and launches one instance over (slots of the class) x chunks x tiles workgroups
+template <int INV, int STRIDED, int NS, int LOGC, int FINAL, int REDUCE, int MAC = 0> static void launch_one(const Ntt2Args &a, hipStream_t s, bool fp) {
     constexpr unsigned THREADS = STRIDED ? (1u << (NS + LOGC - 3)) : N2_THREADS;
+    const unsigned blocks = (unsigned)((a.nsel * a.chunks) << a.tiles_per_row_log);
     if (fp) {
-        N2_KTAG("ntt2_fp_kernel<%d, %d, %d, %d, %d, %d, 0>", INV, STRIDED, NS, LOGC, FINAL, REDUCE);
-        TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<INV, STRIDED, NS, LOGC, FINAL, REDUCE>), dim3(blocks), dim3(THREADS), 0, s, a);
+        N2_KTAG("ntt2_fp_kernel<%d, %d, %d, %d, %d, %d, %d>", INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC);
+        TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC>), dim3(blocks), dim3(THREADS), 0, s, a);
         launch_check("ntt2_fp_kernel");
         return;
     }
-    N2_KTAG("ntt2_kernel<%d, %d, %d, %d, %d, %d, 0>", INV, STRIDED, NS, LOGC, FINAL, REDUCE); // the instance's name as rocprofv3 prints it
-    TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<INV, STRIDED, NS, LOGC, FINAL, REDUCE>), dim3(blocks), dim3(THREADS), 0, s, a);
+    N2_KTAG("ntt2_kernel<%d, %d, %d, %d, %d, %d, %d>", INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC);
+    TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<INV, STRIDED, NS, LOGC, FINAL, REDUCE, MAC>), dim3(blocks), dim3(THREADS), 0, s, a);
     launch_check("ntt2_kernel");
 }
-template <int INV, int NS> static void launch_contig(const Ntt2Args &a, unsigned blocks, bool final_pass, hipStream_t s, bool fp = false) {
-    if (final_pass) launch_one<INV, 0, NS, 0, INV ? 2 : 1, 0>(a, blocks, s, fp);
-    else launch_one<INV, 0, NS, 0, 0, 0>(a, blocks, s, fp);
+template <int INV, int NS> static void launch_contig(const Ntt2Args &a, bool final_pass, hipStream_t s, bool fp) {
+    if (final_pass) launch_one<INV, 0, NS, 0, INV ? 2 : 1, 0>(a, s, fp);
+    else launch_one<INV, 0, NS, 0, 0, 0>(a, s, fp);
 }
-template <int INV, int NS> static void launch_strided(const Ntt2Args &a, unsigned blocks, bool final_pass, bool reduce, hipStream_t s, int md_kind = -1, bool skip_diag = false,
-                                                      bool fp = false) {
+template <int INV, int NS> static void launch_strided(const Ntt2Args &a, bool reduce, hipStream_t s, bool fp, int md_kind = -1, bool skip_diag = false) {
     constexpr int LOGC = N2_LOGT - NS;
     if (INV) { // the strided pass is the last inverse pass
-        if (md_kind == 0) launch_one<1, 1, NS, LOGC, 3, 0>(a, blocks, s, fp);
-        else if (md_kind == 2) launch_one<1, 1, NS, LOGC, 4, 0>(a, blocks, s, fp);
-        else launch_one<1, 1, NS, LOGC, 2, 0>(a, blocks, s, fp);
+        if (md_kind == 0) launch_one<1, 1, NS, LOGC, 3, 0>(a, s, fp);
+        else if (md_kind == 2) launch_one<1, 1, NS, LOGC, 4, 0>(a, s, fp);
+        else launch_one<1, 1, NS, LOGC, 2, 0>(a, s, fp);
     } else {
-        (void)final_pass;
         if constexpr (NS == 6) { // N = 2^15: 32 columns = 256-byte runs; the wide form doubles them (n2_wide).  (N = 2^16, NS = 7, 16 -> 32 columns: measured 4 % SLOWER on BGV)
             // not the digit-expanding pass of the key switch (reduce): it writes L + 1 rows per row read and is bound by those writes -- measured
             // 0-4 % SLOWER wide (2105-2110 -> 2118-2150 us at the headline, 2023-2035 -> 2105-2120 on the 49-bit twin); the plain pass: 1609-1636 -> 1432-1438
-            if (!reduce && n2_wide(blocks)) {
+            if (!reduce && n2_wide((unsigned)((a.nsel * a.chunks) << a.tiles_per_row_log))) {
                 Ntt2Args w = a;
                 w.tiles_per_row_log = a.tiles_per_row_log - 1;
                 stats::counter(stats::NTT2_WIDE_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
-                launch_one<0, 1, NS, LOGC + 1, 0, 0>(w, blocks >> 1, s, fp);
+                launch_one<0, 1, NS, LOGC + 1, 0, 0>(w, s, fp);
                 return;
             }
         }
-        if (reduce && skip_diag) launch_one<0, 1, NS, LOGC, 0, 2>(a, blocks, s, fp);
-        else if (reduce) launch_one<0, 1, NS, LOGC, 0, 1>(a, blocks, s, fp);
-        else launch_one<0, 1, NS, LOGC, 0, 0>(a, blocks, s, fp);
+        if (reduce && skip_diag) launch_one<0, 1, NS, LOGC, 0, 2>(a, s, fp);
+        else if (reduce) launch_one<0, 1, NS, LOGC, 0, 1>(a, s, fp);
+        else launch_one<0, 1, NS, LOGC, 0, 0>(a, s, fp);
+    }
+}
+// Stage split: the contiguous pass takes k2 stages (nine; ten at N = 2^17, which keeps 16 columns in the strided pass), the strided pass k1 = logn - k2
+static void stage_split(int logn, int &k1, int &k2) {
+    k2 = logn - 9 > 7 ? logn - 7 : 9;
+    k1 = logn - k2;
+}
+// the one place that turns the split into template arguments: f(NS of the strided pass, NS of the contiguous pass)
+template <class F> static void with_stages(int k1, int k2, F &&f) {
+    using std::integral_constant;
+    if (k2 == 10 && k1 == 7) return f(integral_constant<int, 7>{}, integral_constant<int, 10>{});
+    if (k2 != 9) throw Error(ST_LOGIC_ERROR, "ntt2 plan");
+    switch (k1) {
+    case 3: return f(integral_constant<int, 3>{}, integral_constant<int, 9>{});
+    case 4: return f(integral_constant<int, 4>{}, integral_constant<int, 9>{});
+    case 5: return f(integral_constant<int, 5>{}, integral_constant<int, 9>{});
+    case 6: return f(integral_constant<int, 6>{}, integral_constant<int, 9>{});
+    case 7: return f(integral_constant<int, 7>{}, integral_constant<int, 9>{});
+    default: throw Error(ST_LOGIC_ERROR, "ntt2 plan");
     }
 }
 // stages per round of the two passes, in execution order (forward: Plan<>::r as written; inverse: reversed)
@@ -1066,130 +1086,133 @@ static int pass_rounds(int ns, bool inverse, int (&out)[4]) {
     for (int i = 0; i < n; i++) out[i] = inverse ? r[n - 1 - i] : r[i];
     return n;
 }
-// the output slots of a launch by class: FP64 instances for the primes below 2^50 (map.fp), the integer instances for the rest
-static unsigned select_class(const LimbMap &map, unsigned slot_begin, unsigned slot_count, bool fp, uint8_t (&sel)[64]) {
-    unsigned n = 0;
-    for (unsigned i = slot_begin; i < slot_begin + slot_count; i++)
-        if ((bool)((map.fp >> i) & 1) == fp) sel[n++] = (uint8_t)i;
-    return n;
-}
-
-// rows are laid out r = (o * period + i) * inner + k; src (optional, forward only): item o, digit k at src + o*src_ostride + k*N
-void launch_ntt2(u64 *data, const u64 *src, u64 src_ostride, bool src_reduce, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn,
-                 bool inverse, hipStream_t stream, bool src_same_layout, u64 src_bound) {
-    launch_ntt2_slots(data, src, src_ostride, src_reduce, primes, map, rows, logn, inverse, stream, src_same_layout, src_bound, 0, map.period, nullptr);
-}
-// the general form: only the prime slots [slot_begin, slot_begin + slot_count) of the pattern; md (inverse, inner == 1): the last pass ends in
-// the key-switch mod-down instead of storing (Ntt2ModDown, kernels.h).  host_primes (the context's registry, indexed by map.id) switches the
-// FP64 instances on for the slots in map.fp: without it every slot takes the integer kernels.
-void launch_ntt2_slots(u64 *data, const u64 *src, u64 src_ostride, bool src_reduce, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn,
-                       bool inverse, hipStream_t stream, bool src_same_layout, u64 src_bound, unsigned slot_begin, unsigned slot_count, const Ntt2ModDown *md,
-                       unsigned passes, unsigned plan_begin, unsigned plan_count) {
-    const u64 *host_primes = map.host_primes;
-    if (plan_count && plan_begin + plan_count > map.period) throw Error(ST_INVALID_ARGUMENT, "ntt2: plan slot range");
-    if (rows == 0 || slot_count == 0) return;
-    if (slot_begin + slot_count > map.period) throw Error(ST_INVALID_ARGUMENT, "ntt2: slot range");
-    const bool partial = slot_begin != 0 || slot_count != map.period;
-    if ((partial || md || passes != 3) && (!inverse || src)) throw Error(ST_LOGIC_ERROR, "ntt2: slot ranges, single passes and the mod-down epilogue belong to the in-place inverse transform");
-    if (md && !(passes & 2)) throw Error(ST_LOGIC_ERROR, "ntt2: the mod-down epilogue rides on the second pass");
-    if (md && map.inner != 1) throw Error(ST_LOGIC_ERROR, "ntt2: the mod-down epilogue takes one row per (item, prime)");
-    if (!ntt2_supported(logn)) throw Error(ST_LOGIC_ERROR, "ntt2: unsupported size");
-    const size_t per_outer = (size_t)map.period * map.inner;
-    if (rows % per_outer) throw Error(ST_INVALID_ARGUMENT, "ntt2: row count must be a multiple of the limb pattern");
-    if (src && inverse) throw Error(ST_LOGIC_ERROR, "ntt2: out-of-place input is only supported by the forward transform");
-    int k2 = 9;
-    if (logn - k2 > 7) k2 = logn - 7;
-    const int k1 = logn - k2;
+// what every launch over these rows shares, everything else zero; m_total = outer * inner rows per prime slot
+static Ntt2Args common_args(u64 *data, const PrimeDesc *primes, const LimbMap &map, int logn, size_t m_total) {
     Ntt2Args a;
+    std::memset(&a, 0, sizeof(a));
     a.data = data;
-    a.src = nullptr;
-    a.src_ostride = 0;
     a.primes = primes;
     a.map = map;
     a.logn = logn;
     a.tiles_per_row_log = (unsigned)(logn - N2_LOGT);
-    a.m_total = (unsigned)(rows / per_outer * map.inner);
-    // rows per workgroup (they share the prime: twiddles loaded once): up to 8, or the digits of one key-switch group -- fewer when the launch is
-    // small, so that a single ciphertext still spreads over the chip (B = 1: 224 workgroups of four rows each left three quarters of the SIMDs'
-    // wave slots empty; one row each is 896 workgroups)
-    a.rows_per_wg = a.m_total < 8 ? a.m_total : (map.inner > 1 ? (map.inner <= 16 ? map.inner : 8) : 8);
-    a.rows_per_wg = plan_per_workgroup(a.m_total, a.rows_per_wg, (size_t)slot_count << a.tiles_per_row_log);
+    a.m_total = (unsigned)m_total;
+    return a;
+}
+// rows per workgroup (they share the prime: twiddles loaded once): up to `cap`, fewer when the launch over `slots` primes is small (plan_per_workgroup)
+static void set_rows_per_wg(Ntt2Args &a, unsigned cap, unsigned slots) {
+    a.rows_per_wg = plan_per_workgroup(a.m_total, cap, (size_t)slots << a.tiles_per_row_log);
     a.chunks = (a.m_total + a.rows_per_wg - 1) / a.rows_per_wg;
-    a.src_reduce = 0;
-    a.src_same_layout = 0;
-    a.src2 = nullptr; a.src_slots = 0; a.src_split = 0;
-    a.slot_fastest = 0;
+}
+// One prime class of a launch -- the FP64 instances for the primes below 2^50 (map.fp), the integer instances for the rest: its slots and, for the
+// FP64 class, the reduction sites of the first and of the second pass in execution order with the bound the walk ended at (fpmod.h)
+struct ClassPlan {
+    bool fp;
+    unsigned nsel;
+    uint8_t sel[64];
+    unsigned mask1, mask2;
+    u64 pmax;
+    double out_bound;
+};
+static void set_class(Ntt2Args &a, const ClassPlan &k, unsigned mask) {
+    a.nsel = k.nsel;
+    std::memcpy(a.sel, k.sel, sizeof(a.sel));
+    a.fp_red_mask = mask;
+}
+// The classes of the slots [slot_begin, slot_begin + slot_count) in launch order, integer first (by_class == false: every slot takes the integer
+// kernels).  The FP64 walk starts from canonical inputs, or from residues below src_max of another prime (the key switch's digits), and runs over
+// the rounds of both passes.  plan_count != 0: a pass launched on its own inherits the lazy doubles of a first pass that ran over MORE slots -- the
+// walk must assume the largest prime of every slot that shared that pass, or this launch would plan from a smaller bound than the data really carries.
+static int plan_classes(const LimbMap &map, unsigned slot_begin, unsigned slot_count, bool by_class, bool inverse, int k1, int k2, u64 src_max,
+                        unsigned plan_begin, unsigned plan_count, ClassPlan (&out)[2]) {
+    int n = 0;
+    for (int cls = 0; cls < (by_class ? 2 : 1); cls++) {
+        ClassPlan &k = out[n];
+        std::memset(&k, 0, sizeof(k));
+        k.fp = cls == 1;
+        for (unsigned i = slot_begin; i < slot_begin + slot_count; i++)
+            if (!by_class || (bool)((map.fp >> i) & 1) == k.fp) k.sel[k.nsel++] = (uint8_t)i;
+        if (!k.nsel) continue;
+        n++;
+        if (!k.fp) continue;
+        const u64 *host_primes = map.host_primes;
+        if (!host_primes) throw Error(ST_LOGIC_ERROR, "ntt2 ks_mac: the FP64 class needs the host prime list"); // (only the key switch classes without it)
+        u64 pmin = ~0ull;
+        for (unsigned i = 0; i < k.nsel; i++) { const u64 p = host_primes[map.id[k.sel[i]]]; k.pmax = std::max(k.pmax, p); pmin = std::min(pmin, p); }
+        for (unsigned i = plan_begin; i < plan_begin + plan_count; i++)
+            if ((map.fp >> i) & 1) k.pmax = std::max(k.pmax, host_primes[map.id[i]]);
+        int r1[4], r2[4];
+        const int n1 = pass_rounds(inverse ? k2 : k1, inverse, r1), n2 = pass_rounds(inverse ? k1 : k2, inverse, r2);
+        const double b_in = std::max(1.0, (double)src_max / (double)pmin);
+        const FpPlan p1 = inverse ? fp_plan_inv(k.pmax, b_in, r1, n1) : fp_plan(k.pmax, b_in, r1, n1);
+        const FpPlan p2 = inverse ? fp_plan_inv(k.pmax, p1.out_bound, r2, n2) : fp_plan(k.pmax, p1.out_bound, r2, n2);
+        if (p1.out_bound < 0 || p2.out_bound < 0) throw Error(ST_LOGIC_ERROR, "ntt2: FP64 bound walk");
+        k.mask1 = p1.mask; k.mask2 = p2.mask; k.out_bound = p2.out_bound;
+    }
+    return n;
+}
+
+void launch_ntt2(const Ntt2Request &r, hipStream_t stream) {
+    const LimbMap &map = r.map;
+    const Ntt2ModDown *md = r.md;
+    const unsigned slot_begin = r.slot_begin, slot_count = r.slot_count == NTT_ALL_SLOTS ? map.period : r.slot_count;
+    const bool inverse = r.inverse, run_first = r.passes != Ntt2Passes::SECOND, run_second = r.passes != Ntt2Passes::FIRST;
+    if (r.plan_count && r.plan_begin + r.plan_count > map.period) throw Error(ST_INVALID_ARGUMENT, "ntt2: plan slot range");
+    if (r.rows == 0 || slot_count == 0) return;
+    if (slot_begin + slot_count > map.period) throw Error(ST_INVALID_ARGUMENT, "ntt2: slot range");
+    const bool partial = slot_begin != 0 || slot_count != map.period;
+    if ((partial || md || r.passes != Ntt2Passes::BOTH) && (!inverse || r.src.ptr)) throw Error(ST_LOGIC_ERROR, "ntt2: slot ranges, single passes and the mod-down epilogue belong to the in-place inverse transform");
+    if (md && !run_second) throw Error(ST_LOGIC_ERROR, "ntt2: the mod-down epilogue rides on the second pass");
+    if (md && map.inner != 1) throw Error(ST_LOGIC_ERROR, "ntt2: the mod-down epilogue takes one row per (item, prime)");
+    if (!ntt2_supported(r.logn)) throw Error(ST_LOGIC_ERROR, "ntt2: unsupported size");
+    const size_t per_outer = (size_t)map.period * map.inner;
+    if (r.rows % per_outer) throw Error(ST_INVALID_ARGUMENT, "ntt2: row count must be a multiple of the limb pattern");
+    if (r.src.ptr && inverse) throw Error(ST_LOGIC_ERROR, "ntt2: out-of-place input is only supported by the forward transform");
+    int k1, k2;
+    stage_split(r.logn, k1, k2);
+    Ntt2Args a = common_args(r.data, r.primes, map, r.logn, r.rows / per_outer * map.inner);
+    // up to 8 rows per workgroup, or the digits of one key-switch group -- fewer when the launch is small, so that a single ciphertext still spreads
+    // over the chip (B = 1: 224 workgroups of four rows each left three quarters of the SIMDs' wave slots empty; one row each is 896 workgroups)
+    set_rows_per_wg(a, a.m_total < 8 ? a.m_total : (map.inner > 1 ? (map.inner <= 16 ? map.inner : 8) : 8), slot_count);
     a.slot_begin = slot_begin;
+    a.md_base_polys = 1;
     if (md) {
         a.md_ct = md->ct; a.md_ct_bstride = md->ct_bstride; a.md_dl = md->dl; a.md_qk = md->qk; a.md_half = md->half;
         a.md_share = md->share;
-        a.md_base = md->base; a.md_base_bstride = md->base_bstride; a.md_base_polys = md->base_polys;
+        a.md_base = md->base.ptr; a.md_base_bstride = md->base.bstride; a.md_base_polys = md->base.polys;
         if (md->kind == 2 && !md->share) throw Error(ST_LOGIC_ERROR, "ntt2: the BGV mod-down needs the special limb's shares");
     }
     // the digit-reducing form of the first pass (unfused key switch) keeps the integer kernels: its FP64 twin lives in launch_ntt2_ks_mac
-    const bool fp_ok = host_primes && !(src && src_reduce);
-    for (int cls = 0; cls < 2; cls++) {
-        const bool fp = cls == 1;
-        if (fp && !fp_ok) break;
-        a.nsel = 0;
-        if (fp_ok) a.nsel = select_class(map, slot_begin, slot_count, fp, a.sel);
-        else for (unsigned i = 0; i < slot_count; i++) a.sel[a.nsel++] = (uint8_t)(slot_begin + i);
-        if (!a.nsel) continue;
+    const bool digits = r.src.ptr && r.src.kind == Ntt2Source::KS_DIGITS;
+    // Mod-down epilogue: the rows of DIFFERENT primes read one shared row per item (the special limb; BGV: its 16-byte shares).  Slot-major, the readers
+    // of a shared tile were a whole prime's workgroups apart and every one of them fetched it from HBM (traffic 1.51x the rows at N = 2^16).  Slot
+    // fastest, they are tiles_per_row workgroups apart -- a multiple of 8, so the hardware's round-robin deals them to the SAME XCD, back to back: one
+    // fetch into that L2 serves the class.  (The strided pass's twiddles are a handful of wave-uniform words per prime: nothing to lose in L2.)
+    // Same-box A/B at BGV N = 2^16 (profiles/r06_md_order_ab.txt): the FP64 mod-down 3545 -> 2449 us, the workload 4908 -> 5066 ops/s (+3.2 %).
+    static const int md_order = [] { const char *e = probe_env("TROYHIP_NTT2_MD_ORDER"); return e ? std::atoi(e) : 1; }();
+    ClassPlan cls[2];
+    const int ncls = plan_classes(map, slot_begin, slot_count, map.host_primes && !digits, inverse, k1, k2, 0, r.plan_begin, r.plan_count, cls);
+    for (int c = 0; c < ncls; c++) {
+        const ClassPlan &k = cls[c];
+        const bool fp = k.fp;
         stats::counter(fp ? stats::NTT2_FP_LAUNCHES : stats::NTT2_INT_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
-        unsigned mask1 = 0, mask2 = 0; // reduction sites of the first and of the second pass in execution order (fpmod.h)
-        if (fp) {
-            u64 pmax = 0;
-            for (unsigned i = 0; i < a.nsel; i++) pmax = std::max(pmax, host_primes[map.id[a.sel[i]]]);
-            // a pass launched on its own inherits the lazy doubles of a first pass that ran over MORE slots: the walk must assume the largest prime
-            // of every slot that shared that pass, or this launch would plan from a smaller bound than the data really carries
-            if (plan_count) {
-                uint8_t mates[64];
-                const unsigned n = select_class(map, plan_begin, plan_count, true, mates);
-                for (unsigned i = 0; i < n; i++) pmax = std::max(pmax, host_primes[map.id[mates[i]]]);
-            }
-            int r1[4], r2[4];
-            const int n1 = pass_rounds(inverse ? k2 : k1, inverse, r1), n2 = pass_rounds(inverse ? k1 : k2, inverse, r2);
-            const FpPlan p1 = inverse ? fp_plan_inv(pmax, 1.0, r1, n1) : fp_plan(pmax, 1.0, r1, n1);
-            const FpPlan p2 = inverse ? fp_plan_inv(pmax, p1.out_bound, r2, n2) : fp_plan(pmax, p1.out_bound, r2, n2);
-            if (p1.out_bound < 0 || p2.out_bound < 0) throw Error(ST_LOGIC_ERROR, "ntt2: FP64 bound walk");
-            mask1 = p1.mask; mask2 = p2.mask;
-        }
-        const unsigned blocks = (unsigned)((a.nsel * a.chunks) << a.tiles_per_row_log);
-        auto contig = [&](auto inv_tag, const Ntt2Args &args, bool final_pass) {
-            constexpr int INV = decltype(inv_tag)::value;
-            if (k2 == 9) launch_contig<INV, 9>(args, blocks, final_pass, stream, fp);
-            else if (k2 == 10) launch_contig<INV, 10>(args, blocks, final_pass, stream, fp);
-            else throw Error(ST_LOGIC_ERROR, "ntt2 plan");
-        };
-        auto strided = [&](auto inv_tag, const Ntt2Args &args, bool reduce) {
-            constexpr int INV = decltype(inv_tag)::value;
-            switch (k1) {
-            case 3: launch_strided<INV, 3>(args, blocks, false, reduce, stream, md ? md->kind : -1, false, fp); break;
-            case 4: launch_strided<INV, 4>(args, blocks, false, reduce, stream, md ? md->kind : -1, false, fp); break;
-            case 5: launch_strided<INV, 5>(args, blocks, false, reduce, stream, md ? md->kind : -1, false, fp); break;
-            case 6: launch_strided<INV, 6>(args, blocks, false, reduce, stream, md ? md->kind : -1, false, fp); break;
-            case 7: launch_strided<INV, 7>(args, blocks, false, reduce, stream, md ? md->kind : -1, false, fp); break;
-            default: throw Error(ST_LOGIC_ERROR, "ntt2 plan");
-            }
-        };
         Ntt2Args first = a, second = a;
-        first.fp_red_mask = mask1;
-        second.fp_red_mask = mask2;
-        if (!inverse) {
-            if (src) { first.src = src; first.src_ostride = src_ostride; first.src_reduce = src_reduce; first.src_bound = src_bound; first.src_same_layout = src_same_layout; first.slot_fastest = src_reduce && !src_same_layout; }
-            if (passes & 1) strided(std::integral_constant<int, 0>{}, first, src && src_reduce);
-            if (passes & 2) contig(std::integral_constant<int, 0>{}, second, true);
-        } else {
-            if (passes & 1) contig(std::integral_constant<int, 1>{}, first, false);
-            // Mod-down epilogue: the rows of DIFFERENT primes read one shared row per item (the special limb; BGV: its 16-byte shares).  Slot-major, the readers
-            // of a shared tile were a whole prime's workgroups apart and every one of them fetched it from HBM (traffic 1.51x the rows at N = 2^16).  Slot
-            // fastest, they are tiles_per_row workgroups apart -- a multiple of 8, so the hardware's round-robin deals them to the SAME XCD, back to back: one
-            // fetch into that L2 serves the class.  (The strided pass's twiddles are a handful of wave-uniform words per prime: nothing to lose in L2.)
-            // Same-box A/B at BGV N = 2^16 (profiles/r06_md_order_ab.txt): the FP64 mod-down 3545 -> 2449 us, the workload 4908 -> 5066 ops/s (+3.2 %).
-            static const int md_order = [] { const char *e = probe_env("TROYHIP_NTT2_MD_ORDER"); return e ? std::atoi(e) : 1; }();
+        set_class(first, k, k.mask1);
+        set_class(second, k, k.mask2);
+        with_stages(k1, k2, [&](auto ns1, auto ns2) {
+            constexpr int NS1 = decltype(ns1)::value, NS2 = decltype(ns2)::value;
+            if (!inverse) {
+                if (r.src.ptr) {
+                    first.src = r.src.ptr; first.src_ostride = r.src.ostride; first.src_bound = r.src.bound;
+                    first.src_reduce = digits; first.src_same_layout = !digits; first.slot_fastest = digits;
+                }
+                if (run_first) launch_strided<0, NS1>(first, digits, stream, fp);
+                if (run_second) launch_contig<0, NS2>(second, true, stream, fp);
+                return;
+            }
+            if (run_first) launch_contig<1, NS2>(first, false, stream, fp);
             if (md) second.slot_fastest = md_order;
-            if (passes & 2) strided(std::integral_constant<int, 1>{}, second, false);
-        }
+            if (run_second) launch_strided<1, NS1>(second, false, stream, fp, md ? md->kind : -1);
+        });
     }
 }
 
@@ -1197,106 +1220,63 @@ void launch_ntt2_slots(u64 *data, const u64 *src, u64 src_ostride, bool src_redu
 // second pass.  D receives only the first pass; acc [outer][2][period][N] the reduced sums.  Rows are grouped per (o, slot):
 // a workgroup takes all `inner` digits of one group, so its 16 accumulators see every term.
 // The output primes are split into two classes, each with its own pair of launches: primes below 2^50 (map.fp) run the FP64 instances
-// (ntt2_fp_kernel: 8-instruction butterflies, D holds doubles for those slots), the rest the integer instances.  host_primes = the
+// (ntt2_fp_kernel: 8-instruction butterflies, D holds doubles for those slots), the rest the integer instances.  map.host_primes = the
 // context's prime registry (indexed by map.id; digit k is a residue of host_primes[k]).
-template <int NS> static void launch_ks_first(const Ntt2Args &first, unsigned blocks, bool fp, bool skip_diag, hipStream_t stream) {
-    launch_strided<0, NS>(first, blocks, false, true, stream, -1, skip_diag, fp); // (launch_one names and launches the FP64 instance)
-}
-void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const PrimeDesc *primes, const LimbMap &map, size_t rows, int logn, const u64 *key, u64 *acc,
-                        const uint8_t *key_limb, unsigned K, const u64 *ckks_target, u64 t_bstride, bool lazy, u64 src_bound, hipStream_t stream) {
-    const u64 *host_primes = map.host_primes;
+void launch_ntt2_ks_mac(u64 *D, const u64 *src, u64 src_ostride, const LimbMap &map, size_t rows, const u64 *key, u64 *acc, const u64 *ckks_target, u64 t_bstride,
+                        bool lazy, u64 src_bound, const KsArgs &ks, hipStream_t stream) {
+    const int logn = ks.logn;
     if (rows == 0) return;
     if (!ntt2_supported(logn) || logn - 9 > 7 || logn - 9 < 3) throw Error(ST_LOGIC_ERROR, "ntt2 ks_mac: unsupported size");
     const size_t per_outer = (size_t)map.period * map.inner;
     if (rows % per_outer || map.inner > 63) throw Error(ST_INVALID_ARGUMENT, "ntt2 ks_mac: bad row pattern");
-    const int k1 = logn - 9;
-    Ntt2Args a;
-    std::memset(&a, 0, sizeof(a));
-    a.data = D;
-    a.primes = primes;
-    a.map = map;
-    a.logn = logn;
-    a.tiles_per_row_log = (unsigned)(logn - N2_LOGT);
-    a.m_total = (unsigned)(rows / per_outer * map.inner);
+    Ntt2Args a = common_args(D, ks.primes, map, logn, rows / per_outer * map.inner);
     a.rows_per_wg = map.inner;
     a.chunks = a.m_total / a.rows_per_wg;
     const bool skip_diag = ckks_target != nullptr; // CKKS: rows (digit k == output slot) are the NTT-form input, not expanded
-    for (int cls = 0; cls < 2; cls++) {
-        a.nsel = 0;
-        for (unsigned i = 0; i < map.period; i++)
-            if ((int)((map.fp >> i) & 1) == cls) a.sel[a.nsel++] = (uint8_t)i;
-        if (!a.nsel) continue;
-        const bool fp = cls == 1;
+    // the FP64 class walks the value bound through both passes from the digits' bound: those of a prime of 50 bits and more do not fit a double
+    // exactly and take an integer Barrett step before the conversion, the others enter as they are
+    u64 src_wide = 0, src_narrow_max = 0;
+    for (unsigned k = 0; map.host_primes && k < map.inner; k++) {
+        if (map.host_primes[k] >> TROY_FP_MAX_BITS) src_wide |= u64(1) << k; else src_narrow_max = std::max(src_narrow_max, map.host_primes[k]);
+    }
+    ClassPlan cls[2];
+    const int ncls = plan_classes(map, 0, map.period, true, false, logn - 9, 9, src_narrow_max, 0, 0, cls);
+    for (int c = 0; c < ncls; c++) {
+        const ClassPlan &k = cls[c];
+        const bool fp = k.fp;
         stats::counter(fp ? stats::KS_FP_LAUNCHES : stats::KS_INT_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
-        a.fp_src_wide = 0; a.fp_red_mask = 0; a.fp_acc_every = 0;
-        unsigned mask2 = 0;
-        if (fp) { // walk the value bound through both passes (fpmod.h): where to reduce, how often the accumulators must be
-            if (!host_primes) throw Error(ST_LOGIC_ERROR, "ntt2 ks_mac: the FP64 class needs the host prime list");
-            u64 pmax = 0, pmin = ~0ull, src_narrow_max = 0;
-            for (unsigned i = 0; i < a.nsel; i++) { const u64 p = host_primes[map.id[a.sel[i]]]; pmax = std::max(pmax, p); pmin = std::min(pmin, p); }
-            for (unsigned k = 0; k < map.inner; k++) {
-                if (host_primes[k] >> TROY_FP_MAX_BITS) a.fp_src_wide |= u64(1) << k; else src_narrow_max = std::max(src_narrow_max, host_primes[k]);
-            }
-            const double b_in = std::max(1.0, (double)src_narrow_max / (double)pmin);
-            int r1[4], n1 = 0;
-            switch (k1) {
-            case 3: for (int r : Plan<3>::r) if (r) r1[n1++] = r; break;
-            case 4: for (int r : Plan<4>::r) if (r) r1[n1++] = r; break;
-            case 5: for (int r : Plan<5>::r) if (r) r1[n1++] = r; break;
-            case 6: for (int r : Plan<6>::r) if (r) r1[n1++] = r; break;
-            default: for (int r : Plan<7>::r) if (r) r1[n1++] = r; break;
-            }
-            const FpPlan p1 = fp_plan(pmax, b_in, r1, n1);
-            const int r2[3] = {3, 3, 3};
-            const FpPlan p2 = fp_plan(pmax, p1.out_bound, r2, 3);
-            a.fp_red_mask = p1.mask;
-            mask2 = p2.mask;
-            const double lim = 0x1p53 / (double)pmax * 0.98, tb = 0.5 + 3.0 * std::max(p2.out_bound, 1.0) * (double)pmax * 0x1p-53;
+        if (fp) { // how often the accumulators must be reduced
+            a.fp_src_wide = src_wide;
+            const double lim = 0x1p53 / (double)k.pmax * 0.98, tb = 0.5 + 3.0 * std::max(k.out_bound, 1.0) * (double)k.pmax * 0x1p-53;
             const double n = std::floor((lim - 0.5 - 0x1p-40) / tb);
             if (n < 1.0) throw Error(ST_LOGIC_ERROR, "ntt2 ks_mac: FP64 accumulator bound");
             a.fp_acc_every = n >= (double)map.inner ? 0u : (unsigned)n;
         }
         Ntt2Args first = a;
+        set_class(first, k, k.mask1);
         first.src = src; first.src_ostride = src_ostride; first.src_reduce = 1; first.src_bound = src_bound;
         first.slot_fastest = 1;
         first.skip_diag = skip_diag;
         // the first pass need not keep the digits of a group in one workgroup (only the accumulating second pass does): small launches split them
-        first.rows_per_wg = plan_per_workgroup(a.m_total, a.rows_per_wg, (size_t)a.nsel << a.tiles_per_row_log);
-        first.chunks = (a.m_total + first.rows_per_wg - 1) / first.rows_per_wg;
-        const unsigned blocks1 = (unsigned)((a.nsel * first.chunks) << a.tiles_per_row_log);
-        switch (k1) {
-        case 3: launch_ks_first<3>(first, blocks1, fp, skip_diag, stream); break;
-        case 4: launch_ks_first<4>(first, blocks1, fp, skip_diag, stream); break;
-        case 5: launch_ks_first<5>(first, blocks1, fp, skip_diag, stream); break;
-        case 6: launch_ks_first<6>(first, blocks1, fp, skip_diag, stream); break;
-        default: launch_ks_first<7>(first, blocks1, fp, skip_diag, stream); break;
-        }
+        set_rows_per_wg(first, a.rows_per_wg, k.nsel);
         Ntt2Args second = a;
-        second.fp_red_mask = mask2;
+        set_class(second, k, k.mask2);
         // groups per workgroup of the accumulating pass: 4 where the grid then still covers the resident workgroups (two per compute unit at this kernel's
         // register count) four times over, else 2, else 1 -- a single ciphertext keeps one group per workgroup and spreads over the chip as before
         second.mac_groups = a.chunks;
         second.mac_units = fp ? 1 : 4;
-        while (second.mac_units > 1 && (size_t)((a.chunks + second.mac_units - 1) / second.mac_units) * ((size_t)a.nsel << a.tiles_per_row_log) < 8 * (size_t)device_cus())
+        while (second.mac_units > 1 && (size_t)((a.chunks + second.mac_units - 1) / second.mac_units) * ((size_t)k.nsel << a.tiles_per_row_log) < 8 * (size_t)device_cus())
             second.mac_units >>= 1;
         second.chunks = (a.chunks + second.mac_units - 1) / second.mac_units;
         if (!fp) stats::counter(stats::KS_INT_GROUPS_PER_WG).fetch_add(second.mac_units, std::memory_order_relaxed); // (summed over the launches: the tests read the choice)
-        const unsigned blocks2 = (unsigned)((a.nsel * second.chunks) << a.tiles_per_row_log);
-        second.mac_key = key; second.mac_acc = acc; second.mac_target = ckks_target; second.mac_tstride = t_bstride; second.mac_K = K;
+        second.mac_key = key; second.mac_acc = acc; second.mac_target = ckks_target; second.mac_tstride = t_bstride; second.mac_K = (unsigned)ks.K;
         second.mac_lazy = lazy;
-        std::memcpy(second.mac_key_limb, key_limb, map.period);
-        if (fp) {
-            N2_KTAG("ntt2_fp_kernel<0, 0, 9, 0, 1, 0, %d>", skip_diag ? 3 : 1);
-            if (skip_diag) TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
-            else TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
-        } else if (skip_diag) {
-            N2_KTAG("ntt2_kernel<0, 0, 9, 0, 1, 0, 3>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 3>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
-        } else {
-            N2_KTAG("ntt2_kernel<0, 0, 9, 0, 1, 0, 1>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 1>), dim3(blocks2), dim3(N2_THREADS), 0, stream, second);
-        }
-        launch_check("ntt2_kernel(ks_mac)");
+        std::memcpy(second.mac_key_limb, ks.key_limb, map.period);
+        with_stages(logn - 9, 9, [&](auto ns1, auto) {
+            launch_strided<0, decltype(ns1)::value>(first, true, stream, fp, -1, skip_diag);
+            if (skip_diag) launch_one<0, 0, 9, 0, 1, 0, 3>(second, stream, fp);
+            else launch_one<0, 0, 9, 0, 1, 0, 1>(second, stream, fp);
+        });
     }
 }
 
@@ -1307,85 +1287,40 @@ bool ntt2_tensor_supported(int logn) { return ntt2_supported(logn) && logn - 9 >
 bool ntt2_ks_mac_supported(int logn) { return ntt2_tensor_supported(logn); }
 void launch_ntt2_tensor(u64 *xa, const u64 *src_a, u64 *xb, const u64 *src_b, u64 *out, const PrimeDesc *primes, const LimbMap &map, size_t batch, int logn,
                         hipStream_t stream, unsigned src_slots) {
-    const u64 *host_primes = map.host_primes;
     if (!batch) return;
     if (!ntt2_tensor_supported(logn) || map.inner != 1) throw Error(ST_LOGIC_ERROR, "ntt2 tensor: unsupported shape");
-    const int k1 = logn - 9;
     const bool same = xa == xb; // squaring: one operand, transformed once
     // src_slots != 0: both bases of a BEHZ product in one launch -- the first src_slots slots of every polynomial come from the operands, the rest lie
     // in xa / xb already; when the b-part follows the a-part in memory the first pass of both operands is ONE launch
     const bool joint = src_slots && !same && xb == xa + ((batch * 2 * map.period) << logn);
     if (src_slots && (!src_a || !src_b || src_slots > map.period)) throw Error(ST_LOGIC_ERROR, "ntt2 tensor: operands of the merged form");
-    for (int cls = 0; cls < 2; cls++) { // one set of launches per prime class (FP64 instances below 2^50)
-        const bool fp = cls == 1;
-        if (fp && !host_primes) break;
-        uint8_t sel[64];
-        unsigned nsel = 0;
-        if (host_primes) nsel = select_class(map, 0, map.period, fp, sel);
-        else for (unsigned i = 0; i < map.period; i++) sel[nsel++] = (uint8_t)i;
-        if (!nsel) continue;
+    ClassPlan cls[2];
+    const int ncls = plan_classes(map, 0, map.period, map.host_primes != nullptr, false, logn - 9, 9, 0, 0, 0, cls);
+    for (int c = 0; c < ncls; c++) { // one set of launches per prime class
+        const ClassPlan &k = cls[c];
+        const bool fp = k.fp;
         stats::counter(fp ? stats::NTT2_FP_LAUNCHES : stats::NTT2_INT_LAUNCHES).fetch_add(1, std::memory_order_relaxed);
-        unsigned mask1 = 0, mask2 = 0;
-        if (fp) {
-            u64 pmax = 0;
-            for (unsigned i = 0; i < nsel; i++) pmax = std::max(pmax, host_primes[map.id[sel[i]]]);
-            int r1[4], r2[4];
-            const int n1 = pass_rounds(k1, false, r1), n2 = pass_rounds(9, false, r2);
-            const FpPlan p1 = fp_plan(pmax, 1.0, r1, n1), p2 = fp_plan(pmax, p1.out_bound, r2, n2);
-            mask1 = p1.mask; mask2 = p2.mask;
-        }
-        for (int part = 0; part < (same || joint ? 1 : 2); part++) { // first pass of both operands (rows = batch * 2 * limbs each)
-            Ntt2Args a;
-            std::memset(&a, 0, sizeof(a));
-            a.data = part ? xb : xa;
-            const u64 *src = part ? src_b : src_a;
-            a.primes = primes;
-            a.map = map;
-            a.logn = logn;
-            a.tiles_per_row_log = (unsigned)(logn - N2_LOGT);
-            a.m_total = (unsigned)(batch * (joint ? 4 : 2));
-            a.nsel = nsel;
-            std::memcpy(a.sel, sel, sizeof(sel));
-            a.fp_red_mask = mask1;
-            a.rows_per_wg = plan_per_workgroup(a.m_total, a.m_total < 8 ? a.m_total : 8, (size_t)nsel << a.tiles_per_row_log);
-            a.chunks = (a.m_total + a.rows_per_wg - 1) / a.rows_per_wg;
-            if (src_slots) { a.src = src; a.src2 = src_b; a.src_same_layout = 2; a.src_slots = src_slots; a.src_split = joint ? (unsigned)(batch * 2) : ~0u; }
-            else if (src) { a.src = src; a.src_same_layout = 1; }
-            const unsigned blocks = (unsigned)((nsel * a.chunks) << a.tiles_per_row_log);
-            switch (k1) {
-            case 3: launch_strided<0, 3>(a, blocks, false, false, stream, -1, false, fp); break;
-            case 4: launch_strided<0, 4>(a, blocks, false, false, stream, -1, false, fp); break;
-            case 5: launch_strided<0, 5>(a, blocks, false, false, stream, -1, false, fp); break;
-            case 6: launch_strided<0, 6>(a, blocks, false, false, stream, -1, false, fp); break;
-            default: launch_strided<0, 7>(a, blocks, false, false, stream, -1, false, fp); break;
+        with_stages(logn - 9, 9, [&](auto ns1, auto) {
+            for (int part = 0; part < (same || joint ? 1 : 2); part++) { // first pass of both operands (rows = batch * 2 * limbs each)
+                Ntt2Args a = common_args(part ? xb : xa, primes, map, logn, batch * (joint ? 4 : 2));
+                const u64 *src = part ? src_b : src_a;
+                set_class(a, k, k.mask1);
+                set_rows_per_wg(a, a.m_total < 8 ? a.m_total : 8, k.nsel);
+                if (src_slots) { a.src = src; a.src2 = src_b; a.src_same_layout = 2; a.src_slots = src_slots; a.src_split = joint ? (unsigned)(batch * 2) : ~0u; }
+                else if (src) { a.src = src; a.src_same_layout = 1; }
+                launch_strided<0, decltype(ns1)::value>(a, false, stream, fp);
             }
-        }
-        Ntt2Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.data = xa; a.tensor_b = xb; a.tensor_out = out;
-        a.primes = primes;
-        a.map = map;
-        a.logn = logn;
-        a.tiles_per_row_log = (unsigned)(logn - N2_LOGT);
-        a.m_total = (unsigned)(batch * 4);
-        a.nsel = nsel;
-        std::memcpy(a.sel, sel, sizeof(sel));
-        a.fp_red_mask = mask2;
+        });
+        Ntt2Args a = common_args(xa, primes, map, logn, batch * 4);
+        a.tensor_b = xb; a.tensor_out = out;
+        set_class(a, k, k.mask2);
         a.rows_per_wg = 4;
         // integer instances: up to four ciphertexts per workgroup, as the key-switch accumulating pass (three resident workgroups per compute unit here)
         a.mac_groups = (unsigned)batch;
         a.mac_units = fp ? 1 : 4;
-        while (a.mac_units > 1 && (size_t)((a.mac_groups + a.mac_units - 1) / a.mac_units) * ((size_t)nsel << a.tiles_per_row_log) < 12 * (size_t)device_cus()) a.mac_units >>= 1;
+        while (a.mac_units > 1 && (size_t)((a.mac_groups + a.mac_units - 1) / a.mac_units) * ((size_t)k.nsel << a.tiles_per_row_log) < 12 * (size_t)device_cus()) a.mac_units >>= 1;
         a.chunks = (a.mac_groups + a.mac_units - 1) / a.mac_units;
-        const unsigned blocks = (unsigned)((nsel * a.chunks) << a.tiles_per_row_log);
-        if (fp) {
-            N2_KTAG("ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 2>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_fp_kernel<0, 0, 9, 0, 1, 0, 2>), dim3(blocks), dim3(N2_THREADS), 0, stream, a);
-        } else {
-            N2_KTAG("ntt2_kernel<0, 0, 9, 0, 1, 0, 2>");
-            TROY_LAUNCH(HIP_KERNEL_NAME(ntt2_kernel<0, 0, 9, 0, 1, 0, 2>), dim3(blocks), dim3(N2_THREADS), 0, stream, a);
-        }
-        launch_check("ntt2_kernel(tensor)");
+        launch_one<0, 0, 9, 0, 1, 0, 2>(a, stream, fp);
     }
 }
 
