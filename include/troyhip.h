@@ -103,7 +103,12 @@ int troyhip_device_pci_bus_id(int device, char *out, size_t capacity);
 /* TEST SUPPORT: runs one primitive of the device arithmetic (kernelutils.cuh:94-404 counterparts in modarith.h / bfly.h) on n device
  * operands.  op: 0 barrett64(a), 1 barrett128(a = lo, b = hi), 2 mulmod(a, b), 3 mul_shoup(a, w = b, quotient c), 4 mul_lazy (result
  * in [0, 2p)), 5 reduce_prod(a * b), 6 / 7 / 11 / 12 forward butterflies (guarded, guard-free, SGPR-twiddle forms; X = a, Y = b,
- * twiddle c; out = canonical X', Y' interleaved), 8 / 13 inverse butterflies, 9 last inverse stage (aux = N^-1), 10 128-bit MAC */
+ * twiddle c; out = canonical X', Y' interleaved), 8 / 13 inverse butterflies, 9 last inverse stage (aux = N^-1), 10 128-bit MAC.
+ * Ops 20 .. 57 return the RAW words of the lazy-range primitives (every butterfly form, lite_reduce, lean_final4, the key-switch fold, the
+ * 128-bit accumulators, the FP64 forms of fpmod.h): the list with buffer layouts heads troy_amd/csrc/selftest.hip.  An op that is not
+ * listed, a missing buffer or a prime outside the class the op is defined for is TROYHIP_INVALID_ARGUMENT: nothing is launched.  So is
+ * op 10 (and 46) with an n that is no multiple of four: the accumulation takes terms in fours and used to drop a shorter tail silently.
+ * The FP64 ops that take twiddles (51, 55 .. 57) synchronise the stream. */
 int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t p, uint64_t aux, uint64_t *out, uint64_t n, void *stream);
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */

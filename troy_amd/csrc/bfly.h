@@ -326,6 +326,17 @@ template <bool UNI = false, bool EXACT = false> __device__ __forceinline__ void 
 #pragma unroll
     for (int i = 0; i < 4; i++) Y[i] = UNI ? mul_acc0_u(d[i], w_scaled[i].op, q[i], c.negp) : mul_acc0(d[i], w_scaled[i].op, q[i], c.negp);
 }
+// a wave-uniform twiddle into scalar registers (the *_u forms read their operand straight from SGPRs)
+__device__ __forceinline__ Shoup to_sgpr(const Shoup w) {
+#ifdef TROYHIP_CPU_EMUL
+    return w;
+#else
+    Shoup r;
+    r.op = mk64(__builtin_amdgcn_readfirstlane(lo32(w.op)), __builtin_amdgcn_readfirstlane(hi32(w.op)));
+    r.quo = mk64(__builtin_amdgcn_readfirstlane(lo32(w.quo)), __builtin_amdgcn_readfirstlane(hi32(w.quo)));
+    return r;
+#endif
+}
 // any x < 2^64 -> the same residue in [0, 4p), for p >= 2^33: q = floor(hi32(x) * floor(2^64/p) / 2^32) is at most 2.5 below x / p
 // (never above).  4 instructions per value -- the price of dropping the range guard from several inverse stages in a row.
 __device__ __forceinline__ void lite_reduce4(u64 (&x)[4], u32 mu, const PrimeConst &c) {
@@ -369,6 +380,25 @@ template <int NV> __device__ __forceinline__ void lean_final(u64 (&x)[NV], const
 __device__ __forceinline__ void reduce4_from_8p(u64 (&x)[4], const PrimeConst &c) { csub4(x, c.four_p); csub4(x, c.two_p); csub4(x, c.p); }
 __device__ __forceinline__ void reduce4_from_4p(u64 (&x)[4], const PrimeConst &c) { csub4(x, c.two_p); csub4(x, c.p); }
 
+
+// The key-switch sum fold: four 128-bit sums hi 2^64 + lo, whatever their 128 bits, primes in [2^33, 2^61) -> canonical residues in `lo`.
+//   lo -> below 3.5p by a 32-bit quotient estimate (lite_reduce4: at most 2.5 below lo / p);
+//   hi 2^64 = hi r64 mod p, r64 = 2^64 mod p with its Shoup quotient, lazily in [0, 3p) (the butterflies' multiply, operand in scalar registers: the caller
+//   passes to_sgpr(r64)), added onto lo by the multiply's own addend: below 6.5p, which fits 64 bits because every prime the context registers is below
+//   2^61 (the butterflies' 8p needs the same);
+//   then lean_final4 (anything below 64p, primes below 2^58; lf = make_lean_final) or three conditional subtractions.
+// `pre` receives the value before that final step (the device probe reads it; the product kernel does not, and pays nothing for it).
+__device__ __forceinline__ void ks_fold4(u64 (&lo)[4], const u64 (&hi)[4], u64 (&pre)[4], const Shoup r64, u32 mu, bool lean, const LeanFinal lf, const PrimeConst &c) {
+    const Shoup w4[4] = {r64, r64, r64, r64};
+    u64 q[4];
+    lite_reduce4(lo, mu, c);
+    mulhi_approx4_u(q, hi, w4);
+#pragma unroll
+    for (int i = 0; i < 4; i++) lo[i] = mul_acc_u(lo[i], hi[i], r64.op, q[i], c.negp);
+#pragma unroll
+    for (int i = 0; i < 4; i++) pre[i] = lo[i];
+    if (lean) lean_final4(lo, lf, c); else reduce4_from_8p(lo, c);
+}
 
 // ---- 128-bit multiply-accumulate, four independent accumulators: acc[i] += x[i] * k[i]  (acc < 2^128 by the caller's bound)
 // 10 instructions per term (4 v_mad_u64_u32 + 6 carry adds); every carry is consumed by the next step of the same lane

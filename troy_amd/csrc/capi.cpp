@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "build_id.h"
 #include "hostcrypto.h"
+#include "fpmod.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -414,6 +415,24 @@ int troyhip_mem_info(size_t *free_bytes, size_t *total_bytes) { return guard([&]
 int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t p, uint64_t aux, uint64_t *out, uint64_t n, void *stream) {
     return guard([&] {
         if (!a || !out || p < 2 || (p >> 61)) throw Error(ST_INVALID_ARGUMENT, "modarith probe arguments");
+        // every op of selftest.hip: the buffers it reads and the class of primes it is defined for [2^lo, 2^hi)
+        struct ProbeOp { int first, last; bool b, c; int lo, hi; };
+        static const ProbeOp ops[] = {
+            {0, 0, false, false, 1, 61}, {1, 2, true, false, 1, 61}, {3, 4, true, true, 1, 61}, {5, 5, true, false, 1, 61}, {6, 9, true, true, 1, 61},
+            {10, 10, true, false, 1, 61}, {11, 13, true, true, 1, 61},
+            {20, 37, true, true, 1, 61},                                  // raw butterflies
+            {40, 41, false, false, 33, 61}, {42, 42, false, false, 33, 58}, {43, 44, false, false, 1, 61}, // lite_reduce*, lean_final4, reduce4_from_*
+            {45, 45, true, false, 33, 61}, {46, 46, true, false, 1, 61}, // the key-switch fold, mac128x4
+            {50, 50, false, false, 1, TROY_FP_MAX_BITS}, {51, 51, false, true, 1, TROY_FP_MAX_BITS}, {52, 52, true, false, 1, TROY_FP_MAX_BITS},
+            {53, 54, false, false, 1, TROY_FP_MAX_BITS}, {55, 57, true, true, 1, TROY_FP_MAX_BITS},
+        };
+        const ProbeOp *po = nullptr;
+        for (const ProbeOp &o : ops)
+            if (op >= o.first && op <= o.last) po = &o;
+        if (!po) throw Error(ST_INVALID_ARGUMENT, "modarith probe: no such op");
+        if ((po->b && !b) || (po->c && !c)) throw Error(ST_INVALID_ARGUMENT, "modarith probe: the op reads a buffer that was not given");
+        if ((p >> po->lo) == 0 || (p >> po->hi) != 0) throw Error(ST_INVALID_ARGUMENT, "modarith probe: the prime is outside the op's class");
+        if ((op == 10 || op == 46) && (n & 3)) throw Error(ST_INVALID_ARGUMENT, "modarith probe: mac128x4 takes terms in fours");
         launch_modarith_probe(op, a, b, c, p, aux, out, n, on(stream));
     });
 }

@@ -202,7 +202,7 @@ static bool fp_allowed() {
 static bool fp_prime(u64 p) { return fp_allowed() && p < (u64(1) << TROY_FP_MAX_BITS); }
 // the FP64 twins of the two scalar constants of a descriptor; call again whenever inv_n / iroot_last_scaled are rescaled
 static void set_fp_consts(PrimeDesc &d) {
-    auto pair = [&](const Shoup &w) { return Shoup{fp_bits((double)w.op), fp_bits((double)w.op / (double)d.p)}; };
+    auto pair = [&](const Shoup &w) { return fp_twiddle_pair(w.op, d.p); };
     d.inv_n_fp = d.root_fp ? pair(d.inv_n) : Shoup{0, 0};
     d.iroot_last_scaled_fp = d.root_fp ? pair(d.iroot_last_scaled) : Shoup{0, 0};
 }
@@ -261,7 +261,7 @@ void Context::upload_tables() {
         if (fp_prime(tb.p)) { // the same twiddles as pairs of doubles (w, w / p): both exact / correctly rounded on the host (fpmod.h)
             auto to_fp = [&](const std::vector<Shoup> &v) {
                 std::vector<Shoup> f(v.size());
-                for (size_t j = 0; j < v.size(); j++) f[j] = Shoup{fp_bits((double)v[j].op), fp_bits((double)v[j].op / (double)tb.p)};
+                for (size_t j = 0; j < v.size(); j++) f[j] = fp_twiddle_pair(v[j].op, tb.p);
                 return f;
             };
             d.root_fp = upload(to_fp(tb.root), dev_allocs_);

@@ -28,6 +28,10 @@ TROY_HD double fp_from_u64(u64 x) { return fp_of_bits(x | 0x4330000000000000ull)
 // d = an integer in [0, 2^52)
 TROY_HD u64 fp_to_u64(double d) { return fp_bits(d + 4503599627370496.0) & 0x000fffffffffffffull; }
 
+// host side: the FP64 twin (w, w / p) of a table constant w < p, as every entry of PrimeDesc::root_fp / iroot_fp and the two scalar constants carry it:
+// w exact, w / p correctly rounded (one IEEE division)
+inline Shoup fp_twiddle_pair(u64 w, u64 p) { return Shoup{fp_bits((double)w), fp_bits((double)w / (double)p)}; }
+
 #if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__ && !defined(TROYHIP_CPU_EMUL)
 // the prime is wave-uniform: keep (p, 1 / p) in scalar registers (the conversion and the division run on the vector unit, whose results the
 // compiler would otherwise hold in four VGPRs for the whole kernel)

@@ -115,17 +115,6 @@ template <int STRIDED, int NS, int LOGC> __device__ __forceinline__ unsigned g_i
 
 // One round = R consecutive stages on G = 8 >> R groups of 2^R register-resident points per thread.
 //   forward: local stages LS .. LS+R-1 (gaps shrink);  inverse: local stages LS .. LS+R-1 (gaps grow)
-__device__ __forceinline__ Shoup to_sgpr(const Shoup w) {
-#ifdef TROYHIP_CPU_EMUL
-    return w;
-#else
-    Shoup r;
-    r.op = mk64(__builtin_amdgcn_readfirstlane(lo32(w.op)), __builtin_amdgcn_readfirstlane(hi32(w.op)));
-    r.quo = mk64(__builtin_amdgcn_readfirstlane(lo32(w.quo)), __builtin_amdgcn_readfirstlane(hi32(w.quo)));
-    return r;
-#endif
-}
-
 template <int INV, int STRIDED, int NS, int LOGC, int LS, int R> struct Round {
     static constexpr int G = 8 >> R;                       // groups per thread
     static constexpr int THREADS = STRIDED ? (1 << (NS + LOGC - 3)) : N2_THREADS; // a strided pass owns 2^(NS + LOGC) points: 2048 (256 threads) or, wide, 4096 (512)
@@ -936,29 +925,21 @@ __device__ __forceinline__ void ntt2_body(const Ntt2Args &a) {
                     for (int e = 0; e < 8; e++) lin[e] = fp_canonical(facc[cpt][e], fc, m.p);
                 } else if (pd.p >> 33) {
                     // Primes of 34 bits and more (wave-uniform): the generic two-word Barrett step (three high and three low 64-bit products per sum, about 70
-                    // instructions) gives way to a fold of the sum hi 2^64 + lo, whatever its 128 bits:  lo -> below 3.5p by a 32-bit quotient estimate
-                    // (lite_reduce4);  hi 2^64 = hi r64 mod p, r64 = 2^64 mod p with its Shoup quotient, lazily in [0, 3p) (the butterflies' multiply, operand in
-                    // scalar registers), added onto lo by the multiply's own addend: below 6.5p, which fits 64 bits because every prime the context
-                    // registers is below 2^61 (the butterflies' 8p needs the same);  then lean_final4 (anything below 64p, primes below 2^58) or three
-                    // conditional subtractions.  27-30 instructions per sum, the same residue, the same stored words.
+                    // instructions) gives way to the fold of the sum hi 2^64 + lo (ks_fold4, bfly.h): 27-30 instructions per sum, the same residue, the same
+                    // stored words.
                     const PrimeConst pc = make_prime_const(pd.p);
                     const LeanFinal lf = lean ? make_lean_final(pd.p, pd.cr1) : LeanFinal{0, 0};
                     const Shoup r64 = to_sgpr(pd.r64);
-                    const Shoup w4[4] = {r64, r64, r64, r64};
 #pragma unroll
                     for (int g = 0; g < 2; g++) {
-                        u64 lo[4], hi[4], q[4];
+                        u64 lo[4], hi[4], pre[4];
 #pragma unroll
                         for (int i = 0; i < 4; i++) {
                             const Acc128 &sum = macc[cpt][g][i];
                             lo[i] = mk64(sum.a0, sum.a1);
                             hi[i] = mk64(sum.a2, sum.a3);
                         }
-                        lite_reduce4(lo, (u32)pd.cr1, pc);
-                        mulhi_approx4_u(q, hi, w4);
-#pragma unroll
-                        for (int i = 0; i < 4; i++) lo[i] = mul_acc_u(lo[i], hi[i], r64.op, q[i], pc.negp);
-                        if (lean) lean_final4(lo, lf, pc); else reduce4_from_8p(lo, pc);
+                        ks_fold4(lo, hi, pre, r64, (u32)pd.cr1, lean, lf, pc);
 #pragma unroll
                         for (int i = 0; i < 4; i++) lin[4 * g + i] = lo[i];
                     }
