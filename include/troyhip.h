@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -266,6 +266,26 @@ int troyhip_rotate(troyhip_context *ctx, troyhip_ct *ct, int steps, int conjugat
  * Counter "hoist_slabs" (troyhip_stat): slabs run so far. */
 int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
                                  int n_elts, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* Hoisted linear transform (the "double hoisting" / lazy mod-down of Halevi-Shoup and Bossuat et al.; no reference counterpart):
+ *   out item b = sum_r plains[r] * (Galois automorphism galois_elts[r] of in item b),
+ * ONE batch of size-2 ciphertexts -- what a caller of troyhip_apply_galois_hoisted does next (the diagonal method of a plain matrix times an encrypted
+ * vector, convolutions by rotations, the linear layers of bootstrapping) in one call.  The plaintexts are applied in the extended basis (data primes and
+ * the special prime) BEFORE the mod-down, so the sum over the rotations is formed inside the gathered inner product: one accumulator and one mod-down
+ * per item instead of n_elts, nothing of size n_elts in memory.
+ * plains_ntt_keylevel[r]: device, [K][N] in NTT form at the KEY level (K = all key primes): what troyhip_plain_to_ntt(limbs = K) writes for BFV / BGV and
+ * troyhip_ckks_encode(limbs = K) for CKKS; row j serves data prime j at every level, row K - 1 the special prime.  The plaintexts are shared by the
+ * whole batch.  galois_keys[r]: as troyhip_apply_galois_hoisted (not read for element 1, may be null there; no NAF decomposition).  Elements may repeat
+ * with different plaintexts.  If every element is 1 the result is the plain multiply-accumulate: no key is read, there is no mod-down.
+ * out->data, out->batch_stride are INPUTS (room for `batch` size-2 items, not overlapping in); the call sets the other fields: size 2, the operand's limbs,
+ * form and correction factor, scale = in->scale * plain_scale (one plain_scale for all plaintexts, as troyhip_multiply_plain_accumulate; CKKS refuses
+ * "scale out of bounds").  The result decrypts to what the composition of troyhip_apply_galois, the plaintext products and the additions decrypts to,
+ * with ONE rounding instead of n_elts; its limbs are this library's own and are a function of the multiset of (element, key, plaintext) and the
+ * ciphertext alone (not of the order, n_elts' split into launches, the batch size or the scratch limit).  No baby-step / giant-step here.
+ * Scratch per item, no factor n_elts:  N (rl dl [+ dl for CKKS] + 2 rl + 2 dl + dl [BFV / BGV] + 2 dl + 4) words plus 384, dl = in->limbs, rl = dl + 1.
+ * scratch_limit_words bounds the arena request (0: 2^28 words); the call works in slabs of items under it; below one item it is refused.
+ * Counter "hoist_lt_slabs" (troyhip_stat): slabs run so far.  Stream-ordered. */
+int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                     const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, uint64_t scratch_limit_words, uint64_t batch, void *stream);
 int troyhip_transform_to_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);            /* transformToNttInplace(Ciphertext) */
 int troyhip_transform_from_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);          /* transformFromNttInplace */
 int troyhip_multiply_plain_ntt(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *plain, double plain_scale, uint64_t batch, void *stream); /* multiplyPlainInplace, NTT-form operands */

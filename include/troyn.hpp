@@ -1979,6 +1979,42 @@ public:
     std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return applyGaloisHoistedBatch(Ciphertext::pointers(a), elts, gk); }
     std::vector<std::vector<Ciphertext>> rotateRowsHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
     std::vector<std::vector<Ciphertext>> rotateVectorHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
+    // Hoisted linear transform (troyhip_galois_plain_sum_hoisted; the reference has no such call):
+    //   sum_r plains[r] * applyGalois(a, elts[r])   as ONE call and ONE ciphertext,
+    // the plaintexts applied in the extended basis before the single mod-down.  The plaintexts are in NTT form at the KEY level (transformToNttInplace(plain,
+    // context.keyParmsID()) for BFV / BGV, CKKSEncoder::encode(values, context.keyParmsID(), scale, plain) for CKKS) and share one scale; anything else is
+    // refused.  Element 1 / step 0 needs no key.  The result decrypts to what the composition of the existing calls decrypts to; its limbs are the library's own.
+    Ciphertext applyGaloisPlainSumHoisted(const Ciphertext &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const {
+        std::vector<Ciphertext> r = applyGaloisPlainSumHoistedBatch(std::vector<const Ciphertext *>{&a}, elts, plains, gk);
+        return std::move(r[0]);
+    }
+    Ciphertext rotateRowsPlainSumHoisted(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumHoisted(a, eltsOfSteps(steps), plains, gk); }
+    Ciphertext rotateVectorPlainSumHoisted(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumHoisted(a, eltsOfSteps(steps), plains, gk); }
+    // over a batch (Ciphertext::packBatch members or any ciphertexts of one shape): result[b] for item b, the plaintexts shared; the results are one slab run
+    std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const {
+        if (elts.empty() || plains.size() != elts.size()) throw std::invalid_argument("hoisted linear transform takes at least one Galois element and one plaintext per element");
+        std::vector<const uint64_t *> keys(elts.size(), nullptr), pls(elts.size(), nullptr);
+        for (size_t r = 0; r < elts.size(); r++) {
+            if (!plains[r].isNttForm() || plains[r].parmsID() != c_.keyParmsID()) throw std::invalid_argument("plain_ntt is not in NTT form at the key level");
+            if (plains[r].scale() != plains[0].scale()) throw std::invalid_argument("scale mismatch");
+            pls[r] = plains[r].device();
+            if (elts[r] == 1) continue;
+            if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
+            if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
+            keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+        }
+        if (a.empty()) return {};
+        if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
+        std::vector<Ciphertext> pa;
+        const troyhip_ct va = runOf(a, pa);
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, a[0]->coeffModulusSize());
+        troyhip_ct t = *out[0].raw();
+        const double plain_scale = c_.parms().scheme() == SchemeType::ckks ? plains[0].scale() : 1.0;
+        check(troyhip_galois_plain_sum_hoisted(h(), &va, &t, elts.data(), keys.data(), pls.data(), (int)elts.size(), plain_scale, 0, a.size(), nullptr));
+        for (auto &c : out) c.copyMeta(t);
+        return out;
+    }
+    std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return applyGaloisPlainSumHoistedBatch(Ciphertext::pointers(a), elts, plains, gk); }
     void transformToNttInplace(Ciphertext &a) const { check(troyhip_transform_to_ntt(h(), a.raw(), 1, nullptr)); }
     void transformFromNttInplace(Ciphertext &a) const { check(troyhip_transform_from_ntt(h(), a.raw(), 1, nullptr)); }
     void transformToNtt(const Ciphertext &a, Ciphertext &d) const { d = a; transformToNttInplace(d); }     // :246-250

@@ -715,6 +715,44 @@ class Evaluator:
             raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
         return self.applyGaloisHoisted(a, [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps], galois_keys, scratch_limit_words)
 
+    # -- hoisted linear transform (troyhip_galois_plain_sum_hoisted: no reference counterpart)
+    def applyGaloisPlainSumHoisted(self, a, galois_elts, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        """sum_r plains[r] * applyGalois(a, galois_elts[r]) as ONE call and ONE Ciphertext batch: the plaintexts are applied in the extended basis before
+        the single mod-down per item.  plains: DeviceBuffer of K * N words each, NTT form at the KEY level (transformPlainToNtt(plain, K) for BFV / BGV,
+        CKKSEncoder.encode(..., limbs=K) for CKKS), shared by the batch.  Element 1 reads no key.  The scale becomes a.scale * plain_scale."""
+        elts = [int(g) for g in galois_elts]
+        plains = list(plains)
+        if not elts or len(plains) != len(elts):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element and one plaintext per element")
+        ptrs, pls = [], []
+        for g, p in zip(elts, plains):
+            idx = GaloisKeys.getIndex(g)
+            if g != 1 and not galois_keys.hasKey(idx):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Galois key not present")
+            if p is not None and p.words < self.context.key_limbs * self.context.N:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "plain_ntt must hold [K][N] words (NTT form at the key level)")
+            ptrs.append(galois_keys.keys[idx].ptr if g != 1 else None)
+            pls.append(p.ptr if p is not None else None)
+        R = len(elts)
+        out = Ciphertext(self.context, a.batch, 2, a.limbs, a.is_ntt_form, a.scale, a.correction_factor)
+        si, so = a.struct(), out.struct()
+        self._chk(self.lib.troyhip_galois_plain_sum_hoisted(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), (C.c_void_p * R)(*pls),
+                                                            R, C.c_double(plain_scale), C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        out._absorb(so)
+        return out
+
+    def rotateRowsPlainSumHoisted(self, a, steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        if self.context.scheme not in (BFV, BGV):
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        elts = [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps]
+        return self.applyGaloisPlainSumHoisted(a, elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def rotateVectorPlainSumHoisted(self, a, steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        if self.context.scheme != CKKS:
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        elts = [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps]
+        return self.applyGaloisPlainSumHoisted(a, elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
     def _rotate(self, a, steps, conjugate, galois_keys):
         elts = [2 * i + 1 for i in galois_keys.keys]
         n = len(elts)

@@ -336,3 +336,49 @@ class Conv2dHelper:
 
     def deserializeOutputs(self, evaluator, context, stream):  # LinearHelperCKKS.cuh:698-713
         return _deserialize_terms(evaluator, context, self.getTotalBatchSize(), self.outputChannels, self._required, stream)
+
+
+class DiagonalMatvec:
+    """y = M x for a plain d x d matrix M and an encrypted vector x by the diagonal method (Halevi-Shoup), as ONE hoisted call
+    (Evaluator.rotate*PlainSumHoisted): y = sum_r diag_r (.) rot(x, r), the nonzero diagonals only.  d is a power of two
+    dividing the row length N / 2; x is tiled with period d over the row (BFV / BGV: over both rows), and so is y.  No baby-step / giant-step."""
+
+    def __init__(self, context, matrix):
+        m = np.asarray(matrix)
+        row = context.N // 2
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1 or m.shape[0] & (m.shape[0] - 1) or row % m.shape[0]:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "matrix must be d x d, d a power of two dividing the row length N / 2")
+        self.context, self.matrix, self.d, self.row = context, m, m.shape[0], row
+        k = np.arange(self.d)
+        diags = [m[k, (k + r) % self.d] for r in range(self.d)]  # diag_r[k] = M[k][(k + r) mod d]
+        self.steps = [r for r in range(self.d) if np.any(diags[r] != 0)]
+        self.diagonals = {r: np.tile(diags[r], row // self.d) for r in self.steps}
+        self.plains, self.plain_scale = None, 1.0
+
+    def requiredSteps(self):
+        """the rotation steps whose Galois keys apply() needs (step 0 needs none)"""
+        return [r for r in self.steps if r]
+
+    def encodeDiagonals(self, encoder, scale=None):
+        """the key-level NTT plaintexts of the nonzero diagonals: encoder = BatchEncoder (BFV / BGV) or CKKSEncoder with `scale`"""
+        ctx = self.context
+        K = ctx.key_limbs
+        if ctx.scheme == capi.CKKS:
+            if scale is None:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "CKKS diagonals need a scale")
+            self.plains = [api.DeviceBuffer.from_numpy(encoder.encode(self.diagonals[r], scale, limbs=K)) for r in self.steps]
+            self.plain_scale = float(scale)
+        else:
+            ev = api.Evaluator(ctx)
+            self.plains = [ev.transformPlainToNtt(api.DeviceBuffer.from_numpy(encoder.encode(np.concatenate([self.diagonals[r]] * 2))), K) for r in self.steps]
+            self.plain_scale = 1.0
+        return self.plains
+
+    def apply(self, evaluator, ct, galois_keys):
+        """the single hoisted call; ct encrypts x tiled with period d"""
+        if self.plains is None:
+            raise capi.LogicError(capi.LOGIC_ERROR, "encodeDiagonals has not been called")
+        if not self.steps:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the matrix is zero")
+        fn = evaluator.rotateVectorPlainSumHoisted if self.context.scheme == capi.CKKS else evaluator.rotateRowsPlainSumHoisted
+        return fn(ct, self.steps, self.plains, galois_keys, self.plain_scale)

@@ -821,6 +821,18 @@ int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, tro
         store(o, out);
     });
 }
+int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                     const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_elts < 1 || !galois_elts || !galois_keys || !plains_ntt_keylevel) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        std::vector<KsKey> keys((size_t)n_elts);
+        for (int i = 0; i < n_elts; i++) keys[(size_t)i] = KsKey{galois_keys[i]};
+        CtBatch o = view(out);
+        need(ctx)->ev.galois_plain_sum_hoisted(view(in), o, galois_elts, keys.data(), plains_ntt_keylevel, n_elts, plain_scale, batch, scratch_limit_words, on(stream));
+        store(o, out);
+    });
+}
 
 static void rotate_internal(troyhip_context *ctx, CtBatch &x, int steps, const uint32_t *elts, const uint64_t *const *keys, int n_keys, u64 batch, hipStream_t s) {
     if (steps == 0) return; // evaluator_cuda.cu:2140-2143

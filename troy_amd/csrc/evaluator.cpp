@@ -767,6 +767,103 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
     out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = in.scale; out.cf = in.cf;
 }
 
+// Hoisted linear transform (no reference counterpart): sum_r plains[r] * (Galois element elts[r] of the operand), the plaintexts
+// applied in the extended basis BEFORE the mod-down, so that the sum over the rotations is formed inside the gathered inner product: one accumulator and
+// one mod-down per item whatever R is, nothing of size R in memory.  Scratch per item (no factor R):
+//   N (rl dl [D] + dl [CKKS: c1 in coefficient form] + 2 rl [acc] + 2 dl [base] + dl [BFV / BGV: c0 in NTT form] + 2 dl + 4 [what the second half carves])
+// A slab is a run of items that fits under the limit; the rotations of a slab run HOIST_MAX_ROT per launch, later launches accumulating.
+void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
+                                         u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (R < 1 || !elts || !keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
+    bool any_rot = false, any_one = false;
+    for (int r = 0; r < R; r++) {
+        if (!(elts[r] & 1) || elts[r] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+        if (elts[r] != 1 && !keys[r].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+        if (!plains[r]) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
+        (elts[r] == 1 ? any_one : any_rot) = true;
+    }
+    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    check_ks_form(in.ntt);
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
+    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "hoisted linear transform: more than 63 digits");
+    const double new_scale = in.scale * plain_scale;
+    if (c.scheme == SCHEME_CKKS && !scale_ok(new_scale, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = new_scale; out.cf = in.cf;
+    if (!batch) return;
+    {   // every rotation reads the whole operand: the destination must not share a word with it
+        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 2 * pw;
+        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform: destination must be a distinct buffer");
+    }
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const int polys = any_one ? 2 : 1;
+    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
+    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
+    const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + 2 * rl + 2 * dl + (ckks ? 0 : dl) + 2 * dl + 4);
+    if (per_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one ciphertext");
+    const u64 bs = std::min<u64>(batch, (limit - slack) / per_item);
+
+    c.arena.begin(s);
+    c.arena.reserve(bs * per_item + slack);
+    u64 *D = c.arena.take(bs * rl * dl * N);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw);
+    const size_t mark = c.arena.mark();
+    const LimbMap map = c.ct_map(L);
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        const KsPlan k = ks_plan(L, nb);
+        const KsArgs &a = k.a;
+        // the digits of this run of items, once: D[b][i][j] = NTT_{p_i}(d_j mod p_i); D[b][j][j] is c1's own limb j in NTT form
+        const u64 *coeff = c1;
+        u64 coeff_bs = in.bstride;
+        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
+        ks_expand_digits(coeff, coeff_bs, D, k, s);
+        HoistLtArgs h;
+        auto flush = [&](bool rotations) {
+            if (!h.rots) return;
+            if (rotations) launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
+            else if (ckks) launch_hoist_lt_base(c0, in.bstride, c1, in.bstride, N, base, (u64)polys * pw, polys, a, h, s);
+            else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, base, (u64)polys * pw, polys, a, h, s);
+            std::memset(&h, 0, sizeof(h));
+            h.accumulate = 1; // later launches of the same phase add to what this one stored
+        };
+        // the extended-basis accumulators: every element other than 1, HOIST_MAX_ROT per launch
+        std::memset(&h, 0, sizeof(h));
+        for (int r = 0; r < R; r++) {
+            if (elts[r] == 1) continue;
+            h.key[h.rots] = keys[r].data; h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
+            if (++h.rots == HOIST_MAX_ROT) flush(true);
+        }
+        flush(true);
+        // the base in NTT form: every element, c0 read through the index map (element 1: in place) and c1 for element 1
+        if (!ckks) {
+            launch_copy_strided(c0, in.bstride, c0n, pw, pw, nb, s);
+            launch_ntt(c0n, c.d_desc, map, nb * dl, c.logn, false, s);
+        }
+        std::memset(&h, 0, sizeof(h));
+        for (int r = 0; r < R; r++) {
+            h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
+            if (++h.rots == HOIST_MAX_ROT) flush(false);
+        }
+        flush(false);
+        if (!ckks) launch_ntt(base, c.d_desc, map, nb * polys * dl, c.logn, true, s);
+        CtBatch o = out;
+        o.data = out.data + b0 * out.bstride;
+        if (!any_rot) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, nb, s); // every element is 1: the result is the base, no key read, no mod-down
+        else {
+            c.arena.rewind(mark);
+            ks_acc_to_ct(o, acc, k, s, KsBase{base, (u64)polys * pw, polys});
+        }
+        stats::counter(stats::HOIST_LT_SLABS)++;
+    }
+}
+
 void Evaluator::transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s) { // evaluator_cuda.cu:1950-1985
     check_ct(ct);
     if (ct.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted is already in NTT form");

@@ -72,6 +72,12 @@ public:
     // item; element 1 is a copy and reads no key.  The arena request stays under scratch_limit_words (0: 2^28 words), in slabs where needed.
     // The limbs are NOT those of apply_galois; the decryption is.
     void apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    // Hoisted linear transform: out item b = sum_r plains[r] * (Galois automorphism elts[r] of in item b), ONE batch (out.data / out.bstride are the
+    // caller's, distinct from in).  plains[r]: [K][N] NTT form at the key level, shared by the batch; applied in the extended basis before the one
+    // mod-down per item.  keys[r] is not read where elts[r] == 1.  out.scale = in.scale * plain_scale.  Scratch: no factor R (evaluator.cpp); the
+    // arena request stays under scratch_limit_words (0: 2^28 words), in slabs of items where needed.  DESIGN.md section 4.11.
+    void galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
+                                  u64 scratch_limit_words, hipStream_t s);
     void transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void transform_from_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void multiply_plain_ntt(CtBatch &ct, const u64 *plain, double plain_scale, u64 batch, hipStream_t s);

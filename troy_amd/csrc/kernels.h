@@ -187,6 +187,15 @@ void launch_ks_mac(const u64 *D, const u64 *key, const u64 *ckks_target, u64 t_b
 enum { HOIST_MAX_ROT = 16 };
 struct HoistArgs { const u64 *key[HOIST_MAX_ROT]; uint32_t elt[HOIST_MAX_ROT]; u32 rots; };
 void launch_hoist_mac(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistArgs &h, hipStream_t s);
+// hoisted linear transform: the same gathered inner products, each times one plaintext word, summed over the rotations of the launch:
+//   acc[b * 2 + k][i][n] (+)= sum_r pt[r][limb(i)][n] * (sum_j opnd(b,i,j)[pi_r(n)] * key[r][j][k][limb(i)][n] mod p_i) mod p_i
+// pt[r]: [K][N] NTT form at the key level, shared by the batch; no element of the launch is 1; accumulate: start from the canonical words acc holds
+struct HoistLtArgs { const u64 *key[HOIST_MAX_ROT]; const u64 *pt[HOIST_MAX_ROT]; uint32_t elt[HOIST_MAX_ROT]; u32 rots, accumulate; };
+void launch_hoist_lt(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistLtArgs &h, hipStream_t s);
+// its base, NTT form: base[b][0][j][n] (+)= sum_r pt[r][j][n] c0[b][j][pi_r(n)]; polys == 2: base[b][1][j][n] (+)= sum_{r: elt[r] == 1} pt[r][j][n] c1[b][j][n].
+// c0 / c1: NTT-form limbs, item b at + b * bstride, limb j of c0 at + j N, of c1 at + j * c1_lstride; h.key is not read
+void launch_hoist_lt_base(const u64 *c0, u64 c0_bstride, const u64 *c1, u64 c1_bstride, u64 c1_lstride, u64 *base, u64 base_bstride, int polys, const KsArgs &a,
+                          const HoistLtArgs &h, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

@@ -702,6 +702,128 @@ template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void hoist_mac_ker
         acc[((o * 2 + 1) * rl + i) * N + n] = barrett128(v1.lo, v1.hi, m);
     }
 }
+// Hoisted linear transform: the gathered inner products of hoist_mac_kernel, each multiplied by one plaintext word and SUMMED over the
+// rotations of the launch inside the thread,
+//   acc[b * 2 + k][i][n] (+)= sum_r pt_r[limb(i)][n] * (sum_j opnd(b,i,j)[pi_r(n)] * key_r[j][k][limb(i)][n] mod p_i) mod p_i,
+// so one accumulator per item reaches memory, written once by one thread, whatever the number of rotations.  Thread-to-(i, n) mapping, index map, block
+// order (batch group fastest) and the two instances are hoist_mac_kernel's:
+//   ROT4 == false: four batch items of one rotation at a time (each key and plaintext word used four times), eight outer accumulators;
+//   ROT4 == true:  four rotations of ONE item at a time, two outer accumulators.
+// The outer accumulation is lazy with ONE final Barrett step per launch.  ROT4: 128 bits, every term (a canonical inner sum < p) * (a plaintext word < p)
+// < 2^120 for p < 2^60, at most HOIST_MAX_ROT = 16 of them per launch: below 2^124.  Batched instance: eight 128-bit accumulators cost two of its four
+// waves per SIMD (180 VGPRs, two waves), so each term is reduced (mulmod, canonical < 2^60) and the sum is 64 bits: at most 16 terms, below 2^64
+// (146 VGPRs, three waves; DESIGN.md section 4.11 has the compiler's resource report).  A later launch of the same call (accumulate) adds its reduced
+// sum to the canonical word the earlier one stored.
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void hoist_lt_kernel(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, KsArgs a, HoistLtArgs h) {
+    constexpr int NO = ROT4 ? 1 : 4; // items per thread
+    const u64 N = u64(1) << a.logn, rl = a.dl + 1;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4);
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over (dl + 1) * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 i = idx >> a.logn;
+    const Mod m = mod_of(a.primes[a.key_id[i]]);
+    const u64 kl = a.key_limb[i];
+    // item of accumulator t; a ragged last group recomputes its last member and stores nothing for it
+    u64 bb[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        bb[t] = b < a.batch ? b : a.batch - 1;
+    }
+    U128 o0[NO], o1[NO];
+#pragma unroll
+    for (int t = 0; t < NO; t++) o0[t] = o1[t] = U128{0, 0};
+    const u32 steps = ROT4 ? (h.rots + 3) / 4 : h.rots;
+    for (u32 st = 0; st < steps; st++) {
+        u32 rr[4], src[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const u32 r = ROT4 ? st * 4 + t : st;
+            rr[t] = r < h.rots ? r : h.rots - 1;
+            if (ROT4 || t == 0) src[t] = galois_ntt_index(n, h.elt[rr[t]], a.logn);
+            else src[t] = src[0];
+        }
+        MacAcc s0[4], s1[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); }
+        for (u64 j = 0; j < a.dl; j++) {
+            const u64 koff = ((j * 2) * a.K + kl) * N + n;
+            u64 k0[4], k1[4], x[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (ROT4 || t == 0) { const u64 *kp = h.key[rr[t]] + koff; k0[t] = kp[0]; k1[t] = kp[a.K * N]; }
+                else { k0[t] = k0[0]; k1[t] = k1[0]; }
+                const u64 *xp = (ckks_target && i == j) ? ckks_target + bb[t] * t_bstride + j * N : D + ((bb[t] * rl + i) * a.dl + j) * N;
+                x[t] = xp[src[t]];
+            }
+            mac4(s0, x, k0);
+            mac4(s1, x, k1);
+        }
+        // the inner sums of this rotation (of these four), reduced, times the rotation's plaintext word, onto the outer accumulators
+        u64 w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (ROT4 && st * 4 + t >= h.rots) break;
+            if (ROT4 || t == 0) w = h.pt[rr[t]][kl * N + n];
+            const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+            if (ROT4) {
+                mac128(o0[0], barrett128(v0.lo, v0.hi, m), w);
+                mac128(o1[0], barrett128(v1.lo, v1.hi, m), w);
+            } else {
+                o0[t].lo += mulmod(barrett128(v0.lo, v0.hi, m), w, m);
+                o1[t].lo += mulmod(barrett128(v1.lo, v1.hi, m), w, m);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NO; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (b >= a.batch) break;
+        u64 *p0 = acc + ((b * 2 + 0) * rl + i) * N + n, *p1 = acc + ((b * 2 + 1) * rl + i) * N + n;
+        u64 r0 = barrett128(o0[t].lo, o0[t].hi, m), r1 = barrett128(o1[t].lo, o1[t].hi, m);
+        if (h.accumulate) { r0 = addmod(r0, *p0, m.p); r1 = addmod(r1, *p1, m.p); } // the canonical words an earlier launch of this call stored
+        *p0 = r0;
+        *p1 = r1;
+    }
+}
+// What the hoisted linear transform accumulates onto, in NTT form (the plaintext-weighted sum of the rotated c0, and of c1 itself for element 1):
+//   base[b][0][j][n] (+)= sum_r pt_r[j][n] * c0[b][j][pi_r(n)],   base[b][1][j][n] (+)= sum_{r: elt_r == 1} pt_r[j][n] * c1[b][j][n]   mod q_j.
+// Grid x: quarter-row windows, y: (polynomial, limb), z: batch item; a thread owns the coefficients n0 + t N / 4 (four MacAcc sums, at most 16 terms each).
+__global__ __launch_bounds__(EW_THREADS) void hoist_lt_base_kernel(const u64 *c0, u64 c0_bstride, const u64 *c1, u64 c1_bstride, u64 c1_lstride, u64 *base, u64 base_bstride,
+                                                                   KsArgs a, HoistLtArgs h) {
+    const u32 N = 1u << a.logn, quarter = N >> 2;
+    const u32 n0 = blockIdx.x * EW_THREADS + threadIdx.x;
+    if (n0 >= quarter) return;
+    const u32 j = blockIdx.y % (u32)a.dl, poly = blockIdx.y / (u32)a.dl;
+    const Mod m = mod_of(a.primes[a.key_id[j]]);
+    for (u64 b = blockIdx.z; b < a.batch; b += gridDim.z) {
+        const u64 *row = poly ? c1 + b * c1_bstride + (u64)j * c1_lstride : c0 + b * c0_bstride + (u64)j * N;
+        MacAcc s[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) mac_zero(s[t]);
+        for (u32 r = 0; r < h.rots; r++) {
+            if (poly && h.elt[r] != 1) continue;
+            u64 x[4], w[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const u32 n = n0 + t * quarter;
+                x[t] = row[poly ? n : galois_ntt_index(n, h.elt[r], a.logn)];
+                w[t] = h.pt[r][(u64)j * N + n];
+            }
+            mac4(s, x, w);
+        }
+        u64 *o = base + b * base_bstride + ((u64)poly * a.dl + j) * N + n0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const U128 v = mac_value(s[t]);
+            u64 res = barrett128(v.lo, v.hi, m);
+            if (h.accumulate) res = addmod(res, o[t * quarter], m.p);
+            o[t * quarter] = res;
+        }
+    }
+}
 // BFV (kind 0) / BGV (kind 2) mod-down, everything in coefficient form (evaluator.cpp:2528-2648):
 //   ct[b][k][j][n] += (acc_j - [t']_{q_j} + [half]_{q_j}) * qk^-1 mod q_j, t' = (acc_last + half) mod qk       (BFV)
 //   ct[b][k][j][n] += (acc_j - [acc_last]_{q_j} - [k_t]_{q_j} * qk) * qk^-1,  k_t = -acc_last * qk^-1 mod t     (BGV)
@@ -797,6 +919,29 @@ void launch_hoist_mac(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *
     if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(hoist_mac_kernel<true>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
     else TROY_LAUNCH(HIP_KERNEL_NAME(hoist_mac_kernel<false>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
     launch_check("hoist_mac_kernel");
+}
+void launch_hoist_lt(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistLtArgs &h, hipStream_t s) {
+    if (a.dl >= 64) throw Error(ST_LOGIC_ERROR, "hoist_lt: more than 63 digits");
+    if (!h.rots || h.rots > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "hoist_lt: 1 .. 16 rotations of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.key[r] || !h.pt[r] || h.elt[r] == 1) throw Error(ST_LOGIC_ERROR, "hoist_lt: every rotation takes a key and a plaintext; element 1 belongs to the base");
+    const bool rot4 = a.batch <= 2 && h.rots > 1; // as launch_hoist_mac
+    const u64 windows = ceil_div((a.dl + 1) << a.logn, EW_THREADS);
+    const u64 blocks = windows * (rot4 ? a.batch : (a.batch + 3) / 4);
+    if (blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, "hoist_lt: batch too large for one launch");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(hoist_lt_kernel<true>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(hoist_lt_kernel<false>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    launch_check("hoist_lt_kernel");
+}
+void launch_hoist_lt_base(const u64 *c0, u64 c0_bstride, const u64 *c1, u64 c1_bstride, u64 c1_lstride, u64 *base, u64 base_bstride, int polys, const KsArgs &a,
+                          const HoistLtArgs &h, hipStream_t s) {
+    if (a.logn < 2) throw Error(ST_LOGIC_ERROR, "hoist_lt_base: four coefficients per thread");
+    if (!h.rots || h.rots > HOIST_MAX_ROT || !a.batch || polys < 1 || polys > 2) throw Error(ST_LOGIC_ERROR, "hoist_lt_base: 1 .. 16 elements of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.pt[r]) throw Error(ST_LOGIC_ERROR, "hoist_lt_base: every element takes a plaintext");
+    const dim3 grid((unsigned)ceil_div((u64(1) << a.logn) / 4, EW_THREADS), (unsigned)(polys * a.dl), (unsigned)std::min<u64>(a.batch, 65535));
+    TROY_LAUNCH(hoist_lt_base_kernel, grid, dim3(EW_THREADS), 0, s, c0, c0_bstride, c1, c1_bstride, c1_lstride, base, base_bstride, a, h);
+    launch_check("hoist_lt_base_kernel");
 }
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s) {
     u64 total = a.batch * 2 * a.dl << a.logn;
