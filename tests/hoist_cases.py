@@ -17,15 +17,25 @@ from troy_amd.capi import BFV, BGV, CKKS
 BENCH = {  # bench.py's workload parameters (tools/encrypt_bench.py SHAPES)
     "bfv_n32768_l14": dict(scheme=BFV, N=32768, bits=[60] + [58] * 13 + [60], tbits=20),
     "bgv_n65536_relin_rot": dict(scheme=BGV, N=65536, bits=[60] + [50] * 13 + [60], tbits=20),
+    "ckks_n32768_chain": dict(scheme=CKKS, N=32768, bits=[60] + [40] * 13 + [60], tbits=0),
 }
 SMALL = ["bfv_n64_k3", "bgv_n128_k4", "ckks_n128_k6"]          # batch 5 (a blocked group of four and a remainder), R = 3
-MEDIUM = ["cfgA_bfv_n4096_k3", "bgv_n4096_k3", "ckks_n4096_k4"]  # batch 2, R = 5 with element 1: the single-pass and fused mod-down routes
+# batch 2, R = 5 with element 1: 60 rows per launch of the second half, far below the single-pass threshold (four rows per workgroup slot of the chip:
+# 4096 rows at N = 4096 on 256 CUs) -- the merged two-pass mod-down (BFV, BGV) and the element-wise CKKS correction; the large-launch routes are
+# check_large_route's
+MEDIUM = ["cfgA_bfv_n4096_k3", "bgv_n4096_k3", "ckks_n4096_k4"]
 NARROW = ["nar_bfv_n4096_k3"]                                    # primes below 2^33: the element-wise epilogue
 KEY_SEED = 7100
 
 
 def config(name):
     return BENCH[name] if name in BENCH else cases.CONFIGS[name]
+
+
+def adhoc(scheme, N, bits, tbits=None):
+    """(name, parameters) of a set no table names: Setup(*adhoc(...))"""
+    tbits = 0 if scheme == CKKS else (tbits or (20 if N >= 4096 else 10))
+    return "%s_n%d_%s" % ({BFV: "bfv", BGV: "bgv", CKKS: "ckks"}[scheme], N, "_".join(map(str, bits))), dict(scheme=scheme, N=N, bits=list(bits), tbits=tbits)
 
 
 def obj(a):
@@ -35,9 +45,11 @@ def obj(a):
 class Setup:
     """one parameter set; synthetic uniform keys (the arithmetic is oblivious to key validity), one per Galois element, seeded by the element"""
 
-    def __init__(self, name):
-        cfg = self.cfg = config(name)
+    def __init__(self, name, cfg=None, patterns=("uniform", "uniform", "uniform")):
+        """patterns: synth.edge_rows patterns of (ciphertext, keys, plaintexts)"""
+        cfg = self.cfg = cfg or config(name)
         self.name, self.scheme, self.N = name, cfg["scheme"], cfg["N"]
+        self.ct_pattern, self.key_pattern, self.pt_pattern = patterns
         N = self.N
         self.primes = [int(p) for p in api.CoeffModulus.Create(N, cfg["bits"])]
         self.t = int(api.PlainModulus.Batching(N, cfg["tbits"])) if cfg["tbits"] else 0
@@ -52,6 +64,14 @@ class Setup:
     def levels(self):
         return sorted({self.ctx.first_limbs, self.ctx.last_limbs}, reverse=True)
 
+    def all_levels(self):
+        return list(range(self.ctx.first_limbs, self.ctx.last_limbs - 1, -1))
+
+    def three_levels(self):
+        """the first, one middle and the last level"""
+        f, l = self.ctx.first_limbs, self.ctx.last_limbs
+        return sorted({f, (f + l) // 2, l}, reverse=True)
+
     def key(self, elt, rows_only=None):
         """the key of element `elt`: on the device in self.gk, on the host [K-1][2][K][N]; the synthetic generator and its device twin agree, so a large
         key is filled on the device and only the rows the model reads (digits below `rows_only`) come back"""
@@ -59,9 +79,10 @@ class Setup:
         K, N = self.K, self.N
         if elt not in self.host_keys:
             if rows_only is None:
-                k = synth.uniform_kswitch_key(KEY_SEED + elt, self.primes, N)
+                k = synth.edge_rows(self.key_pattern, KEY_SEED + elt, self.primes, (K - 1) * 2 * K, N).reshape(K - 1, 2, K, N)
                 self.gk.set(idx, k)
             else:
+                assert self.key_pattern == "uniform"
                 buf = api.DeviceBuffer((K - 1) * 2 * K * N)
                 self.ctx.fill_uniform(buf, (K - 1) * 2 * K, self.primes, KEY_SEED + elt)
                 self.gk.set_device(idx, buf)
@@ -71,7 +92,7 @@ class Setup:
         return self.host_keys[elt]
 
     def inputs(self, limbs, batch, seed):
-        return synth.uniform_ct(seed, self.primes[:limbs], 2, self.N, batch)
+        return synth.edge_ct(self.ct_pattern, seed, self.primes[:limbs], 2, self.N, batch, ntt_form=self.ntt)
 
     def ct(self, data):
         """an odd batch leaves room for a third polynomial per item: the operand is then a strided batch"""
@@ -147,18 +168,124 @@ def model_item(S, ct, elt, key):
     return out
 
 
-def check_model(S, limbs, batch, R, seed, items=None, rows_only=None):
-    """every limb of every output item (or of `items`) equals the model"""
+def check_model(S, limbs, batch, R, seed, items=None, rows_only=None, elts=None, rots=None, limit=0):
+    """every limb of every output item (or of `items`) of every rotation (or of the positions `rots`) equals the model"""
     data = S.inputs(limbs, batch, seed)
-    elts = S.elts(R)
-    got = S.hoisted(data, elts, rows_only=rows_only)
+    elts = S.elts(R) if elts is None else list(elts)
+    R = len(elts)
+    got = S.hoisted(data, elts, limit=limit, rows_only=rows_only)
     assert got.shape == (R, batch, 2, limbs, S.N)
     for r, g in enumerate(elts):
+        if rots is not None and r not in rots:
+            continue
         for b in (range(batch) if items is None else items):
             exp = model_item(S, data[b], g, S.host_keys.get(g))
             assert np.array_equal(got[r, b], exp), (S.name, limbs, "rotation", r, "element", g, "item", b)
             assert all((got[r, b, :, j] < np.uint64(S.primes[j])).all() for j in range(limbs))
     return got, data, elts
+
+
+def many_elts(S, R, one_at=None):
+    """R distinct Galois elements other than 1: 3, 2N - 1, 2N - 3, N + 1, then a seeded spread over the odd numbers below 2N (all of them from R = N - 1 on);
+    `one_at`: element 1 put at that position on top of them"""
+    N = S.N
+    rest = [int(g) for g in 2 * np.random.default_rng(N).permutation(np.arange(1, N)) + 1]
+    e = list(dict.fromkeys([3, 2 * N - 1, 2 * N - 3, N + 1] + rest))[:R]
+    assert len(e) == R and all(g & 1 and 1 < g < 2 * N for g in e)
+    return e if one_at is None else e[:one_at] + [1] + e[one_at:]
+
+
+# ---------------------------------------------------------------- the routes only large launches take
+ROUTE_STATS = ("ntt1_int_launches", "ntt1_fp_launches", "ntt2_int_launches", "ntt2_fp_launches")
+
+
+def route_stats():
+    lib = api.KernelProvider.lib()
+    return {n: capi.stat(n, lib) for n in ROUTE_STATS}
+
+
+def delta(after, before):
+    return {n: after[n] - before[n] for n in after}
+
+
+_cus = []
+
+
+def device_cus():
+    """compute units of device 0 as the library counts them (ntt1.hip device_cus): both thresholds below scale with it.  torch is asked in a child
+    process, once: it brings a HIP runtime of its own, which finds no device in a process where the library's runtime has opened it"""
+    import subprocess
+    import sys
+    if not _cus:
+        out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        _cus.append(int(out.stdout.split()[-1]))
+    return _cus[0]
+
+
+def single_pass_rows(N, cus):
+    """ntt1_supported (ntt1.hip): four rows per workgroup slot of the chip -- one workgroup per CU at N >= 2^14, two at 2^13, four at 2^12"""
+    logn = N.bit_length() - 1
+    assert 12 <= logn <= 15
+    return 4 * cus * {12: 4, 13: 2}.get(logn, 1)
+
+
+def unmerged_rows(N, cus):
+    """the smallest row count at which Context::small_launch (context.cpp: (rows * N >> 11) < 64 CUs) is false"""
+    return -(-((64 * cus) << 11) // N)
+
+
+def items_for(rows, rows_per_item, extra=1):
+    """the smallest item count whose launch has `rows` rows, and `extra` more so that a ragged group occurs"""
+    return -(-rows // rows_per_item) + extra
+
+
+def check_large_route(S, limbs, batch, elts, seed, rows_only=None, limit=0, model_rots=None, alone=True):
+    """ONE hoisted call of `batch` items: items 0, the middle one and the last of the first and the last rotation (or of the positions `model_rots`)
+    against the model; with `alone`, EVERY item of every rotation bit-for-bit against the same call at batch 1 (the small-launch routes, which the model
+    pins at the small shapes).  -> the path-counter deltas (the large call, one call at batch 1)"""
+    data = S.inputs(limbs, batch, seed)
+    R = len(elts)
+    for g in elts:
+        if g != 1:
+            S.key(g, rows_only)
+    s0 = route_stats()
+    got = S.hoisted(data, elts, limit=limit, rows_only=rows_only)
+    big = delta(route_stats(), s0)
+    one = None
+    for b in range(batch if alone else 1):
+        s0 = route_stats()
+        got1 = S.hoisted(data[b:b + 1], elts, rows_only=rows_only)[:, 0]
+        one = one or delta(route_stats(), s0)
+        assert np.array_equal(got1, got[:, b]), (S.name, "item", b, "differs from the same call at batch 1")
+    for r in sorted({0, R - 1} if model_rots is None else model_rots):
+        for b in sorted({0, batch // 2, batch - 1}):
+            exp = model_item(S, data[b], elts[r], S.host_keys.get(elts[r]))
+            assert np.array_equal(got[r, b], exp), (S.name, limbs, "rotation", r, "element", elts[r], "item", b)
+    print(S.name, "batch", batch, "R", R, "counters of the large call", big, "of the call at batch 1", one)
+    return big, one
+
+
+def single_pass(d):
+    return d["ntt1_int_launches"] + d["ntt1_fp_launches"]
+
+
+def two_pass(d):
+    return d["ntt2_int_launches"] + d["ntt2_fp_launches"]
+
+
+# ---------------------------------------------------------------- prime classes, limb counts and levels
+INT_SETS = [[60, 60, 60, 60, 60], [58, 58, 58, 58], [60, 58, 50, 49, 60]]  # the integer instances (guarded at 60 bits, guard-free at 58) with more than one digit
+FP_WIDTHS = [34, 40, 41, 47, 48, 49, 50]                                    # the FP64 instances' range, edge to edge (50 bits: the first integer width)
+MIXED_SETS = [[50, 30, 50, 30, 45, 60], [60, 22, 24, 60]]                   # wide and narrow primes in one modulus
+LIMB_COUNTS = list(range(2, 19))                                            # K = 2: one digit; K above 15 leaves the fused shapes
+EVERY_LEVEL = [(K, limbs) for K in (8, 18) for limbs in range(K - 2, 0, -1)]     # below the first level, which LIMB_COUNTS runs
+SCHEMES = {"bfv": BFV, "bgv": BGV, "ckks": CKKS}
+
+
+def int_setup(scheme, N, bits):
+    return Setup(*adhoc(SCHEMES[scheme], N, bits, 40 if scheme == "bfv" and bits == INT_SETS[0] and N == 128 else None))
 
 
 # ---------------------------------------------------------------- independence
@@ -343,3 +470,52 @@ def check_python_layer(S):
     first = got[0]
     del got  # a result outlives its siblings
     assert np.array_equal(first.cpu(), ref[0])
+
+
+# ---------------------------------------------------------------- more than HOIST_MAX_ROT = 16 elements
+def slab_plan(S, limbs, batch, R, limit=0):
+    """(items, rotations) per slab as Evaluator::apply_galois_hoisted plans them (evaluator.cpp), restated"""
+    N, dl, rl = S.N, limbs, limbs + 1
+    limit = limit or 1 << 28
+    slack = 32 * 8 + 128
+    per_item, per_rot_item = N * (rl * dl + (dl if S.ntt else 0)), N * (2 * rl + 3 * dl + 4)
+    if batch * (per_item + per_rot_item) + slack <= limit:
+        return batch, min(R, 16, (limit - slack - batch * per_item) // (batch * per_rot_item))
+    return (limit - slack) // (per_item + per_rot_item), 1
+
+
+def expected_slabs(S, limbs, batch, elts, limit=0):
+    """a slab is up to `rs` consecutive elements other than 1, of a run of `bs` items"""
+    bs, rs = slab_plan(S, limbs, batch, len(elts), limit)
+    runs, n = [], 0
+    for g in list(elts) + [1]:
+        if g == 1:
+            runs += [n] if n else []
+            n = 0
+        else:
+            n += 1
+    return -(-batch // bs) * sum(-(-n // rs) for n in runs)
+
+
+def check_many_elements(S, limbs, batch, R, seed):
+    """R elements, element 1 in their middle: every output against the model under the default scratch limit (slabs of 16 rotations and a remainder), and
+    bit-for-bit the same under a limit that allows 7 rotations per slab and one that allows a single one; the slab counter follows the slab arithmetic"""
+    elts = many_elts(S, R - 1, one_at=(R - 1) // 2)
+    s0 = slabs()
+    ref, data, _ = check_model(S, limbs, batch, R, seed, elts=elts)
+    want = expected_slabs(S, limbs, batch, elts)
+    assert slabs() - s0 == want == -(-((R - 1) // 2) // 16) + -(-(R - 1 - (R - 1) // 2) // 16), (S.name, R, batch)
+    for rs in (7, 1):
+        limit = scratch_words(S, limbs, batch, rs)
+        assert slab_plan(S, limbs, batch, R, limit) == (batch, rs)
+        s0 = slabs()
+        assert np.array_equal(S.hoisted(data, elts, limit=limit), ref), (S.name, R, batch, "rotations per slab", rs)
+        assert slabs() - s0 == expected_slabs(S, limbs, batch, elts, limit) > want, (S.name, R, batch, rs)
+
+
+def check_every_element(S, limbs, batch, count, seed):
+    """`count` distinct elements other than 1 (all of them at count = N - 1) and element 1, a key per element: every output against the model --
+    galois_ntt_index over the elements of a ring"""
+    elts = many_elts(S, count, one_at=count // 2)
+    check_model(S, limbs, batch, len(elts), seed, elts=elts, items=[0])
+    return elts

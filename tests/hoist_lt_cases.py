@@ -21,23 +21,38 @@ PLAIN_SEED = 8200
 
 def plains_of(S, R, seed=PLAIN_SEED):
     """R synthetic plaintexts [R][K][N], uniform residues of all K key primes (the arithmetic is oblivious to what they encode)"""
-    return synth.uniform_ct(seed, S.primes, 1, S.N, R)[:, 0]
+    return synth.edge_rows(S.pt_pattern, seed, S.primes, R * S.K, S.N).reshape(R, S.K, S.N)
 
 
-def fused(S, data, elts, pts, limit=0, rows_only=None, ct=None):
-    """-> [batch][2][limbs][N] through the Python layer"""
+def fused(S, data, elts, pts, limit=0, rows_only=None, ct=None, bufs=None):
+    """-> [batch][2][limbs][N] through the Python layer (bufs: the plaintexts `pts` already on the device)"""
     for g in elts:
         if g != 1:
             S.key(g, rows_only)
-    bufs = [api.DeviceBuffer.from_numpy(p) for p in pts]
+    bufs = [api.DeviceBuffer.from_numpy(p) for p in pts] if bufs is None else bufs
     out = S.ev.applyGaloisPlainSumHoisted(S.ct(data) if ct is None else ct, elts, bufs, S.gk, scratch_limit_words=limit)
     assert (out.size(), out.limbs, out.is_ntt_form, out.batch) == (2, data.shape[2], S.ntt, data.shape[0])
     return out.cpu()
 
 
 # ---------------------------------------------------------------- the definition, in exact integers
-def model_item(S, ct, elts, keys, pts):
-    """sum_r pts[r] * (element elts[r] of the ciphertext ct [2][dl][N]) under keys[r] [K-1][2][K][N] -> [2][dl][N]"""
+MAC_TERMS, MAC_OPERAND = 63, 1 << 61   # poly.hip MacAcc: fewer than 64 terms of operands below 2^61
+BOUNDS = {"inner": MAC_TERMS * MAC_OPERAND ** 2, "base": MAC_TERMS * MAC_OPERAND ** 2,  # the sums a MacAcc holds
+          "outer128": 1 << 124,  # hoist_lt_kernel<true>: at most 16 products of canonical words per launch, "below 2^124"
+          "outer64": 1 << 64}    # hoist_lt_kernel<false>: at most 16 reduced products per launch, "below 2^64"
+LAUNCH = 16                      # HOIST_MAX_ROT
+
+
+def note(trace, name, values):
+    if trace is not None:
+        trace[name] = max(trace.get(name, 0), int(np.max(values)))
+
+
+def model_item(S, ct, elts, keys, pts, trace=None):
+    """sum_r pts[r] * (element elts[r] of the ciphertext ct [2][dl][N]) under keys[r] [K-1][2][K][N] -> [2][dl][N]
+    trace: a dict that receives the largest value each lazy accumulator of the kernels holds for these inputs, as exact integers ("inner": the sum
+    over the digits before its reduction; "outer128" / "outer64": the sum over the rotations of one launch of hoist_lt_kernel<true> / <false>;
+    "base": the sum over the elements of one launch of hoist_lt_base_kernel) -- to be held against BOUNDS"""
     N, K, primes = S.N, S.K, S.primes
     dl = ct.shape[1]
     qk = primes[K - 1]
@@ -48,29 +63,49 @@ def model_item(S, ct, elts, keys, pts):
     d = coeff[1]
     # steps 1 - 3: per rotation the inner product over the rotated digits, canonical, times the plaintext row of the output prime, summed
     acc = np.zeros((2, dl + 1, N), dtype=object)
+    launch = np.zeros((2, 2, dl + 1, N), dtype=object)  # [128-bit form, 64-bit form]: what the outer accumulators of the current launch hold
+    in_launch = 0
     for g, key, pt in zip(elts, keys, pts):
         if g == 1:
             continue
+        if in_launch == LAUNCH:
+            launch[:] = 0
+            in_launch = 0
+        in_launch += 1
         for i, p in enumerate(out_primes):
             inner = np.zeros((2, N), dtype=object)
             for j in range(dl):
                 e = oracle.ntt_standalone(N, p, oracle.apply_galois(N, g, p, d[j] % np.uint64(p)), 1)
                 for k in range(2):
                     inner[k] += obj(e) * obj(key[j, k, key_limb[i]])
+            note(trace, "inner", inner)
             inner %= p
             for k in range(2):
                 acc[k, i] += obj(pt[key_limb[i]]) * inner[k]
+                if trace is not None:
+                    launch[0, k, i] += obj(pt[key_limb[i]]) * inner[k]
+                    launch[1, k, i] += obj(pt[key_limb[i]]) * inner[k] % p
+        if trace is not None:
+            note(trace, "outer128", launch[0])
+            note(trace, "outer64", launch[1])
     for i, p in enumerate(out_primes):
         acc[:, i] %= p
     # steps 4 - 6: the base in NTT form, back in the ciphertext's own form
     base = np.zeros((2, dl, N), dtype=object)
     for j in range(dl):
         q = primes[j]
-        for g, pt in zip(elts, pts):
+        launch = np.zeros((2, N), dtype=object)
+        for r, (g, pt) in enumerate(zip(elts, pts)):
+            if r % LAUNCH == 0:
+                launch[:] = 0
             rot = oracle.ntt_standalone(N, q, oracle.apply_galois(N, g, q, coeff[0][j]) if g != 1 else coeff[0][j], 1)
             base[0, j] += obj(pt[j]) * obj(rot)
+            launch[0] += obj(pt[j]) * obj(rot)
             if g == 1:
-                base[1, j] += obj(pt[j]) * obj(oracle.ntt_standalone(N, q, coeff[1][j], 1))
+                one = obj(pt[j]) * obj(oracle.ntt_standalone(N, q, coeff[1][j], 1))
+                base[1, j] += one
+                launch[1] += one
+            note(trace, "base", launch)
         base[:, j] %= q
         if not S.ntt:
             for k in range(2):
@@ -103,15 +138,17 @@ def model_item(S, ct, elts, keys, pts):
     return out
 
 
-def check_model(S, limbs, batch, elts, seed, items=None, rows_only=None):
-    """every limb of every output item (or of `items`) equals the model and is canonical"""
+def check_model(S, limbs, batch, elts, seed, items=None, rows_only=None, limit=0, trace=None):
+    """every limb of every output item (or of `items`) equals the model and is canonical; trace: see model_item"""
     data = S.inputs(limbs, batch, seed)
     pts = plains_of(S, len(elts), PLAIN_SEED + seed)
-    got = fused(S, data, elts, pts, rows_only=rows_only)
+    got = fused(S, data, elts, pts, limit=limit, rows_only=rows_only)
     assert got.shape == (batch, 2, limbs, S.N)
     keys = [S.host_keys.get(g) for g in elts]
     for b in (range(batch) if items is None else items):
-        exp = model_item(S, data[b], elts, keys, pts)
+        exp = model_item(S, data[b], elts, keys, pts, trace)
+        for name, v in (trace or {}).items():  # a pattern past a documented precondition is no test of the kernel: this comes first
+            assert v < BOUNDS[name], (S.name, "the inputs break the documented bound of", name, v, BOUNDS[name])
         assert np.array_equal(got[b], exp), (S.name, limbs, "item", b, elts)
         assert all((got[b, :, j] < np.uint64(S.primes[j])).all() for j in range(limbs))
     return got, data, pts
@@ -389,3 +426,101 @@ def check_python_layer(S):
     got = fn(S.ct(data), steps, [api.DeviceBuffer.from_numpy(p) for p in pts], S.gk, plain_scale=2.0)
     assert isinstance(got, api.Ciphertext) and got.scale == 2.0
     assert np.array_equal(got.cpu(), ref)
+
+
+# ---------------------------------------------------------------- the routes only large launches take
+def check_both_calls(S, limbs, seed, batch=3):
+    """both hoisted calls at R = 3 against the model on item 0: rotations by (step 1, the conjugation, step 1 again), the linear transform over
+    (step 1, element 1, the conjugation)"""
+    e = S.elts(3)
+    HC.check_model(S, limbs, batch, 3, seed, items=[0])
+    check_model(S, limbs, batch, [e[0], 1, e[1]], seed, items=[0])
+
+
+def check_large_route(S, limbs, batch, elts, seed, rows_only=None, limit=0):
+    """ONE call of `batch` items: items 0, the middle one and the last against the model; EVERY item bit-for-bit against the same call at batch 1 (the
+    small-launch routes, which the model pins at the small shapes).  -> the path-counter deltas (the large call, the first batch-1 call)"""
+    data = S.inputs(limbs, batch, seed)
+    pts = plains_of(S, len(elts), PLAIN_SEED + seed)
+    for g in elts:
+        if g != 1:
+            S.key(g, rows_only)
+    bufs = [api.DeviceBuffer.from_numpy(p) for p in pts]
+    s0 = HC.route_stats()
+    got = fused(S, data, elts, pts, limit=limit, rows_only=rows_only, bufs=bufs)
+    big = HC.delta(HC.route_stats(), s0)
+    one = None
+    for b in range(batch):
+        s0 = HC.route_stats()
+        alone = fused(S, data[b:b + 1], elts, pts, rows_only=rows_only, bufs=bufs)[0]
+        one = one or HC.delta(HC.route_stats(), s0)
+        assert np.array_equal(alone, got[b]), (S.name, "item", b, "differs from the same call at batch 1")
+    keys = [S.host_keys.get(g) for g in elts]
+    for b in sorted({0, batch // 2, batch - 1}):
+        assert np.array_equal(got[b], model_item(S, data[b], elts, keys, pts)), (S.name, limbs, "item", b, elts)
+    print(S.name, "batch", batch, "elements", elts, "counters of the large call", big, "of the call at batch 1", one)
+    return big, one
+
+
+# ---------------------------------------------------------------- both hoisted calls as one hash, for the library's switches
+def hoisted_hash(name, cfg=None, batch=3, seed=4343):
+    """SHA-256 over the limbs of one applyGaloisHoisted and one applyGaloisPlainSumHoisted call (synthetic keys, R = 5 with element 1, first level): what
+    a child process under one of the library's switches must reproduce (cases.mul_relin_hash is the counterpart for multiply, relinearize, rotate)"""
+    import cases
+    S = HC.Setup(name, cfg)
+    limbs = S.ctx.first_limbs
+    data = S.inputs(limbs, batch, seed)
+    elts = S.elts(5)
+    return cases.sha(S.hoisted(data, elts)) + ":" + cases.sha(fused(S, data, elts, plains_of(S, 5, PLAIN_SEED + seed)))
+
+
+def hoisted_hashes_in_child(sets, env, timeout=900):
+    """hoisted_hash of every (name, cfg) of `sets` in a child process under `env` (the library reads its switches once per process)"""
+    import os
+    import subprocess
+    import sys
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import troy_amd as ta, hoist_lt_cases as LT\n"
+            "ta.KernelProvider.initialize(0)\n"
+            "print(' '.join(LT.hoisted_hash(n, c) for n, c in %r))\n") % (tests_dir, os.path.dirname(tests_dir), list(sets))
+    out = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=timeout)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return out.stdout.split()[-len(sets):]
+
+
+# ---------------------------------------------------------------- residues at the ends of their range
+EDGE_SETS = [[60, 60, 60], [50, 49, 50]]  # the widest primes of the integer instances; the last FP64 width (49 bits) and the first integer one (50)
+
+
+def edge_placements(pattern, every=True):
+    """(ciphertext, keys, plaintexts) patterns: `pattern` on each operand alone, the others uniform, and on all three"""
+    u = "uniform"
+    alone = [(pattern, u, u), (u, pattern, u), (u, u, pattern)] if pattern != "zero" else [(pattern, u, u)]  # a zero key or plaintext alone: a zero sum
+    return (alone if every else []) + [(pattern,) * 3]
+
+
+def check_edges(S, limbs, batch, seed, R=16):
+    """both calls with R = 16 elements other than 1 (sixteen terms per launch: the stated bound of both outer accumulators) on the edge patterns S was made
+    with: first the model's own accumulators against the documented bounds (check_model: a pattern past a precondition would be no test of the kernel),
+    then the limbs against the model -- every item and rotation at batch 1, the first and the last item (of the first and the last rotation) of a
+    batch.  -> the largest accumulator values the model saw, as fractions of their bounds"""
+    elts = HC.many_elts(S, R)
+    trace = {}
+    items = None if batch == 1 else [0, batch - 1]
+    check_model(S, limbs, batch, elts, seed, items=items, trace=trace)
+    HC.check_model(S, limbs, batch, R, seed, elts=elts, items=items, rots=None if batch == 1 else [0, R - 1])
+    return {n: trace[n] / BOUNDS[n] for n in trace}
+
+
+def check_edge_pattern(scheme, bits, pattern, N=128, batches=(1, 5), alone_batches=None, every=None, seed=900):
+    """check_edges for every placement of `pattern` (BGV, whose inner product and outer sums are BFV's: all three operands only) at batch 1 (four
+    rotations per thread, 128-bit outer sums) and batch 5 (the batched instance, 64-bit outer sums); alone_batches: the batches of the placements on
+    one operand alone, where they differ.  -> {placement: fractions}"""
+    seen = {}
+    for pats in edge_placements(pattern, every=scheme != "bgv" if every is None else every):
+        S = HC.Setup(*HC.adhoc(HC.SCHEMES[scheme], N, bits, 40 if bits[0] == 60 and N == 128 else None), patterns=pats)
+        for batch in (batches if len(set(pats)) == 1 or alone_batches is None else alone_batches):
+            f = check_edges(S, S.ctx.first_limbs, batch, seed + batch)
+            seen[pats] = {n: max(f[n], seen.get(pats, {}).get(n, 0)) for n in f}
+    return seen
