@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -280,12 +280,33 @@ int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, tro
  * form and correction factor, scale = in->scale * plain_scale (one plain_scale for all plaintexts, as troyhip_multiply_plain_accumulate; CKKS refuses
  * "scale out of bounds").  The result decrypts to what the composition of troyhip_apply_galois, the plaintext products and the additions decrypts to,
  * with ONE rounding instead of n_elts; its limbs are this library's own and are a function of the multiset of (element, key, plaintext) and the
- * ciphertext alone (not of the order, n_elts' split into launches, the batch size or the scratch limit).  No baby-step / giant-step here.
+ * ciphertext alone (not of the order, n_elts' split into launches, the batch size or the scratch limit).  Baby-step / giant-step: troyhip_galois_plain_sum_bsgs below.
  * Scratch per item, no factor n_elts:  N (rl dl [+ dl for CKKS] + 2 rl + 2 dl + dl [BFV / BGV] + 2 dl + 4) words plus 384, dl = in->limbs, rl = dl + 1.
  * scratch_limit_words bounds the arena request (0: 2^28 words); the call works in slabs of items under it; below one item it is refused.
  * Counter "hoist_lt_slabs" (troyhip_stat): slabs run so far.  Stream-ordered. */
 int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
                                      const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* Baby-step / giant-step linear transform (no reference counterpart): the hoisted linear transform above for MANY rotations,
+ *   out item b = sum_i galois_{giant_elts[i]}( u_i ),   u_i = sum_{j : pt[i][j] != null} pt[i][j] * galois_{baby_elts[j]}(in item b),
+ * pt[i][j] = plains_ntt_keylevel[i * n_baby + j] (giant-major; each [K][N] in NTT form at the KEY level, shared by the batch, as above).  A NULL entry
+ * means the term is absent (a zero diagonal).  R = n_baby * n_giant rotations cost n_baby + n_giant - 2 keys and key streams instead of R - 1: a
+ * caller that wants sum_r d_r * rot(x, r), r = i * n1 + j, passes baby steps j, giant steps i * n1 and pt[i][j] = the encoding of rot(d_r, -i * n1).
+ * u_i is byte for byte what troyhip_galois_plain_sum_hoisted returns for the present babies and plaintexts of row i; the giant stage expands the digits of
+ * each u_i.c1, sums the gathered inner products of all giants in the extended basis and runs ONE mod-down.  A baby or a row with no present plaintext
+ * is skipped and its key is not read (may be null); element 1 reads no key in either list; a null key for any other used element is refused
+ * ("Galois key not present").  Elements may repeat in either list.  1 <= n_baby, n_giant <= 64; a table with no present entry is refused.
+ * out->data, out->batch_stride are INPUTS (room for `batch` size-2 items, not overlapping in); the call sets size 2, the operand's limbs, form and
+ * correction factor, scale = in->scale * plain_scale (CKKS refuses "scale out of bounds").  The limbs are a function of the ciphertext and the SET of
+ * rows (giant, key, {(baby, key, plaintext)}) alone: not of the order of the babies or the rows, the chunking into launches, the batch size or the
+ * scratch limit.  They DO depend on the factorisation: another split of the same R rotations rounds differently (n_giant + 1 roundings) and has other
+ * limbs; every split decrypts to the same sum under the noise bound.
+ * Scratch per item, N words each (dl = in->limbs, rl = dl + 1, w = min(16, used babies other than 1), n2 = used rows, gc = rows per chunk <= 16):
+ *   rl dl [+ dl CKKS] + w 2 rl + n2 2 rl + dl [BFV / BGV] + 2 rl + 2 dl  +  gc (4 dl + rl dl [+ dl CKKS] + 2 dl + 4),   plus 640 words.
+ * scratch_limit_words bounds the arena request (0: 2^28 words): the whole batch with as many rows per chunk as fit, else slabs of items with one row
+ * per chunk; below one item with one row it is refused.  Counter "bsgs_slabs" (troyhip_stat): slabs run so far.  Stream-ordered. */
+int troyhip_galois_plain_sum_bsgs(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                  const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel, double plain_scale,
+                                  uint64_t scratch_limit_words, uint64_t batch, void *stream);
 int troyhip_transform_to_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);            /* transformToNttInplace(Ciphertext) */
 int troyhip_transform_from_ntt(troyhip_context *ctx, troyhip_ct *ct, uint64_t batch, void *stream);          /* transformFromNttInplace */
 int troyhip_multiply_plain_ntt(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *plain, double plain_scale, uint64_t batch, void *stream); /* multiplyPlainInplace, NTT-form operands */

@@ -2015,6 +2015,60 @@ public:
         return out;
     }
     std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return applyGaloisPlainSumHoistedBatch(Ciphertext::pointers(a), elts, plains, gk); }
+    // Baby-step / giant-step linear transform (troyhip_galois_plain_sum_bsgs; the reference has no such call):
+    //   sum_i applyGalois( sum_j plains[i][j] * applyGalois(a, babies[j]), giants[i] )   as ONE call and ONE ciphertext,
+    // babies.size() + giants.size() keys for babies.size() * giants.size() rotations, one mod-down for all giants.  plains: one row per giant, one entry
+    // per baby, each a key-level NTT plaintext as in applyGaloisPlainSumHoisted or nullptr for an absent term (a zero diagonal); the present ones share
+    // one scale.  An element that no present plaintext uses, and element 1 / step 0, needs no key.  Another split of the same rotations has other limbs.
+    using PlainTable = std::vector<std::vector<const Plaintext *>>;
+    Ciphertext applyGaloisPlainSumBsgs(const Ciphertext &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const {
+        std::vector<Ciphertext> r = applyGaloisPlainSumBsgsBatch(std::vector<const Ciphertext *>{&a}, babies, giants, plains, gk);
+        return std::move(r[0]);
+    }
+    Ciphertext rotateRowsPlainSumBsgs(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumBsgs(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
+    Ciphertext rotateVectorPlainSumBsgs(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumBsgs(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
+    std::vector<Ciphertext> applyGaloisPlainSumBsgsBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const {
+        const size_t n1 = babies.size(), n2 = giants.size();
+        if (!n1 || !n2) throw std::invalid_argument("baby-step / giant-step transform takes at least one baby and one giant element");
+        if (plains.size() != n2) throw std::invalid_argument("baby-step / giant-step transform takes one row of plaintexts per giant and one entry (or null) per baby");
+        std::vector<const uint64_t *> pls(n1 * n2, nullptr), bk(n1, nullptr), gkeys(n2, nullptr);
+        std::vector<char> baby_used(n1, 0), giant_used(n2, 0);
+        const Plaintext *first = nullptr;
+        for (size_t i = 0; i < n2; i++) {
+            if (plains[i].size() != n1) throw std::invalid_argument("baby-step / giant-step transform takes one row of plaintexts per giant and one entry (or null) per baby");
+            for (size_t j = 0; j < n1; j++) {
+                const Plaintext *p = plains[i][j];
+                if (!p) continue;
+                if (!p->isNttForm() || p->parmsID() != c_.keyParmsID()) throw std::invalid_argument("plain_ntt is not in NTT form at the key level");
+                if (!first) first = p;
+                if (p->scale() != first->scale()) throw std::invalid_argument("scale mismatch");
+                pls[i * n1 + j] = p->device();
+                baby_used[j] = giant_used[i] = 1;
+            }
+        }
+        if (!first) throw std::invalid_argument("baby-step / giant-step transform takes at least one plaintext");
+        auto look_up = [&](const std::vector<uint32_t> &elts, const std::vector<char> &used, std::vector<const uint64_t *> &keys) {
+            for (size_t r = 0; r < elts.size(); r++) {
+                if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
+                if (elts[r] == 1 || !used[r]) continue;
+                if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
+                keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+            }
+        };
+        look_up(babies, baby_used, bk);
+        look_up(giants, giant_used, gkeys);
+        if (a.empty()) return {};
+        if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
+        std::vector<Ciphertext> pa;
+        const troyhip_ct va = runOf(a, pa);
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, a[0]->coeffModulusSize());
+        troyhip_ct t = *out[0].raw();
+        const double plain_scale = c_.parms().scheme() == SchemeType::ckks ? first->scale() : 1.0;
+        check(troyhip_galois_plain_sum_bsgs(h(), &va, &t, babies.data(), bk.data(), (int)n1, giants.data(), gkeys.data(), (int)n2, pls.data(), plain_scale, 0, a.size(), nullptr));
+        for (auto &c : out) c.copyMeta(t);
+        return out;
+    }
+    std::vector<Ciphertext> applyGaloisPlainSumBsgsBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const { return applyGaloisPlainSumBsgsBatch(Ciphertext::pointers(a), babies, giants, plains, gk); }
     void transformToNttInplace(Ciphertext &a) const { check(troyhip_transform_to_ntt(h(), a.raw(), 1, nullptr)); }
     void transformFromNttInplace(Ciphertext &a) const { check(troyhip_transform_from_ntt(h(), a.raw(), 1, nullptr)); }
     void transformToNtt(const Ciphertext &a, Ciphertext &d) const { d = a; transformToNttInplace(d); }     // :246-250

@@ -753,6 +753,55 @@ class Evaluator:
         elts = [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps]
         return self.applyGaloisPlainSumHoisted(a, elts, plains, galois_keys, plain_scale, scratch_limit_words)
 
+    # -- baby-step / giant-step linear transform (troyhip_galois_plain_sum_bsgs: no reference counterpart)
+    def applyGaloisPlainSumBsgs(self, a, baby_elts, giant_elts, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        """sum_i applyGalois(sum_j plains[i][j] * applyGalois(a, baby_elts[j]), giant_elts[i]) as ONE call: len(baby_elts) + len(giant_elts) keys for
+        len(baby_elts) * len(giant_elts) rotations, one mod-down for all giants.  plains: len(giant_elts) lists of len(baby_elts) DeviceBuffer (K * N words,
+        NTT form at the KEY level, as applyGaloisPlainSumHoisted) or None for an absent term.  The keys of elements no present plaintext uses are not needed."""
+        babies, giants = [int(g) for g in baby_elts], [int(g) for g in giant_elts]
+        table = [list(row) for row in plains]
+        n1, n2 = len(babies), len(giants)
+        if not babies or not giants:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element")
+        if len(table) != n2 or any(len(row) != n1 for row in table):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "baby-step / giant-step transform takes one row of plaintexts per giant and one entry (or None) per baby")
+        pls = []
+        for row in table:
+            for p in row:
+                if p is not None and p.words < self.context.key_limbs * self.context.N:
+                    raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "plain_ntt must hold [K][N] words (NTT form at the key level)")
+                pls.append(p.ptr if p is not None else None)
+
+        def key_ptrs(elts, used):
+            ptrs = []
+            for g, u in zip(elts, used):
+                idx = GaloisKeys.getIndex(g)
+                if g != 1 and u and not galois_keys.hasKey(idx):
+                    raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Galois key not present")
+                ptrs.append(galois_keys.keys[idx].ptr if g != 1 and galois_keys.hasKey(idx) else None)
+            return ptrs
+        bk = key_ptrs(babies, [any(row[j] is not None for row in table) for j in range(n1)])
+        gk = key_ptrs(giants, [any(p is not None for p in row) for row in table])
+        out = Ciphertext(self.context, a.batch, 2, a.limbs, a.is_ntt_form, a.scale, a.correction_factor)
+        si, so = a.struct(), out.struct()
+        self._chk(self.lib.troyhip_galois_plain_sum_bsgs(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * n1)(*babies), (C.c_void_p * n1)(*bk), n1,
+                                                         (C.c_uint32 * n2)(*giants), (C.c_void_p * n2)(*gk), n2, (C.c_void_p * (n1 * n2))(*pls),
+                                                         C.c_double(plain_scale), C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        out._absorb(so)
+        return out
+
+    def rotateRowsPlainSumBsgs(self, a, baby_steps, giant_steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        if self.context.scheme not in (BFV, BGV):
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        elt = lambda s: self.context.galois_elt_from_step(int(s)) if int(s) else 1
+        return self.applyGaloisPlainSumBsgs(a, [elt(s) for s in baby_steps], [elt(s) for s in giant_steps], plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def rotateVectorPlainSumBsgs(self, a, baby_steps, giant_steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        if self.context.scheme != CKKS:
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        elt = lambda s: self.context.galois_elt_from_step(int(s)) if int(s) else 1
+        return self.applyGaloisPlainSumBsgs(a, [elt(s) for s in baby_steps], [elt(s) for s in giant_steps], plains, galois_keys, plain_scale, scratch_limit_words)
+
     def _rotate(self, a, steps, conjugate, galois_keys):
         elts = [2 * i + 1 for i in galois_keys.keys]
         n = len(elts)

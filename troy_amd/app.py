@@ -341,7 +341,8 @@ class Conv2dHelper:
 class DiagonalMatvec:
     """y = M x for a plain d x d matrix M and an encrypted vector x by the diagonal method (Halevi-Shoup), as ONE hoisted call
     (Evaluator.rotate*PlainSumHoisted): y = sum_r diag_r (.) rot(x, r), the nonzero diagonals only.  d is a power of two
-    dividing the row length N / 2; x is tiled with period d over the row (BFV / BGV: over both rows), and so is y.  No baby-step / giant-step."""
+    dividing the row length N / 2; x is tiled with period d over the row (BFV / BGV: over both rows), and so is y.  One key per nonzero diagonal: from a few
+    dozen diagonals on, DiagonalMatvecBSGS below (baby-step / giant-step) needs far fewer keys."""
 
     def __init__(self, context, matrix):
         m = np.asarray(matrix)
@@ -382,3 +383,61 @@ class DiagonalMatvec:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the matrix is zero")
         fn = evaluator.rotateVectorPlainSumHoisted if self.context.scheme == capi.CKKS else evaluator.rotateRowsPlainSumHoisted
         return fn(ct, self.steps, self.plains, galois_keys, self.plain_scale)
+
+
+class DiagonalMatvecBSGS:
+    """y = M x as DiagonalMatvec, by baby steps and giant steps (Evaluator.rotate*PlainSumBsgs): with r = i n1 + j,
+        y = sum_i rot( sum_j rot(diag_{i n1 + j}, -i n1) (.) rot(x, j), i n1 ),        rot(v, s)[k] = v[k + s],
+    so n1 = baby_steps baby rotations and d / n1 giant rotations serve all d diagonals: n1 + d / n1 - 2 Galois keys instead of d - 1, and one key stream
+    per baby and per giant instead of one per diagonal.  Zero diagonals are absent terms; a baby step or a giant row that only zero diagonals use needs no
+    key.  baby_steps: a power of two dividing d (default: the one nearest sqrt(6 d)), with baby_steps and d / baby_steps <= 64."""
+
+    def __init__(self, context, matrix, baby_steps=None):
+        m = np.asarray(matrix)
+        row = context.N // 2
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1 or m.shape[0] & (m.shape[0] - 1) or row % m.shape[0]:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "matrix must be d x d, d a power of two dividing the row length N / 2")
+        d = m.shape[0]
+        if baby_steps is None:
+            baby_steps = min((1 << e for e in range(d.bit_length()) if (1 << e) <= 64 and d >> e <= 64), key=lambda n1: abs(n1 - (6 * d) ** 0.5), default=0)
+        n1 = int(baby_steps)
+        if n1 < 1 or n1 & (n1 - 1) or d % n1 or n1 > 64 or d // n1 > 64:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "baby_steps must be a power of two dividing d, with baby_steps and d / baby_steps at most 64")
+        self.context, self.matrix, self.d, self.row, self.n1, self.n2 = context, m, d, row, n1, d // n1
+        k = np.arange(d)
+        diags = [m[k, (k + r) % d] for r in range(d)]  # diag_r[k] = M[k][(k + r) mod d]
+        self.steps = [r for r in range(d) if np.any(diags[r] != 0)]
+        # pt[i][j] encodes rot(diag_{i n1 + j}, -i n1): the tiled diagonal rotates as a tile
+        self.diagonals = {r: np.tile(np.roll(diags[r], (r // n1) * n1), row // d) for r in self.steps}
+        self.baby_steps = list(range(n1))
+        self.giant_steps = [i * n1 for i in range(self.n2)]
+        self.plains, self.plain_scale = None, 1.0
+
+    def requiredSteps(self):
+        """the rotation steps whose Galois keys apply() needs: the baby steps and the giant steps a nonzero diagonal uses (step 0 needs none)"""
+        return sorted({r % self.n1 for r in self.steps if r % self.n1} | {(r // self.n1) * self.n1 for r in self.steps if r // self.n1})
+
+    def encodeDiagonals(self, encoder, scale=None):
+        """the n2 x n1 table of key-level NTT plaintexts (None: a zero diagonal): encoder = BatchEncoder (BFV / BGV) or CKKSEncoder with `scale`"""
+        ctx = self.context
+        K = ctx.key_limbs
+        if ctx.scheme == capi.CKKS:
+            if scale is None:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "CKKS diagonals need a scale")
+            enc = lambda v: api.DeviceBuffer.from_numpy(encoder.encode(v, scale, limbs=K))
+            self.plain_scale = float(scale)
+        else:
+            ev = api.Evaluator(ctx)
+            enc = lambda v: ev.transformPlainToNtt(api.DeviceBuffer.from_numpy(encoder.encode(np.concatenate([v] * 2))), K)
+            self.plain_scale = 1.0
+        self.plains = [[enc(self.diagonals[i * self.n1 + j]) if i * self.n1 + j in self.diagonals else None for j in range(self.n1)] for i in range(self.n2)]
+        return self.plains
+
+    def apply(self, evaluator, ct, galois_keys):
+        """the single baby-step / giant-step call; ct encrypts x tiled with period d"""
+        if self.plains is None:
+            raise capi.LogicError(capi.LOGIC_ERROR, "encodeDiagonals has not been called")
+        if not self.steps:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the matrix is zero")
+        fn = evaluator.rotateVectorPlainSumBsgs if self.context.scheme == capi.CKKS else evaluator.rotateRowsPlainSumBsgs
+        return fn(ct, self.baby_steps, self.giant_steps, self.plains, galois_keys, self.plain_scale)

@@ -833,6 +833,24 @@ int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in,
         store(o, out);
     });
 }
+int troyhip_galois_plain_sum_bsgs(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                  const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel, double plain_scale,
+                                  uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains_ntt_keylevel)
+            throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
+        if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx); // the context is bound before the stream is looked at: argument evaluation order is unspecified
+        hipStream_t s = on(stream);
+        std::vector<KsKey> bk((size_t)n_baby), gk((size_t)n_giant);
+        for (int i = 0; i < n_baby; i++) bk[(size_t)i] = KsKey{baby_keys[i]};
+        for (int i = 0; i < n_giant; i++) gk[(size_t)i] = KsKey{giant_keys[i]};
+        CtBatch o = view(out);
+        handle->ev.galois_plain_sum_bsgs(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains_ntt_keylevel, plain_scale, batch, scratch_limit_words, s);
+        store(o, out);
+    });
+}
 
 static void rotate_internal(troyhip_context *ctx, CtBatch &x, int steps, const uint32_t *elts, const uint64_t *const *keys, int n_keys, u64 batch, hipStream_t s) {
     if (steps == 0) return; // evaluator_cuda.cu:2140-2143

@@ -864,6 +864,184 @@ void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const 
     }
 }
 
+// Baby-step / giant-step linear transform (no reference counterpart):
+//   out = sum_i galois_{G_i}(u_i),   u_i = sum_{j: plains[i * n_baby + j] != null} plains[i * n_baby + j] * galois_{g_j}(in)
+// u_i is what galois_plain_sum_hoisted returns for the present babies of row i (the same kernels and the same second half, run once over all the rows
+// of a chunk); the giants then cost one digit expansion, one key stream and -- all of them together -- one mod-down.  Babies and rows with no present
+// plaintext are skipped and their keys are not read.  The used rows run with the giants other than 1 first (the result does not depend on the order).
+// Scratch per item of a slab, in units of N words (dl = limbs, rl = dl + 1, w = min(16, used babies other than 1), n2' = used rows, gc = rows per chunk):
+//   rl dl [D] + dl [CKKS: c1 in coefficient form] + w 2 rl [W] + n2' 2 rl [accU] + dl [BFV / BGV: c0 in NTT form] + 2 rl [acc] + 2 dl [base]
+//   + gc (2 dl [baseU] + 2 dl [u] + rl dl [digits of u.c1] + dl [CKKS: u.c1 in coefficient form] + 2 dl + 4 [what a second half carves])
+// A slab is the whole batch with as many rows per chunk as fit (16 at the most), or -- where one row of the whole batch does not fit -- a run of items
+// with one row per chunk.  Below one item with one row per chunk the call is refused.
+void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                                      const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
+        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
+    if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+    for (int j = 0; j < n_baby; j++)
+        if (!(baby_elts[j] & 1) || baby_elts[j] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+    for (int i = 0; i < n_giant; i++)
+        if (!(giant_elts[i] & 1) || giant_elts[i] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+    // what is used: the babies other than 1 (inner products), the babies that are 1 (base only), the rows with the giants other than 1 first
+    std::vector<int> rot_babies, rows;
+    bool any_present = false;
+    for (int j = 0; j < n_baby; j++) {
+        bool used = false;
+        for (int i = 0; i < n_giant; i++) used = used || plains[(size_t)i * n_baby + j];
+        any_present = any_present || used;
+        if (used && baby_elts[j] != 1) {
+            if (!baby_keys[j].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+            rot_babies.push_back(j);
+        }
+    }
+    if (!any_present) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n_giant; i++) {
+            bool used = false;
+            for (int j = 0; j < n_baby; j++) used = used || plains[(size_t)i * n_baby + j];
+            if (!used || (giant_elts[i] == 1) != (pass == 1)) continue;
+            if (giant_elts[i] != 1 && !giant_keys[i].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+            rows.push_back(i);
+        }
+    const u64 n_rot_rows = (u64)std::count_if(rows.begin(), rows.end(), [&](int i) { return giant_elts[i] != 1; });
+    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    check_ks_form(in.ntt);
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
+    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "baby-step / giant-step transform: more than 63 digits");
+    const double new_scale = in.scale * plain_scale;
+    if (c.scheme == SCHEME_CKKS && !scale_ok(new_scale, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = new_scale; out.cf = in.cf;
+    if (!batch) return;
+    {   // every rotation reads the whole operand: the destination must not share a word with it
+        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 2 * pw;
+        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform: destination must be a distinct buffer");
+    }
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const u64 n2 = rows.size(), nrb = rot_babies.size(), wb = std::min<u64>(nrb, HOIST_MAX_ROT);
+    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
+    const u64 slack = 32 * 16 + 128; // Arena::take rounds each of at most sixteen blocks up to 32 words
+    const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + wb * 2 * rl + n2 * 2 * rl + (ckks ? 0 : dl) + 2 * rl + 2 * dl);
+    const u64 per_row_item = N * (2 * dl + 2 * dl + rl * dl + (ckks ? dl : 0) + 2 * dl + 4);
+    if (per_item + per_row_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one giant step of one ciphertext");
+    u64 bs = batch, gc = 1;
+    if (batch * (per_item + per_row_item) + slack <= limit) gc = std::min<u64>({n2, (u64)HOIST_MAX_ROT, (limit - slack - batch * per_item) / (batch * per_row_item)});
+    else bs = (limit - slack) / (per_item + per_row_item);
+
+    c.arena.begin(s);
+    c.arena.reserve(bs * per_item + gc * bs * per_row_item + slack);
+    u64 *D = c.arena.take(bs * rl * dl * N);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *W = nrb ? c.arena.take(wb * bs * 2 * rl * N) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * 2 * rl * N) : nullptr;
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw);
+    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
+    u64 *baseU = c.arena.take(gc * bs * 2 * pw), *U = nrb ? c.arena.take(gc * bs * 2 * pw) : baseU; // no baby other than 1: u is its base
+    u64 *DG = n_rot_rows ? c.arena.take(gc * bs * rl * dl * N) : nullptr, *ttG = n_rot_rows && ckks ? c.arena.take(gc * bs * dl * N) : nullptr;
+    const size_t mark = c.arena.mark();
+    const LimbMap map = c.ct_map(L);
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        KsPlan k = ks_plan(L, nb);
+        KsArgs &a = k.a;
+        // stage 1: the digits of this run of items, once; D[b][j][j] is c1's own limb j in NTT form
+        const u64 *coeff = c1;
+        u64 coeff_bs = in.bstride;
+        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
+        ks_expand_digits(coeff, coeff_bs, D, k, s);
+        // stages 2 and 3: the baby inner products, HOIST_MAX_ROT at a time, kept only until every row has taken its plaintext-weighted share of them
+        for (u64 j0 = 0; j0 < nrb; j0 += HOIST_MAX_ROT) {
+            HoistArgs hm;
+            std::memset(&hm, 0, sizeof(hm));
+            hm.rots = (u32)std::min<u64>(HOIST_MAX_ROT, nrb - j0);
+            for (u32 j = 0; j < hm.rots; j++) { hm.elt[j] = baby_elts[rot_babies[j0 + j]]; hm.key[j] = baby_keys[rot_babies[j0 + j]].data; }
+            launch_hoist_mac(D, ckks ? c1 : nullptr, in.bstride, W, a, hm, s);
+            for (u64 r0 = 0; r0 < n2; r0 += BSGS_MAX_ROWS) {
+                BsgsInnerArgs hi;
+                std::memset(&hi, 0, sizeof(hi));
+                hi.rows = (u32)std::min<u64>(BSGS_MAX_ROWS, n2 - r0);
+                hi.babies = hm.rots; hi.row0 = (u32)r0; hi.accumulate = j0 ? 1 : 0;
+                bool any = false;
+                for (u32 r = 0; r < hi.rows; r++)
+                    for (u32 j = 0; j < hm.rots; j++)
+                        if (const u64 *p = plains[(size_t)rows[r0 + r] * n_baby + rot_babies[j0 + j]]) { hi.pt[r][j] = p; hi.mask[r] |= 1u << j; any = true; }
+                if (any || !hi.accumulate) launch_bsgs_inner(W, accU, a, hi, s);
+            }
+        }
+        if (!ckks) {
+            launch_copy_strided(c0, in.bstride, c0n, pw, pw, nb, s);
+            launch_ntt(c0n, c.d_desc, map, nb * dl, c.logn, false, s);
+        }
+        bool acc_started = false;
+        for (u64 i0 = 0; i0 < n2; i0 += gc) {
+            const u64 gn = std::min(gc, n2 - i0);
+            // the bases of the rows, in NTT form, as galois_plain_sum_hoisted makes them: every present pair of the row, both polynomials
+            for (u64 ii = 0; ii < gn; ii++) {
+                u64 *bu = baseU + ii * nb * 2 * pw;
+                HoistLtArgs h;
+                std::memset(&h, 0, sizeof(h));
+                auto flush = [&] {
+                    if (!h.rots) return;
+                    if (ckks) launch_hoist_lt_base(c0, in.bstride, c1, in.bstride, N, bu, 2 * pw, 2, a, h, s);
+                    else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, bu, 2 * pw, 2, a, h, s);
+                    std::memset(&h, 0, sizeof(h));
+                    h.accumulate = 1;
+                };
+                for (int j = 0; j < n_baby; j++)
+                    if (const u64 *p = plains[(size_t)rows[i0 + ii] * n_baby + j]) {
+                        h.pt[h.rots] = p; h.elt[h.rots] = baby_elts[j];
+                        if (++h.rots == HOIST_MAX_ROT) flush();
+                    }
+                flush();
+            }
+            if (!ckks) launch_ntt(baseU, c.d_desc, map, gn * nb * 2 * dl, c.logn, true, s);
+            // u_i of the chunk: ONE second half over rows x items
+            CtBatch o = out;
+            if (nrb) {
+                o.data = U; o.bstride = 2 * pw;
+                a.batch = gn * nb;
+                c.arena.rewind(mark);
+                ks_acc_to_ct(o, accU + i0 * nb * 2 * rl * N, k, s, KsBase{baseU, 2 * pw, 2});
+                a.batch = nb;
+            }
+            // stage 4: the digits of the u_i.c1 whose giant is not 1 (they lead the chunk), the giant sum and its base
+            u64 gr = 0;
+            while (gr < gn && giant_elts[rows[i0 + gr]] != 1) gr++;
+            if (gr) {
+                KsPlan kg = ks_plan(L, gr * nb);
+                const u64 *cg = U + pw;
+                u64 cg_bs = 2 * pw;
+                if (ckks) cg = ks_coeff_target(U + pw, cg_bs, ttG, kg, s);
+                ks_expand_digits(cg, cg_bs, DG, kg, s);
+                HoistSumArgs hs;
+                std::memset(&hs, 0, sizeof(hs));
+                hs.rots = (u32)gr; hs.accumulate = acc_started ? 1 : 0;
+                hs.d_rstride = nb * rl * dl * N; hs.t_rstride = nb * 2 * pw;
+                for (u64 r = 0; r < gr; r++) { hs.elt[r] = giant_elts[rows[i0 + r]]; hs.key[r] = giant_keys[rows[i0 + r]].data; }
+                launch_hoist_sum(DG, ckks ? U + pw : nullptr, 2 * pw, acc, a, hs, s);
+                acc_started = true;
+            }
+            BsgsBaseArgs hb;
+            std::memset(&hb, 0, sizeof(hb));
+            hb.rots = (u32)gn; hb.accumulate = i0 ? 1 : 0;
+            for (u64 r = 0; r < gn; r++) hb.elt[r] = giant_elts[rows[i0 + r]];
+            launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, a, hb, s);
+        }
+        CtBatch o = out;
+        o.data = out.data + b0 * out.bstride;
+        if (!acc_started) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, nb, s); // every used giant is 1: the sum of the u_i, no key read, no second mod-down
+        else {
+            c.arena.rewind(mark);
+            ks_acc_to_ct(o, acc, k, s, KsBase{base, 2 * pw, 2});
+        }
+        stats::counter(stats::BSGS_SLABS)++;
+    }
+}
+
 void Evaluator::transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s) { // evaluator_cuda.cu:1950-1985
     check_ct(ct);
     if (ct.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted is already in NTT form");

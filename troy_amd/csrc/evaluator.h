@@ -78,6 +78,14 @@ public:
     // arena request stays under scratch_limit_words (0: 2^28 words), in slabs of items where needed.  DESIGN.md section 4.11.
     void galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
                                   u64 scratch_limit_words, hipStream_t s);
+    // Baby-step / giant-step linear transform: out item b = sum_i galois_{giant_elts[i]}(u_i), u_i = sum_j plains[i * n_baby + j] * galois_{baby_elts[j]}(in
+    // item b) over the non-null plaintexts (a null entry is an absent term), ONE batch, out distinct from in.  u_i is byte for byte what
+    // galois_plain_sum_hoisted returns for row i; the giants share one mod-down.  n_baby + n_giant keys instead of n_baby * n_giant; the keys of unused
+    // elements and of element 1 are not read.  The result depends on the set of rows, not on their order, the order of the babies, the batch size or the
+    // scratch limit; it DOES depend on the factorisation (another split of the same rotations rounds differently).  Scratch per item: evaluator.cpp;
+    // the arena request stays under scratch_limit_words (0: 2^28 words), in slabs of items and chunks of rows.  DESIGN.md section 4.12.
+    void galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                               const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s);
     void transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void transform_from_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void multiply_plain_ntt(CtBatch &ct, const u64 *plain, double plain_scale, u64 batch, hipStream_t s);

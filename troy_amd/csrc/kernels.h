@@ -196,6 +196,21 @@ void launch_hoist_lt(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *a
 // c0 / c1: NTT-form limbs, item b at + b * bstride, limb j of c0 at + j N, of c1 at + j * c1_lstride; h.key is not read
 void launch_hoist_lt_base(const u64 *c0, u64 c0_bstride, const u64 *c1, u64 c1_bstride, u64 c1_lstride, u64 *base, u64 base_bstride, int polys, const KsArgs &a,
                           const HoistLtArgs &h, hipStream_t s);
+// baby-step / giant-step linear transform.  Stage 3, the inner sums of up to BSGS_MAX_ROWS giant rows over the kept baby inner
+// products W (what launch_hoist_mac wrote for `babies` elements of the batch a.batch):
+//   accU[((row0 + r) * batch + b) * 2 + k][i][n] (+)= sum_{j: bit j of mask[r]} pt[r][j][limb(i)][n] * W[(j * batch + b) * 2 + k][i][n] mod p_i
+// accumulate == 0: every row of the launch is stored (zero where mask[r] == 0); accumulate != 0: added to the canonical words stored before
+enum { BSGS_MAX_ROWS = 8 };
+struct BsgsInnerArgs { const u64 *pt[BSGS_MAX_ROWS][HOIST_MAX_ROT]; u32 mask[BSGS_MAX_ROWS]; u32 rows, babies, row0, accumulate; };
+void launch_bsgs_inner(const u64 *W, u64 *accU, const KsArgs &a, const BsgsInnerArgs &h, hipStream_t s);
+// stage 4, the giant sum: launch_hoist_lt without the plaintext factor, giant r reading its own digits D + r * d_rstride (and, CKKS, its own NTT-form
+// target ckks_target + r * t_rstride):  acc[b * 2 + k][i][n] (+)= sum_r (sum_j opnd_r(b,i,j)[pi_r(n)] * key[r][j][k][limb(i)][n] mod p_i) mod p_i
+struct HoistSumArgs { const u64 *key[HOIST_MAX_ROT]; uint32_t elt[HOIST_MAX_ROT]; u32 rots, accumulate; u64 d_rstride, t_rstride; };
+void launch_hoist_sum(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistSumArgs &h, hipStream_t s);
+// its base, in the ciphertext's form: base[b][0] (+)= sum_r sigma_{elt[r]}(u_r[b].c0), base[b][1] (+)= sum_{r: elt[r] == 1} u_r[b].c1; u_r[b] ([2][dl][N])
+// at u + r * u_rstride + b * u_bstride; elt_inv is filled by the launcher
+struct BsgsBaseArgs { uint32_t elt[HOIST_MAX_ROT], elt_inv[HOIST_MAX_ROT]; u32 rots, accumulate; };
+void launch_bsgs_base(bool ntt_form, const u64 *u, u64 u_rstride, u64 u_bstride, u64 *base, u64 base_bstride, const KsArgs &a, BsgsBaseArgs h, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

@@ -824,6 +824,145 @@ __global__ __launch_bounds__(EW_THREADS) void hoist_lt_base_kernel(const u64 *c0
         }
     }
 }
+// Baby-step / giant-step linear transform, stage 3: the inner sums of the giant rows over the kept baby inner products W,
+//   accU[(row * batch + b) * 2 + k][i][n] (+)= sum_{j in mask[row]} pt[row][j][limb(i)][n] * W[(j * batch + b) * 2 + k][i][n] mod p_i.
+// Element-wise: a thread owns one (item, k, i, n) and keeps the W words of the launch's babies (at most HOIST_MAX_ROT = 16) in registers while it walks
+// the rows, one plaintext word per PRESENT pair (the row's bitmask is workgroup-uniform: an absent pair costs a scalar branch).  Every accU word is
+// written once, by one thread.  The sum of a row is lazy in 128 bits: at most 16 products of canonical words below 2^60, below 2^124 (the bound of
+// hoist_lt_kernel<true>); `accumulate` (a later chunk of babies) adds the reduced sum to the canonical word the first chunk stored and skips the rows it
+// has nothing for; the first chunk stores every row of the launch, a zero where it has nothing.  Block order: (item, k) fastest, so the workgroups in
+// flight share a window of the plaintexts.  102 VGPRs, four waves per SIMD, scratch 0.
+__global__ __launch_bounds__(EW_THREADS) void bsgs_inner_kernel(const u64 *W, u64 *accU, KsArgs a, BsgsInnerArgs h) {
+    const u64 N = u64(1) << a.logn, rl = a.dl + 1;
+    const u32 groups = (u32)a.batch * 2;
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over (dl + 1) * N
+    if (idx >= rl << a.logn) return;
+    const u64 n = idx & (N - 1), i = idx >> a.logn;
+    const Mod m = mod_of(a.primes[a.key_id[i]]);
+    const u64 kl = a.key_limb[i];
+    const u64 bk = g; // (item, k): b * 2 + k
+    u64 w[HOIST_MAX_ROT];
+#pragma unroll
+    for (int j = 0; j < HOIST_MAX_ROT; j++) w[j] = (u32)j < h.babies ? W[((((u64)j * a.batch) * 2 + bk) * rl + i) * N + n] : 0;
+    for (u32 r = 0; r < h.rows; r++) {
+        const u32 mask = h.mask[r];
+        if (h.accumulate && !mask) continue;
+        U128 o{0, 0};
+#pragma unroll
+        for (int j = 0; j < HOIST_MAX_ROT; j++) {
+            if (!((mask >> j) & 1)) continue;
+            mac128(o, w[j], h.pt[r][j][kl * N + n]);
+        }
+        u64 *dst = accU + ((((u64)(h.row0 + r) * a.batch) * 2 + bk) * rl + i) * N + n;
+        u64 v = barrett128(o.lo, o.hi, m);
+        if (h.accumulate) v = addmod(v, *dst, m.p);
+        *dst = v;
+    }
+}
+// Stage 4: the giant sum.  The sibling of hoist_lt_kernel -- its (i, n) mapping, index map, workgroup order (batch group fastest) and mac4 / MacAcc
+// inner loop -- with rotation r reading its OWN digit block (D + r * d_rstride: the digits of u_r.c1) and no plaintext factor:
+//   acc[b * 2 + k][i][n] (+)= sum_r (sum_j opnd_r(b,i,j)[pi_r(n)] * key_r[j][k][limb(i)][n] mod p_i) mod p_i.
+//   ROT4 == false: four batch items of one giant at a time (each key word used four times), eight outer sums;
+//   ROT4 == true:  four giants of ONE item at a time, two outer sums.
+// One Barrett step per giant; the outer sums hold at most HOIST_MAX_ROT = 16 canonical words below 2^60 in 64 bits, below 2^64, and are reduced once
+// per launch.  `accumulate` (a later chunk of giants) adds to the canonical words the earlier launch stored.
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void hoist_sum_kernel(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, KsArgs a, HoistSumArgs h) {
+    constexpr int NO = ROT4 ? 1 : 4; // items per thread
+    const u64 N = u64(1) << a.logn, rl = a.dl + 1;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4);
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over (dl + 1) * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 i = idx >> a.logn;
+    const Mod m = mod_of(a.primes[a.key_id[i]]);
+    const u64 kl = a.key_limb[i];
+    // item of accumulator t; a ragged last group recomputes its last member and stores nothing for it
+    u64 bb[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        bb[t] = b < a.batch ? b : a.batch - 1;
+    }
+    u64 o0[NO], o1[NO];
+#pragma unroll
+    for (int t = 0; t < NO; t++) o0[t] = o1[t] = 0;
+    const u32 steps = ROT4 ? (h.rots + 3) / 4 : h.rots;
+    for (u32 st = 0; st < steps; st++) {
+        u32 rr[4], src[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const u32 r = ROT4 ? st * 4 + t : st;
+            rr[t] = r < h.rots ? r : h.rots - 1;
+            if (ROT4 || t == 0) src[t] = galois_ntt_index(n, h.elt[rr[t]], a.logn);
+            else src[t] = src[0];
+        }
+        MacAcc s0[4], s1[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); }
+        for (u64 j = 0; j < a.dl; j++) {
+            const u64 koff = ((j * 2) * a.K + kl) * N + n;
+            u64 k0[4], k1[4], x[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (ROT4 || t == 0) { const u64 *kp = h.key[rr[t]] + koff; k0[t] = kp[0]; k1[t] = kp[a.K * N]; }
+                else { k0[t] = k0[0]; k1[t] = k1[0]; }
+                const u64 *xp = (ckks_target && i == j) ? ckks_target + rr[t] * h.t_rstride + bb[t] * t_bstride + j * N
+                                                        : D + rr[t] * h.d_rstride + ((bb[t] * rl + i) * a.dl + j) * N;
+                x[t] = xp[src[t]];
+            }
+            mac4(s0, x, k0);
+            mac4(s1, x, k1);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (ROT4 && st * 4 + t >= h.rots) break;
+            const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+            o0[ROT4 ? 0 : t] += barrett128(v0.lo, v0.hi, m);
+            o1[ROT4 ? 0 : t] += barrett128(v1.lo, v1.hi, m);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NO; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (b >= a.batch) break;
+        u64 *p0 = acc + ((b * 2 + 0) * rl + i) * N + n, *p1 = acc + ((b * 2 + 1) * rl + i) * N + n;
+        u64 r0 = barrett64(o0[t], m), r1 = barrett64(o1[t], m);
+        if (h.accumulate) { r0 = addmod(r0, *p0, m.p); r1 = addmod(r1, *p1, m.p); } // the canonical words an earlier launch of this call stored
+        *p0 = r0;
+        *p1 = r1;
+    }
+}
+// What the giant sum accumulates onto, in the ciphertext's own form (NTT: through the index map; coefficient form: the gather of galois_coeff_kernel
+// with its sign):  base[b][0][j][n] (+)= sum_r sigma_r(u_r[b].c0)[j][n],  base[b][1][j][n] (+)= sum_{r: elt[r] == 1} u_r[b].c1[j][n]  mod q_j.
+// u_r[b] at u + r * u_rstride + b * u_bstride, [2][dl][N].  Grid x: coefficient windows, y: (polynomial, limb), z: batch item; at most 16 canonical
+// words below 2^60 per sum, in 64 bits.
+template <bool NTT> __global__ __launch_bounds__(EW_THREADS) void bsgs_base_kernel(const u64 *u, u64 u_rstride, u64 u_bstride, u64 *base, u64 base_bstride, KsArgs a, BsgsBaseArgs h) {
+    const u32 N = 1u << a.logn;
+    const u32 n = blockIdx.x * EW_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const u32 j = blockIdx.y % (u32)a.dl, poly = blockIdx.y / (u32)a.dl;
+    const Mod m = mod_of(a.primes[a.key_id[j]]);
+    for (u64 b = blockIdx.z; b < a.batch; b += gridDim.z) {
+        u64 sum = 0;
+        for (u32 r = 0; r < h.rots; r++) {
+            if (poly && h.elt[r] != 1) continue;
+            const u64 *row = u + r * u_rstride + b * u_bstride + ((u64)poly * a.dl + j) * N;
+            if (poly || h.elt[r] == 1) sum += row[n];
+            else if (NTT) sum += row[galois_ntt_index(n, h.elt[r], a.logn)];
+            else {
+                const u32 n0 = (n * h.elt_inv[r]) & (2 * N - 1);
+                const u64 v = row[n0 & (N - 1)];
+                sum += (n0 >> a.logn) ? negmod(v, m.p) : v;
+            }
+        }
+        u64 *o = base + b * base_bstride + ((u64)poly * a.dl + j) * N + n;
+        u64 res = barrett64(sum, m);
+        if (h.accumulate) res = addmod(res, *o, m.p);
+        *o = res;
+    }
+}
 // BFV (kind 0) / BGV (kind 2) mod-down, everything in coefficient form (evaluator.cpp:2528-2648):
 //   ct[b][k][j][n] += (acc_j - [t']_{q_j} + [half]_{q_j}) * qk^-1 mod q_j, t' = (acc_last + half) mod qk       (BFV)
 //   ct[b][k][j][n] += (acc_j - [acc_last]_{q_j} - [k_t]_{q_j} * qk) * qk^-1,  k_t = -acc_last * qk^-1 mod t     (BGV)
@@ -942,6 +1081,43 @@ void launch_hoist_lt_base(const u64 *c0, u64 c0_bstride, const u64 *c1, u64 c1_b
     const dim3 grid((unsigned)ceil_div((u64(1) << a.logn) / 4, EW_THREADS), (unsigned)(polys * a.dl), (unsigned)std::min<u64>(a.batch, 65535));
     TROY_LAUNCH(hoist_lt_base_kernel, grid, dim3(EW_THREADS), 0, s, c0, c0_bstride, c1, c1_bstride, c1_lstride, base, base_bstride, a, h);
     launch_check("hoist_lt_base_kernel");
+}
+void launch_bsgs_inner(const u64 *W, u64 *accU, const KsArgs &a, const BsgsInnerArgs &h, hipStream_t s) {
+    if (!h.rows || h.rows > BSGS_MAX_ROWS || !h.babies || h.babies > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "bsgs_inner: 1 .. 8 rows over 1 .. 16 babies of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rows; r++) {
+        if (h.mask[r] >> h.babies) throw Error(ST_LOGIC_ERROR, "bsgs_inner: a row names a baby the launch does not hold");
+        for (u32 j = 0; j < h.babies; j++)
+            if (((h.mask[r] >> j) & 1) && !h.pt[r][j]) throw Error(ST_LOGIC_ERROR, "bsgs_inner: every present pair takes a plaintext");
+    }
+    const u64 blocks = ceil_div((a.dl + 1) << a.logn, EW_THREADS) * a.batch * 2;
+    if (blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, "bsgs_inner: batch too large for one launch");
+    TROY_LAUNCH(bsgs_inner_kernel, dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, W, accU, a, h);
+    launch_check("bsgs_inner_kernel");
+}
+void launch_hoist_sum(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *acc, const KsArgs &a, const HoistSumArgs &h, hipStream_t s) {
+    if (a.dl >= 64) throw Error(ST_LOGIC_ERROR, "hoist_sum: more than 63 digits");
+    if (!h.rots || h.rots > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "hoist_sum: 1 .. 16 giants of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.key[r] || h.elt[r] == 1) throw Error(ST_LOGIC_ERROR, "hoist_sum: every giant takes a key; element 1 belongs to the base");
+    const bool rot4 = a.batch <= 2 && h.rots > 1; // as launch_hoist_mac
+    const u64 windows = ceil_div((a.dl + 1) << a.logn, EW_THREADS);
+    const u64 blocks = windows * (rot4 ? a.batch : (a.batch + 3) / 4);
+    if (blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, "hoist_sum: batch too large for one launch");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(hoist_sum_kernel<true>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(hoist_sum_kernel<false>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, D, ckks_target, t_bstride, acc, a, h);
+    launch_check("hoist_sum_kernel");
+}
+void launch_bsgs_base(bool ntt_form, const u64 *u, u64 u_rstride, u64 u_bstride, u64 *base, u64 base_bstride, const KsArgs &a, BsgsBaseArgs h, hipStream_t s) {
+    if (!h.rots || h.rots > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "bsgs_base: 1 .. 16 giants of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rots; r++) { // g^-1 mod 2N by Newton steps, as launch_galois
+        uint32_t inv = 1;
+        for (int it = 0; it < 5; it++) inv *= 2u - h.elt[r] * inv;
+        h.elt_inv[r] = inv & (uint32_t)((2u << a.logn) - 1);
+    }
+    const dim3 grid((unsigned)ceil_div(u64(1) << a.logn, EW_THREADS), (unsigned)(2 * a.dl), (unsigned)std::min<u64>(a.batch, 65535));
+    if (ntt_form) TROY_LAUNCH(HIP_KERNEL_NAME(bsgs_base_kernel<true>), grid, dim3(EW_THREADS), 0, s, u, u_rstride, u_bstride, base, base_bstride, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(bsgs_base_kernel<false>), grid, dim3(EW_THREADS), 0, s, u, u_rstride, u_bstride, base, base_bstride, a, h);
+    launch_check("bsgs_base_kernel");
 }
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s) {
     u64 total = a.batch * 2 * a.dl << a.logn;
