@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -315,6 +315,24 @@ int troyhip_multiply_plain_ntt(troyhip_context *ctx, troyhip_ct *ct, const uint6
  * (app/LinearHelperCKKS.cuh:227-248 MatmulHelper::matmul, :536-556 Conv2dHelper::conv2d): same residues, every operand read once. */
 int troyhip_multiply_plain_accumulate(troyhip_context *ctx, const troyhip_ct *const *cts, const uint64_t *const *plains, int count, double plain_scale, troyhip_ct *out,
                                       uint64_t batch, void *stream);
+/* Sum of ciphertext products, relinearized once (lazy relinearization and lazy scale-down; no reference counterpart):
+ *   out item i = sum_{r < count} a_descs[r] item i (x) b_descs[r] item i,   a size-3 ciphertext; ONE troyhip_relinearize (CKKS: and one rescale) follows.
+ * 1 <= count <= 16 pairs of batches of size-2 ciphertexts, all at one level, in the form troyhip_multiply takes for the scheme, `batch` items each.  An
+ * operand may repeat; a_descs[r] == b_descs[r] squares.  out_desc->data, ->batch_stride are INPUTS (room for three polynomials per item, sharing no word
+ * with an operand); the call sets size 3, limbs, form, scale (CKKS: a_0.scale * b_0.scale) and correction factor (BGV: a_0.cf * b_0.cf mod t).
+ * CKKS, BGV: byte for byte troyhip_multiply per pair followed by troyhip_add; every pair's scale product must pass troyhip_add's closeness test against
+ * pair 0's ("scale mismatch"), every BGV pair's correction-factor product must equal pair 0's ("correction factor mismatch").
+ * BFV: the integer tensors of the pairs are summed before ONE floor and ONE Shenoy-Kumaresan step -- not the sum of the products' limbs (which rounds
+ * count times); at count == 1 the limbs of troyhip_multiply.  The auxiliary base must hold count products: count <= troyhip_multiply_sum_max_terms,
+ * else "too many products for the auxiliary base".  The limbs do not depend on which auxiliary base is in use; the accepted count does.
+ * BGV / BFV keep the transformed operands of a chunk of pairs under scratch_limit_words (0: 2^28 words): as many pairs per chunk as fit, else runs of
+ * items with one pair per chunk; below one item with one pair the call is refused.  The result does not depend on the chunking.  Counter
+ * "mulsum_chunks" (troyhip_stat): chunks run so far.  Stream-ordered. */
+int troyhip_multiply_sum(troyhip_context *ctx, const troyhip_ct *const *a_descs, const troyhip_ct *const *b_descs, int count, troyhip_ct *out_desc, uint64_t batch,
+                         uint64_t scratch_limit_words, void *stream);
+/* the largest count troyhip_multiply_sum accepts at the level with `limbs` primes: 16 for CKKS and BGV; BFV: the largest R <= 16 with
+ * 32 + bits(t) + bits(q) + ceil(log2 R) < aux_bits * (|B| + 1), the reference's size rule for the auxiliary base with R products folded in */
+int troyhip_multiply_sum_max_terms(const troyhip_context *ctx, int limbs, int *out);
 /* ---- plaintext operands in coefficient form.  BFV/BGV: plain = plain_coeff_count coefficients mod t per item
  * (device memory); plain_batch_stride = words between the plaintexts of consecutive batch items, 0 = one plaintext for all. ---- */
 /* addPlainInplace / subPlainInplace (src/evaluator_cuda.cu:1654-1720, src/utils/scalingvariant_cuda.cu:21-176).

@@ -1842,6 +1842,34 @@ public:
     }
     void squareInplace(Ciphertext &a) const { multiplyInplace(a, a); }
     void square(const Ciphertext &a, Ciphertext &d) const { multiply(a, a, d); }
+    // Sum of products, relinearized once (troyhip_multiply_sum; the reference has no such call): dst = sum_r a[r] * b[r], size 3,
+    // 1 .. 16 pairs of size-2 ciphertexts of one level; a[r] may be b[r] (a square) and a ciphertext may appear in many pairs.  CKKS / BGV: limb for limb
+    // multiply + add.  BFV: one floor over the summed integer tensors, at most multiplySumMaxTerms() pairs.  innerProduct relinearizes the sum once.
+    void multiplySum(const std::vector<const Ciphertext *> &a, const std::vector<const Ciphertext *> &b, Ciphertext &dst) const {
+        if (a.empty() || a.size() != b.size() || a.size() > 16) throw std::invalid_argument("multiply_sum takes 1 to 16 products");
+        std::vector<const troyhip_ct *> pa(a.size()), pb(b.size());
+        for (size_t r = 0; r < a.size(); r++) {
+            if (!a[r] || !b[r]) throw std::invalid_argument("null ciphertext descriptor");
+            pa[r] = a[r]->raw();
+            pb[r] = b[r]->raw();
+        }
+        Ciphertext out;
+        out.resize(a[0]->polyModulusDegree(), a[0]->coeffModulusSize(), 3);
+        check(troyhip_multiply_sum(h(), pa.data(), pb.data(), (int)a.size(), out.raw(), 1, 0, nullptr));
+        out.bind(*a[0]);
+        dst = std::move(out);
+    }
+    void innerProduct(const std::vector<const Ciphertext *> &a, const std::vector<const Ciphertext *> &b, const RelinKeys &k, Ciphertext &dst) const {
+        Ciphertext sum;
+        multiplySum(a, b, sum);
+        relinearize(sum, k, dst);
+    }
+    // the largest number of pairs multiplySum accepts at the level with `limbs` primes (0: the first data level): 16, or what the BFV auxiliary base holds
+    int multiplySumMaxTerms(size_t limbs = 0) const {
+        int n = 0;
+        check(troyhip_multiply_sum_max_terms(h(), (int)(limbs ? limbs : c_.firstContextData()->parms().coeffModulus().size()), &n));
+        return n;
+    }
     void relinearizeInplace(Ciphertext &a, const RelinKeys &k) const { // to size 2 from any size <= 16 (src/evaluator_cuda.cu:703-744)
         const size_t need = a.size() > 2 ? a.size() - 2 : 0;
         std::vector<const uint64_t *> keys(need ? need : 1, nullptr);
@@ -2158,6 +2186,40 @@ public:
     std::vector<Ciphertext> multiplyBatch(const std::vector<Ciphertext> &a, const std::vector<Ciphertext> &b) const { return multiplyBatch(Ciphertext::pointers(a), Ciphertext::pointers(b)); }
     std::vector<Ciphertext> squareBatch(const std::vector<const Ciphertext *> &a) const { return multiplyBatch(a, a); }
     std::vector<Ciphertext> squareBatch(const std::vector<Ciphertext> &a) const { return squareBatch(Ciphertext::pointers(a)); }
+    // multiplySum / innerProduct over batches: a[r] and b[r] are runs of `count` slab members (allocateBatch / packBatch; anything else is packed first,
+    // a run that appears twice once); item i of the result = sum_r a[r][i] * b[r][i].  ONE library call for the whole batch.
+    std::vector<Ciphertext> multiplySumBatch(const std::vector<std::vector<const Ciphertext *>> &a, const std::vector<std::vector<const Ciphertext *>> &b) const {
+        if (a.empty() || a.size() != b.size() || a.size() > 16) throw std::invalid_argument("multiply_sum takes 1 to 16 products");
+        const size_t R = a.size(), count = a[0].size();
+        if (!count) return {};
+        std::vector<std::vector<Ciphertext>> packed;
+        packed.reserve(2 * R);
+        std::vector<std::pair<const std::vector<const Ciphertext *> *, troyhip_ct>> seen;
+        std::vector<troyhip_ct> views(2 * R);
+        std::vector<const troyhip_ct *> pa(R), pb(R);
+        for (size_t r = 0; r < 2 * R; r++) {
+            const std::vector<const Ciphertext *> &run = r < R ? a[r] : b[r - R];
+            if (run.size() != count) throw std::invalid_argument("multiplySumBatch: operand counts differ");
+            bool found = false;
+            for (auto &s : seen)
+                if (*s.first == run) { views[r] = s.second; found = true; break; }
+            if (!found) {
+                packed.emplace_back();
+                views[r] = runOf(run, packed.back());
+                seen.emplace_back(&run, views[r]);
+            }
+            (r < R ? pa[r] : pb[r - R]) = &views[r];
+        }
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(count, *a[0][0], 3, a[0][0]->coeffModulusSize());
+        troyhip_ct t = *out[0].raw();
+        check(troyhip_multiply_sum(h(), pa.data(), pb.data(), (int)R, &t, count, 0, nullptr));
+        for (auto &c : out) c.copyMeta(t);
+        return out;
+    }
+    std::vector<Ciphertext> innerProductBatch(const std::vector<std::vector<const Ciphertext *>> &a, const std::vector<std::vector<const Ciphertext *>> &b, const RelinKeys &k) const {
+        const std::vector<Ciphertext> sum = multiplySumBatch(a, b);
+        return relinearizeBatch(Ciphertext::pointers(sum), k);
+    }
     void multiplyInplaceBatch(const std::vector<Ciphertext *> &a, const std::vector<const Ciphertext *> &b) const {
         std::vector<Ciphertext> out = multiplyBatch(std::vector<const Ciphertext *>(a.begin(), a.end()), b);
         for (size_t i = 0; i < a.size(); i++) *a[i] = std::move(out[i]);

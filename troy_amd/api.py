@@ -453,6 +453,35 @@ class Evaluator:
         a.__dict__.update(out.__dict__)
         return a
 
+    # -- sum of products, relinearized once (troyhip_multiply_sum: no reference counterpart)
+    def multiplySum(self, as_, bs, scratch_limit_words=0):
+        """sum_r as_[r] (x) bs[r] as ONE size-3 batch: 1 .. 16 pairs of size-2 batches of one level and item count; operands may repeat, as_[r] may be
+        bs[r] (a square).  CKKS / BGV: byte for byte multiply per pair + add.  BFV: one floor over the summed integer tensors; at most
+        multiplySumMaxTerms() pairs.  relinearizeInplace (CKKS: then rescaleToNext) follows once: innerProduct."""
+        if not 1 <= len(as_) <= 16 or len(as_) != len(bs):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "multiply_sum takes 1 to 16 products")
+        a0 = as_[0]
+        out = Ciphertext(a0.context, a0.batch, 3, a0.limbs, capacity=3)
+        sa, sb = [a.struct() for a in as_], [b.struct() for b in bs]
+        pa = (C.POINTER(CtStruct) * len(sa))(*[C.pointer(st) for st in sa])
+        pb = (C.POINTER(CtStruct) * len(sb))(*[C.pointer(st) for st in sb])
+        so = out.struct()
+        self._chk(self.lib.troyhip_multiply_sum(self.context.h, pa, pb, len(sa), C.byref(so), C.c_uint64(a0.batch), C.c_uint64(scratch_limit_words), self.stream))
+        out._absorb(so)
+        return out
+
+    def innerProduct(self, as_, bs, relin_keys):
+        """sum_r as_[r] * bs[r], size 2: multiplySum and ONE relinearization"""
+        out = self.multiplySum(as_, bs)
+        self.relinearizeInplace(out, relin_keys)
+        return out
+
+    def multiplySumMaxTerms(self, limbs=None):
+        """the largest number of pairs multiplySum accepts at the level with `limbs` primes (default: the first data level)"""
+        n = C.c_int(0)
+        self._chk(self.lib.troyhip_multiply_sum_max_terms(self.context.h, self.context.first_limbs if limbs is None else limbs, C.byref(n)))
+        return n.value
+
     def square(self, a):
         return self.multiply(a, a)
 

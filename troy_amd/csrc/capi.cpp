@@ -898,6 +898,26 @@ int troyhip_multiply_plain_accumulate(troyhip_context *ctx, const troyhip_ct *co
         store(o, out);
     });
 }
+int troyhip_multiply_sum(troyhip_context *ctx, const troyhip_ct *const *a_descs, const troyhip_ct *const *b_descs, int count, troyhip_ct *out_desc, uint64_t batch,
+                         uint64_t scratch_limit_words, void *stream) {
+    return guard([&] {
+        if (!a_descs || !b_descs || count < 1 || count > 16) throw Error(ST_INVALID_ARGUMENT, "multiply_sum takes 1 to 16 products");
+        if (!out_desc) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx); // the context is bound before the stream is looked at: argument evaluation order is unspecified
+        hipStream_t s = on(stream);
+        CtBatch va[16], vb[16];
+        for (int i = 0; i < count; i++) { va[i] = view(a_descs[i]); vb[i] = view(b_descs[i]); }
+        CtBatch o = view(out_desc);
+        handle->ev.multiply_sum(va, vb, count, o, batch, scratch_limit_words, s);
+        store(o, out_desc);
+    });
+}
+int troyhip_multiply_sum_max_terms(const troyhip_context *ctx, int limbs, int *out) {
+    return guard([&] {
+        if (!out) throw Error(ST_INVALID_ARGUMENT, "null");
+        *out = need(ctx)->ev.multiply_sum_max_terms(limbs);
+    }, false);
+}
 int troyhip_add_plain(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *plain, uint64_t plain_coeff_count, uint64_t plain_batch_stride, double plain_scale,
                       int subtract, uint64_t batch, void *stream) {
     return guard([&] {

@@ -1097,6 +1097,154 @@ void Evaluator::multiply_plain_accumulate(const CtBatch *cts, const u64 *const *
     out.size = a0.size; out.limbs = a0.limbs; out.ntt = true; out.scale = new_scale; out.cf = a0.cf;
 }
 
+// Sum of ciphertext products, relinearized once by the caller (no reference counterpart): out = sum_r a_r (x) b_r, size 3.
+// CKKS and BGV: byte for byte what multiply per pair and add give (exact arithmetic, a linear transform).  BFV: the integer tensors of the pairs are
+// summed BEFORE the one floor and the one Shenoy-Kumaresan step (hostmath.cpp above RnsLevel::build: D = sum_r D_r, F = floor(t D / q) - alpha').
+// The auxiliary base holds the reference's margin for ONE product; R of them need ceil(log2 R) more bits: multiply_sum_max_terms.
+// Scratch of BGV / BFV, per item of a run, in words (mw = N (limbs + |Bsk|), BGV: |Bsk| = 0): 3 mw [the sums] + pairs per chunk x 4 mw [the transformed
+// operands].  A run is the whole batch with as many pairs per chunk as fit, or -- where one pair of the whole batch does not fit -- a run of items
+// with one pair per chunk; later chunks accumulate.  Below one item with one pair the call is refused.
+int Evaluator::multiply_sum_max_terms(int limbs) const {
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (c.scheme != SCHEME_BFV) return TENSOR_SUM_MAX;
+    const host::RnsLevel &r = c.level(limbs).rns;
+    const int t_bits = c.t ? 64 - __builtin_clzll(c.t) : 0;
+    const int need = 32 + t_bits + host::bit_length_of_product(r.q), room = r.aux_bits * ((int)r.B.size() + 1);
+    int terms = 1; // need < room by RnsLevel::build; R is accepted while need + ceil(log2 R) < room
+    while (terms < TENSOR_SUM_MAX && need + (32 - __builtin_clz((unsigned)(2 * terms - 1))) < room) terms *= 2;
+    return terms;
+}
+size_t Evaluator::scratch_multiply_sum(int limbs, int count, u64 batch) const {
+    if (c.scheme == SCHEME_CKKS) return (size_t)batch * 3 * c.N * limbs + 64;
+    const size_t mw = (size_t)c.N * (limbs + (c.scheme == SCHEME_BFV ? c.level(limbs).rns.Bsk.size() : 0));
+    return (size_t)batch * mw * (3 + 4 * (size_t)count) + 32 * 8 + 128;
+}
+void Evaluator::multiply_sum(const CtBatch *as, const CtBatch *bs_, int count, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    if (count < 1 || count > TENSOR_SUM_MAX || !as || !bs_) throw Error(ST_INVALID_ARGUMENT, "multiply_sum takes 1 to 16 products");
+    const int L = as[0].limbs;
+    const u64 N = c.N, pw = poly_words(c, L);
+    double scale0 = 1.0;
+    u64 cf0 = 1;
+    for (int r = 0; r < count; r++) {
+        const CtBatch &a = as[r], &b = bs_[r];
+        check_ct(a);
+        check_ct(b);
+        if (a.size != 2 || b.size != 2) throw Error(ST_INVALID_ARGUMENT, "multiply_sum takes size-2 operands");
+        if (a.limbs != L || b.limbs != L) throw Error(ST_INVALID_ARGUMENT, "encrypted1 and encrypted2 parameter mismatch");
+        if (c.scheme == SCHEME_BFV && (a.ntt || b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
+        if (c.scheme == SCHEME_CKKS && !(a.ntt && b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
+        if (c.scheme == SCHEME_BGV && (a.ntt || b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
+        if (c.scheme == SCHEME_CKKS) { // what multiply says of the pair, then what add says of its product against pair 0's
+            const double sc = a.scale * b.scale;
+            if (!scale_ok(sc, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+            if (!r) scale0 = sc;
+            else if (!(sc == scale0 || std::fabs(scale0 - sc) < std::ldexp(std::max(std::fabs(scale0), 1.0), -40))) throw Error(ST_INVALID_ARGUMENT, "scale mismatch");
+        } else if (c.scheme == SCHEME_BGV) {
+            const u64 cf = host::mul_mod(a.cf % c.t, b.cf % c.t, c.t);
+            if (!r) cf0 = cf;
+            else if (cf != cf0) throw Error(ST_INVALID_ARGUMENT, "correction factor mismatch");
+        }
+    }
+    if (c.scheme == SCHEME_BFV && count > multiply_sum_max_terms(L)) throw Error(ST_INVALID_ARGUMENT, "too many products for the auxiliary base");
+    if (!out.data || out.bstride < 3 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    if (batch)
+        for (int r = 0; r < 2 * count; r++) { // every pair reads its operands whole: the destination must not share a word with any of them
+            const CtBatch &x = r < count ? as[r] : bs_[r - count];
+            const u64 *x_end = x.data + (batch - 1) * x.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 3 * pw;
+            if (out.data < x_end && x.data < out_end) throw Error(ST_INVALID_ARGUMENT, "the destination cannot be one of the operands");
+        }
+    out.size = 3; out.limbs = L; out.ntt = as[0].ntt; out.scale = c.scheme == SCHEME_CKKS ? scale0 : as[0].scale; out.cf = c.scheme == SCHEME_BGV ? cf0 : as[0].cf;
+    if (!batch) return;
+    const LimbMap qmap = c.ct_map(L);
+    auto dense = [](u64 items, u64 bstride, u64 words) { return items == 1 || bstride == words; }; // one item has no stride
+    TensorSumArgs t;
+    if (c.scheme == SCHEME_CKKS) { // one launch straight from the operands, strides and all
+        std::memset(&t, 0, sizeof(t));
+        t.count = count;
+        for (int r = 0; r < count; r++) { t.a[r] = as[r].data; t.a_bstride[r] = as[r].bstride; t.b[r] = bs_[r].data; t.b_bstride[r] = bs_[r].bstride; }
+        if (dense(batch, out.bstride, 3 * pw)) launch_tensor_sum(t, out.data, 3 * pw, c.d_desc, qmap, c.logn, L, batch, s);
+        else {
+            c.arena.begin(s);
+            c.arena.reserve(scratch_multiply_sum(L, count, batch));
+            u64 *d = c.arena.take(batch * 3 * pw);
+            launch_tensor_sum(t, d, 3 * pw, c.d_desc, qmap, c.logn, L, batch, s);
+            launch_copy_strided(d, 3 * pw, out.data, out.bstride, 3 * pw, batch, s);
+        }
+        stats::counter(stats::MULSUM_CHUNKS)++;
+        return;
+    }
+    const bool bfv = c.scheme == SCHEME_BFV;
+    const Level *lv = bfv ? &c.level(L) : nullptr;
+    const u64 nbk = bfv ? lv->rns.Bsk.size() : 0, bw = nbk * N, mw = pw + bw;
+    const LimbMap bmap = bfv ? c.ids_map(lv->bsk_ids) : qmap;
+    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
+    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
+    // a pair is budgeted its two operands (4 mw) even where the chunk transforms an operand once (a square, a vector shared by every pair): such calls
+    // may run in more chunks than their scratch needs -- conservative, and the plan depends on the counts alone, not on which buffers repeat
+    const u64 per_item = 3 * mw, per_pair_item = 4 * mw;
+    if (per_item + per_pair_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one product of one ciphertext");
+    u64 bs = batch, pc = 1;
+    if (batch * (per_item + per_pair_item) + slack <= limit) pc = std::min<u64>((u64)count, (limit - slack - batch * per_item) / (batch * per_pair_item));
+    else bs = (limit - slack) / (per_item + per_pair_item);
+
+    c.arena.begin(s);
+    c.arena.reserve(bs * per_item + pc * bs * per_pair_item + slack);
+    u64 *xq = c.arena.take(pc * bs * 4 * pw), *xb = bfv ? c.arena.take(pc * bs * 4 * bw) : nullptr;
+    u64 *dq = c.arena.take(bs * 3 * pw), *db = bfv ? c.arena.take(bs * 3 * bw) : nullptr;
+    for (u64 i0 = 0; i0 < batch; i0 += bs) {
+        const u64 ni = std::min(bs, batch - i0);
+        u64 *o = out.data + i0 * out.bstride;
+        const bool dense_out = dense(ni, out.bstride, 3 * pw);
+        u64 *d = !bfv && dense_out ? o : dq; // BGV: a dense destination holds the sums themselves
+        for (int r0 = 0; r0 < count; r0 += (int)pc) {
+            const int pn = std::min<int>((int)pc, count - r0);
+            // the operands of the chunk, each transformed once however often it appears (a square, a vector shared by the rows of a matrix)
+            std::vector<const CtBatch *> slots;
+            auto slot_of = [&](const CtBatch &x) -> u64 {
+                for (size_t k = 0; k < slots.size(); k++)
+                    if (slots[k]->data == x.data && slots[k]->bstride == x.bstride) return k;
+                const u64 k = slots.size();
+                slots.push_back(&x);
+                const u64 *src = x.data + i0 * x.bstride;
+                u64 *x_q = xq + k * ni * 2 * pw;
+                const bool in_place = dense(ni, x.bstride, 2 * pw); // consumed where it lies: the extension and the out-of-place transform read it
+                if (!in_place) launch_copy_strided(src, x.bstride, x_q, 2 * pw, 2 * pw, ni, s);
+                if (bfv) launch_behz_extend(in_place ? src : x_q, pw, xb + k * ni * 2 * bw, bw, c.d_desc, *lv->behz, N, ni * 2, s);
+                if (in_place) launch_ntt_from(x_q, src, c.d_desc, qmap, ni * 2 * L, c.logn, s);
+                else launch_ntt(x_q, c.d_desc, qmap, ni * 2 * L, c.logn, false, s);
+                return k;
+            };
+            TensorSumArgs tb;
+            std::memset(&t, 0, sizeof(t));
+            t.count = pn;
+            t.accumulate = r0 ? 1 : 0;
+            tb = t;
+            for (int j = 0; j < pn; j++) {
+                const u64 ka = slot_of(as[r0 + j]), kb = slot_of(bs_[r0 + j]);
+                t.a[j] = xq + ka * ni * 2 * pw; t.b[j] = xq + kb * ni * 2 * pw; t.a_bstride[j] = t.b_bstride[j] = 2 * pw;
+                if (bfv) { tb.a[j] = xb + ka * ni * 2 * bw; tb.b[j] = xb + kb * ni * 2 * bw; tb.a_bstride[j] = tb.b_bstride[j] = 2 * bw; }
+            }
+            if (bfv) launch_ntt(xb, c.d_desc, bmap, slots.size() * ni * 2 * nbk, c.logn, false, s); // the extensions of the chunk lie back to back
+            launch_tensor_sum(t, d, 3 * pw, c.d_desc, qmap, c.logn, L, ni, s);
+            if (bfv) launch_tensor_sum(tb, db, 3 * bw, c.d_desc, bmap, c.logn, nbk, ni, s);
+            stats::counter(stats::MULSUM_CHUNKS)++;
+        }
+        if (bfv) {
+            // ONE inverse transform (the factors of the floor step ride on its N^-1 constants where the floor kernel takes pre-scaled inputs), ONE floor
+            // and Shenoy-Kumaresan step, exactly as multiply runs them
+            const PrimeDesc *idesc = behz_floor_prescaled(*lv->behz) ? lv->behz->floor_desc : c.d_desc;
+            launch_ntt(dq, idesc, qmap, ni * 3 * L, c.logn, true, s);
+            launch_ntt(db, idesc, bmap, ni * 3 * nbk, c.logn, true, s);
+            u64 *res = dense_out ? o : xq; // the transformed operands are dead by now, and larger
+            launch_behz_floor_sk(dq, pw, db, bw, res, pw, c.d_desc, *lv->behz, N, ni * 3, s);
+            if (!dense_out) launch_copy_strided(res, 3 * pw, o, out.bstride, 3 * pw, ni, s);
+        } else {
+            launch_ntt(d, c.d_desc, qmap, ni * 3 * L, c.logn, true, s);
+            if (!dense_out) launch_copy_strided(d, 3 * pw, o, out.bstride, 3 * pw, ni, s);
+        }
+    }
+}
+
 // ---- plaintext operands ----
 static PlainArgs plain_args(Context &c, int limbs, u64 n_coeffs, u64 plain_bstride, u64 items, u64 cf) {
     if (limbs < 1 || limbs > c.K) throw Error(ST_INVALID_ARGUMENT, "parms_id is not valid for the current context");

@@ -92,8 +92,16 @@ public:
     // out = sum_i cts[i] (x) plains[i]: the multiplyPlain + addInplace loop of a linear layer as one pass (NTT-form operands of one level)
     void multiply_plain_accumulate(const CtBatch *cts, const u64 *const *plains, int count, double plain_scale, CtBatch &out, u64 batch, hipStream_t s);
 
+    // out = sum_r as[r] (x) bs[r], 1 <= count <= 16 pairs of size-2 batches of one level, size 3: lazy relinearization (and for BFV ONE floor and
+    // Shenoy-Kumaresan step over the summed integer tensors).  out.data / out.bstride are the caller's (three polynomials per item, none of the
+    // operands).  CKKS / BGV: byte for byte multiply per pair + add.  BFV: count <= multiply_sum_max_terms(limbs).  BGV / BFV hold the transformed
+    // operands of a chunk of pairs under scratch_limit_words (0: 2^28 words); the result does not depend on the chunking.  DESIGN.md section 4.13.
+    void multiply_sum(const CtBatch *as, const CtBatch *bs, int count, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    int multiply_sum_max_terms(int limbs) const; // the largest count multiply_sum accepts at a level: 16, or what the BFV auxiliary base holds
+
     // scratch words needed by the ops (so callers can pre-reserve outside timed regions)
     size_t scratch_multiply(int sa, int sb, int limbs, u64 batch) const;
+    size_t scratch_multiply_sum(int limbs, int count, u64 batch) const; // with every pair in one chunk
     size_t scratch_switch_key(int limbs, u64 batch) const;
 
 private:

@@ -149,6 +149,12 @@ void launch_add_plain(int kind, bool sub, u64 *ct0, u64 ct_bstride, const u64 *p
 void launch_plain_lift(const u64 *plain, u64 *lifted, const PlainArgs &a, hipStream_t s);
 void launch_tensor(int s1, int s2, const u64 *a, const u64 *b, u64 *out, u64 a_bstride, u64 b_bstride, const PrimeDesc *primes, const LimbMap &map,
                    int logn, u64 limbs, u64 batch, hipStream_t s);
+// sum of `count` <= 16 tensors of size-2 operands in one pass: out[b][k][l][n] = sum_r sum_{i+j=k} a_r[b][i][l][n] b_r[b][j][l][n] mod p_l,
+// k = 0 .. 2.  Operand r of item b at a[r] + b * a_bstride[r], [2][limbs][N], CANONICAL residues; out item b at out + b * out_bstride, [3][limbs][N].
+// accumulate != 0: the reduced sums are added to the canonical words `out` holds (a later chunk of pairs).
+enum { TENSOR_SUM_MAX = 16 };
+struct TensorSumArgs { const u64 *a[TENSOR_SUM_MAX]; const u64 *b[TENSOR_SUM_MAX]; u64 a_bstride[TENSOR_SUM_MAX]; u64 b_bstride[TENSOR_SUM_MAX]; int count, accumulate; };
+void launch_tensor_sum(const TensorSumArgs &x, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 batch, hipStream_t s);
 void launch_galois(bool ntt_form, const u64 *in, u64 in_bstride, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, uint32_t elt, u64 limbs,
                    u64 batch, hipStream_t s);
 

@@ -322,6 +322,70 @@ void launch_tensor(int s1, int s2, const u64 *a, const u64 *b, u64 *out, u64 a_b
     launch_check("tensor_any_kernel");
 }
 
+// Sum of up to 16 tensors of size-2 operands, one pass: out[b][k][l][n] = sum_r sum_{i+j=k} a_r[b][i][l][n] b_r[b][j][l][n] mod p_l.
+// tensor_kernel's mapping (x: pairs of coefficients of a row, y: limb, z: item, a stride loop beyond 65535 items; two coefficients = 16 bytes per thread,
+// every index from the block id).  The operand pointers and strides are kernel arguments (workgroup-uniform: scalar loads).  A thread keeps the three
+// outputs of its two coefficients in six 128-bit sums, walks the pairs loading a_r[0], a_r[1], b_r[0], b_r[1] (four independent 16-byte loads per pair),
+// reduces each sum ONCE and stores 16 bytes per output: no atomics, every operand word read once, every output word written once.
+// Bound: the operands are CANONICAL residues (ciphertext limbs as every call of the library stores them; the stores of the forward transforms:
+// ntt.hip, ntt1.hip and the FINAL store of ntt2.hip reduce to [0, p)) of primes below 2^61, so a product is below 2^122; the middle output holds
+// 2 count <= 32 of them: below 2^127.  barrett128 returns the canonical residue of ANY 128-bit value (its quotient is floor(x floor(2^128 / p) / 2^128)
+// exactly, at most one short of floor(x / p)).
+// accumulate: a later chunk of pairs adds its reduced sum to the canonical word an earlier chunk stored (addmod), as bsgs_inner_kernel does.
+__global__ __launch_bounds__(EW_THREADS) void tensor_sum_kernel(TensorSumArgs x, u64 *out, u64 out_bstride, const PrimeDesc *primes, LimbMap map, int logn, u32 limbs, u32 batch) {
+    const u32 n = (blockIdx.x * EW_THREADS + threadIdx.x) * 2; // two coefficients (16 bytes) per thread
+    const u64 N = u64(1) << logn;
+    if (n >= N) return;
+    const u32 l = blockIdx.y;
+    const Mod m = mod_of(primes[map.id[l]]);
+    const u64 o0 = (u64)l * N + n, o1 = ((u64)limbs + l) * N + n; // polynomial 0 and 1 of an operand
+    for (u32 bb = blockIdx.z; bb < batch; bb += gridDim.z) {
+        U128 s[3][2];
+#pragma unroll
+        for (int d = 0; d < 3; d++) s[d][0] = s[d][1] = U128{0, 0};
+        for (int r = 0; r < x.count; r++) {
+            const u64 *pa = x.a[r] + (u64)bb * x.a_bstride[r], *pb = x.b[r] + (u64)bb * x.b_bstride[r];
+            const ulonglong2 a0 = *reinterpret_cast<const ulonglong2 *>(pa + o0), a1 = *reinterpret_cast<const ulonglong2 *>(pa + o1);
+            const ulonglong2 b0 = *reinterpret_cast<const ulonglong2 *>(pb + o0), b1 = *reinterpret_cast<const ulonglong2 *>(pb + o1);
+            mac128(s[0][0], a0.x, b0.x);
+            mac128(s[0][1], a0.y, b0.y);
+            mac128(s[1][0], a0.x, b1.x);
+            mac128(s[1][1], a0.y, b1.y);
+            mac128(s[1][0], a1.x, b0.x);
+            mac128(s[1][1], a1.y, b0.y);
+            mac128(s[2][0], a1.x, b1.x);
+            mac128(s[2][1], a1.y, b1.y);
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            u64 *o = out + (u64)bb * out_bstride + ((u64)d * limbs + l) * N + n;
+            ulonglong2 v;
+            v.x = barrett128(s[d][0].lo, s[d][0].hi, m);
+            v.y = barrett128(s[d][1].lo, s[d][1].hi, m);
+            if (x.accumulate) {
+                const ulonglong2 old = *reinterpret_cast<const ulonglong2 *>(o);
+                v.x = addmod(old.x, v.x, m.p);
+                v.y = addmod(old.y, v.y, m.p);
+            }
+            *reinterpret_cast<ulonglong2 *>(o) = v;
+        }
+    }
+}
+void launch_tensor_sum(const TensorSumArgs &x, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 batch, hipStream_t s) {
+    if (!batch || !limbs) return;
+    if (logn < 1) throw Error(ST_LOGIC_ERROR, "tensor_sum: N < 2");
+    if (x.count < 1 || x.count > TENSOR_SUM_MAX || limbs > 65535 || !out || (batch > 1 && out_bstride < (3 * limbs << logn))) throw Error(ST_LOGIC_ERROR, "tensor_sum: 1 .. 16 pairs, a destination of three polynomials");
+    for (int r = 0; r < x.count; r++)
+        if (!x.a[r] || !x.b[r] || (batch > 1 && (x.a_bstride[r] < (2 * limbs << logn) || x.b_bstride[r] < (2 * limbs << logn)))) throw Error(ST_LOGIC_ERROR, "tensor_sum: every pair takes two size-2 operands");
+    // two coefficients per 16-byte access: an item must start on an even word (the strides of a caller's CKKS batches arrive here as they are)
+    bool odd = batch > 1 && (out_bstride & 1);
+    for (int r = 0; r < x.count; r++) odd = odd || (batch > 1 && ((x.a_bstride[r] | x.b_bstride[r]) & 1));
+    if (odd) throw Error(ST_INVALID_ARGUMENT, "multiply_sum: batch strides must be even");
+    const dim3 grid((unsigned)ceil_div((u64(1) << logn) / 2, EW_THREADS), (unsigned)limbs, (unsigned)std::min<u64>(batch, 65535));
+    TROY_LAUNCH(tensor_sum_kernel, grid, dim3(EW_THREADS), 0, s, x, out, out_bstride, primes, map, logn, (u32)limbs, (u32)batch);
+    launch_check("tensor_sum_kernel");
+}
+
 // ---------------------------------------------------------------- Galois (a-6 / A.11)
 // coefficient form: out[(i*g) mod N] = +-in[i]   (src/utils/galois.cpp:143-162).  One launch covers `batch` items of `limbs` rows
 // each; item b reads in + b * in_bstride and writes out + b * out_bstride.
