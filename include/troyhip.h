@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -333,6 +333,32 @@ int troyhip_multiply_sum(troyhip_context *ctx, const troyhip_ct *const *a_descs,
 /* the largest count troyhip_multiply_sum accepts at the level with `limbs` primes: 16 for CKKS and BGV; BFV: the largest R <= 16 with
  * 32 + bits(t) + bits(q) + ceil(log2 R) < aux_bits * (|B| + 1), the reference's size rule for the auxiliary base with R products folded in */
 int troyhip_multiply_sum_max_terms(const troyhip_context *ctx, int limbs, int *out);
+/* Sum of scalar multiples of ciphertexts plus a constant polynomial, one pass over every operand, no plaintext streams (no reference counterpart; DESIGN.md
+ * section 4.14):   out item i = sum_{r < count} scalars[r] * cts[r] item i + constant.
+ * 1 <= count <= 16 operands of ONE size (1 .. 16) and ONE form.  out->limbs is an INPUT, as are out->data and out->batch_stride: BFV / BGV operands have
+ * exactly out->limbs limbs, CKKS operands at least that many (their leading out->limbs rows are read where they lie: CKKS modSwitchToNext is a drop).
+ * scalars: HOST words [count][out->limbs], the residue of scalar r modulo prime l at scalars[r * out->limbs + l]; constant: HOST words [out->limbs] or NULL, the
+ * residues of the constant coefficient (NTT form: of every value).  Every word must be below its prime ("scalar is not reduced modulo its prime").  The
+ * destination shares no word with an operand.  The call sets size, form, scale = out_scale and correction factor = out_cf: at this level the caller owns their
+ * meaning.  Stream-ordered: the words are copied before the call returns and uploaded on the stream.  Counter "poly_scalar_sums". */
+int troyhip_scalar_combine(troyhip_context *ctx, const troyhip_ct *const *cts, const uint64_t *scalars, const uint64_t *constant, int count, troyhip_ct *out, double out_scale,
+                           uint64_t out_cf, uint64_t batch, void *stream);
+/* p(x) = c_0 + c_1 x + .. + c_degree x^degree slot-wise on a batch of size-2 ciphertexts in the form troyhip_multiply takes, by Paterson-Stockmeyer (DESIGN.md
+ * section 4.14): k = baby_steps (a power of two in 2 .. 16; 0: the smallest with k^2 >= degree + 1), m = ceil((degree + 1) / k) <= 17 blocks, 1 <= degree <= 255.
+ * Powers x^j = x^ceil(j/2) x^floor(j/2) (j <= k) and X^i = X^ceil(i/2) X^floor(i/2), X = x^k, each multiply -> relinearize -> level step (CKKS rescale, BGV
+ * mod switch, BFV none), only those a nonzero coefficient needs; every block u_i = sum_j c_(ik+j) x^j is ONE scalar sum; result = u_0 + relinearize(sum_(i>=1)
+ * u_i (x) X^i) through ONE troyhip_multiply_sum (BFV: chunks of troyhip_multiply_sum_max_terms pairs, added at size 3) and ONE relinearization, then the level step.
+ * coeffs_mod_t: degree + 1 HOST words below t (BFV, BGV; coeffs NULL).  coeffs: degree + 1 HOST doubles, real coefficients only (CKKS; coeffs_mod_t NULL).
+ * Scales and correction factors are absorbed in the scalars.  CKKS: the result's scale is exactly out_scale (0: in->scale); a scalar is round(c * target scale
+ * / scale(x^j)), and a plan in which that ratio falls below 2^20 is refused ("scale too small for the coefficients").  BGV: any operand correction factor.
+ * The constants are added as troyhip_add_plain adds a constant polynomial.  out->data, ->batch_stride are INPUTS (two polynomials per item at the result's
+ * level: in->limbs - depth, BFV in->limbs; troyhip_polynomial_depth).  Intermediates come from the caching pool (troyhip_malloc's) and go back stream-ordered.
+ * scratch_limit_words is handed to troyhip_multiply_sum.  Counters "poly_products" (power products and pairs of the sum), "poly_relins", "poly_scalar_sums". */
+int troyhip_evaluate_polynomial(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint64_t *coeffs_mod_t, const double *coeffs, int degree, int baby_steps,
+                                double out_scale, const uint64_t *relin_key, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* the plan of troyhip_evaluate_polynomial, a host-only function of (degree, baby_steps): *levels = primes consumed (CKKS, BGV; BFV: 0), *baby_steps_used = k.
+ * With lb = ceil(log2 min(degree, k - 1)): m == 1: lb + 1; else max(lb + 1, log2 k + ceil(log2(m - 1))) + 1.  Either pointer may be NULL. */
+int troyhip_polynomial_depth(const troyhip_context *ctx, int degree, int baby_steps, int *levels, int *baby_steps_used);
 /* ---- plaintext operands in coefficient form.  BFV/BGV: plain = plain_coeff_count coefficients mod t per item
  * (device memory); plain_batch_stride = words between the plaintexts of consecutive batch items, 0 = one plaintext for all. ---- */
 /* addPlainInplace / subPlainInplace (src/evaluator_cuda.cu:1654-1720, src/utils/scalingvariant_cuda.cu:21-176).

@@ -1870,6 +1870,37 @@ public:
         check(troyhip_multiply_sum_max_terms(h(), (int)(limbs ? limbs : c_.firstContextData()->parms().coeffModulus().size()), &n));
         return n;
     }
+    // Scalar sums and polynomial evaluation (troyhip_scalar_combine, troyhip_evaluate_polynomial; the reference has no such calls).
+    // linearCombination: dst = sum_r weights[r] * cts[r] (+ constant) in ONE pass over 1 .. 16 ciphertexts of one size, level and form, no plaintext
+    // streams.  BFV / BGV: integers mod t (lifted centered; the constant as addPlain adds a constant polynomial), equal correction factors.  CKKS: doubles,
+    // applied as round(w * weight_scale); equal scales; dst.scale() = ct.scale() * weight_scale.
+    void linearCombination(const std::vector<const Ciphertext *> &cts, const std::vector<uint64_t> &weights, Ciphertext &dst, const uint64_t *constant = nullptr) const {
+        need(SchemeType::ckks, false);
+        const ScalarTable t = scalarTable(cts, weights.size(), [&](size_t r) { return weights[r]; }, constant, nullptr, nullptr, 0.0);
+        combine(cts, t, dst);
+    }
+    void linearCombination(const std::vector<const Ciphertext *> &cts, const std::vector<double> &weights, double weight_scale, Ciphertext &dst, const double *constant = nullptr) const {
+        need(SchemeType::ckks, true);
+        const ScalarTable t = scalarTable(cts, weights.size(), [](size_t) { return uint64_t(0); }, nullptr, weights.data(), constant, weight_scale);
+        combine(cts, t, dst);
+    }
+    // evaluatePolynomial: dst = p(a) slot-wise, p = coeffs[0] + coeffs[1] x + .. by Paterson-Stockmeyer: shared powers, one scalar sum per giant block, ONE
+    // multiplySum and ONE relinearization for all block x giant-power products.  baby_steps: a power of two in 2 .. 16, 0 = the smallest k with
+    // k^2 >= degree + 1.  The result lies polynomialDepth(degree) levels below a (BFV: at its level); CKKS: its scale is exactly out_scale (0: a.scale()).
+    void evaluatePolynomial(const Ciphertext &a, const std::vector<uint64_t> &coeffs, const RelinKeys &k, Ciphertext &dst, int baby_steps = 0) const {
+        need(SchemeType::ckks, false);
+        polynomial(a, coeffs.data(), nullptr, coeffs.size(), k, dst, baby_steps, 0.0);
+    }
+    void evaluatePolynomial(const Ciphertext &a, const std::vector<double> &coeffs, const RelinKeys &k, Ciphertext &dst, int baby_steps = 0, double out_scale = 0.0) const {
+        need(SchemeType::ckks, true);
+        polynomial(a, nullptr, coeffs.data(), coeffs.size(), k, dst, baby_steps, out_scale);
+    }
+    // levels evaluatePolynomial consumes (BFV: 0), a function of (degree, baby_steps) alone; *baby_steps_used: the k in use
+    int polynomialDepth(int degree, int baby_steps = 0, int *baby_steps_used = nullptr) const {
+        int levels = 0;
+        check(troyhip_polynomial_depth(h(), degree, baby_steps, &levels, baby_steps_used));
+        return levels;
+    }
     void relinearizeInplace(Ciphertext &a, const RelinKeys &k) const { // to size 2 from any size <= 16 (src/evaluator_cuda.cu:703-744)
         const size_t need = a.size() > 2 ? a.size() - 2 : 0;
         std::vector<const uint64_t *> keys(need ? need : 1, nullptr);
@@ -2220,6 +2251,32 @@ public:
         const std::vector<Ciphertext> sum = multiplySumBatch(a, b);
         return relinearizeBatch(Ciphertext::pointers(sum), k);
     }
+    // linearCombination / evaluatePolynomial over batches: cts[r] is a run of `count` slab members (anything else is packed first); item i of the result =
+    // sum_r weights[r] * cts[r][i] (+ constant).  ONE library call for the whole batch.
+    std::vector<Ciphertext> linearCombinationBatch(const std::vector<std::vector<const Ciphertext *>> &cts, const std::vector<uint64_t> &weights, const uint64_t *constant = nullptr) const {
+        need(SchemeType::ckks, false);
+        if (cts.empty() || cts[0].empty()) return {};
+        std::vector<const Ciphertext *> heads;
+        for (auto &run : cts) heads.push_back(run.empty() ? nullptr : run[0]);
+        return combineBatch(cts, scalarTable(heads, weights.size(), [&](size_t r) { return weights[r]; }, constant, nullptr, nullptr, 0.0));
+    }
+    std::vector<Ciphertext> linearCombinationBatch(const std::vector<std::vector<const Ciphertext *>> &cts, const std::vector<double> &weights, double weight_scale,
+                                                   const double *constant = nullptr) const {
+        need(SchemeType::ckks, true);
+        if (cts.empty() || cts[0].empty()) return {};
+        std::vector<const Ciphertext *> heads;
+        for (auto &run : cts) heads.push_back(run.empty() ? nullptr : run[0]);
+        return combineBatch(cts, scalarTable(heads, weights.size(), [](size_t) { return uint64_t(0); }, nullptr, weights.data(), constant, weight_scale));
+    }
+    std::vector<Ciphertext> evaluatePolynomialBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint64_t> &coeffs, const RelinKeys &k, int baby_steps = 0) const {
+        need(SchemeType::ckks, false);
+        return polynomialBatch(a, coeffs.data(), nullptr, coeffs.size(), k, baby_steps, 0.0);
+    }
+    std::vector<Ciphertext> evaluatePolynomialBatch(const std::vector<const Ciphertext *> &a, const std::vector<double> &coeffs, const RelinKeys &k, int baby_steps = 0,
+                                                    double out_scale = 0.0) const {
+        need(SchemeType::ckks, true);
+        return polynomialBatch(a, nullptr, coeffs.data(), coeffs.size(), k, baby_steps, out_scale);
+    }
     void multiplyInplaceBatch(const std::vector<Ciphertext *> &a, const std::vector<const Ciphertext *> &b) const {
         std::vector<Ciphertext> out = multiplyBatch(std::vector<const Ciphertext *>(a.begin(), a.end()), b);
         for (size_t i = 0; i < a.size(); i++) *a[i] = std::move(out[i]);
@@ -2490,6 +2547,126 @@ private:
             keys[i] = key_of(k, RelinKeys::getIndex(i + 2));
         }
         return keys;
+    }
+    // ---- scalar sums and polynomial evaluation
+    struct ScalarTable { std::vector<uint64_t> scalars, constant; double scale; uint64_t cf; };
+    static uint64_t residue(__int128 v, uint64_t p) { const __int128 r = v % (__int128)p; return (uint64_t)(r < 0 ? r + (__int128)p : r); }
+    static uint64_t inverse(uint64_t a, uint64_t p) { // a^-1 mod p, p prime
+        unsigned __int128 r = 1, b = a % p;
+        for (uint64_t e = p - 2; e; e >>= 1, b = b * b % p)
+            if (e & 1) r = r * b % p;
+        return (uint64_t)r;
+    }
+    // the residues of the weights (and of the constant) at the level of heads[0], with the checks of the Python layer and its messages
+    template <class W> ScalarTable scalarTable(const std::vector<const Ciphertext *> &heads, size_t n_weights, W weight, const uint64_t *constant, const double *fweights,
+                                               const double *fconstant, double weight_scale) const {
+        if (heads.empty() || heads.size() > 16 || heads.size() != n_weights) throw std::invalid_argument("scalar_combine takes 1 to 16 terms");
+        for (const Ciphertext *c : heads)
+            if (!c) throw std::invalid_argument("null ciphertext descriptor");
+        const Ciphertext &a0 = *heads[0];
+        const size_t L = a0.coeffModulusSize();
+        const std::vector<Modulus> &q = c_.parms().coeffModulus(); // every prime of the key level; a level keeps the leading ones
+        if (L > q.size()) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        ScalarTable t;
+        t.scale = a0.scale();
+        t.cf = a0.correctionFactor();
+        for (const Ciphertext *c : heads) {
+            if (c->coeffModulusSize() != L || c->size() != a0.size()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+            if (fweights && c->scale() != a0.scale()) throw std::invalid_argument("scale mismatch");
+            if (!fweights && c->correctionFactor() != a0.correctionFactor()) throw std::invalid_argument("correction factor mismatch");
+        }
+        if (fweights) {
+            t.scale = a0.scale() * weight_scale;
+            for (size_t r = 0; r < n_weights; r++) {
+                const __int128 v = (__int128)std::roundl((long double)fweights[r] * (long double)weight_scale);
+                for (size_t l = 0; l < L; l++) t.scalars.push_back(residue(v, q[l].value()));
+            }
+            if (fconstant) {
+                const __int128 v = (__int128)std::roundl((long double)*fconstant * (long double)t.scale);
+                for (size_t l = 0; l < L; l++) t.constant.push_back(residue(v, q[l].value()));
+            }
+            return t;
+        }
+        const uint64_t tm = c_.parms().plainModulus().value();
+        for (size_t r = 0; r < n_weights; r++) {
+            const uint64_t w = weight(r);
+            if (w >= tm) throw std::invalid_argument("coefficient is not reduced modulo the plain modulus");
+            const __int128 v = w > tm / 2 ? (__int128)w - (__int128)tm : (__int128)w; // lifted centered
+            for (size_t l = 0; l < L; l++) t.scalars.push_back(residue(v, q[l].value()));
+        }
+        if (constant) {
+            const uint64_t m = *constant;
+            if (m >= tm) throw std::invalid_argument("coefficient is not reduced modulo the plain modulus");
+            if (c_.parms().scheme() == SchemeType::bgv) {
+                const uint64_t v = (uint64_t)((unsigned __int128)m * (t.cf % tm) % tm);
+                for (size_t l = 0; l < L; l++) t.constant.push_back(v % q[l].value());
+            } else { // BFV: m Delta + floor((m (q mod t) + (t + 1) / 2) / t), Delta = floor(q / t) = -(q mod t) t^-1 mod q_l: the scaling variant of addPlain
+                unsigned __int128 q_mod_t = 1;
+                for (size_t l = 0; l < L; l++) q_mod_t = q_mod_t * (q[l].value() % tm) % tm;
+                const uint64_t fix = (uint64_t)(((unsigned __int128)m * q_mod_t + (tm + 1) / 2) / tm);
+                for (size_t l = 0; l < L; l++) {
+                    const uint64_t p = q[l].value();
+                    const uint64_t qt = (uint64_t)(q_mod_t % p), delta = (uint64_t)((unsigned __int128)(qt ? p - qt : 0) * inverse(tm % p, p) % p);
+                    t.constant.push_back((uint64_t)(((unsigned __int128)m * delta + fix) % p));
+                }
+            }
+        }
+        return t;
+    }
+    void combine(const std::vector<const Ciphertext *> &cts, const ScalarTable &t, Ciphertext &dst) const {
+        std::vector<const troyhip_ct *> p(cts.size());
+        for (size_t r = 0; r < cts.size(); r++) p[r] = cts[r]->raw();
+        Ciphertext out;
+        out.resize(cts[0]->polyModulusDegree(), cts[0]->coeffModulusSize(), cts[0]->size());
+        check(troyhip_scalar_combine(h(), p.data(), t.scalars.data(), t.constant.empty() ? nullptr : t.constant.data(), (int)cts.size(), out.raw(), t.scale, t.cf, 1, nullptr));
+        out.bind(*cts[0]);
+        dst = std::move(out);
+    }
+    std::vector<Ciphertext> combineBatch(const std::vector<std::vector<const Ciphertext *>> &cts, const ScalarTable &t) const {
+        const size_t R = cts.size(), count = cts[0].size();
+        std::vector<std::vector<Ciphertext>> packed;
+        packed.reserve(R);
+        std::vector<troyhip_ct> views(R);
+        std::vector<const troyhip_ct *> p(R);
+        for (size_t r = 0; r < R; r++) {
+            if (cts[r].size() != count) throw std::invalid_argument("linearCombinationBatch: operand counts differ");
+            packed.emplace_back();
+            views[r] = runOf(cts[r], packed.back());
+            p[r] = &views[r];
+        }
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(count, *cts[0][0], cts[0][0]->size(), cts[0][0]->coeffModulusSize());
+        troyhip_ct d = *out[0].raw();
+        check(troyhip_scalar_combine(h(), p.data(), t.scalars.data(), t.constant.empty() ? nullptr : t.constant.data(), (int)R, &d, t.scale, t.cf, count, nullptr));
+        for (auto &c : out) c.copyMeta(d);
+        return out;
+    }
+    size_t polynomialLimbs(const Ciphertext &a, size_t n_coeffs, int baby_steps) const {
+        if (n_coeffs < 2) throw std::invalid_argument("the polynomial degree must lie in 1 .. 255");
+        const size_t levels = (size_t)polynomialDepth((int)n_coeffs - 1, baby_steps);
+        if (a.coeffModulusSize() <= levels) throw std::invalid_argument("not enough levels for this polynomial");
+        return a.coeffModulusSize() - levels;
+    }
+    void polynomial(const Ciphertext &a, const uint64_t *cm, const double *cf, size_t n_coeffs, const RelinKeys &k, Ciphertext &dst, int baby_steps, double out_scale) const {
+        const size_t limbs = polynomialLimbs(a, n_coeffs, baby_steps);
+        const uint64_t *key = k.hasKey(2) ? key_of(k, RelinKeys::getIndex(2)) : nullptr;
+        Ciphertext out;
+        out.resize(a.polyModulusDegree(), limbs, 2);
+        check(troyhip_evaluate_polynomial(h(), a.raw(), out.raw(), cm, cf, (int)n_coeffs - 1, baby_steps, out_scale, key, 0, 1, nullptr));
+        out.bind(a);
+        dst = std::move(out);
+    }
+    std::vector<Ciphertext> polynomialBatch(const std::vector<const Ciphertext *> &a, const uint64_t *cm, const double *cf, size_t n_coeffs, const RelinKeys &k, int baby_steps,
+                                            double out_scale) const {
+        if (a.empty()) return {};
+        const size_t limbs = polynomialLimbs(*a[0], n_coeffs, baby_steps);
+        const uint64_t *key = k.hasKey(2) ? key_of(k, RelinKeys::getIndex(2)) : nullptr;
+        std::vector<Ciphertext> pa;
+        const troyhip_ct va = runOf(a, pa);
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, limbs);
+        troyhip_ct t = *out[0].raw();
+        check(troyhip_evaluate_polynomial(h(), &va, &t, cm, cf, (int)n_coeffs - 1, baby_steps, out_scale, key, 0, a.size(), nullptr));
+        for (auto &c : out) c.copyMeta(t);
+        return out;
     }
     template <class F> std::vector<Ciphertext> nextBatch(const std::vector<const Ciphertext *> &a, F fn) const {
         if (a.empty()) return {};

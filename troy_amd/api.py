@@ -482,6 +482,87 @@ class Evaluator:
         self._chk(self.lib.troyhip_multiply_sum_max_terms(self.context.h, self.context.first_limbs if limbs is None else limbs, C.byref(n)))
         return n.value
 
+    # -- scalar sums and polynomial evaluation (troyhip_scalar_combine, troyhip_evaluate_polynomial: no reference counterpart)
+    def linearCombination(self, cts, weights, constant=None, weight_scale=None):
+        """sum_r weights[r] * cts[r] + constant as ONE pass over the operands: 1 .. 16 batches of one size, level and form.
+        BFV / BGV: weights and constant are integers mod t (lifted centered; the constant as addPlain adds a constant polynomial), the correction factors
+        must be equal.  CKKS: floats, applied as round(w * weight_scale) (default: the operands' scale); the scales must be equal and
+        out.scale = ct.scale * weight_scale."""
+        ctx = self.context
+        if not 1 <= len(cts) <= 16 or len(cts) != len(weights):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "scalar_combine takes 1 to 16 terms")
+        a0 = cts[0]
+        primes = ctx.coeff_modulus[:a0.limbs]
+        for a in cts:
+            if a.limbs != a0.limbs or a.size() != a0.size() or a.batch != a0.batch:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "encrypted1 and encrypted2 parameter mismatch")
+        if ctx.scheme == capi.CKKS:
+            if any(a.scale != a0.scale for a in cts):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "scale mismatch")
+            ws = float(a0.scale if weight_scale is None else weight_scale)
+            ints = [int(round(float(w) * ws)) for w in weights]
+            out_scale, out_cf = a0.scale * ws, a0.correction_factor
+            const = None if constant is None else [int(round(float(constant) * out_scale)) % p for p in primes]
+        else:
+            t = ctx.plain_modulus
+            if weight_scale is not None:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "weight_scale is a CKKS argument")
+            if any(a.correction_factor != a0.correction_factor for a in cts):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "correction factor mismatch")
+            if any(not 0 <= int(w) < t for w in weights) or (constant is not None and not 0 <= int(constant) < t):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "coefficient is not reduced modulo the plain modulus")
+            ints = [int(w) - t if int(w) > t // 2 else int(w) for w in weights]
+            out_scale, out_cf = a0.scale, a0.correction_factor
+            const = None
+            if constant is not None and ctx.scheme == capi.BGV:
+                const = [int(constant) * out_cf % t % p for p in primes]
+            elif constant is not None:  # BFV: m Delta + floor((m (q mod t) + (t + 1) / 2) / t), the scaling variant of addPlain
+                q = 1
+                for p in primes:
+                    q *= p
+                const = [(int(constant) * (q // t) + (int(constant) * (q % t) + (t + 1) // 2) // t) % p for p in primes]
+        table = np.array([[w % p for p in primes] for w in ints], dtype=np.uint64)
+        carr = None if const is None else np.array(const, dtype=np.uint64)
+        out = Ciphertext(ctx, a0.batch, a0.size(), a0.limbs, capacity=a0.size())
+        sts = [a.struct() for a in cts]
+        ptrs = (C.POINTER(CtStruct) * len(sts))(*[C.pointer(st) for st in sts])
+        so = out.struct()
+        self._chk(self.lib.troyhip_scalar_combine(ctx.h, ptrs, _u64p(table), None if carr is None else _u64p(carr), len(sts), C.byref(so), C.c_double(out_scale),
+                                                  C.c_uint64(out_cf), C.c_uint64(a0.batch), self.stream))
+        out._absorb(so)
+        return out
+
+    def polynomialDepth(self, degree, baby_steps=0):
+        """(levels consumed, baby steps in use) of evaluatePolynomial: a function of (degree, baby_steps) alone; BFV consumes no level"""
+        lv, k = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.troyhip_polynomial_depth(self.context.h, int(degree), int(baby_steps), C.byref(lv), C.byref(k)))
+        return lv.value, k.value
+
+    def evaluatePolynomial(self, ct, coeffs, relin_keys, baby_steps=0, out_scale=None, scratch_limit_words=0):
+        """p(ct) slot-wise, p = coeffs[0] + coeffs[1] x + .. (Paterson-Stockmeyer: shared powers, one scalar sum per block, ONE multiplySum and ONE
+        relinearization for all block x giant-power products).  BFV / BGV: integers mod t.  CKKS: real floats; the result's scale is exactly out_scale
+        (default: ct.scale).  The result lies polynomialDepth(degree)[0] levels below ct (BFV: at its level)."""
+        ctx = self.context
+        degree = len(coeffs) - 1
+        levels, _ = self.polynomialDepth(degree, baby_steps)
+        if ctx.scheme == capi.CKKS:
+            arr = np.ascontiguousarray(coeffs, dtype=np.float64)
+            cm, cf = None, arr.ctypes.data_as(C.POINTER(C.c_double))
+        else:
+            if any(not 0 <= int(v) < ctx.plain_modulus for v in coeffs):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "coefficient is not reduced modulo the plain modulus")
+            arr = np.array([int(v) for v in coeffs], dtype=np.uint64)
+            cm, cf = _u64p(arr), None
+        if ct.limbs - levels < 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "not enough levels for this polynomial")
+        out = Ciphertext(ctx, ct.batch, 2, ct.limbs - levels, capacity=2)
+        key = relin_keys.keys[0].ptr if relin_keys is not None and relin_keys.hasKey(0) else None
+        si, so = ct.struct(), out.struct()
+        self._chk(self.lib.troyhip_evaluate_polynomial(ctx.h, C.byref(si), C.byref(so), cm, cf, degree, int(baby_steps), C.c_double(0.0 if out_scale is None else out_scale),
+                                                       C.c_void_p(key), C.c_uint64(scratch_limit_words), C.c_uint64(ct.batch), self.stream))
+        out._absorb(so)
+        return out
+
     def square(self, a):
         return self.multiply(a, a)
 

@@ -60,7 +60,7 @@ SYMBOLS = [
     "troyhip_context_behz_bases", "troyhip_context_ntt_tables", "troyhip_test_modarith", "troyhip_ktime_enable", "troyhip_ktime_report", "troyhip_blake2b", "troyhip_random_bytes", "troyhip_context_parms_id", "troyhip_context_release_stream", "troyhip_context_reserve_scratch",
     "troyhip_context_scratch_words", "troyhip_galois_elt_from_step", "troyhip_ntt", "troyhip_fill_uniform",
     "troyhip_negate", "troyhip_add", "troyhip_sub", "troyhip_multiply", "troyhip_relinearize", "troyhip_relinearize_keys", "troyhip_relinearize_to", "troyhip_switch_key",
-    "troyhip_mod_switch_to_next", "troyhip_rescale_to_next", "troyhip_apply_galois", "troyhip_apply_galois_hoisted", "troyhip_galois_plain_sum_hoisted", "troyhip_galois_plain_sum_bsgs", "troyhip_multiply_sum", "troyhip_multiply_sum_max_terms", "troyhip_rotate",
+    "troyhip_mod_switch_to_next", "troyhip_rescale_to_next", "troyhip_apply_galois", "troyhip_apply_galois_hoisted", "troyhip_galois_plain_sum_hoisted", "troyhip_galois_plain_sum_bsgs", "troyhip_multiply_sum", "troyhip_multiply_sum_max_terms", "troyhip_scalar_combine", "troyhip_evaluate_polynomial", "troyhip_polynomial_depth", "troyhip_rotate",
     "troyhip_transform_to_ntt", "troyhip_transform_from_ntt", "troyhip_multiply_plain_ntt", "troyhip_add_plain", "troyhip_multiply_plain",
     "troyhip_stat", "troyhip_build_id", "troyhip_host_batch_encode", "troyhip_host_batch_decode", "troyhip_plain_to_ntt", "troyhip_decrypt", "troyhip_apply_key_switching", "troyhip_negacyclic_shift", "troyhip_divide_by_poly_modulus_degree",
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",

@@ -918,6 +918,45 @@ int troyhip_multiply_sum_max_terms(const troyhip_context *ctx, int limbs, int *o
         *out = need(ctx)->ev.multiply_sum_max_terms(limbs);
     }, false);
 }
+int troyhip_scalar_combine(troyhip_context *ctx, const troyhip_ct *const *cts, const uint64_t *scalars, const uint64_t *constant, int count, troyhip_ct *out,
+                           double out_scale, uint64_t out_cf, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!cts || count < 1 || count > 16) throw Error(ST_INVALID_ARGUMENT, "scalar_combine takes 1 to 16 terms");
+        if (!out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx);
+        hipStream_t s = on(stream);
+        CtBatch v[16];
+        for (int i = 0; i < count; i++) v[i] = view(cts[i]);
+        CtBatch o = view(out);
+        handle->ev.scalar_combine(v, scalars, constant, count, o, out_scale, out_cf, batch, s);
+        store(o, out);
+    });
+}
+int troyhip_evaluate_polynomial(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint64_t *coeffs_mod_t, const double *coeffs, int degree, int baby_steps,
+                                double out_scale, const uint64_t *relin_key, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx);
+        hipStream_t s = on(stream);
+        const CtBatch x = view(in);
+        CtBatch o = view(out);
+        // the intermediates outlive every sub-operation's use of the context arena: they come from the caching pool and go back to it when the call has
+        // queued its work -- the pool orders their reuse against the streams it knows
+        DeviceAlloc mem;
+        mem.get = [](size_t words) { return (u64 *)DevicePool::instance().get(words * sizeof(u64)); };
+        mem.put = [](u64 *p) { DevicePool::instance().put(p); };
+        handle->ev.evaluate_polynomial(x, o, coeffs_mod_t, coeffs, degree, baby_steps, out_scale, KsKey{relin_key}, scratch_limit_words, batch, mem, s);
+        store(o, out);
+    });
+}
+int troyhip_polynomial_depth(const troyhip_context *ctx, int degree, int baby_steps, int *levels, int *baby_steps_used) {
+    return guard([&] {
+        const auto *handle = need(ctx);
+        const PolyPlan p = Evaluator::plan_polynomial(degree, baby_steps);
+        if (levels) *levels = handle->ctx.scheme == SCHEME_BFV ? 0 : p.depth;
+        if (baby_steps_used) *baby_steps_used = p.k;
+    }, false);
+}
 int troyhip_add_plain(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *plain, uint64_t plain_coeff_count, uint64_t plain_batch_stride, double plain_scale,
                       int subtract, uint64_t batch, void *stream) {
     return guard([&] {

@@ -1316,6 +1316,362 @@ void Evaluator::multiply_plain(CtBatch &ct, const u64 *plain, u64 n_coeffs, u64 
     transform_from_ntt(ct, batch, s);
 }
 
+// ---- scalar sums and polynomial evaluation (no reference counterpart) ----
+Evaluator::~Evaluator() {
+    for (auto &st : staged_) (void)hipEventDestroy(st.done);
+}
+void Evaluator::upload(std::vector<u64> &&words, u64 *dst, hipStream_t s) {
+    // the copies that have read their words give them up; a long queue of pending ones waits for its oldest
+    for (auto it = staged_.begin(); it != staged_.end();) {
+        if (staged_.size() > 64 && it == staged_.begin()) HIP_CHECK(hipEventSynchronize(it->done));
+        else if (hipEventQuery(it->done) != hipSuccess) { (void)hipGetLastError(); ++it; continue; }
+        (void)hipEventDestroy(it->done);
+        it = staged_.erase(it);
+    }
+    staged_.emplace_back();
+    Staged &st = staged_.back();
+    st.words = std::move(words);
+    st.done = nullptr;
+    if (hipEventCreateWithFlags(&st.done, hipEventDisableTiming) != hipSuccess) { staged_.pop_back(); throw Error(ST_LOGIC_ERROR, "hipEventCreate failed"); }
+    HIP_CHECK(hipMemcpyAsync(dst, st.words.data(), st.words.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipEventRecord(st.done, s));
+}
+
+void Evaluator::scalar_combine_device(const CtBatch *cts, const u64 *d_scalars, const u64 *d_constant, int count, CtBatch &out, double out_scale, u64 out_cf, u64 batch,
+                                      hipStream_t s) {
+    const CtBatch &a0 = cts[0];
+    ScalarSumArgs x;
+    std::memset(&x, 0, sizeof(x));
+    x.count = count;
+    x.ntt = a0.ntt ? 1 : 0;
+    for (int r = 0; r < count; r++) { x.ct[r] = cts[r].data; x.ct_bstride[r] = cts[r].bstride; x.ct_limbs[r] = (u32)cts[r].limbs; }
+    launch_scalar_sum(x, d_scalars, d_constant, out.data, out.bstride, c.d_desc, c.ct_map(out.limbs), c.logn, out.limbs, a0.size, batch, s);
+    out.size = a0.size; out.ntt = a0.ntt; out.scale = out_scale; out.cf = out_cf;
+    stats::counter(stats::POLY_SCALAR_SUMS)++;
+}
+
+void Evaluator::scalar_combine(const CtBatch *cts, const u64 *scalars, const u64 *constant, int count, CtBatch &out, double out_scale, u64 out_cf, u64 batch, hipStream_t s) {
+    if (count < 1 || count > SCALAR_SUM_MAX || !cts) throw Error(ST_INVALID_ARGUMENT, "scalar_combine takes 1 to 16 terms");
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    const int L = out.limbs;
+    if (!c.is_data_level(L)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (!scalars) throw Error(ST_INVALID_ARGUMENT, "null scalars");
+    const CtBatch &a0 = cts[0];
+    for (int r = 0; r < count; r++) {
+        const CtBatch &a = cts[r];
+        check_ct(a);
+        if (a.size != a0.size || (c.scheme == SCHEME_CKKS ? a.limbs < L : a.limbs != L)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 and encrypted2 parameter mismatch");
+        if (a.ntt != a0.ntt) throw Error(ST_INVALID_ARGUMENT, "NTT form mismatch");
+    }
+    const u64 words = (u64)a0.size * poly_words(c, L);
+    if (!out.data || out.bstride < words) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    for (int l = 0; l < L; l++) {
+        for (int r = 0; r < count; r++)
+            if (scalars[(size_t)r * L + l] >= c.primes[l]) throw Error(ST_INVALID_ARGUMENT, "scalar is not reduced modulo its prime");
+        if (constant && constant[l] >= c.primes[l]) throw Error(ST_INVALID_ARGUMENT, "scalar is not reduced modulo its prime");
+    }
+    if (batch)
+        for (int r = 0; r < count; r++) { // every term reads its operand whole: the destination must not share a word with any of them
+            const CtBatch &a = cts[r];
+            const u64 *a_end = a.data + (batch - 1) * a.bstride + (u64)a.size * poly_words(c, a.limbs), *out_end = out.data + (batch - 1) * out.bstride + words;
+            if (out.data < a_end && a.data < out_end) throw Error(ST_INVALID_ARGUMENT, "the destination cannot be one of the operands");
+        }
+    if (!batch) { out.size = a0.size; out.ntt = a0.ntt; out.scale = out_scale; out.cf = out_cf; return; }
+    // the table: [count][L] scalars, then [L] constants, in the context's scratch behind everything already queued on the stream
+    std::vector<u64> table(scalars, scalars + (size_t)count * L);
+    if (constant) table.insert(table.end(), constant, constant + L);
+    c.arena.begin(s);
+    c.arena.reserve(table.size() + 64);
+    u64 *d = c.arena.take(table.size());
+    upload(std::move(table), d, s);
+    scalar_combine_device(cts, d, constant ? d + (size_t)count * L : nullptr, count, out, out_scale, out_cf, batch, s);
+}
+
+static int ceil_log2(int n) { int r = 0; while ((1 << r) < n) r++; return r; }
+PolyPlan Evaluator::plan_polynomial(int degree, int baby_steps) {
+    if (degree < 1 || degree > 255) throw Error(ST_INVALID_ARGUMENT, "the polynomial degree must lie in 1 .. 255");
+    int k = baby_steps;
+    if (!k) for (k = 2; k * k < degree + 1;) k *= 2;
+    if (k != 2 && k != 4 && k != 8 && k != 16) throw Error(ST_INVALID_ARGUMENT, "baby_steps must be a power of two in 2 .. 16");
+    PolyPlan p;
+    p.k = k;
+    p.m = (degree + k) / k; // ceil((degree + 1) / k)
+    if (p.m > 17) throw Error(ST_INVALID_ARGUMENT, "too few baby steps for this degree");
+    p.lb = ceil_log2(std::min(degree, k - 1));
+    if (p.m == 1) p.P = p.lb; // u_0 alone: formed at the level of its highest power, then the level step
+    else p.P = std::max(p.lb + 1, ceil_log2(k) + ceil_log2(p.m - 1)); // the blocks are formed one level above the products; X^(m-1) lies log2 k + ceil(log2(m - 1)) down
+    p.depth = p.P + 1;
+    return p;
+}
+
+namespace {
+// the residue of round(v) for |v| up to 2^16000: the 64-bit significand of the long double times a power of two
+u64 residue_of(long double v, u64 p) {
+    const bool neg = v < 0;
+    long double a = neg ? -v : v;
+    u64 r;
+    if (a < 18446744073709551616.0L) { // below 2^64: the rounded integer itself (it may round up to 2^64)
+        const long double ra = std::roundl(a);
+        r = ra >= 18446744073709551616.0L ? host::pow_mod(2 % p, 64, p) : (u64)ra % p;
+    } else {
+        int e = 0;
+        const long double f = std::frexp(a, &e); // a = f 2^e, f in [0.5, 1): f 2^64 is an integer of 64 bits
+        const u64 mant = (u64)std::ldexp(f, 64);
+        r = host::mul_mod(mant % p, host::pow_mod(2 % p, (u64)(e - 64), p), p);
+    }
+    return neg && r ? p - r : r;
+}
+struct PoolBlocks { // what a call took from the caching pool goes back when it ends, error or not: stream-ordered reuse is the pool's
+    const DeviceAlloc &mem;
+    std::vector<u64 *> blocks;
+    explicit PoolBlocks(const DeviceAlloc &m) : mem(m) {}
+    u64 *get(size_t words) { u64 *p = mem.get(words ? words : 1); blocks.push_back(p); return p; }
+    ~PoolBlocks() { for (u64 *p : blocks) mem.put(p); }
+};
+} // namespace
+
+void Evaluator::evaluate_polynomial(const CtBatch &in, CtBatch &out, const u64 *coeffs_mod_t, const double *coeffs, int degree, int baby_steps, double out_scale,
+                                    const KsKey &relin, u64 scratch_limit_words, u64 batch, const DeviceAlloc &mem, hipStream_t s) {
+    const PolyPlan pl = plan_polynomial(degree, baby_steps);
+    const bool ckks = c.scheme == SCHEME_CKKS, bfv = c.scheme == SCHEME_BFV, bgv = c.scheme == SCHEME_BGV;
+    if (ckks ? (!coeffs || coeffs_mod_t) : (!coeffs_mod_t || coeffs)) throw Error(ST_INVALID_ARGUMENT, "the coefficients do not match the scheme");
+    check_ct(in);
+    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "evaluate_polynomial takes a size-2 operand");
+    if (bfv && in.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
+    if (ckks && !in.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
+    if (bgv && in.ntt) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
+    const int k = pl.k, m = pl.m, L0 = in.limbs;
+    std::vector<char> nz(degree + 1);
+    for (int j = 0; j <= degree; j++) {
+        if (!ckks && coeffs_mod_t[j] >= c.t) throw Error(ST_INVALID_ARGUMENT, "coefficient is not reduced modulo the plain modulus");
+        if (ckks && !std::isfinite(coeffs[j])) throw Error(ST_INVALID_ARGUMENT, "coefficient is not finite");
+        nz[j] = ckks ? coeffs[j] != 0.0 : coeffs_mod_t[j] != 0;
+    }
+    if (std::find(nz.begin(), nz.end(), 1) == nz.end()) throw Error(ST_INVALID_ARGUMENT, "every coefficient is zero");
+    auto lv = [&](int level) { return bfv ? 0 : level; }; // BFV consumes no level
+    auto limbs_at = [&](int level) { return L0 - lv(level); };
+    if (!bfv && !c.is_data_level(L0 - pl.depth)) throw Error(ST_INVALID_ARGUMENT, "not enough levels for this polynomial");
+    const int L_out = limbs_at(pl.depth);
+    if (!out.data || out.bstride < 2 * poly_words(c, L_out)) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    if (ckks) {
+        if (out_scale == 0.0) out_scale = in.scale;
+        if (!(out_scale > 0) || !std::isfinite(out_scale) || !scale_ok(in.scale, L0)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    }
+    // ---- what is needed: a power that no present coefficient reaches is not computed
+    std::vector<char> block_nz(m, 0), need_b(k + 1, 0), need_g(m + 1, 0);
+    for (int j = 0; j <= degree; j++)
+        if (nz[j]) { block_nz[j / k] = 1; if (j % k) need_b[j % k] = 1; }
+    bool any_pair = false;
+    for (int i = 1; i < m; i++) if (block_nz[i]) { need_g[i] = 1; any_pair = true; }
+    for (int i = m - 1; i >= 2; i--) if (need_g[i]) need_g[(i + 1) / 2] = need_g[i / 2] = 1;
+    if (any_pair) need_b[k] = 1; // X = x^k
+    for (int i = 0; i < m; i++) { // a block of its constant alone rides on x with the scalar 0
+        bool terms = false;
+        for (int j = 1; j < k && i * k + j <= degree; j++) terms = terms || nz[i * k + j];
+        if (block_nz[i] && !terms) need_b[1] = 1;
+    }
+    for (int j = k; j >= 2; j--) if (need_b[j]) need_b[(j + 1) / 2] = need_b[j / 2] = 1;
+    bool any_product = any_pair;
+    for (int j = 2; j <= k; j++) any_product = any_product || need_b[j];
+    if (any_product && !relin.data) throw Error(ST_INVALID_ARGUMENT, "not enough relinearization keys");
+    if (!batch) { out.size = 2; out.limbs = L_out; out.ntt = in.ntt; out.scale = ckks ? out_scale : in.scale; out.cf = in.cf; return; }
+
+    PoolBlocks pool(mem);
+    const u64 pw0 = poly_words(c, L0);
+    u64 *tmp3 = pool.get(batch * 3 * pw0), *tmp2 = pool.get(batch * 2 * pw0);
+    auto fresh = [&](int level, int size) { // a dense batch at a level; the sub-operation fills in the rest
+        CtBatch x;
+        x.limbs = limbs_at(level);
+        x.size = size;
+        x.bstride = (u64)size * poly_words(c, x.limbs);
+        x.data = pool.get(batch * x.bstride);
+        return x;
+    };
+    auto level_step = [&](const CtBatch &x, CtBatch &dst) {
+        if (ckks) rescale_to_next(x, dst, batch, s);
+        else mod_switch_to_next(x, dst, batch, s);
+    };
+    // a power: its versions by level (levels consumed below the operand), the first one where it was computed
+    struct Node { std::map<int, CtBatch> at; int top = -1; };
+    std::vector<Node> baby(k + 1), giant(m + 1);
+    baby[1].at[0] = in;
+    baby[1].top = 0;
+    auto at_level = [&](Node &nd, int level) -> const CtBatch & { // brought down one level at a time (CKKS: a drop), each version kept for the next reader
+        level = lv(level);
+        if (nd.top < 0 || level < nd.top) throw Error(ST_LOGIC_ERROR, "evaluate_polynomial: a power is read above its level");
+        for (int l = nd.top; l < level; l++)
+            if (!nd.at.count(l + 1)) {
+                CtBatch d = fresh(l + 1, 2);
+                mod_switch_to_next(nd.at[l], d, batch, s);
+                nd.at[l + 1] = d;
+            }
+        return nd.at[level];
+    };
+    auto product = [&](Node &na, Node &nb, Node &dst) { // multiply -> relinearize -> the level step; the factor at the higher level is brought down first
+        const int level = std::max(na.top, nb.top);
+        const CtBatch a = at_level(na, level), b = at_level(nb, level);
+        CtBatch t3;
+        t3.data = tmp3;
+        t3.bstride = 3 * poly_words(c, a.limbs);
+        multiply(a, b, t3, batch, s);
+        CtBatch r;
+        if (bfv) {
+            r = fresh(0, 2);
+            relinearize_to(t3, r, &relin, 1, batch, s);
+            dst.top = 0;
+        } else {
+            CtBatch t2;
+            t2.data = tmp2;
+            t2.bstride = 2 * poly_words(c, a.limbs);
+            relinearize_to(t3, t2, &relin, 1, batch, s);
+            r = fresh(level + 1, 2);
+            level_step(t2, r);
+            dst.top = level + 1;
+        }
+        dst.at[dst.top] = r;
+        stats::counter(stats::POLY_PRODUCTS)++;
+        stats::counter(stats::POLY_RELINS)++;
+    };
+    for (int j = 2; j <= k; j++)
+        if (need_b[j]) product(baby[(j + 1) / 2], baby[j / 2], baby[j]);
+    if (any_pair) giant[1] = baby[k];
+    for (int i = 2; i < m; i++)
+        if (need_g[i]) product(giant[(i + 1) / 2], giant[i / 2], giant[i]);
+
+    // ---- the blocks: u_i = sum_j c_(ik+j) x^j at the scale / correction factor that makes every product u_i (x) X^i alike; u_0 joins the relinearized sum
+    const int Lv_blk = m == 1 ? pl.lb : pl.P - 1; // the level the blocks i >= 1 (m == 1: u_0) are formed at, one level step above the products
+    const u64 t = c.t;
+    long double S = 0; // CKKS: the scale of the products and of u_0, one prime above out_scale
+    if (ckks) {
+        const int lS = m == 1 ? pl.lb : pl.P;
+        S = (long double)out_scale * (long double)c.primes[limbs_at(lS) - 1];
+        if (!scale_ok((double)S, limbs_at(lS))) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    }
+    struct Job { int i, level; std::vector<CtBatch> ops; std::vector<int> js; size_t offset; bool has_const; long double target; u64 F; CtBatch out; };
+    std::vector<Job> jobs;
+    std::vector<CtBatch> pair_x; // X^i at the level of the products, beside jobs[.] of i >= 1
+    std::vector<u64> table;
+    for (int pass = 0; pass < 2; pass++) // the blocks of the products first, u_0 last
+        for (int i = pass ? 0 : 1; i < (pass ? 1 : m); i++) {
+            if (!block_nz[i]) continue;
+            Job jb;
+            jb.i = i;
+            const bool direct = i == 0 && m > 1; // u_0 beside products: formed at their level and scale, no level step of its own
+            jb.level = direct ? pl.P : Lv_blk;
+            jb.has_const = nz[i * k] != 0;
+            jb.F = 1;
+            jb.target = 0;
+            const int Lb = limbs_at(jb.level);
+            CtBatch X;
+            if (i) { X = at_level(giant[i], pl.P); pair_x.push_back(X); }
+            if (ckks) {
+                jb.target = direct || m == 1 ? S : S / (long double)X.scale * (long double)c.primes[Lb - 1];
+                if (!scale_ok((double)jb.target, Lb)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+            } else if (bgv && i) {
+                // the product's correction factor is F * q_last^-1 (the block's level step) * cf(X^i): F makes it 1 for every pair
+                u64 inv;
+                const u64 down = host::mul_mod(c.level(Lb).rns.inv_q_last_mod_t, X.cf % t, t);
+                if (!host::inv_mod(down, t, inv)) throw Error(ST_LOGIC_ERROR, "invalid correction factor");
+                jb.F = inv;
+            }
+            for (int j = 1; j < k && i * k + j <= degree; j++)
+                if (nz[i * k + j]) jb.js.push_back(j);
+            if (jb.js.empty()) jb.js.push_back(1);
+            for (int j : jb.js) jb.ops.push_back(ckks ? baby[j].at[baby[j].top] : at_level(baby[j], jb.level)); // a CKKS operand is read where it lies
+            jb.offset = table.size();
+            for (size_t r = 0; r < jb.js.size(); r++) {
+                const int j = jb.js[r];
+                const CtBatch &x = jb.ops[r];
+                if (ckks) {
+                    const long double ratio = jb.target / (long double)x.scale, cj = (long double)coeffs[i * k + j];
+                    if (cj != 0 && ratio < 1048576.0L) throw Error(ST_INVALID_ARGUMENT, "scale too small for the coefficients");
+                    for (int l = 0; l < Lb; l++) table.push_back(residue_of(cj * ratio, c.primes[l]));
+                } else {
+                    u64 sc = coeffs_mod_t[i * k + j];
+                    if (bgv) {
+                        u64 inv;
+                        if (!host::inv_mod(x.cf % t, t, inv)) throw Error(ST_INVALID_ARGUMENT, "invalid correction factor");
+                        sc = host::mul_mod(host::mul_mod(sc, jb.F, t), inv, t);
+                    }
+                    for (int l = 0; l < Lb; l++) { // lifted centered: s - t for s > t / 2
+                        const u64 p = c.primes[l], neg = (t - sc) % p;
+                        table.push_back(sc > t / 2 ? (neg ? p - neg : 0) : sc % p);
+                    }
+                }
+            }
+            if (jb.has_const) { // what add_plain adds for the constant polynomial c_(ik)
+                if (ckks) {
+                    for (int l = 0; l < Lb; l++) table.push_back(residue_of((long double)coeffs[i * k] * jb.target, c.primes[l]));
+                } else if (bgv) {
+                    const u64 v = host::mul_mod(coeffs_mod_t[i * k], jb.F, t);
+                    for (int l = 0; l < Lb; l++) table.push_back(v % c.primes[l]);
+                } else {
+                    const PlainArgs a = plain_args(c, Lb, 1, 0, 1, 1);
+                    const u64 mval = coeffs_mod_t[i * k];
+                    const u64 fix = (u64)(((unsigned __int128)mval * a.q_mod_t + a.thr) / t);
+                    for (int l = 0; l < Lb; l++) table.push_back((u64)(((unsigned __int128)mval * a.delta[l] + fix) % c.primes[l]));
+                }
+            }
+            jobs.push_back(std::move(jb));
+        }
+    u64 *d_table = pool.get(table.size());
+    upload(std::move(table), d_table, s);
+    for (Job &jb : jobs) {
+        const int Lb = limbs_at(jb.level), n = (int)jb.js.size();
+        const bool direct = jb.i == 0 && m > 1;
+        CtBatch u = fresh(jb.level, 2);
+        const u64 *d_s = d_table + jb.offset;
+        scalar_combine_device(jb.ops.data(), d_s, jb.has_const ? d_s + (size_t)n * Lb : nullptr, n, u, ckks ? (double)jb.target : in.scale, bgv ? jb.F : in.cf, batch, s);
+        if (direct || bfv) { jb.out = u; continue; }
+        if (m == 1) { jb.out = u; continue; } // its level step writes the result
+        jb.out = fresh(jb.level + 1, 2);
+        level_step(u, jb.out);
+    }
+
+    // ---- result = u_0 + relinearize(sum_i u_i (x) X^i), then the level step
+    const Job *u0 = !jobs.empty() && jobs.back().i == 0 ? &jobs.back() : nullptr;
+    const int n_pairs = (int)pair_x.size();
+    auto finish = [&](CtBatch &acc) { // acc: size 2 at the level above the result (BFV: at its level), not the destination
+        u64 *d = out.data;
+        const u64 bs = out.bstride;
+        if (bfv) {
+            launch_copy_strided(acc.data, acc.bstride, d, bs, 2 * poly_words(c, L0), batch, s);
+            out = acc;
+            out.data = d;
+            out.bstride = bs;
+        } else {
+            level_step(acc, out);
+            if (ckks) out.scale = out_scale; // S was chosen one prime above it
+        }
+    };
+    if (!n_pairs) {
+        CtBatch acc = u0->out;
+        finish(acc);
+        return;
+    }
+    CtBatch sum3;
+    sum3.data = tmp3;
+    sum3.bstride = 3 * poly_words(c, limbs_at(pl.P));
+    const int per = bfv ? multiply_sum_max_terms(L0) : TENSOR_SUM_MAX;
+    CtBatch as[TENSOR_SUM_MAX], bs_[TENSOR_SUM_MAX];
+    for (int r0 = 0; r0 < n_pairs; r0 += per) { // BFV: chunks the auxiliary base holds, joined by size-3 adds before the one relinearization
+        const int n = std::min(per, n_pairs - r0);
+        for (int r = 0; r < n; r++) { as[r] = jobs[r0 + r].out; bs_[r] = pair_x[r0 + r]; }
+        if (!r0) multiply_sum(as, bs_, n, sum3, batch, scratch_limit_words, s);
+        else {
+            CtBatch part = fresh(pl.P, 3);
+            multiply_sum(as, bs_, n, part, batch, scratch_limit_words, s);
+            add_sub(sum3, part, batch, false, s);
+        }
+        stats::counter(stats::POLY_PRODUCTS) += n;
+    }
+    CtBatch acc = fresh(pl.P, 2);
+    relinearize_to(sum3, acc, &relin, 1, batch, s);
+    stats::counter(stats::POLY_RELINS)++;
+    if (u0) add_sub(acc, u0->out, batch, false, s);
+    finish(acc);
+}
+
 // applyKeySwitchingInplace (evaluator_cuda.cu:1365-1378): c1 is the target, c1 := 0, switch with the given key
 void Evaluator::apply_key_switching(CtBatch &ct, const KsKey &key, u64 batch, hipStream_t s) {
     check_ct(ct);

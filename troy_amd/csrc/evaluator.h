@@ -5,6 +5,8 @@
 #pragma once
 #include "context.h"
 #include "kernels.h"
+#include <functional>
+#include <list>
 
 namespace troyhip {
 
@@ -31,6 +33,20 @@ struct KsKey {
 struct KsPlan {
     KsArgs a;
     LimbMap digit_map, acc_map;
+};
+
+// The plan of a polynomial evaluation, a function of (degree, baby steps) alone.  Levels count the primes consumed below the operand.
+struct PolyPlan {
+    int k;      // baby steps: the powers x^1 .. x^(k-1) and X = x^k
+    int m;      // blocks u_0 .. u_(m-1) of k coefficients, giant powers X^1 .. X^(m-1)
+    int lb;     // level of the highest baby power a block reads: ceil(log2 min(degree, k - 1))
+    int P;      // level of the products u_i (x) X^i (m == 1: the level u_0 is formed at)
+    int depth;  // levels consumed (CKKS, BGV; BFV consumes none): P + 1
+};
+// device memory for intermediates that outlive a sub-operation (the caching pool behind troyhip_malloc / troyhip_free)
+struct DeviceAlloc {
+    std::function<u64 *(size_t)> get; // words
+    std::function<void(u64 *)> put;
 };
 
 class Evaluator {
@@ -99,6 +115,21 @@ public:
     void multiply_sum(const CtBatch *as, const CtBatch *bs, int count, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s);
     int multiply_sum_max_terms(int limbs) const; // the largest count multiply_sum accepts at a level: 16, or what the BFV auxiliary base holds
 
+    // out = sum_r scalars[r][.] * cts[r] + constant: 1 <= count <= 16 operands of one size (1 .. 16) and one form; out.limbs,
+    // out.data and out.bstride are INPUTS; BFV / BGV operands have out.limbs limbs, CKKS operands at least that many (their leading rows are read where
+    // they lie).  scalars: HOST [count][out.limbs] residues, constant: HOST [out.limbs] residues or null, each below its prime.  Sets size, form,
+    // scale = out_scale and correction factor = out_cf: at this level the caller owns their meaning.  The destination is none of the operands.
+    void scalar_combine(const CtBatch *cts, const u64 *scalars, const u64 *constant, int count, CtBatch &out, double out_scale, u64 out_cf, u64 batch, hipStream_t s);
+    // out = p(in) slot-wise, p = c_0 + c_1 x + .. + c_degree x^degree, by Paterson-Stockmeyer: shared powers, one scalar sum per
+    // giant block, all block x giant-power products in one multiply_sum and ONE relinearization.  coeffs_mod_t (BFV, BGV) or coeffs (CKKS).  Intermediates
+    // come from `mem` (every sub-operation begins the context arena) and go back stream-ordered.  out.data / out.bstride are the caller's.
+    void evaluate_polynomial(const CtBatch &in, CtBatch &out, const u64 *coeffs_mod_t, const double *coeffs, int degree, int baby_steps, double out_scale, const KsKey &relin,
+                             u64 scratch_limit_words, u64 batch, const DeviceAlloc &mem, hipStream_t s);
+    // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
+    // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
+    static PolyPlan plan_polynomial(int degree, int baby_steps);
+    ~Evaluator();
+
     // scratch words needed by the ops (so callers can pre-reserve outside timed regions)
     size_t scratch_multiply(int sa, int sb, int limbs, u64 batch) const;
     size_t scratch_multiply_sum(int limbs, int count, u64 batch) const; // with every pair in one chunk
@@ -122,6 +153,13 @@ private:
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void balance_correction(u64 f1, u64 f2, u64 &f, u64 &e1, u64 &e2) const;
     void scalar_mul(CtBatch &a, u64 scalar, u64 batch, hipStream_t s);
+    // scalar_combine behind its checks, on DEVICE tables ([count][limbs] scalars, [limbs] constant or null)
+    void scalar_combine_device(const CtBatch *cts, const u64 *d_scalars, const u64 *d_constant, int count, CtBatch &out, double out_scale, u64 out_cf, u64 batch, hipStream_t s);
+    // host words to device memory on the stream, as DeviceEncryptor::upload does: the words are kept until the copy has read them (an event per upload; no wait unless
+    // many are pending)
+    struct Staged { std::vector<u64> words; hipEvent_t done; };
+    std::list<Staged> staged_;
+    void upload(std::vector<u64> &&words, u64 *dst, hipStream_t s);
 };
 
 } // namespace troyhip

@@ -325,6 +325,14 @@ void launch_modarith_probe(int op, const u64 *a, const u64 *b, const u64 *c, u64
 struct MulPlainAccArgs { const u64 *ct[16]; u64 ct_bstride[16]; const u64 *plain[16]; int count; };
 void launch_mul_plain_acc(const MulPlainAccArgs &x, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 size, u64 batch,
                           hipStream_t s);
+// sum of scalar multiples of up to 16 ciphertexts plus a constant polynomial (poly.hip):
+//   out[b][k][l][n] = sum_r scalars[r * limbs + l] * ct_r[b][k][l][n] + [k == 0] constant[l] e(n) mod p_l,  e = 1 (ntt) or [n == 0] (coefficient form).
+// Operand r of item b at ct[r] + b * ct_bstride[r], [size][ct_limbs[r]][N] with ct_limbs[r] >= limbs (its leading `limbs` rows are read); out item b at
+// out + b * out_bstride, [size][limbs][N].  scalars ([count][limbs]) and constant ([limbs] or null) are DEVICE words, canonical residues.
+enum { SCALAR_SUM_MAX = 16 };
+struct ScalarSumArgs { const u64 *ct[SCALAR_SUM_MAX]; u64 ct_bstride[SCALAR_SUM_MAX]; u32 ct_limbs[SCALAR_SUM_MAX]; int count, ntt; };
+void launch_scalar_sum(const ScalarSumArgs &x, const u64 *scalars, const u64 *constant, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn,
+                       u64 limbs, u64 size, u64 batch, hipStream_t s);
 
 // ---- behz.hip ----
 // base-change matrix entry split into 21-bit limbs (m = m0 + m1 2^21 + m2 2^42): see behz.hip

@@ -158,6 +158,72 @@ void launch_mul_plain_acc(const MulPlainAccArgs &x, u64 *out, u64 out_bstride, c
     launch_check("mul_plain_acc_kernel");
 }
 
+// Sum of scalar multiples of up to 16 ciphertexts plus a constant polynomial, one pass:
+//   out[b][k][l][n] = (sum_{r < count} s[r][l] * ct_r[b][k][l][n] + [k == 0] * const[l] * e(n)) mod p_l,   e(n) = 1 in NTT form (a constant polynomial is
+//   constant at every point), e(n) = [n == 0] in coefficient form.
+// mul_plain_acc_kernel's mapping (x: pairs of coefficients of a row, y: row = polynomial x limb, z: item, a stride loop beyond 65535 items; 16 bytes per
+// access; every index from the block id).  The operand pointers, strides and limb counts are kernel arguments; the count x limbs scalars and the limbs
+// constants do not fit there (16 x 63 words) and lie in device scratch, read one word per (limb, term): the address is workgroup-uniform (scalar loads).
+// Operand r keeps ITS OWN limb count: polynomial k, limb l of an item lies at (k * ct_limbs[r] + l) * N, so a CKKS operand of a higher level is read where
+// it lies (its leading `limbs` rows are the operand one level down: CKKS modSwitchToNext is a drop).
+// Bound: residues and scalars are canonical, below primes under 2^61: a product is below 2^122, 16 of them and one constant below 2^126 + 2^61 < 2^128;
+// barrett128 returns the canonical residue of ANY 128-bit value.  No atomics; every operand word read once, every output word written once.
+__global__ __launch_bounds__(EW_THREADS) void scalar_sum_kernel(ScalarSumArgs x, const u64 *__restrict__ scalars, const u64 *__restrict__ constant, u64 *out, u64 out_bstride,
+                                                                const PrimeDesc *primes, LimbMap map, int logn, u32 limbs, u32 batch) {
+    const u32 n = (blockIdx.x * EW_THREADS + threadIdx.x) * 2; // two coefficients per pair
+    const u32 N = 1u << logn, span = N / MPA_PAIRS < 2 ? 2 : N / MPA_PAIRS; // pair j of this thread: coefficients n + j span, n + j span + 1
+    if (n >= span) return;
+    const u32 row = blockIdx.y, k = row / limbs, l = row - k * limbs; // workgroup-uniform: one short division per workgroup
+    const Mod m = mod_of(prime_of(primes, map, l));
+    const u64 cv = constant && k == 0 ? constant[l] : 0;
+    for (u32 b = blockIdx.z; b < batch; b += gridDim.z) {
+        U128 s[MPA_PAIRS][2];
+#pragma unroll
+        for (int j = 0; j < MPA_PAIRS; j++) {
+            s[j][0] = U128{x.ntt || n + j * span == 0 ? cv : 0, 0};
+            s[j][1] = U128{x.ntt ? cv : 0, 0};
+        }
+        for (int t = 0; t < x.count; t++) {
+            const u64 w = scalars[(u32)t * limbs + l];
+            const u64 *src = x.ct[t] + (u64)b * x.ct_bstride[t] + (((u64)k * x.ct_limbs[t] + l) << logn) + n;
+            ulonglong2 v[MPA_PAIRS];
+#pragma unroll
+            for (int j = 0; j < MPA_PAIRS; j++) v[j] = j && n + j * span >= N ? ulonglong2{0, 0} : *reinterpret_cast<const ulonglong2 *>(src + j * span);
+#pragma unroll
+            for (int j = 0; j < MPA_PAIRS; j++) {
+                mac128(s[j][0], v[j].x, w);
+                mac128(s[j][1], v[j].y, w);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < MPA_PAIRS; j++) {
+            if (j && n + j * span >= N) continue;
+            ulonglong2 o;
+            o.x = barrett128(s[j][0].lo, s[j][0].hi, m);
+            o.y = barrett128(s[j][1].lo, s[j][1].hi, m);
+            *reinterpret_cast<ulonglong2 *>(out + (u64)b * out_bstride + ((u64)row << logn) + n + j * span) = o;
+        }
+    }
+}
+void launch_scalar_sum(const ScalarSumArgs &x, const u64 *scalars, const u64 *constant, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn,
+                       u64 limbs, u64 size, u64 batch, hipStream_t s) {
+    if (!batch || !size || !limbs) return;
+    if (logn < 1) throw Error(ST_LOGIC_ERROR, "scalar_sum: two coefficients per access");
+    if (x.count < 1 || x.count > SCALAR_SUM_MAX || size > 16 || size * limbs > 65535 || !scalars || !out || (batch > 1 && out_bstride < (size * limbs << logn)))
+        throw Error(ST_LOGIC_ERROR, "scalar_sum: 1 .. 16 terms, a destination of `size` polynomials");
+    bool odd = batch > 1 && (out_bstride & 1);
+    for (int r = 0; r < x.count; r++) {
+        if (!x.ct[r] || x.ct_limbs[r] < limbs || (batch > 1 && x.ct_bstride[r] < (size * x.ct_limbs[r] << logn))) throw Error(ST_LOGIC_ERROR, "scalar_sum: every term takes an operand of `size` polynomials");
+        odd = odd || (batch > 1 && (x.ct_bstride[r] & 1));
+    }
+    // two coefficients per 16-byte access: an item must start on an even word
+    if (odd) throw Error(ST_INVALID_ARGUMENT, "scalar_combine: batch strides must be even");
+    const u64 span = std::max<u64>((u64(1) << logn) / MPA_PAIRS, 2);
+    const unsigned gx = (unsigned)ceil_div(span / 2, EW_THREADS), gz = (unsigned)std::min<u64>(batch, 65535);
+    TROY_LAUNCH(scalar_sum_kernel, dim3(gx, (unsigned)(size * limbs), gz), dim3(EW_THREADS), 0, s, x, scalars, constant, out, out_bstride, primes, map, logn, (u32)limbs, (u32)batch);
+    launch_check("scalar_sum_kernel");
+}
+
 // ---------------------------------------------------------------- plaintext operands
 // addPlain / subPlain on c0 (evaluator_cuda.cu:1654-1720):
 //   BFV  (scalingvariant_cuda.cu:21-176 multiplyAdd/SubPlainWithScalingVariant): c0_l[j] +-= m_j * Delta_l + floor((m_j (q mod t) + (t+1)/2) / t)
