@@ -48,6 +48,11 @@ static bool primes_at_least_33_bits(const Context &c, int limbs) { // what the l
 }
 
 static inline u64 poly_words(const Context &c, int limbs) { return (u64)limbs * c.N; }
+// whether two strided batches share a word: `items` > 0 items of `words` words, `bstride` apart (an empty batch touches nothing, and (items - 1) * bstride
+// would wrap: the callers ask for none)
+static bool batches_overlap(const u64 *a, u64 a_items, u64 a_bstride, u64 a_words, const u64 *b, u64 b_items, u64 b_bstride, u64 b_words) {
+    return a < b + (b_items - 1) * b_bstride + b_words && b < a + (a_items - 1) * a_bstride + a_words;
+}
 
 void Evaluator::check_ct(const CtBatch &a) const {
     if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
@@ -187,8 +192,8 @@ void Evaluator::multiply(const CtBatch &a, const CtBatch &b, CtBatch &out, u64 b
     // polynomials are dense -- the single-ciphertext calls of the reference's interface take the fused, copy-free paths too
     auto dense = [&](u64 bstride, u64 words) { return batch == 1 || bstride == words; };
 
+    check_product_form(a.ntt, b.ntt);
     if (c.scheme == SCHEME_BFV) {
-        if (a.ntt || b.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
         const Level &lv = c.level(L);
         const int nb = (int)lv.rns.Bsk.size();
         const u64 bw = (u64)nb * N;
@@ -271,7 +276,6 @@ void Evaluator::multiply(const CtBatch &a, const CtBatch &b, CtBatch &out, u64 b
             launch_copy_strided(res, ds * pw, out.data, out.bstride, ds * pw, batch, s);
         }
     } else if (c.scheme == SCHEME_CKKS) {
-        if (!(a.ntt && b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
         new_scale = a.scale * b.scale;
         if (!scale_ok(new_scale, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
         if (out.data != a.data && out.data != b.data && dense(out.bstride, (u64)ds * pw)) {
@@ -283,7 +287,6 @@ void Evaluator::multiply(const CtBatch &a, const CtBatch &b, CtBatch &out, u64 b
             launch_copy_strided(d, ds * pw, out.data, out.bstride, ds * pw, batch, s);
         }
     } else {
-        if (a.ntt || b.ntt) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
         // BGV (evaluator_cuda.cu:463-500): NTT -> tensor -> INTT.  Dense size-2 operands go through the fused transform + tensor
         // pass pair (consumed in place, like the q base of the BFV path); a fresh dense destination is written directly.
         const int sp = sa + sb;
@@ -344,6 +347,11 @@ void Evaluator::check_ks_form(bool ntt) const {
     if (c.scheme == SCHEME_BFV && ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
     if (c.scheme == SCHEME_CKKS && !ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
     if (c.scheme == SCHEME_BGV && ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+}
+void Evaluator::check_product_form(bool a_ntt, bool b_ntt) const { // the reference's wording, its misspelling included
+    if (c.scheme == SCHEME_BFV && (a_ntt || b_ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
+    if (c.scheme == SCHEME_CKKS && !(a_ntt && b_ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
+    if (c.scheme == SCHEME_BGV && (a_ntt || b_ntt)) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
 }
 // bring a CKKS target to coefficient form (evaluator_cuda.cu:1215-1216)
 const u64 *Evaluator::ks_coeff_target(const u64 *target, u64 &t_bstride, u64 *tt, const KsPlan &k, hipStream_t s) {
@@ -592,11 +600,7 @@ void Evaluator::mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hip
                             ntt1_supported(c.logn, c.ct_map(nl), batch * in.size * nl, Ntt1Feature::CORRECTION);
     // the output ranges [out.data + b out.bstride, + size npw) must not overlap what a later row still reads: when the two batches share memory
     // (a direct C-ABI caller rescaling a strided batch onto itself) the input is staged first, as every strided input was before the fused path
-    bool overlaps = false;
-    if (batch) { // an empty batch touches nothing (and (batch - 1) * stride would wrap)
-        const u64 *in_end = in.data + (batch - 1) * in.bstride + (u64)in.size * pw, *out_end = out.data + (batch - 1) * out.bstride + (u64)in.size * npw;
-        overlaps = out.data < in_end && in.data < out_end;
-    }
+    const bool overlaps = batch && batches_overlap(out.data, batch, out.bstride, (u64)in.size * npw, in.data, batch, in.bstride, (u64)in.size * pw);
     bool staged = false;
     if ((!dense_in && !ckks_fused) || overlaps) {
         staged = true;
@@ -683,44 +687,106 @@ void Evaluator::apply_galois(CtBatch &ct, uint32_t elt, const KsKey &key, u64 ba
     switch_key(ct, t1, pw, key, batch, s, KsBase{t0, pw});
 }
 
-// Hoisted rotations (Halevi-Shoup; no reference counterpart, DESIGN.md section 4.10): the digits of c1 are decomposed, extended and transformed ONCE
-// per item; every Galois element then costs a gathered inner product over them (the automorphism is a permutation in NTT form), sigma(c0) and the
-// second half of the key switch.  Scratch per slab of `bs` items and `rs` rotations:
-//   bs N (rl dl [D] + dl [CKKS: c1 in coefficient form]) + rs bs N (2 rl [acc] + dl [sigma(c0)] + 2 dl + 4 [what the second half carves])
-// A slab is the whole batch times as many consecutive rotations as fit (HOIST_MAX_ROT at the most), or -- where one rotation of the whole batch does
-// not fit -- a run of items times one rotation; the digits of a run of items are made once for all its rotations either way.
+// ---- what the one-call operations share ----
+// The scratch plan of a call that works through its batch in slabs of items and, within a slab, through its units (rotations, rows, products) in
+// chunks, under limit_words (0: the default): a slab is the whole batch with as many units per chunk as fit (unit_cap at the most), or -- where one
+// unit of the whole batch does not fit -- a run of items with one unit per chunk.  per_unit_item == 0: nothing is held per unit, a slab is a run of
+// items.  Below one item with one unit the call is refused with the caller's text.
+struct SlabPlan { u64 items, units, words; }; // items per slab, units per chunk, words to reserve
 static const u64 HOIST_DEFAULT_SCRATCH_WORDS = u64(1) << 28; // 2 GiB: troyhip.h documents it
-void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s) {
-    check_ct(in);
-    if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
-    for (int r = 0; r < R; r++) {
+static u64 slab_slack(u64 blocks) { return 32 * blocks + 128; } // Arena::take rounds each of at most `blocks` blocks up to 32 words
+static SlabPlan plan_slabs(u64 limit_words, u64 blocks, u64 per_item, u64 per_unit_item, u64 batch, u64 unit_cap, const char *too_small) {
+    const u64 limit = limit_words ? limit_words : HOIST_DEFAULT_SCRATCH_WORDS, slack = slab_slack(blocks), one = per_item + per_unit_item;
+    if (one + slack > limit) throw Error(ST_INVALID_ARGUMENT, too_small);
+    SlabPlan p{std::min(batch, (limit - slack) / one), 1, 0};
+    if (p.items == batch && per_unit_item) p.units = std::min(unit_cap, (limit - slack - batch * per_item) / (batch * per_unit_item));
+    p.words = p.items * per_item + p.units * p.items * per_unit_item + slack;
+    return p;
+}
+// the Galois elements of a hoisted call and the keys it will read: none for element 1, none where key_needed(r) is false (keys == null: the elements alone)
+template <class F> static void check_galois_elts(const Context &c, const uint32_t *elts, const KsKey *keys, int n, F key_needed) {
+    for (int r = 0; r < n; r++) {
         if (!(elts[r] & 1) || elts[r] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
-        if (elts[r] != 1 && !keys[r].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+        if (keys && elts[r] != 1 && key_needed(r) && !keys[r].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
     }
+}
+static bool every_key(int) { return true; }
+bool Evaluator::hoist_operands(const char *what, const CtBatch &in, CtBatch &out, const double *plain_scale, u64 out_items, u64 batch) const {
     if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
     if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
     check_ks_form(in.ntt);
+    const u64 pw = poly_words(c, in.limbs);
+    if (in.limbs >= 64) throw Error(ST_LOGIC_ERROR, std::string(what) + ": more than 63 digits");
+    const double scale = plain_scale ? in.scale * *plain_scale : in.scale;
+    if (plain_scale && c.scheme == SCHEME_CKKS && !scale_ok(scale, in.limbs)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    out.size = 2; out.limbs = in.limbs; out.ntt = in.ntt; out.scale = scale; out.cf = in.cf;
+    // every rotation reads the whole operand: the destination must not share a word with it
+    if (batch && batches_overlap(out.data, out_items, out.bstride, 2 * pw, in.data, batch, in.bstride, 2 * pw))
+        throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": destination must be a distinct buffer");
+    return batch != 0;
+}
+// D[b][i][j] = NTT_{p_i}(d_j mod p_i) of c1's digits d_j; D[b][j][j] is c1's own limb j in NTT form
+void Evaluator::hoist_digits(const u64 *c1, u64 bstride, u64 *D, u64 *tt, const KsPlan &k, hipStream_t s) {
+    if (c.scheme == SCHEME_CKKS) c1 = ks_coeff_target(c1, bstride, tt, k, s);
+    ks_expand_digits(c1, bstride, D, k, s);
+}
+void Evaluator::hoist_c0_to_ntt(const u64 *c0, u64 bstride, u64 *c0n, const KsArgs &a, hipStream_t s) {
+    launch_copy_strided(c0, bstride, c0n, a.dl * c.N, a.dl * c.N, a.batch, s);
+    launch_ntt(c0n, c.d_desc, c.ct_map((int)a.dl), a.batch * a.dl, c.logn, false, s);
+}
+// every present term, HOIST_MAX_ROT per launch: c0 is read through the index map of the element (element 1: in place) and, polys == 2, c1 for element 1.
+// CKKS reads the operand where it lies (c1 follows c0); BFV / BGV read c0n (hoist_c0_to_ntt) and c1's own limbs in D
+void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const u64 *D, int polys, u64 *dst,
+                              const KsArgs &a, hipStream_t s) {
+    const u64 N = c.N, dl = a.dl, rl = dl + 1, pw = dl * N;
+    HoistLtArgs h;
+    std::memset(&h, 0, sizeof(h));
+    auto flush = [&] {
+        if (!h.rots) return;
+        if (c.scheme == SCHEME_CKKS) launch_hoist_lt_base(c0, bstride, c0 + pw, bstride, N, dst, (u64)polys * pw, polys, a, h, s);
+        else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, dst, (u64)polys * pw, polys, a, h, s);
+        std::memset(&h, 0, sizeof(h));
+        h.accumulate = 1; // later launches add to what this one stored
+    };
+    for (int i = 0; i < n; i++)
+        if (plains[i]) {
+            h.pt[h.rots] = plains[i]; h.elt[h.rots] = elts[i];
+            if (++h.rots == HOIST_MAX_ROT) flush();
+        }
+    flush();
+}
+void Evaluator::hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s) {
+    const u64 pw = k.a.dl * c.N;
+    CtBatch o = out;
+    o.data = out.data + b0 * out.bstride;
+    if (!switched) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, k.a.batch, s); // the result is the base: no key read, no mod-down
+    else {
+        c.arena.rewind(mark);
+        ks_acc_to_ct(o, acc, k, s, KsBase{base, (u64)polys * pw, polys});
+    }
+}
+
+// Hoisted rotations (Halevi-Shoup; no reference counterpart, DESIGN.md section 4.10): the digits of c1 are decomposed, extended and transformed ONCE
+// per item; every Galois element then costs a gathered inner product over them (the automorphism is a permutation in NTT form), sigma(c0) and the
+// second half of the key switch.  Scratch per slab of `bs` items and `rs` rotations (plan_slabs; the digits of a run of items are made once for all
+// its rotations):
+//   bs N (rl dl [D] + dl [CKKS: c1 in coefficient form]) + rs bs N (2 rl [acc] + dl [sigma(c0)] + 2 dl + 4 [what the second half carves])
+void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+    check_galois_elts(c, elts, keys, R, every_key);
+    if (!hoist_operands("hoisted rotations", in, out, nullptr, (u64)R * batch, batch)) return; // the destination holds R batches back to back
     const int L = in.limbs;
     const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
-    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "hoisted rotations: more than 63 digits");
-    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
-    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = in.scale; out.cf = in.cf;
-    if (!batch) return;
-    {   // the destination holds R batches back to back and must not share a word with the operand, which every rotation reads
-        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + ((u64)R * batch - 1) * out.bstride + 2 * pw;
-        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations: destination must be a distinct buffer");
-    }
     const bool ckks = c.scheme == SCHEME_CKKS;
-    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
-    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
     const u64 per_item = N * (rl * dl + (ckks ? dl : 0)), per_rot_item = N * (2 * rl + dl + 2 * dl + 4);
-    if (per_item + per_rot_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one rotation of one ciphertext");
-    u64 bs = batch, rs = 1;
-    if (batch * (per_item + per_rot_item) + slack <= limit) rs = std::min<u64>({(u64)R, (u64)HOIST_MAX_ROT, (limit - slack - batch * per_item) / (batch * per_rot_item)});
-    else bs = (limit - slack) / (per_item + per_rot_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, 8, per_item, per_rot_item, batch, std::min<u64>(R, HOIST_MAX_ROT), "scratch_limit_words is too small for one rotation of one ciphertext");
+    const u64 bs = plan.items, rs = plan.units;
+    if (rs > 1 && bs != batch) throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch"); // the widened second half below
 
     c.arena.begin(s);
-    c.arena.reserve(bs * per_item + rs * bs * per_rot_item + slack);
+    c.arena.reserve(plan.words);
     u64 *D = c.arena.take(bs * rl * dl * N);
     u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
     u64 *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
@@ -731,11 +797,7 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
         KsPlan k = ks_plan(L, nb);
         KsArgs &a = k.a;
-        // the digits of this run of items, once: D[b][i][j] = NTT_{p_i}(d_j mod p_i)
-        const u64 *coeff = c1;
-        u64 coeff_bs = in.bstride;
-        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
-        ks_expand_digits(coeff, coeff_bs, D, k, s);
+        hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
         for (int r0 = 0; r0 < R;) {
             if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
                 launch_copy_strided(c0, in.bstride, out.data + ((u64)r0 * batch + b0) * out.bstride, out.bstride, 2 * pw, nb, s);
@@ -754,60 +816,43 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
             // the second half of the key switch over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
             CtBatch o = out;
             o.data = out.data + ((u64)r0 * batch + b0) * out.bstride;
-            o.size = 2; o.limbs = L; o.ntt = in.ntt;
             a.batch = (u64)h.rots * nb;
             c.arena.rewind(mark);
-            if (h.rots == 1 || nb == batch) ks_acc_to_ct(o, acc, k, s, KsBase{sig0, pw});
-            else throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch");
+            ks_acc_to_ct(o, acc, k, s, KsBase{sig0, pw});
             a.batch = nb;
             stats::counter(stats::HOIST_SLABS)++;
             r0 += (int)h.rots;
         }
     }
-    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = in.scale; out.cf = in.cf;
 }
 
 // Hoisted linear transform (no reference counterpart): sum_r plains[r] * (Galois element elts[r] of the operand), the plaintexts
 // applied in the extended basis BEFORE the mod-down, so that the sum over the rotations is formed inside the gathered inner product: one accumulator and
 // one mod-down per item whatever R is, nothing of size R in memory.  Scratch per item (no factor R):
 //   N (rl dl [D] + dl [CKKS: c1 in coefficient form] + 2 rl [acc] + 2 dl [base] + dl [BFV / BGV: c0 in NTT form] + 2 dl + 4 [what the second half carves])
-// A slab is a run of items that fits under the limit; the rotations of a slab run HOIST_MAX_ROT per launch, later launches accumulating.
+// A slab is a run of items that fits under the limit (plan_slabs, nothing per unit); the rotations of a slab run HOIST_MAX_ROT per launch, later launches
+// accumulating.
 void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
                                          u64 scratch_limit_words, hipStream_t s) {
     check_ct(in);
     if (R < 1 || !elts || !keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
     bool any_rot = false, any_one = false;
-    for (int r = 0; r < R; r++) {
-        if (!(elts[r] & 1) || elts[r] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
-        if (elts[r] != 1 && !keys[r].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    for (int r = 0; r < R; r++) { // one term at a time, unlike the other two calls: a missing plaintext is reported before what is wrong with a later term
+        check_galois_elts(c, elts + r, keys + r, 1, every_key);
         if (!plains[r]) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
         (elts[r] == 1 ? any_one : any_rot) = true;
     }
-    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
-    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
-    check_ks_form(in.ntt);
+    if (!hoist_operands("hoisted linear transform", in, out, &plain_scale, batch, batch)) return;
     const int L = in.limbs;
     const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
-    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "hoisted linear transform: more than 63 digits");
-    const double new_scale = in.scale * plain_scale;
-    if (c.scheme == SCHEME_CKKS && !scale_ok(new_scale, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
-    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
-    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = new_scale; out.cf = in.cf;
-    if (!batch) return;
-    {   // every rotation reads the whole operand: the destination must not share a word with it
-        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 2 * pw;
-        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform: destination must be a distinct buffer");
-    }
     const bool ckks = c.scheme == SCHEME_CKKS;
     const int polys = any_one ? 2 : 1;
-    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
-    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
     const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + 2 * rl + 2 * dl + (ckks ? 0 : dl) + 2 * dl + 4);
-    if (per_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one ciphertext");
-    const u64 bs = std::min<u64>(batch, (limit - slack) / per_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, 8, per_item, 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
+    const u64 bs = plan.items;
 
     c.arena.begin(s);
-    c.arena.reserve(bs * per_item + slack);
+    c.arena.reserve(plan.words);
     u64 *D = c.arena.take(bs * rl * dl * N);
     u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
     u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
@@ -819,47 +864,27 @@ void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const 
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
         const KsPlan k = ks_plan(L, nb);
         const KsArgs &a = k.a;
-        // the digits of this run of items, once: D[b][i][j] = NTT_{p_i}(d_j mod p_i); D[b][j][j] is c1's own limb j in NTT form
-        const u64 *coeff = c1;
-        u64 coeff_bs = in.bstride;
-        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
-        ks_expand_digits(coeff, coeff_bs, D, k, s);
-        HoistLtArgs h;
-        auto flush = [&](bool rotations) {
-            if (!h.rots) return;
-            if (rotations) launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
-            else if (ckks) launch_hoist_lt_base(c0, in.bstride, c1, in.bstride, N, base, (u64)polys * pw, polys, a, h, s);
-            else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, base, (u64)polys * pw, polys, a, h, s);
-            std::memset(&h, 0, sizeof(h));
-            h.accumulate = 1; // later launches of the same phase add to what this one stored
-        };
+        hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
         // the extended-basis accumulators: every element other than 1, HOIST_MAX_ROT per launch
+        HoistLtArgs h;
         std::memset(&h, 0, sizeof(h));
+        auto flush = [&] {
+            if (!h.rots) return;
+            launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
+            std::memset(&h, 0, sizeof(h));
+            h.accumulate = 1; // later launches add to what this one stored
+        };
         for (int r = 0; r < R; r++) {
             if (elts[r] == 1) continue;
             h.key[h.rots] = keys[r].data; h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
-            if (++h.rots == HOIST_MAX_ROT) flush(true);
+            if (++h.rots == HOIST_MAX_ROT) flush();
         }
-        flush(true);
-        // the base in NTT form: every element, c0 read through the index map (element 1: in place) and c1 for element 1
-        if (!ckks) {
-            launch_copy_strided(c0, in.bstride, c0n, pw, pw, nb, s);
-            launch_ntt(c0n, c.d_desc, map, nb * dl, c.logn, false, s);
-        }
-        std::memset(&h, 0, sizeof(h));
-        for (int r = 0; r < R; r++) {
-            h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
-            if (++h.rots == HOIST_MAX_ROT) flush(false);
-        }
-        flush(false);
+        flush();
+        // the base in NTT form: every element
+        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, a, s);
+        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, D, polys, base, a, s);
         if (!ckks) launch_ntt(base, c.d_desc, map, nb * polys * dl, c.logn, true, s);
-        CtBatch o = out;
-        o.data = out.data + b0 * out.bstride;
-        if (!any_rot) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, nb, s); // every element is 1: the result is the base, no key read, no mod-down
-        else {
-            c.arena.rewind(mark);
-            ks_acc_to_ct(o, acc, k, s, KsBase{base, (u64)polys * pw, polys});
-        }
+        hoist_lt_finish(any_rot, out, b0, acc, base, polys, mark, k, s); // every element is 1 (polys == 2): the base
         stats::counter(stats::HOIST_LT_SLABS)++;
     }
 }
@@ -872,68 +897,43 @@ void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const 
 // Scratch per item of a slab, in units of N words (dl = limbs, rl = dl + 1, w = min(16, used babies other than 1), n2' = used rows, gc = rows per chunk):
 //   rl dl [D] + dl [CKKS: c1 in coefficient form] + w 2 rl [W] + n2' 2 rl [accU] + dl [BFV / BGV: c0 in NTT form] + 2 rl [acc] + 2 dl [base]
 //   + gc (2 dl [baseU] + 2 dl [u] + rl dl [digits of u.c1] + dl [CKKS: u.c1 in coefficient form] + 2 dl + 4 [what a second half carves])
-// A slab is the whole batch with as many rows per chunk as fit (16 at the most), or -- where one row of the whole batch does not fit -- a run of items
-// with one row per chunk.  Below one item with one row per chunk the call is refused.
+// The units of plan_slabs are the rows (16 per chunk at the most).
 void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
                                       const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s) {
     check_ct(in);
     if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
         throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
     if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-    for (int j = 0; j < n_baby; j++)
-        if (!(baby_elts[j] & 1) || baby_elts[j] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+    // unlike the other two calls: every element of both lists before any key
+    check_galois_elts(c, baby_elts, nullptr, n_baby, every_key);
+    check_galois_elts(c, giant_elts, nullptr, n_giant, every_key);
+    u64 used_babies = 0, used_rows = 0; // bit j / bit i: some plaintext of the column / of the row is present
     for (int i = 0; i < n_giant; i++)
-        if (!(giant_elts[i] & 1) || giant_elts[i] >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
-    // what is used: the babies other than 1 (inner products), the babies that are 1 (base only), the rows with the giants other than 1 first
+        for (int j = 0; j < n_baby; j++)
+            if (plains[(size_t)i * n_baby + j]) { used_babies |= u64(1) << j; used_rows |= u64(1) << i; }
+    check_galois_elts(c, baby_elts, baby_keys, n_baby, [&](int j) { return used_babies >> j & 1; });
+    if (!used_babies) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
+    check_galois_elts(c, giant_elts, giant_keys, n_giant, [&](int i) { return used_rows >> i & 1; });
+    // what is used: the babies other than 1 (inner products; the babies that are 1 enter the base only), the rows with the giants other than 1 first
     std::vector<int> rot_babies, rows;
-    bool any_present = false;
-    for (int j = 0; j < n_baby; j++) {
-        bool used = false;
-        for (int i = 0; i < n_giant; i++) used = used || plains[(size_t)i * n_baby + j];
-        any_present = any_present || used;
-        if (used && baby_elts[j] != 1) {
-            if (!baby_keys[j].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
-            rot_babies.push_back(j);
-        }
-    }
-    if (!any_present) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
+    for (int j = 0; j < n_baby; j++)
+        if ((used_babies >> j & 1) && baby_elts[j] != 1) rot_babies.push_back(j);
     for (int pass = 0; pass < 2; pass++)
-        for (int i = 0; i < n_giant; i++) {
-            bool used = false;
-            for (int j = 0; j < n_baby; j++) used = used || plains[(size_t)i * n_baby + j];
-            if (!used || (giant_elts[i] == 1) != (pass == 1)) continue;
-            if (giant_elts[i] != 1 && !giant_keys[i].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
-            rows.push_back(i);
-        }
+        for (int i = 0; i < n_giant; i++)
+            if ((used_rows >> i & 1) && (giant_elts[i] == 1) == (pass == 1)) rows.push_back(i);
     const u64 n_rot_rows = (u64)std::count_if(rows.begin(), rows.end(), [&](int i) { return giant_elts[i] != 1; });
-    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
-    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
-    check_ks_form(in.ntt);
+    if (!hoist_operands("baby-step / giant-step transform", in, out, &plain_scale, batch, batch)) return;
     const int L = in.limbs;
     const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
-    if (dl >= 64) throw Error(ST_LOGIC_ERROR, "baby-step / giant-step transform: more than 63 digits");
-    const double new_scale = in.scale * plain_scale;
-    if (c.scheme == SCHEME_CKKS && !scale_ok(new_scale, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
-    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
-    out.size = 2; out.limbs = L; out.ntt = in.ntt; out.scale = new_scale; out.cf = in.cf;
-    if (!batch) return;
-    {   // every rotation reads the whole operand: the destination must not share a word with it
-        const u64 *in_end = in.data + (batch - 1) * in.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 2 * pw;
-        if (out.data < in_end && in.data < out_end) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform: destination must be a distinct buffer");
-    }
     const bool ckks = c.scheme == SCHEME_CKKS;
     const u64 n2 = rows.size(), nrb = rot_babies.size(), wb = std::min<u64>(nrb, HOIST_MAX_ROT);
-    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
-    const u64 slack = 32 * 16 + 128; // Arena::take rounds each of at most sixteen blocks up to 32 words
     const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + wb * 2 * rl + n2 * 2 * rl + (ckks ? 0 : dl) + 2 * rl + 2 * dl);
     const u64 per_row_item = N * (2 * dl + 2 * dl + rl * dl + (ckks ? dl : 0) + 2 * dl + 4);
-    if (per_item + per_row_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one giant step of one ciphertext");
-    u64 bs = batch, gc = 1;
-    if (batch * (per_item + per_row_item) + slack <= limit) gc = std::min<u64>({n2, (u64)HOIST_MAX_ROT, (limit - slack - batch * per_item) / (batch * per_row_item)});
-    else bs = (limit - slack) / (per_item + per_row_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, 16, per_item, per_row_item, batch, std::min<u64>(n2, HOIST_MAX_ROT), "scratch_limit_words is too small for one giant step of one ciphertext");
+    const u64 bs = plan.items, gc = plan.units;
 
     c.arena.begin(s);
-    c.arena.reserve(bs * per_item + gc * bs * per_row_item + slack);
+    c.arena.reserve(plan.words);
     u64 *D = c.arena.take(bs * rl * dl * N);
     u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
     u64 *W = nrb ? c.arena.take(wb * bs * 2 * rl * N) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * 2 * rl * N) : nullptr;
@@ -948,11 +948,7 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
         KsPlan k = ks_plan(L, nb);
         KsArgs &a = k.a;
-        // stage 1: the digits of this run of items, once; D[b][j][j] is c1's own limb j in NTT form
-        const u64 *coeff = c1;
-        u64 coeff_bs = in.bstride;
-        if (ckks) coeff = ks_coeff_target(c1, coeff_bs, tt, k, s);
-        ks_expand_digits(coeff, coeff_bs, D, k, s);
+        hoist_digits(c1, in.bstride, D, tt, k, s); // stage 1: of this run of items, once
         // stages 2 and 3: the baby inner products, HOIST_MAX_ROT at a time, kept only until every row has taken its plaintext-weighted share of them
         for (u64 j0 = 0; j0 < nrb; j0 += HOIST_MAX_ROT) {
             HoistArgs hm;
@@ -972,36 +968,16 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
                 if (any || !hi.accumulate) launch_bsgs_inner(W, accU, a, hi, s);
             }
         }
-        if (!ckks) {
-            launch_copy_strided(c0, in.bstride, c0n, pw, pw, nb, s);
-            launch_ntt(c0n, c.d_desc, map, nb * dl, c.logn, false, s);
-        }
+        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, a, s);
         bool acc_started = false;
         for (u64 i0 = 0; i0 < n2; i0 += gc) {
             const u64 gn = std::min(gc, n2 - i0);
             // the bases of the rows, in NTT form, as galois_plain_sum_hoisted makes them: every present pair of the row, both polynomials
-            for (u64 ii = 0; ii < gn; ii++) {
-                u64 *bu = baseU + ii * nb * 2 * pw;
-                HoistLtArgs h;
-                std::memset(&h, 0, sizeof(h));
-                auto flush = [&] {
-                    if (!h.rots) return;
-                    if (ckks) launch_hoist_lt_base(c0, in.bstride, c1, in.bstride, N, bu, 2 * pw, 2, a, h, s);
-                    else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, bu, 2 * pw, 2, a, h, s);
-                    std::memset(&h, 0, sizeof(h));
-                    h.accumulate = 1;
-                };
-                for (int j = 0; j < n_baby; j++)
-                    if (const u64 *p = plains[(size_t)rows[i0 + ii] * n_baby + j]) {
-                        h.pt[h.rots] = p; h.elt[h.rots] = baby_elts[j];
-                        if (++h.rots == HOIST_MAX_ROT) flush();
-                    }
-                flush();
-            }
+            for (u64 ii = 0; ii < gn; ii++) hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, D, 2, baseU + ii * nb * 2 * pw, a, s);
             if (!ckks) launch_ntt(baseU, c.d_desc, map, gn * nb * 2 * dl, c.logn, true, s);
             // u_i of the chunk: ONE second half over rows x items
-            CtBatch o = out;
             if (nrb) {
+                CtBatch o = out;
                 o.data = U; o.bstride = 2 * pw;
                 a.batch = gn * nb;
                 c.arena.rewind(mark);
@@ -1012,11 +988,7 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
             u64 gr = 0;
             while (gr < gn && giant_elts[rows[i0 + gr]] != 1) gr++;
             if (gr) {
-                KsPlan kg = ks_plan(L, gr * nb);
-                const u64 *cg = U + pw;
-                u64 cg_bs = 2 * pw;
-                if (ckks) cg = ks_coeff_target(U + pw, cg_bs, ttG, kg, s);
-                ks_expand_digits(cg, cg_bs, DG, kg, s);
+                hoist_digits(U + pw, 2 * pw, DG, ttG, ks_plan(L, gr * nb), s);
                 HoistSumArgs hs;
                 std::memset(&hs, 0, sizeof(hs));
                 hs.rots = (u32)gr; hs.accumulate = acc_started ? 1 : 0;
@@ -1031,13 +1003,7 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
             for (u64 r = 0; r < gn; r++) hb.elt[r] = giant_elts[rows[i0 + r]];
             launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, a, hb, s);
         }
-        CtBatch o = out;
-        o.data = out.data + b0 * out.bstride;
-        if (!acc_started) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, nb, s); // every used giant is 1: the sum of the u_i, no key read, no second mod-down
-        else {
-            c.arena.rewind(mark);
-            ks_acc_to_ct(o, acc, k, s, KsBase{base, 2 * pw, 2});
-        }
+        hoist_lt_finish(acc_started, out, b0, acc, base, 2, mark, k, s); // every used giant is 1: the sum of the u_i, no second mod-down
         stats::counter(stats::BSGS_SLABS)++;
     }
 }
@@ -1102,8 +1068,7 @@ void Evaluator::multiply_plain_accumulate(const CtBatch *cts, const u64 *const *
 // summed BEFORE the one floor and the one Shenoy-Kumaresan step (hostmath.cpp above RnsLevel::build: D = sum_r D_r, F = floor(t D / q) - alpha').
 // The auxiliary base holds the reference's margin for ONE product; R of them need ceil(log2 R) more bits: multiply_sum_max_terms.
 // Scratch of BGV / BFV, per item of a run, in words (mw = N (limbs + |Bsk|), BGV: |Bsk| = 0): 3 mw [the sums] + pairs per chunk x 4 mw [the transformed
-// operands].  A run is the whole batch with as many pairs per chunk as fit, or -- where one pair of the whole batch does not fit -- a run of items
-// with one pair per chunk; later chunks accumulate.  Below one item with one pair the call is refused.
+// operands].  The units of plan_slabs are the pairs; later chunks accumulate.
 int Evaluator::multiply_sum_max_terms(int limbs) const {
     if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
     if (c.scheme != SCHEME_BFV) return TENSOR_SUM_MAX;
@@ -1117,7 +1082,7 @@ int Evaluator::multiply_sum_max_terms(int limbs) const {
 size_t Evaluator::scratch_multiply_sum(int limbs, int count, u64 batch) const {
     if (c.scheme == SCHEME_CKKS) return (size_t)batch * 3 * c.N * limbs + 64;
     const size_t mw = (size_t)c.N * (limbs + (c.scheme == SCHEME_BFV ? c.level(limbs).rns.Bsk.size() : 0));
-    return (size_t)batch * mw * (3 + 4 * (size_t)count) + 32 * 8 + 128;
+    return (size_t)batch * mw * (3 + 4 * (size_t)count) + slab_slack(8);
 }
 void Evaluator::multiply_sum(const CtBatch *as, const CtBatch *bs_, int count, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s) {
     if (count < 1 || count > TENSOR_SUM_MAX || !as || !bs_) throw Error(ST_INVALID_ARGUMENT, "multiply_sum takes 1 to 16 products");
@@ -1131,9 +1096,7 @@ void Evaluator::multiply_sum(const CtBatch *as, const CtBatch *bs_, int count, C
         check_ct(b);
         if (a.size != 2 || b.size != 2) throw Error(ST_INVALID_ARGUMENT, "multiply_sum takes size-2 operands");
         if (a.limbs != L || b.limbs != L) throw Error(ST_INVALID_ARGUMENT, "encrypted1 and encrypted2 parameter mismatch");
-        if (c.scheme == SCHEME_BFV && (a.ntt || b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
-        if (c.scheme == SCHEME_CKKS && !(a.ntt && b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
-        if (c.scheme == SCHEME_BGV && (a.ntt || b.ntt)) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
+        check_product_form(a.ntt, b.ntt);
         if (c.scheme == SCHEME_CKKS) { // what multiply says of the pair, then what add says of its product against pair 0's
             const double sc = a.scale * b.scale;
             if (!scale_ok(sc, L)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
@@ -1147,12 +1110,10 @@ void Evaluator::multiply_sum(const CtBatch *as, const CtBatch *bs_, int count, C
     }
     if (c.scheme == SCHEME_BFV && count > multiply_sum_max_terms(L)) throw Error(ST_INVALID_ARGUMENT, "too many products for the auxiliary base");
     if (!out.data || out.bstride < 3 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
-    if (batch)
-        for (int r = 0; r < 2 * count; r++) { // every pair reads its operands whole: the destination must not share a word with any of them
-            const CtBatch &x = r < count ? as[r] : bs_[r - count];
-            const u64 *x_end = x.data + (batch - 1) * x.bstride + 2 * pw, *out_end = out.data + (batch - 1) * out.bstride + 3 * pw;
-            if (out.data < x_end && x.data < out_end) throw Error(ST_INVALID_ARGUMENT, "the destination cannot be one of the operands");
-        }
+    for (int r = 0; batch && r < 2 * count; r++) { // every pair reads its operands whole: the destination must not share a word with any of them
+        const CtBatch &x = r < count ? as[r] : bs_[r - count];
+        if (batches_overlap(out.data, batch, out.bstride, 3 * pw, x.data, batch, x.bstride, 2 * pw)) throw Error(ST_INVALID_ARGUMENT, "the destination cannot be one of the operands");
+    }
     out.size = 3; out.limbs = L; out.ntt = as[0].ntt; out.scale = c.scheme == SCHEME_CKKS ? scale0 : as[0].scale; out.cf = c.scheme == SCHEME_BGV ? cf0 : as[0].cf;
     if (!batch) return;
     const LimbMap qmap = c.ct_map(L);
@@ -1177,18 +1138,14 @@ void Evaluator::multiply_sum(const CtBatch *as, const CtBatch *bs_, int count, C
     const Level *lv = bfv ? &c.level(L) : nullptr;
     const u64 nbk = bfv ? lv->rns.Bsk.size() : 0, bw = nbk * N, mw = pw + bw;
     const LimbMap bmap = bfv ? c.ids_map(lv->bsk_ids) : qmap;
-    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
-    const u64 slack = 32 * 8 + 128; // Arena::take rounds each of at most eight blocks up to 32 words
     // a pair is budgeted its two operands (4 mw) even where the chunk transforms an operand once (a square, a vector shared by every pair): such calls
     // may run in more chunks than their scratch needs -- conservative, and the plan depends on the counts alone, not on which buffers repeat
     const u64 per_item = 3 * mw, per_pair_item = 4 * mw;
-    if (per_item + per_pair_item + slack > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one product of one ciphertext");
-    u64 bs = batch, pc = 1;
-    if (batch * (per_item + per_pair_item) + slack <= limit) pc = std::min<u64>((u64)count, (limit - slack - batch * per_item) / (batch * per_pair_item));
-    else bs = (limit - slack) / (per_item + per_pair_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, 8, per_item, per_pair_item, batch, (u64)count, "scratch_limit_words is too small for one product of one ciphertext");
+    const u64 bs = plan.items, pc = plan.units;
 
     c.arena.begin(s);
-    c.arena.reserve(bs * per_item + pc * bs * per_pair_item + slack);
+    c.arena.reserve(plan.words);
     u64 *xq = c.arena.take(pc * bs * 4 * pw), *xb = bfv ? c.arena.take(pc * bs * 4 * bw) : nullptr;
     u64 *dq = c.arena.take(bs * 3 * pw), *db = bfv ? c.arena.take(bs * 3 * bw) : nullptr;
     for (u64 i0 = 0; i0 < batch; i0 += bs) {
@@ -1276,9 +1233,7 @@ static PlainArgs plain_args(Context &c, int limbs, u64 n_coeffs, u64 plain_bstri
 void Evaluator::add_plain(CtBatch &ct, const u64 *plain, u64 n_coeffs, u64 plain_bstride, double plain_scale, bool sub, u64 batch, hipStream_t s) {
     check_ct(ct);
     if (!plain) throw Error(ST_INVALID_ARGUMENT, "plain is not valid for encryption parameters");
-    if (c.scheme == SCHEME_BFV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BFV encrypted cannot be in NTT form");
-    if (c.scheme == SCHEME_CKKS && !ct.ntt) throw Error(ST_INVALID_ARGUMENT, "CKKS encrypted must be in NTT form");
-    if (c.scheme == SCHEME_BGV && ct.ntt) throw Error(ST_INVALID_ARGUMENT, "BGV encrypted cannot be in NTT form");
+    check_ks_form(ct.ntt);
     if (c.scheme == SCHEME_CKKS) {
         if (std::fabs(ct.scale - plain_scale) >= std::ldexp(1.0, -23)) throw Error(ST_INVALID_ARGUMENT, "scale mismatch");
         const PlainArgs a = plain_args(c, ct.limbs, c.N, plain_bstride, batch, 1);
@@ -1437,9 +1392,7 @@ void Evaluator::evaluate_polynomial(const CtBatch &in, CtBatch &out, const u64 *
     if (ckks ? (!coeffs || coeffs_mod_t) : (!coeffs_mod_t || coeffs)) throw Error(ST_INVALID_ARGUMENT, "the coefficients do not match the scheme");
     check_ct(in);
     if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "evaluate_polynomial takes a size-2 operand");
-    if (bfv && in.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 cannot be in NTT form");
-    if (ckks && !in.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted1 or encrypted2 must be in NTT form");
-    if (bgv && in.ntt) throw Error(ST_INVALID_ARGUMENT, "encryped1 or encrypted2 must be not in NTT form");
+    check_product_form(in.ntt, in.ntt);
     const int k = pl.k, m = pl.m, L0 = in.limbs;
     std::vector<char> nz(degree + 1);
     for (int j = 0; j <= degree; j++) {

@@ -149,6 +149,19 @@ private:
     void ks_expand_digits(const u64 *coeff, u64 coeff_bstride, u64 *D, const KsPlan &k, hipStream_t s);
     void ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsPlan &k, hipStream_t s);
     void ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsPlan &k, hipStream_t s, KsBase base);
+    // what the hoisted calls share, each next to its first user in evaluator.cpp:
+    // the digits of the c1 of k.a.batch items (stride bstride) into D; tt: room for c1 in coefficient form (CKKS)
+    void hoist_digits(const u64 *c1, u64 bstride, u64 *D, u64 *tt, const KsPlan &k, hipStream_t s);
+    // the checks of a size-2 operand and its destination of out_items items, and the output's metadata; plain_scale: null for plain rotations.
+    // `what` names the call in the messages.  False: the batch is empty, nothing to do
+    bool hoist_operands(const char *what, const CtBatch &in, CtBatch &out, const double *plain_scale, u64 out_items, u64 batch) const;
+    void hoist_c0_to_ntt(const u64 *c0, u64 bstride, u64 *c0n, const KsArgs &a, hipStream_t s); // BFV / BGV: a dense copy of c0, transformed forward
+    // dst [k.a.batch][polys][dl][N] = sum over the non-null plains[i] of plains[i] * galois_{elts[i]}(c0 and, polys == 2, c1), in NTT form
+    void hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const u64 *D, int polys, u64 *dst, const KsArgs &a,
+                       hipStream_t s);
+    // the result of a slab of a linear transform from item b0 of out on: the base itself (no element other than 1) or the second half over acc onto the base
+    void hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s);
+    void check_product_form(bool a_ntt, bool b_ntt) const; // the form a product of the scheme takes its two operands in
     bool scale_ok(double scale, int limbs) const;
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void balance_correction(u64 f1, u64 f2, u64 &f, u64 &e1, u64 &e2) const;
