@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -377,6 +377,28 @@ int troyhip_apply_key_switching(troyhip_context *ctx, troyhip_ct *ct, const uint
 int troyhip_negacyclic_shift(troyhip_context *ctx, troyhip_ct *ct, uint64_t shift, uint64_t batch, void *stream);
 /* divideByPolyModulusDegreeInplace (src/evaluator_cuda.cu:2259-2273): every limb times N^-1 * mul modulo its prime (LWE packing) */
 int troyhip_divide_by_poly_modulus_degree(troyhip_context *ctx, troyhip_ct *ct, uint64_t mul, uint64_t batch, void *stream);
+/* ---- LWE extraction and packing on the device, one call each.  BFV / BGV, coefficient form, any level.  A dense LWE batch holds
+ * `count` samples of each of `batch` items in device memory: c1 [count][batch][limbs][N] words, c0 [count][batch][limbs] words.  Stream-ordered; nothing is
+ * read back. ---- */
+/* extractLWE (src/evaluator_cuda.cu:2213-2246) for every term of every item: c1_out[j][b] = X^(2N - terms[j]) c1(ct_b) (no shift for term 0), c0_out[j][b][l] =
+ * coefficient terms[j] of limb l of c0(ct_b).  terms: HOST words below N, 1 <= count <= N, repeats allowed.  in->size must be 2 ("Encrypted size must be 2 to
+ * be extracted.").  An operand in NTT form (CKKS) is transformed to coefficient form in scratch first; the operand is not modified.  The destinations share
+ * no word with the operand or with each other. */
+int troyhip_extract_lwes(troyhip_context *ctx, const troyhip_ct *in, const uint64_t *terms, uint64_t count, uint64_t *c1_out, uint64_t *c0_out, uint64_t batch, void *stream);
+/* packLWECiphertexts + fieldTraceInplace + divideByPolyModulusDegreeInplace (src/evaluator_cuda.cu:2248-2340) over a dense LWE batch: out item b is, byte for
+ * byte, what the reference's order of operations gives for the samples [.][b]: coefficient i * (N >> ceil(log2 count)) of its decryption is message i.  Per layer
+ * of the tree and per round of the field trace ONE merge launch and ONE key switch over all (pair, item) units, so the key of element 2^k + 1 is streamed once
+ * per step; a leaf past the count costs nothing.  keys[i] is the Galois key of element key_elts[i]; the elements 2^k + 1, k = 1 .. log2 N, are looked up
+ * ("Galois key not present").  limbs, scale and correction_factor describe the samples and become the result's.  out->data, ->batch_stride are INPUTS (two
+ * polynomials per item), sharing no word with the samples.  The arena request stays under scratch_limit_words (0: 2^28 words): a step that does not fit runs in
+ * chunks of units, and the result does not depend on the limit or on the batch size; below one unit (troyhip_pack_lwes_scratch_words(.., 1, 1)) the call is
+ * refused.  The nodes of the tree come from the caching pool (troyhip_malloc's).  "LWE ciphertexts must not be empty." for count < 1; count > N is refused.
+ * CKKS is TROYHIP_LOGIC_ERROR "unsupported scheme": the reference packs CKKS samples only at count == N (every other count runs its field trace on a
+ * coefficient-form ciphertext, which its key switch refuses), and that case is out of scope here.  Counters "lwe_pack_key_switches", "lwe_pack_chunks". */
+int troyhip_pack_lwes(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t count, int limbs, double scale, uint64_t correction_factor,
+                      const uint32_t *key_elts, const uint64_t *const *keys, int n_keys, troyhip_ct *out, uint64_t batch, uint64_t scratch_limit_words, void *stream);
+/* the arena words troyhip_pack_lwes asks for when every step runs as one chunk: a host-only function of (limbs, count, batch) */
+int troyhip_pack_lwes_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, uint64_t *words);
 /* ---- DecryptorCuda::decrypt (src/decryptor_cuda.cu:61-330; dotProductCtSkArray + decryptScaleAndRound / decryptModt,
  * src/utils/rns_cuda.cu:510-621), SURVEY 8-f3.  secret_key: device [K][N] (NTT form, src/secretkey.h).  plain_out (device):
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */

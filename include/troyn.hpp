@@ -984,6 +984,27 @@ private:
     std::vector<uint64_t> c0_;
 };
 
+// `count` LWE samples of one ciphertext's level, dense on the device (troyhip_extract_lwes / troyhip_pack_lwes): c1 [count][limbs][N]
+// words in coefficient form, c0 [count][limbs] words.  Sample j is what extractLWE returns for term j; nothing of it lives on the host.
+class LWEBatch {
+public:
+    const ParmsID &parmsID() const { return parms_id_; }
+    size_t count() const { return count_; }
+    size_t polyModulusDegree() const { return n_; }
+    size_t coeffModulusSize() const { return limbs_; }
+    double scale() const { return scale_; }
+    uint64_t correctionFactor() const { return cf_; }
+    const DeviceArray &c1() const { return c1_; }
+    const DeviceArray &c0() const { return c0_; }
+private:
+    friend class Evaluator;
+    ParmsID parms_id_;
+    size_t count_ = 0, n_ = 0, limbs_ = 0;
+    double scale_ = 1.0;
+    uint64_t cf_ = 1;
+    DeviceArray c1_, c0_;
+};
+
 class KeyGenerator { // src/keygenerator_cuda.cuh: runs on the CPU
 public:
     // KeyGenerator(context): the key stream is seeded from the operating system's entropy source, as the reference's default
@@ -2477,6 +2498,57 @@ public:
         fieldTraceInplace(ret, automorphism_keys, l);
         if (ckks) transformToNttInplace(ret);
         return ret;
+    }
+    // The same on the device in one call each (troyhip_extract_lwes / troyhip_pack_lwes): nothing goes through the host, and the
+    // packing runs one merge launch and one key switch per layer of the tree and per round of the field trace.  BFV / BGV; packing under CKKS is refused
+    // (the reference packs CKKS samples only at count == N; that case is out of scope).  packLWEs returns, byte for byte, what packLWECiphertexts returns.
+    LWEBatch extractLWEs(const Ciphertext &encrypted, const std::vector<size_t> &terms) const {
+        if (encrypted.size() != 2) throw std::invalid_argument("Encrypted size must be 2 to be extracted.");
+        if (terms.empty()) throw std::invalid_argument("LWE ciphertexts must not be empty.");
+        const size_t N = c_.polyModulusDegree(), L = encrypted.coeffModulusSize();
+        LWEBatch out;
+        out.parms_id_ = encrypted.parmsID(); out.count_ = terms.size(); out.n_ = N; out.limbs_ = L; out.scale_ = encrypted.scale(); out.cf_ = encrypted.correctionFactor();
+        out.c1_.resize(terms.size() * L * N);
+        out.c0_.resize(terms.size() * L);
+        const std::vector<uint64_t> t(terms.begin(), terms.end());
+        check(troyhip_extract_lwes(h(), encrypted.raw(), t.data(), t.size(), out.c1_.get(), out.c0_.get(), 1, nullptr));
+        return out;
+    }
+    Ciphertext packLWEs(const LWEBatch &lwes, const GaloisKeys &automorphism_keys) const {
+        if (!lwes.count_) throw std::invalid_argument("LWE ciphertexts must not be empty.");
+        const size_t N = c_.polyModulusDegree();
+        std::vector<uint32_t> elts;
+        std::vector<const uint64_t *> keys;
+        for (size_t d = 2; d <= N; d <<= 1) { // the automorphisms 2^k + 1 of the layers and of the trace; the library names the one that is missing
+            const uint32_t elt = (uint32_t)(d + 1);
+            if (!automorphism_keys.hasKey(elt)) continue;
+            elts.push_back(elt);
+            keys.push_back(key_of(automorphism_keys, GaloisKeys::getIndex(elt)));
+        }
+        Ciphertext out;
+        out.resize(N, lwes.limbs_, 2);
+        check(troyhip_pack_lwes(h(), lwes.c1_.get(), lwes.c0_.get(), lwes.count_, (int)lwes.limbs_, lwes.scale_, lwes.cf_, elts.data(), keys.data(), (int)elts.size(), out.raw(), 1, 0,
+                                nullptr));
+        out.bind(c_);
+        return out;
+    }
+    Ciphertext packLWEs(const std::vector<LWECiphertext> &lwes, const GaloisKeys &automorphism_keys) const {
+        if (lwes.empty()) throw std::invalid_argument("LWE ciphertexts must not be empty.");
+        for (const LWECiphertext &w : lwes)
+            if (w.parmsID() != lwes[0].parmsID()) throw std::invalid_argument("LWE ciphertexts must have same parmsID.");
+        const size_t N = lwes[0].n_, L = lwes[0].limbs_;
+        LWEBatch b;
+        b.parms_id_ = lwes[0].parms_id_; b.count_ = lwes.size(); b.n_ = N; b.limbs_ = L; b.scale_ = lwes[0].scale_; b.cf_ = lwes[0].cf_;
+        b.c1_.resize(lwes.size() * L * N);
+        std::vector<uint64_t> c0(lwes.size() * L);
+        for (size_t j = 0; j < lwes.size(); j++) {
+            check(troyhip_copy_d2d(b.c1_.get() + j * L * N, lwes[j].c1_.get(), L * N * 8, nullptr));
+            std::copy(lwes[j].c0_.begin(), lwes[j].c0_.end(), c0.begin() + (long)(j * L));
+        }
+        b.c0_.resize(c0.size());
+        check(troyhip_copy_h2d(b.c0_.get(), c0.data(), c0.size() * 8, nullptr));
+        check(troyhip_stream_synchronize(nullptr)); // c0 is a local: the copy has read it before it goes
+        return packLWEs(b, automorphism_keys);
     }
 
 private:

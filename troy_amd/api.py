@@ -341,6 +341,56 @@ class LWECiphertext:
         self.c1, self.c0 = c1, np.ascontiguousarray(c0, dtype=np.uint64)
 
 
+class LWEBatch:
+    """`count` LWE samples of each of `batch` items, dense on the device (troyhip_extract_lwes / troyhip_pack_lwes):
+    c1 [count][batch][limbs][N] words and c0 [count][batch][limbs] words, coefficient form.  Sample j is what extractLWE returns for term j."""
+
+    def __init__(self, context, count, batch, limbs, scale=1.0, correction_factor=1, c1=None, c0=None):
+        self.context, self.count, self.batch, self.limbs = context, int(count), int(batch), int(limbs)
+        self.scale, self.correction_factor = float(scale), int(correction_factor)
+        self.c1 = c1 if c1 is not None else DeviceBuffer(max(self.count * self.batch * self.limbs * context.N, 1))
+        self.c0 = c0 if c0 is not None else DeviceBuffer(max(self.count * self.batch * self.limbs, 1))
+
+    def c1_cpu(self):
+        return self.c1.to_numpy(self.count * self.batch * self.limbs * self.context.N).reshape(self.count, self.batch, self.limbs, self.context.N)
+
+    def c0_cpu(self):
+        return self.c0.to_numpy(self.count * self.batch * self.limbs).reshape(self.count, self.batch, self.limbs)
+
+    def to_list(self):
+        """-> [LWECiphertext] * count (c1 copied device to device, c0 read back: LWECiphertext keeps it on the host)"""
+        words = self.batch * self.limbs * self.context.N
+        c0 = self.c0_cpu()
+        out = []
+        for j in range(self.count):
+            c1 = Ciphertext(self.context, self.batch, 1, self.limbs, False, self.scale, self.correction_factor)
+            c1.buf.copy_from(self.c1, words, src_offset_words=j * words)
+            out.append(LWECiphertext(c1, c0[j]))
+        return out
+
+    @classmethod
+    def from_list(cls, lwes):
+        if not lwes:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE ciphertexts must not be empty.")
+        a = lwes[0].c1
+        ctx, B, L = a.context, a.batch, a.limbs
+        row = L * ctx.N
+        self = cls(ctx, len(lwes), B, L, a.scale, a.correction_factor)
+        c0 = np.zeros((len(lwes), B, L), dtype=np.uint64)
+        for j, lwe in enumerate(lwes):
+            c = lwe.c1
+            if c.context is not ctx or (c.batch, c.limbs, c.size()) != (B, L, 1) or c.is_ntt_form or np.shape(lwe.c0) != (B, L):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE ciphertexts of one call share their shape")
+            if c.bstride == row:
+                self.c1.copy_from(c.buf, B * row, dst_offset_words=j * B * row)
+            else:
+                for b in range(B):
+                    self.c1.copy_from(c.buf, row, src_offset_words=b * c.bstride, dst_offset_words=(j * B + b) * row)
+            c0[j] = lwe.c0
+        self.c0 = DeviceBuffer.from_numpy(c0)
+        return self
+
+
 class KSwitchKeys:
     """KSwitchKeysCuda (src/kswitchkeys_cuda.cuh:43-56): data()[index] = one key-switching key, uploaded from
     the host array [K-1][2][K][N] (NTT form)."""
@@ -767,6 +817,46 @@ class Evaluator:
         if ckks:
             self.transformToNttInplace(ret)
         return ret
+
+    # -- the same on the device in one call each (troyhip_extract_lwes / troyhip_pack_lwes, DESIGN.md section 4.15)
+    def extractLWEs(self, a, terms):
+        """[extractLWE(a, t) for t in terms] as one LWEBatch: one kernel over terms x items, nothing read back"""
+        if a.size() != 2:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Encrypted size must be 2 to be extracted.")
+        terms = [int(t) for t in terms]
+        if not terms:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE ciphertexts must not be empty.")
+        if min(terms) < 0:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "term index out of range")
+        out = LWEBatch(a.context, len(terms), a.batch, a.limbs, a.scale, a.correction_factor)
+        arr = np.array(terms, dtype=np.uint64)
+        st = a.struct()
+        self._chk(self.lib.troyhip_extract_lwes(self.context.h, C.byref(st), _u64p(arr), C.c_uint64(len(terms)), C.c_void_p(out.c1.ptr), C.c_void_p(out.c0.ptr),
+                                                C.c_uint64(a.batch), self.stream))
+        return out
+
+    def packLWEs(self, lwes, galois_keys, scratch_limit_words=0):
+        """packLWECiphertexts(lwes, galois_keys), byte for byte, with one merge launch and one key switch per layer of the tree and per round of the field
+        trace (BFV / BGV).  lwes: an LWEBatch or a list of LWECiphertext."""
+        if not isinstance(lwes, LWEBatch):
+            lwes = LWEBatch.from_list(list(lwes))
+        ctx = self.context
+        elts = [2 * i + 1 for i in galois_keys.keys]
+        e = (C.c_uint32 * max(len(elts), 1))(*elts)
+        k = (C.c_void_p * max(len(elts), 1))(*[galois_keys.keys[i].ptr for i in galois_keys.keys])
+        out = Ciphertext(ctx, lwes.batch, 2, lwes.limbs, capacity=2)
+        so = out.struct()
+        self._chk(self.lib.troyhip_pack_lwes(ctx.h, C.c_void_p(lwes.c1.ptr), C.c_void_p(lwes.c0.ptr), C.c_uint64(lwes.count), int(lwes.limbs), C.c_double(lwes.scale),
+                                             C.c_uint64(lwes.correction_factor), e, k, len(elts), C.byref(so), C.c_uint64(lwes.batch), C.c_uint64(scratch_limit_words),
+                                             self.stream))
+        out._absorb(so)
+        return out
+
+    def packLWEsScratchWords(self, limbs, count, batch):
+        """the arena words packLWEs asks for with every step in one chunk (troyhip_pack_lwes_scratch_words)"""
+        w = C.c_uint64(0)
+        self._chk(self.lib.troyhip_pack_lwes_scratch_words(self.context.h, int(limbs), C.c_uint64(count), C.c_uint64(batch), C.byref(w)))
+        return w.value
 
     def _copy_then(self, fn, a, *args):
         r = a.copy()

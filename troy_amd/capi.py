@@ -63,6 +63,7 @@ SYMBOLS = [
     "troyhip_mod_switch_to_next", "troyhip_rescale_to_next", "troyhip_apply_galois", "troyhip_apply_galois_hoisted", "troyhip_galois_plain_sum_hoisted", "troyhip_galois_plain_sum_bsgs", "troyhip_multiply_sum", "troyhip_multiply_sum_max_terms", "troyhip_scalar_combine", "troyhip_evaluate_polynomial", "troyhip_polynomial_depth", "troyhip_rotate",
     "troyhip_transform_to_ntt", "troyhip_transform_from_ntt", "troyhip_multiply_plain_ntt", "troyhip_add_plain", "troyhip_multiply_plain",
     "troyhip_stat", "troyhip_build_id", "troyhip_host_batch_encode", "troyhip_host_batch_decode", "troyhip_plain_to_ntt", "troyhip_decrypt", "troyhip_apply_key_switching", "troyhip_negacyclic_shift", "troyhip_divide_by_poly_modulus_degree",
+    "troyhip_extract_lwes", "troyhip_pack_lwes", "troyhip_pack_lwes_scratch_words",
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",

@@ -982,6 +982,38 @@ int troyhip_negacyclic_shift(troyhip_context *ctx, troyhip_ct *ct, uint64_t shif
 int troyhip_divide_by_poly_modulus_degree(troyhip_context *ctx, troyhip_ct *ct, uint64_t mul, uint64_t batch, void *stream) {
     return guard([&] { CtBatch x = view(ct); need(ctx)->ev.divide_by_degree(x, mul, batch, on(stream)); store(x, ct); });
 }
+/* LWE extraction and packing on the device (evaluator_cuda.cu:2213-2340) */
+int troyhip_extract_lwes(troyhip_context *ctx, const troyhip_ct *in, const uint64_t *terms, uint64_t count, uint64_t *c1_out, uint64_t *c0_out, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!in) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx);
+        hipStream_t s = on(stream);
+        handle->ev.extract_lwes(view(in), terms, count, c1_out, c0_out, batch, s);
+    });
+}
+int troyhip_pack_lwes(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t count, int limbs, double scale, uint64_t correction_factor,
+                      const uint32_t *key_elts, const uint64_t *const *keys, int n_keys, troyhip_ct *out, uint64_t batch, uint64_t scratch_limit_words, void *stream) {
+    return guard([&] {
+        if (!out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        if (n_keys < 0 || (n_keys && (!key_elts || !keys))) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+        auto *handle = need(ctx);
+        hipStream_t s = on(stream);
+        std::vector<KsKey> k((size_t)n_keys);
+        for (int i = 0; i < n_keys; i++) k[(size_t)i] = KsKey{keys[i]};
+        CtBatch o = view(out);
+        DeviceAlloc mem; // the nodes of the tree outlive every key switch's use of the context arena: the caching pool, as troyhip_evaluate_polynomial
+        mem.get = [](size_t words) { return (u64 *)DevicePool::instance().get(words * sizeof(u64)); };
+        mem.put = [](u64 *p) { DevicePool::instance().put(p); };
+        handle->ev.pack_lwes(c1, c0, count, limbs, scale, correction_factor, key_elts, k.data(), n_keys, o, batch, scratch_limit_words, mem, s);
+        store(o, out);
+    });
+}
+int troyhip_pack_lwes_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null");
+        *words = need(ctx)->ev.pack_lwes_scratch_words(limbs, count, batch);
+    }, false);
+}
 int troyhip_random_bytes(void *out, size_t n) { // the reference seeds its PRNG from std::random_device (src/randomgen.cpp:23,72)
     return guard([&] {
         unsigned char *p = static_cast<unsigned char *>(out);

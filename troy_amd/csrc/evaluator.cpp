@@ -1662,6 +1662,122 @@ void Evaluator::divide_by_degree(CtBatch &ct, u64 mul, u64 batch, hipStream_t s)
     else for (u64 b = 0; b < batch; b++) launch_mul_scalar(ct.data + b * ct.bstride, c.d_desc, map, sc, c.logn, (u64)ct.size * ct.limbs, s);
 }
 
+// ---- LWE extraction and packing in one call ----
+// extractLWE (evaluator_cuda.cu:2213-2246) for every term of every item: one kernel, nothing read back
+void Evaluator::extract_lwes(const CtBatch &in, const u64 *terms, u64 count, u64 *c1_out, u64 *c0_out, u64 batch, hipStream_t s) {
+    check_ct(in);
+    if (in.size != 2) throw Error(ST_INVALID_ARGUMENT, "Encrypted size must be 2 to be extracted.");
+    if (count < 1) throw Error(ST_INVALID_ARGUMENT, "LWE ciphertexts must not be empty.");
+    if (count > c.N) throw Error(ST_INVALID_ARGUMENT, "more LWE ciphertexts than coefficients");
+    if (!terms || !c1_out || !c0_out) throw Error(ST_INVALID_ARGUMENT, "extract_lwes: null pointer");
+    for (u64 j = 0; j < count; j++)
+        if (terms[j] >= c.N) throw Error(ST_INVALID_ARGUMENT, "term index out of range");
+    if (!batch) return;
+    const u64 L = in.limbs, pw = poly_words(c, in.limbs), c1_words = count * batch * pw, c0_words = count * batch * L;
+    if (batches_overlap(c1_out, 1, 0, c1_words, in.data, batch, in.bstride, 2 * pw) || batches_overlap(c0_out, 1, 0, c0_words, in.data, batch, in.bstride, 2 * pw) ||
+        batches_overlap(c1_out, 1, 0, c1_words, c0_out, 1, 0, c0_words))
+        throw Error(ST_INVALID_ARGUMENT, "extract_lwes: the destinations must be distinct buffers");
+    c.arena.begin(s);
+    c.arena.reserve(count + (in.ntt ? batch * 2 * pw : 0) + 128);
+    u64 *d_terms = c.arena.take(count);
+    upload(std::vector<u64>(terms, terms + count), d_terms, s);
+    const u64 *src = in.data;
+    u64 stride = in.bstride;
+    if (in.ntt) { // as extractLWE: a copy in coefficient form, the operand stays as it is
+        u64 *tmp = c.arena.take(batch * 2 * pw);
+        launch_copy_strided(in.data, in.bstride, tmp, 2 * pw, 2 * pw, batch, s);
+        launch_ntt(tmp, c.d_desc, c.ct_map(in.limbs), batch * 2 * L, c.logn, true, s);
+        src = tmp;
+        stride = 2 * pw;
+    }
+    launch_lwe_extract(src, stride, d_terms, c1_out, c0_out, c.d_desc, c.ct_map(in.limbs), c.logn, L, count, batch, s);
+}
+
+// packLWECiphertexts + fieldTraceInplace (evaluator_cuda.cu:2248-2340) over a dense LWE batch.  Nodes are indexed by the BIT-REVERSED position of the
+// reference's list: leaf r is sample r, a layer of n_in nodes merges node r (even) with node r + half (odd), half = 2^(l - layer - 1), into node r of the next
+// layer -- the present nodes of every layer are a prefix, the pairs whose odd is present a prefix of the pairs, and a pair of two absent subtrees has no
+// index at all.  A unit is one pair of one item; a step (layer or trace round) runs its units in chunks: one lwe_merge launch, one key switch whose mod-down
+// writes the merged node.  Arena per unit: the key switch's own scratch and N 3 dl words (base, target) behind it, as apply_galois keeps its temporaries.
+// The nodes live in ONE pool block of the widest merged layer: step k writes node r over the even it was merged from, which no later chunk reads.
+static u64 lwe_pack_unit_words(const Context &c, int limbs) {
+    const u64 N = c.N, dl = limbs, rl = dl + 1;
+    return N * (dl + rl * dl + 2 * rl + 2 * dl + 2) + 3 * dl * N;
+}
+static const u64 LWE_PACK_BLOCKS = 16; // slab_slack(16) = 640 words: the 512 of scratch_switch_key and three rounded blocks
+static int lwe_pack_layers(u64 count) {
+    int l = 0;
+    while ((u64(1) << l) < count) l++;
+    return l;
+}
+u64 Evaluator::pack_lwes_scratch_words(int limbs, u64 count, u64 batch) const {
+    if (count < 1) throw Error(ST_INVALID_ARGUMENT, "LWE ciphertexts must not be empty.");
+    if (count > c.N) throw Error(ST_INVALID_ARGUMENT, "more LWE ciphertexts than coefficients");
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    const int l = lwe_pack_layers(count);
+    const u64 pairs = l ? std::min(count, u64(1) << (l - 1)) : 1;
+    return pairs * std::max<u64>(batch, 1) * lwe_pack_unit_words(c, limbs) + slab_slack(LWE_PACK_BLOCKS);
+}
+void Evaluator::pack_lwes(const u64 *c1, const u64 *c0, u64 count, int limbs, double scale, u64 cf, const uint32_t *key_elts, const KsKey *keys, int n_keys, CtBatch &out,
+                          u64 batch, u64 scratch_limit_words, const DeviceAlloc &mem, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: LWE samples are packed under BFV and BGV");
+    if (count < 1) throw Error(ST_INVALID_ARGUMENT, "LWE ciphertexts must not be empty.");
+    if (count > c.N) throw Error(ST_INVALID_ARGUMENT, "more LWE ciphertexts than coefficients");
+    if (!c1 || !c0 || !out.data || n_keys < 0 || (n_keys && (!key_elts || !keys))) throw Error(ST_INVALID_ARGUMENT, "pack_lwes: null pointer");
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    const u64 N = c.N, pw = poly_words(c, limbs);
+    const int logn = c.logn, l = lwe_pack_layers(count);
+    if (out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    std::vector<KsKey> step_key((size_t)logn + 1); // of element 2^k + 1
+    for (int k = 1; k <= logn; k++) {
+        const uint32_t elt = (uint32_t)((u64(1) << k) + 1);
+        for (int i = 0; i < n_keys; i++)
+            if (key_elts[i] == elt && keys[i].data) step_key[(size_t)k] = keys[i];
+        if (!step_key[(size_t)k].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    }
+    out.size = 2; out.limbs = limbs; out.ntt = false; out.scale = scale; out.cf = cf;
+    if (!batch) return;
+    if (batches_overlap(out.data, batch, out.bstride, 2 * pw, c1, 1, 0, count * batch * pw) || batches_overlap(out.data, batch, out.bstride, 2 * pw, c0, 1, 0, count * batch * (u64)limbs))
+        throw Error(ST_INVALID_ARGUMENT, "pack_lwes: destination must be a distinct buffer");
+    const u64 widest = (l ? std::min(count, u64(1) << (l - 1)) : 1) * batch; // units of the first step
+    const SlabPlan plan = plan_slabs(scratch_limit_words, LWE_PACK_BLOCKS, lwe_pack_unit_words(c, limbs), 0, widest, 1, "scratch_limit_words is too small for one pair of one ciphertext");
+    PoolBlocks pool(mem);
+    u64 *nodes = logn > 1 ? pool.get(widest * 2 * pw) : nullptr;
+    const LimbMap map = c.ct_map(limbs);
+    for (int step = 0; step < logn; step++) {
+        const bool layer = step < l, last = step == logn - 1;
+        // a round of the trace is a merge of the one node with an absent odd
+        const u64 n_in = layer ? std::min(count, u64(1) << (l - step)) : 1, half = layer ? u64(1) << (l - step - 1) : 1;
+        const u64 n_out = std::min(n_in, half), n_both = n_in - n_out;
+        const int k = layer ? step + 1 : logn - (step - l); // the automorphism 2^k + 1: layers count up from 3, the trace down from N + 1
+        u64 *dst = last ? out.data : nodes;
+        const u64 dst_stride = last ? out.bstride : 2 * pw, units = n_out * batch;
+        for (u64 u0 = 0; u0 < units; u0 += plan.items) {
+            const u64 nu = std::min(plan.items, units - u0);
+            c.arena.begin(s);
+            c.arena.reserve(plan.words);
+            (void)c.arena.take(scratch_switch_key(limbs, nu)); // switch_key resets the arena and carves its working set from here; what follows stays intact
+            LweMergeArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.nodes = step ? nodes : nullptr;
+            a.node_stride = 2 * pw;
+            a.c1 = c1; a.c0 = c0;
+            a.base = c.arena.take(nu * 2 * pw);
+            a.target = c.arena.take(nu * pw);
+            a.u0 = u0; a.units = nu; a.u_both = n_both * batch; a.odd_offset = half * batch;
+            a.shift = layer ? N >> (step + 1) : 0;
+            a.limbs = (u64)limbs; a.elt = (uint32_t)((u64(1) << k) + 1); a.logn = logn;
+            launch_lwe_merge(a, c.d_desc, map, s);
+            CtBatch node;
+            node.data = dst + u0 * dst_stride; node.bstride = dst_stride; node.size = 2; node.limbs = limbs; node.ntt = false; node.scale = scale; node.cf = cf;
+            switch_key(node, a.target, pw, step_key[(size_t)k], nu, s, KsBase{a.base, 2 * pw, 2});
+            stats::counter(stats::LWE_PACK_KEY_SWITCHES)++;
+            stats::counter(stats::LWE_PACK_CHUNKS)++;
+        }
+    }
+}
+
 // ---- decryption ----
 u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
     const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;

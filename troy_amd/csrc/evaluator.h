@@ -125,6 +125,18 @@ public:
     // come from `mem` (every sub-operation begins the context arena) and go back stream-ordered.  out.data / out.bstride are the caller's.
     void evaluate_polynomial(const CtBatch &in, CtBatch &out, const u64 *coeffs_mod_t, const double *coeffs, int degree, int baby_steps, double out_scale, const KsKey &relin,
                              u64 scratch_limit_words, u64 batch, const DeviceAlloc &mem, hipStream_t s);
+    // LWE extraction and packing on the device (extractLWE / packLWECiphertexts, evaluator_cuda.cu:2213-2340, for a whole batch in
+    // one call).  A dense LWE batch: c1 [count][batch][limbs][N], c0 [count][batch][limbs], device memory, coefficient form.
+    // extract_lwes: sample j of item b is what extractLWE gives for terms[j] (HOST, below N); an operand in NTT form is transformed in scratch; `in` is not
+    // modified and shares no word with the destinations.
+    void extract_lwes(const CtBatch &in, const u64 *terms, u64 count, u64 *c1_out, u64 *c0_out, u64 batch, hipStream_t s);
+    // pack_lwes: out item b = packLWECiphertexts of the samples [.][b], byte for byte (BFV / BGV; CKKS is refused), ONE merge launch and ONE key switch per
+    // layer of the tree and per round of the field trace over all their (pair, item) units -- or per chunk of units where a layer does not fit under
+    // scratch_limit_words (0: 2^28 words).  keys[i]: the Galois key of element key_elts[i]; needed: 2^k + 1, k = 1 .. log2 N.  The nodes come from `mem`.
+    // The result does not depend on the limit or the batch size.  out.data / out.bstride are the caller's; limbs, scale and cf describe the samples.
+    void pack_lwes(const u64 *c1, const u64 *c0, u64 count, int limbs, double scale, u64 cf, const uint32_t *key_elts, const KsKey *keys, int n_keys, CtBatch &out, u64 batch,
+                   u64 scratch_limit_words, const DeviceAlloc &mem, hipStream_t s);
+    u64 pack_lwes_scratch_words(int limbs, u64 count, u64 batch) const; // what pack_lwes asks of the arena with every layer in one chunk
     // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
     // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
     static PolyPlan plan_polynomial(int degree, int baby_steps);

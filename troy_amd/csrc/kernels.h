@@ -157,6 +157,24 @@ struct TensorSumArgs { const u64 *a[TENSOR_SUM_MAX]; const u64 *b[TENSOR_SUM_MAX
 void launch_tensor_sum(const TensorSumArgs &x, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 batch, hipStream_t s);
 void launch_galois(bool ntt_form, const u64 *in, u64 in_bstride, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, uint32_t elt, u64 limbs,
                    u64 batch, hipStream_t s);
+// LWE extraction and packing on the device, coefficient form.  A dense LWE batch: c1 [count][batch][limbs][N], c0 [count][batch][limbs].
+// extract: c1[j][b] = X^(2N - terms[j]) c1(ct_b), c0[j][b][l] = coefficient terms[j] of limb l of c0(ct_b); ct_b at src + b * src_bstride, [2][limbs][N];
+// terms: DEVICE words below N
+void launch_lwe_extract(const u64 *src, u64 src_bstride, const u64 *terms, u64 *c1, u64 *c0, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 count,
+                        u64 batch, hipStream_t s);
+// One merge step of the packing tree over the units u0 .. u0 + units - 1 (a unit: one pair of one item): with temp = X^shift odd and sigma the automorphism elt,
+//   base[u - u0] = (even0 + temp0 + sigma(even0 - temp0), even1 + temp1)  [2][limbs][N],  target[u - u0] = sigma(even1 - temp1)  [limbs][N]
+// `even` of unit u is node u, `odd` node u + odd_offset where u < u_both and absent (zero) elsewhere -- a leaf past the count, or a round of the field trace.
+// Nodes are ciphertexts [2][limbs][N], node_stride apart; leaf form (nodes == nullptr): node u is sample u of the LWE batch (c1, c0), c0 at coefficient 0, times N^-1.
+struct LweMergeArgs {
+    const u64 *nodes; u64 node_stride;
+    const u64 *c1, *c0;
+    u64 *base, *target;
+    u64 u0, units, u_both, odd_offset, shift, limbs;
+    uint32_t elt;
+    int logn;
+};
+void launch_lwe_merge(const LweMergeArgs &a, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
 
 struct ModSwitchArgs {
     const PrimeDesc *primes;

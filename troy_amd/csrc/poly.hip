@@ -521,6 +521,88 @@ void launch_galois(bool ntt_form, const u64 *in, u64 in_bstride, u64 *out, u64 o
     launch_check("galois_kernel");
 }
 
+// ---------------------------------------------------------------- LWE extraction and packing
+// An x grid over the u64 total, one coefficient per thread as in the two kernels above: no grid dimension grows with the batch or the count but x,
+// which holds 2^31 - 1 blocks.
+static dim3 flat_grid(u64 total, const char *what) {
+    const u64 blocks = (total + EW_THREADS - 1) / EW_THREADS;
+    if (blocks >> 31) throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": more than 2^31 - 1 workgroups");
+    return dim3((unsigned)blocks);
+}
+// extractLWE (evaluator_cuda.cu:2213-2246) for `count` terms of `batch` ciphertexts in one pass: the shifted c1 rows are gathered (one read, one whole-line
+// write, no temporary copy: x^(2N - t) moves coefficient j + t to j, negated past N) and the thread of coefficient 0 of a row picks its c0 word
+__global__ __launch_bounds__(EW_THREADS) void lwe_extract_kernel(const u64 *__restrict__ src, u64 src_bstride, const u64 *__restrict__ terms, u64 *__restrict__ c1,
+                                                                u64 *__restrict__ c0, const PrimeDesc *primes, LimbMap map, int logn, u64 limbs, u64 batch, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << logn, row = i >> logn, j = i & (N - 1), l = row % limbs, sb = row / limbs, b = sb % batch, t = terms[sb / batch];
+    const u64 p = primes[map.id[l]].p;
+    const u64 *ct = src + b * src_bstride + (l << logn);
+    const u64 raw = j + t;
+    u64 v = ct[(limbs << logn) + (raw & (N - 1))];
+    if (raw & N) v = negmod(v, p);
+    c1[i] = v;
+    if (j == 0) c0[row] = ct[t];
+}
+void launch_lwe_extract(const u64 *src, u64 src_bstride, const u64 *terms, u64 *c1, u64 *c0, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 count,
+                        u64 batch, hipStream_t s) {
+    const u64 total = (count * batch * limbs) << logn;
+    if (!total) return;
+    TROY_LAUNCH(lwe_extract_kernel, flat_grid(total, "lwe_extract_kernel"), dim3(EW_THREADS), 0, s, src, src_bstride, terms, c1, c0, primes, map, logn, limbs, batch, total);
+    launch_check("lwe_extract_kernel");
+}
+// One merge step of packLWECiphertexts (evaluator_cuda.cu:2275-2340) or one round of fieldTraceInplace (:2248-2257) up to the key switch, as a GATHER for the
+// reason given at galois_coeff_kernel: output coefficient j reads even and temp = x^shift odd at j (the sum) and at n0 = j g^-1 mod 2N (the difference under
+// the automorphism, negated where n0 >= N); every store is a whole line.  LEAF: the operands are samples of the LWE batch, assembled at term 0 and multiplied
+// by N^-1 on the fly (what assembleLWE + divideByPolyModulusDegreeInplace store); an absent odd is zero, which leaves (even0 + sigma(even0), even1) and
+// sigma(even1) -- a leaf past the count and a round of the trace alike.
+template <bool LEAF> __global__ __launch_bounds__(EW_THREADS) void lwe_merge_kernel(LweMergeArgs a, const PrimeDesc *primes, LimbMap map, uint32_t elt_inv, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << a.logn, row = i >> a.logn, j = i & (N - 1), l = row % a.limbs, ul = row / a.limbs, u = a.u0 + ul, pw = a.limbs << a.logn;
+    const PrimeDesc &pd = primes[map.id[l]];
+    const u64 p = pd.p;
+    const u64 n0 = (j * elt_inv) & (2 * N - 1), jn = n0 & (N - 1);
+    // polynomial k of node `unit` at coefficient idx
+    auto node = [&](u64 unit, int k, u64 idx) -> u64 {
+        if (!LEAF) return a.nodes[unit * a.node_stride + (u64)k * pw + (l << a.logn) + idx];
+        if (k == 0 && idx) return 0;
+        const u64 v = k ? a.c1[((unit * a.limbs + l) << a.logn) + idx] : a.c0[unit * a.limbs + l];
+        return mul_shoup(v, pd.inv_n, p);
+    };
+    u64 s0 = node(u, 0, j), s1 = node(u, 1, j), d0 = node(u, 0, jn), d1 = node(u, 1, jn);
+    if (u < a.u_both) {
+        const u64 o = u + a.odd_offset;
+        auto temp = [&](int k, u64 idx) -> u64 { // coefficient idx of x^shift odd_k, shift < N
+            const u64 v = node(o, k, (idx - a.shift) & (N - 1));
+            return idx < a.shift ? negmod(v, p) : v;
+        };
+        s0 = addmod(s0, temp(0, j), p);
+        s1 = addmod(s1, temp(1, j), p);
+        d0 = submod(d0, temp(0, jn), p);
+        d1 = submod(d1, temp(1, jn), p);
+    }
+    if (n0 >> a.logn) { d0 = negmod(d0, p); d1 = negmod(d1, p); }
+    u64 *base = a.base + ul * 2 * pw + (l << a.logn) + j;
+    base[0] = addmod(s0, d0, p);
+    base[pw] = s1;
+    a.target[ul * pw + (l << a.logn) + j] = d1;
+}
+void launch_lwe_merge(const LweMergeArgs &a, const PrimeDesc *primes, const LimbMap &map, hipStream_t s) {
+    const u64 total = (a.units * a.limbs) << a.logn;
+    if (!total) return;
+    const bool leaf = !a.nodes;
+    if (!a.base || !a.target || (leaf && (!a.c1 || !a.c0)) || !(a.elt & 1) || a.elt >> (a.logn + 1) || a.shift >> a.logn || (!leaf && a.node_stride < (2 * a.limbs << a.logn)))
+        throw Error(ST_LOGIC_ERROR, "lwe_merge: operands");
+    uint32_t inv = 1; // g^-1 mod 2N, as launch_galois finds it
+    for (int it = 0; it < 5; it++) inv *= 2u - a.elt * inv;
+    inv &= (uint32_t)((2u << a.logn) - 1);
+    const dim3 grid = flat_grid(total, "lwe_merge_kernel");
+    if (leaf) TROY_LAUNCH(HIP_KERNEL_NAME(lwe_merge_kernel<true>), grid, dim3(EW_THREADS), 0, s, a, primes, map, inv, total);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(lwe_merge_kernel<false>), grid, dim3(EW_THREADS), 0, s, a, primes, map, inv, total);
+    launch_check("lwe_merge_kernel");
+}
+
 // ---------------------------------------------------------------- mod-switch / rescale (a-4 / A.10)
 // kind 0: BFV divideAndRoundqLastInplace (rns.cpp:805-830); kind 2: BGV modTAndDivideqLastInplace (rns.cpp:1097-1140).
 // in [polys][limbs][N] -> out [polys][limbs-1][N]
