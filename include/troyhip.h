@@ -447,6 +447,45 @@ int troyhip_create_relin_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t se
 int troyhip_create_kswitch_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *new_key, uint64_t *out,
                                void *stream);
 
+/* ---- Key switching with grouped digits ("hybrid" key switching).  NO REFERENCE COUNTERPART: the result is defined in DESIGN.md
+ * section 4.16.  The last special_primes = alpha of the K key primes serve as special primes (product P), 1 <= alpha <= min(8, K - 1); the data limbs are
+ * taken alpha at a time as one digit.  A grouped key is [digits][2][K][N] (NTT form), digits = ceil((K - alpha) / alpha), and serves operands of at most
+ * max_limbs = K - alpha limbs.  At alpha == 1 keys and results are those of the per-prime entries above, byte for byte.  Refusals: alpha out of range
+ * (TROYHIP_INVALID_ARGUMENT "special_primes must lie in 1 .. min(8, key limbs - 1)"), from alpha = 2 on a digit group whose product is longer than P ("special modulus is
+ * smaller than a digit"; one special prime is the reference's key switch and takes any), K < 2 (TROYHIP_LOGIC_ERROR "keyswitching is not supported by the context"). */
+/* digits, max_limbs and the words of one key for `special_primes`; any of the three outputs may be null.  Host-only. */
+int troyhip_grouped_key_shape(const troyhip_context *ctx, int special_primes, int *digits, int *max_limbs, size_t *key_words);
+/* One grouped key on the host (no reference counterpart).  src_kind 1: relinearization (s^2), 2: Galois (galois_elt), 3: key
+ * switching from new_key ([K][N] NTT form); seeds and streams as troyhip_host_relin_key / _galois_key / _kswitch_key, whose warning about seeds applies.
+ * Row j is an encryption of zero with (P mod p_i) * source added on the limbs i of digit group j; the draws per digit are those of the per-prime key. */
+int troyhip_host_kswitch_key_grouped(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, int src_kind, const uint64_t *new_key,
+                                     uint32_t galois_elt, int special_primes, uint64_t *out);
+/* `count` grouped keys on the device (no reference counterpart): outs[i] (device, key_words each) is byte-identical to the host
+ * form with the same seed, source and galois_elts[i].  src_kind 2 takes `count` elements; 1 and 3 take count == 1 (galois_elts unused).  secret_key /
+ * new_key: device [K][N].  A host-only context is refused. */
+int troyhip_create_kswitch_keys_grouped(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, int src_kind, const uint64_t *new_key,
+                                        const uint32_t *galois_elts, uint64_t count, int special_primes, uint64_t *const *outs, void *stream);
+/* troyhip_switch_key with a grouped key (no reference counterpart): ct += key switch of `target` ([limbs][N] per item, the
+ * ciphertext's form).  base != null: ct is first taken as (base, 0) (base_polys == 1) or (base[0], base[1]) (base_polys == 2), items base_batch_stride
+ * apart.  Refusals: "operand has more limbs than the grouped key serves" (limbs > K - alpha), the wrong form for the scheme, a null key, size < 2.  The
+ * arena request stays under scratch_limit_words (0: 2^28 words), in slabs of items; the result does not depend on it or on the batch size.  Counter
+ * "grouped_ks_slabs". */
+int troyhip_switch_key_grouped(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *target, uint64_t target_batch_stride, const uint64_t *base, uint64_t base_batch_stride,
+                               int base_polys, const uint64_t *key, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* relinearize from size 3 to size 2 with a grouped key (no reference counterpart): the operand is read where it lies; out->data,
+ * ->batch_stride are INPUTS (out->data == in->data: in place).  A size-2 operand is copied (in place: left as it is) and no key is read, as the per-prime
+ * relinearization does; other sizes are refused. */
+int troyhip_relinearize_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint64_t *relin_key, int special_primes, uint64_t scratch_limit_words,
+                                uint64_t batch, void *stream);
+/* troyhip_apply_galois with a grouped key (no reference counterpart) */
+int troyhip_apply_galois_grouped(troyhip_context *ctx, troyhip_ct *ct, uint32_t galois_elt, const uint64_t *galois_key, int special_primes, uint64_t scratch_limit_words,
+                                 uint64_t batch, void *stream);
+/* troyhip_apply_key_switching with a grouped key (no reference counterpart) */
+int troyhip_apply_key_switching_grouped(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *kswitch_key, int special_primes, uint64_t scratch_limit_words, uint64_t batch,
+                                        void *stream);
+/* the arena words troyhip_switch_key_grouped asks for with the whole batch in one slab (no reference counterpart); host-only */
+int troyhip_switch_key_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words);
+
 /* ---- Device encoding, `batch` items per call (BatchEncoder / CKKSEncoder).  Item i is BYTE-IDENTICAL to the host form called with item i
  * (DESIGN.md section 4.7).  Every buffer is device memory; strides are in words (u64 or double) between consecutive items; batch in 1 .. 65535.
  * Invalid input returns the host form's status and message.  The outputs feed troyhip_encrypt's `plain` operand directly (BFV [B][N], CKKS

@@ -861,8 +861,18 @@ public:
     // parms_id, [K - 1][2][K][N] words -- or the kernels would read past it (a loaded key can have any shape)
     const uint64_t *device(size_t index, const ParmsID &key_parms_id, size_t key_limbs, size_t poly_modulus_degree) const {
         const auto &a = keys_.at(index);
+        if (special_primes_) throw std::invalid_argument("grouped keys are not supported by this call");
         if (parms_id_ != key_parms_id || key_limbs < 2 || a->size() != (key_limbs - 1) * 2 * key_limbs * poly_modulus_degree)
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
+        return a->get();
+    }
+    // Keys with grouped digits (no reference counterpart): specialPrimes() = alpha > 0, one key is
+    // [ceil((K - alpha) / alpha)][2][K][N]; 0: the reference's keys.  Only relinearize, applyKeySwitching, applyGalois and the rotations take them.
+    int specialPrimes() const noexcept { return special_primes_; }
+    void describeGrouped(int special_primes) { special_primes_ = special_primes; }
+    const uint64_t *deviceGrouped(size_t index, const ParmsID &key_parms_id, size_t key_words) const {
+        const auto &a = keys_.at(index);
+        if (parms_id_ != key_parms_id || a->size() != key_words) throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         return a->get();
     }
     void upload(size_t index, const std::vector<uint64_t> &host) {
@@ -878,6 +888,7 @@ public:
     template <class K> static K replicate(const K &k, int from_device, int to_device) {
         K out;
         out.describe(k.parms_id_, k.n_, k.limbs_);
+        out.special_primes_ = k.special_primes_;
         for (const auto &kv : k.keys_) {
             auto a = std::make_shared<DeviceArray>(kv.second->size());
             check(troyhip_copy_peer(a->get(), to_device, kv.second->get(), from_device, kv.second->size() * 8, nullptr));
@@ -894,6 +905,7 @@ public:
     // save / load (src/kswitchkeys_cuda.cuh:330-356): parms_id, the length of the index vector, and per index the digit count followed by one
     // public-key-format ciphertext [2][K][N] per digit (an index without a key has digit count 0)
     void save(std::ostream &stream) const {
+        if (special_primes_) throw std::invalid_argument("grouped keys are not supported by this call");
         stream.write(reinterpret_cast<const char *>(parms_id_.data()), 32);
         const size_t slots = keys_.empty() ? 0 : keys_.rbegin()->first + 1;
         wire::put<size_t>(stream, slots);
@@ -940,6 +952,7 @@ public:
             fresh[i] = a;
         }
         keys_ = std::move(fresh);
+        special_primes_ = 0;
         parms_id_ = id;
         parms_id_.limbs = (int)limbs;
         n_ = n; limbs_ = limbs;
@@ -948,6 +961,7 @@ protected:
     std::map<size_t, std::shared_ptr<DeviceArray>> keys_;
     ParmsID parms_id_;
     size_t n_ = 0, limbs_ = 0;
+    int special_primes_ = 0;
 };
 class RelinKeys : public KSwitchKeys { // src/relinkeys_cuda.cuh:56-59
 public:
@@ -1098,6 +1112,29 @@ public:
         return k;
     }
 
+    // ---- keys with grouped digits over `special_primes` special primes (no reference counterpart), on the host and on the
+    // device (byte-identical); at special_primes == 1 the words are those of the members above.  The createKeySwitchingKeys calls count together.
+    RelinKeys createRelinKeys(int special_primes) const { RelinKeys r; grouped(r, 1, special_primes, false, {0}, nullptr, lo_); return r; }
+    RelinKeys createRelinKeysOnDevice(int special_primes) const { RelinKeys r; grouped(r, 1, special_primes, true, {0}, nullptr, lo_); return r; }
+    GaloisKeys createGaloisKeys(const std::vector<uint32_t> &galois_elts, int special_primes) const { GaloisKeys g; grouped(g, 2, special_primes, false, galois_elts, nullptr, lo_); return g; }
+    GaloisKeys createGaloisKeysOnDevice(const std::vector<uint32_t> &galois_elts, int special_primes) const { GaloisKeys g; grouped(g, 2, special_primes, true, galois_elts, nullptr, lo_); return g; }
+    GaloisKeys createGaloisKeys(int special_primes) const { return createGaloisKeys(galoisEltsAll(), special_primes); }
+    GaloisKeys createGaloisKeysOnDevice(int special_primes) const { return createGaloisKeysOnDevice(galoisEltsAll(), special_primes); }
+    GaloisKeys createAutomorphismKeys(int special_primes) const { return createGaloisKeys(automorphismElts(), special_primes); }
+    GaloisKeys createAutomorphismKeysOnDevice(int special_primes) const { return createGaloisKeysOnDevice(automorphismElts(), special_primes); }
+    KSwitchKeys createKeySwitchingKeys(const SecretKey &new_key, int special_primes) const {
+        if (new_key.data.size() != sk_.data.size()) throw std::invalid_argument("new_key is not valid for encryption parameters");
+        KSwitchKeys k;
+        grouped(k, 3, special_primes, false, {0}, &new_key, lo_ + kswitch_calls_++);
+        return k;
+    }
+    KSwitchKeys createKeySwitchingKeysOnDevice(const SecretKey &new_key, int special_primes) const {
+        if (new_key.data.size() != sk_.data.size()) throw std::invalid_argument("new_key is not valid for encryption parameters");
+        KSwitchKeys k;
+        grouped(k, 3, special_primes, true, {0}, &new_key, lo_ + kswitch_calls_++);
+        return k;
+    }
+
     // every key rotate / conjugate can ask for: X -> X^(2N-1) and X -> X^(3^(2^i)), X^(3^-(2^i)) (GaloisTool::getEltsAll,
     // src/utils/galois.cpp:101-126)
     std::vector<uint32_t> galoisEltsAll() const {
@@ -1143,6 +1180,37 @@ private:
         pk_.coeff_modulus_size = K;
     }
     size_t ksk_words() const { const size_t K = c_.keyLimbs(); return (K - 1) * 2 * K * c_.polyModulusDegree(); }
+    // keys with grouped digits: source kind 1 relin / 2 Galois (one key per element) / 3 key switching, on the host or in one call on the device
+    template <class Keys> void grouped(Keys &out, int kind, int special_primes, bool on_device, const std::vector<uint32_t> &elts, const SecretKey *new_key, uint64_t lo) const {
+        size_t words = 0;
+        check(troyhip_grouped_key_shape(c_.handle(), special_primes, nullptr, nullptr, &words));
+        out.describe(c_.keyParmsID(), c_.polyModulusDegree(), c_.keyLimbs());
+        out.describeGrouped(special_primes);
+        auto index = [&](uint32_t e) { return kind == 2 ? GaloisKeys::getIndex(e) : size_t(0); };
+        if (!on_device) {
+            for (uint32_t e : elts) {
+                std::vector<uint64_t> h(words);
+                check(troyhip_host_kswitch_key_grouped(c_.handle(), lo, hi_, sk_.data.data(), kind, new_key ? new_key->data.data() : nullptr, e, special_primes, h.data()));
+                out.upload(index(e), h);
+            }
+            return;
+        }
+        if (elts.empty()) return;
+        std::vector<std::shared_ptr<DeviceArray>> keys;
+        std::vector<uint64_t *> table;
+        for (size_t i = 0; i < elts.size(); i++) {
+            keys.push_back(std::make_shared<DeviceArray>(std::max<size_t>(1, words)));
+            table.push_back(keys.back()->get());
+        }
+        std::unique_ptr<DeviceArray> dnew;
+        if (new_key) {
+            dnew.reset(new DeviceArray(new_key->data.size()));
+            check(troyhip_copy_h2d(dnew->get(), new_key->data.data(), new_key->data.size() * 8, nullptr));
+        }
+        check(troyhip_create_kswitch_keys_grouped(c_.handle(), lo, hi_, deviceSecretKey(), kind, dnew ? dnew->get() : nullptr, elts.data(), elts.size(), special_primes, table.data(), nullptr));
+        if (dnew) check(troyhip_stream_synchronize(nullptr)); // dnew is freed on return
+        for (size_t i = 0; i < elts.size(); i++) out.adopt(index(elts[i]), keys[i]);
+    }
     const SEALContext &c_;
     uint64_t lo_, hi_;
     mutable uint64_t kswitch_calls_ = 0;
@@ -1834,6 +1902,14 @@ public:
     const SEALContext &context() const { return c_; }
     // a key-switching key as the kernels take it, refused unless it belongs to this evaluator's context (KSwitchKeys::device)
     const uint64_t *key_of(const KSwitchKeys &k, size_t index) const { return k.device(index, c_.keyParmsID(), c_.keyLimbs(), c_.polyModulusDegree()); }
+    // ... and a key with grouped digits, its size checked against troyhip_grouped_key_shape
+    const uint64_t *grouped_key_of(const KSwitchKeys &k, size_t index) const {
+        size_t words = 0;
+        check(troyhip_grouped_key_shape(h(), k.specialPrimes(), nullptr, nullptr, &words));
+        return k.deviceGrouped(index, c_.keyParmsID(), words);
+    }
+    // (digits, largest operand level in limbs, words of one key) of keys with `special_primes` special primes
+    void groupedKeyShape(int special_primes, int &digits, int &max_limbs, size_t &key_words) const { check(troyhip_grouped_key_shape(h(), special_primes, &digits, &max_limbs, &key_words)); }
     Evaluator(const Evaluator &) = delete;
     Evaluator &operator=(const Evaluator &) = delete;
 
@@ -1923,6 +1999,12 @@ public:
         return levels;
     }
     void relinearizeInplace(Ciphertext &a, const RelinKeys &k) const { // to size 2 from any size <= 16 (src/evaluator_cuda.cu:703-744)
+        if (k.specialPrimes()) { // keys with grouped digits: size 3, in place
+            if (a.size() == 2) return;
+            if (!k.hasKey(2)) throw std::invalid_argument("not enough relinearization keys");
+            check(troyhip_relinearize_grouped(h(), a.raw(), a.raw(), grouped_key_of(k, RelinKeys::getIndex(2)), k.specialPrimes(), 0, 1, nullptr));
+            return;
+        }
         const size_t need = a.size() > 2 ? a.size() - 2 : 0;
         std::vector<const uint64_t *> keys(need ? need : 1, nullptr);
         for (size_t i = 0; i < need; i++) {
@@ -1935,16 +2017,18 @@ public:
     void relinearize(const Ciphertext &a, const RelinKeys &k, Ciphertext &d) const {
         if (a.size() != 3 || &d == &a) { d = a; relinearizeInplace(d, k); return; }
         if (!k.hasKey(2)) throw std::invalid_argument("not enough relinearization keys");
-        const uint64_t *key = key_of(k, RelinKeys::getIndex(2));
+        const uint64_t *key = k.specialPrimes() ? grouped_key_of(k, RelinKeys::getIndex(2)) : key_of(k, RelinKeys::getIndex(2));
         Ciphertext out;
         out.resize(a.polyModulusDegree(), a.coeffModulusSize(), 2);
-        check(troyhip_relinearize_to(h(), a.raw(), out.raw(), &key, 1, 1, nullptr));
+        if (k.specialPrimes()) check(troyhip_relinearize_grouped(h(), a.raw(), out.raw(), key, k.specialPrimes(), 0, 1, nullptr));
+        else check(troyhip_relinearize_to(h(), a.raw(), out.raw(), &key, 1, 1, nullptr));
         out.bind(a);
         d = std::move(out);
     }
     // applyKeySwitchingInplace (evaluator_cuda.cu:1365-1378), negacyclicShiftInplace (:2342-2351)
     void applyKeySwitchingInplace(Ciphertext &a, const KSwitchKeys &k) const {
         if (k.all().size() != 1) throw std::invalid_argument("kswitch_keys.data().size() != 1");
+        if (k.specialPrimes()) { check(troyhip_apply_key_switching_grouped(h(), a.raw(), grouped_key_of(k, k.all().begin()->first), k.specialPrimes(), 0, 1, nullptr)); return; }
         check(troyhip_apply_key_switching(h(), a.raw(), key_of(k, k.all().begin()->first), 1, nullptr));
     }
     void applyKeySwitching(const Ciphertext &a, const KSwitchKeys &k, Ciphertext &d) const { d = a; applyKeySwitchingInplace(d, k); } // src/evaluator_cuda.cuh:104-110
@@ -2007,6 +2091,7 @@ public:
     void rescaleTo(const Ciphertext &a, const ParmsID &parms_id, Ciphertext &d) const { d = a; rescaleToInplace(d, parms_id); } // :193-198
     void applyGaloisInplace(Ciphertext &a, uint32_t galois_elt, const GaloisKeys &gk) const {
         if (!gk.hasKey(galois_elt)) throw std::invalid_argument("Galois key not present");
+        if (gk.specialPrimes()) { check(troyhip_apply_galois_grouped(h(), a.raw(), galois_elt, grouped_key_of(gk, GaloisKeys::getIndex(galois_elt)), gk.specialPrimes(), 0, 1, nullptr)); return; }
         check(troyhip_apply_galois(h(), a.raw(), galois_elt, key_of(gk, GaloisKeys::getIndex(galois_elt)), 1, nullptr));
     }
     void rotateRowsInplace(Ciphertext &a, int steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); rotate(a, steps, 0, gk); }
@@ -2307,6 +2392,14 @@ public:
         if (a.empty()) return {};
         std::vector<Ciphertext> pa;
         const troyhip_ct va = runOf(a, pa);
+        if (k.specialPrimes()) { // keys with grouped digits: size 3 -> 2; size 2 is copied and reads no key, as with per-prime keys
+            if (a[0]->size() > 2 && !k.hasKey(2)) throw std::invalid_argument("not enough relinearization keys");
+            std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, a[0]->coeffModulusSize());
+            troyhip_ct t = *out[0].raw();
+            check(troyhip_relinearize_grouped(h(), &va, &t, a[0]->size() > 2 ? grouped_key_of(k, RelinKeys::getIndex(2)) : nullptr, k.specialPrimes(), 0, a.size(), nullptr));
+            for (auto &c : out) c.copyMeta(t);
+            return out;
+        }
         const std::vector<const uint64_t *> keys = relinKeys(*a[0], k);
         std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], a[0]->size() == 3 ? 2 : a[0]->size(), a[0]->coeffModulusSize());
         troyhip_ct t = *out[0].raw();
@@ -2317,6 +2410,12 @@ public:
     std::vector<Ciphertext> relinearizeBatch(const std::vector<Ciphertext> &a, const RelinKeys &k) const { return relinearizeBatch(Ciphertext::pointers(a), k); }
     void relinearizeInplaceBatch(const std::vector<Ciphertext *> &items, const RelinKeys &k) const {
         inplaceBatch(items, [&](troyhip_ct *v, size_t count, const Ciphertext &head) {
+            if (k.specialPrimes()) {
+                if (head.size() == 2) return;
+                if (!k.hasKey(2)) throw std::invalid_argument("not enough relinearization keys");
+                check(troyhip_relinearize_grouped(h(), v, v, grouped_key_of(k, RelinKeys::getIndex(2)), k.specialPrimes(), 0, count, nullptr));
+                return;
+            }
             const std::vector<const uint64_t *> keys = relinKeys(head, k);
             check(troyhip_relinearize_keys(h(), v, keys.data(), (int)(head.size() > 2 ? head.size() - 2 : 0), count, nullptr));
         });
@@ -2324,8 +2423,11 @@ public:
     void relinearizeInplaceBatch(std::vector<Ciphertext> &items, const RelinKeys &k) const { relinearizeInplaceBatch(Ciphertext::pointers(items), k); }
     void applyKeySwitchingInplaceBatch(const std::vector<Ciphertext *> &items, const KSwitchKeys &k) const {
         if (k.all().size() != 1) throw std::invalid_argument("kswitch_keys.data().size() != 1");
-        const uint64_t *key = key_of(k, k.all().begin()->first);
-        inplaceBatch(items, [&](troyhip_ct *v, size_t count, const Ciphertext &) { check(troyhip_apply_key_switching(h(), v, key, count, nullptr)); });
+        const int alpha = k.specialPrimes();
+        const uint64_t *key = alpha ? grouped_key_of(k, k.all().begin()->first) : key_of(k, k.all().begin()->first);
+        inplaceBatch(items, [&](troyhip_ct *v, size_t count, const Ciphertext &) {
+            check(alpha ? troyhip_apply_key_switching_grouped(h(), v, key, alpha, 0, count, nullptr) : troyhip_apply_key_switching(h(), v, key, count, nullptr));
+        });
     }
     std::vector<Ciphertext> modSwitchToNextBatch(const std::vector<const Ciphertext *> &a) const { return nextBatch(a, troyhip_mod_switch_to_next); }
     std::vector<Ciphertext> modSwitchToNextBatch(const std::vector<Ciphertext> &a) const { return modSwitchToNextBatch(Ciphertext::pointers(a)); }
@@ -2337,8 +2439,11 @@ public:
     void rescaleToNextInplaceBatch(std::vector<Ciphertext> &items) const { rescaleToNextInplaceBatch(Ciphertext::pointers(items)); }
     void applyGaloisInplaceBatch(const std::vector<Ciphertext *> &items, uint32_t galois_elt, const GaloisKeys &gk) const {
         if (!gk.hasKey(galois_elt)) throw std::invalid_argument("Galois key not present");
-        const uint64_t *key = key_of(gk, GaloisKeys::getIndex(galois_elt));
-        inplaceBatch(items, [&](troyhip_ct *v, size_t count, const Ciphertext &) { check(troyhip_apply_galois(h(), v, galois_elt, key, count, nullptr)); });
+        const int alpha = gk.specialPrimes();
+        const uint64_t *key = alpha ? grouped_key_of(gk, GaloisKeys::getIndex(galois_elt)) : key_of(gk, GaloisKeys::getIndex(galois_elt));
+        inplaceBatch(items, [&](troyhip_ct *v, size_t count, const Ciphertext &) {
+            check(alpha ? troyhip_apply_galois_grouped(h(), v, galois_elt, key, alpha, 0, count, nullptr) : troyhip_apply_galois(h(), v, galois_elt, key, count, nullptr));
+        });
     }
     void applyGaloisInplaceBatch(std::vector<Ciphertext> &items, uint32_t galois_elt, const GaloisKeys &gk) const { applyGaloisInplaceBatch(Ciphertext::pointers(items), galois_elt, gk); }
     void rotateRowsInplaceBatch(const std::vector<Ciphertext *> &items, int steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); rotateBatch(items, steps, 0, gk); }
@@ -2759,7 +2864,27 @@ private:
             i = j;
         }
     }
+    // rotate_internal (src/evaluator_cuda.cu:2140-2175) over keys with grouped digits: the key of the step itself, else the NAF terms of the step one by one
+    template <class Apply> void rotateGrouped(int steps, int conj, const GaloisKeys &gk, const Apply &apply) const {
+        const size_t N = c_.polyModulusDegree();
+        if (conj) { apply((uint32_t)(2 * N - 1)); return; }
+        if (steps == 0) return;
+        uint32_t elt = 0;
+        check(troyhip_galois_elt_from_step(h(), steps, &elt));
+        if (gk.hasKey(elt)) { apply(elt); return; }
+        std::vector<int> terms;
+        int v = steps < 0 ? -steps : steps;
+        for (int i = 0; v; i++) { // numth.h:16-36
+            const int z = (v & 1) ? 2 - (v & 3) : 0;
+            v = (v - z) >> 1;
+            if (z) terms.push_back((steps < 0 ? -z : z) * (1 << i));
+        }
+        if (terms.size() == 1) throw std::invalid_argument("Galois key not present");
+        for (int t : terms)
+            if ((size_t)(t < 0 ? -t : t) != N >> 1) rotateGrouped(t, 0, gk, apply);
+    }
     void rotateBatch(const std::vector<Ciphertext *> &items, int steps, int conj, const GaloisKeys &gk) const {
+        if (gk.specialPrimes()) { rotateGrouped(steps, conj, gk, [&](uint32_t e) { applyGaloisInplaceBatch(items, e, gk); }); return; }
         std::vector<uint32_t> elts;
         std::vector<const uint64_t *> ptrs;
         for (auto &kv : gk.all()) { elts.push_back((uint32_t)(2 * kv.first + 1)); ptrs.push_back(kv.second->get()); }
@@ -2783,6 +2908,7 @@ private:
         return elts;
     }
     void rotate(Ciphertext &a, int steps, int conj, const GaloisKeys &gk) const {
+        if (gk.specialPrimes()) { rotateGrouped(steps, conj, gk, [&](uint32_t e) { applyGaloisInplace(a, e, gk); }); return; }
         std::vector<uint32_t> elts;
         std::vector<const uint64_t *> ptrs;
         for (auto &kv : gk.all()) { elts.push_back((uint32_t)(2 * kv.first + 1)); ptrs.push_back(kv.second->get()); }

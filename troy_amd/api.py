@@ -161,6 +161,12 @@ class SEALContext:
         capi.check(self.lib, self.lib.troyhip_galois_elt_from_step(self.h, step, C.byref(out)))
         return out.value
 
+    def grouped_key_shape(self, special_primes):
+        """(digits, max_limbs, key_words) of keys with grouped digits over `special_primes` special primes (troyhip_grouped_key_shape)"""
+        d, l, w = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        capi.check(self.lib, self.lib.troyhip_grouped_key_shape(self.h, int(special_primes), C.byref(d), C.byref(l), C.byref(w)))
+        return d.value, l.value, w.value
+
     def reserve_scratch(self, words):
         capi.check(self.lib, self.lib.troyhip_context_reserve_scratch(self.h, C.c_size_t(int(words))))
 
@@ -393,22 +399,25 @@ class LWEBatch:
 
 class KSwitchKeys:
     """KSwitchKeysCuda (src/kswitchkeys_cuda.cuh:43-56): data()[index] = one key-switching key, uploaded from
-    the host array [K-1][2][K][N] (NTT form)."""
+    the host array [K-1][2][K][N] (NTT form).  special_primes = alpha (no reference counterpart): keys with grouped digits,
+    [ceil((K - alpha) / alpha)][2][K][N]; None: the reference's keys, one digit per data prime."""
 
-    def __init__(self, context):
+    def __init__(self, context, special_primes=None):
         self.context, self.keys = context, {}
+        self.special_primes = None if special_primes is None else int(special_primes)
+        self.digits = context.key_limbs - 1 if special_primes is None else context.grouped_key_shape(self.special_primes)[0]
 
     def set(self, index, host_array):
         a = np.ascontiguousarray(host_array, dtype=np.uint64)
         K, N = self.context.key_limbs, self.context.N
-        if a.shape != (K - 1, 2, K, N):
+        if a.shape != (self.digits, 2, K, N):
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters")
         self.keys[index] = DeviceBuffer.from_numpy(a)
 
     def set_device(self, index, buf):
         """adopt a DeviceBuffer of (K-1) 2 K N words that already holds a key (KeyGenerator.create*(device=True)); no copy"""
         K, N = self.context.key_limbs, self.context.N
-        if not isinstance(buf, DeviceBuffer) or buf.words != (K - 1) * 2 * K * N:
+        if not isinstance(buf, DeviceBuffer) or buf.words != self.digits * 2 * K * N:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters")
         self.keys[index] = buf
 
@@ -443,6 +452,16 @@ class Evaluator:
 
     def _chk(self, rc):
         capi.check(self.lib, rc)
+
+    # -- keys with grouped digits (no reference counterpart): the key-switching calls dispatch on the key set's tag
+    def groupedKeyShape(self, special_primes):
+        """(digits, max_limbs, key_words) of a grouped key with `special_primes` special primes"""
+        return self.context.grouped_key_shape(special_primes)
+
+    @staticmethod
+    def _per_prime_only(keys):
+        if keys is not None and getattr(keys, "special_primes", None) is not None:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "grouped keys are not supported by this call")
 
     # -- negate / add / sub
     def negateInplace(self, a):
@@ -592,6 +611,7 @@ class Evaluator:
         """p(ct) slot-wise, p = coeffs[0] + coeffs[1] x + .. (Paterson-Stockmeyer: shared powers, one scalar sum per block, ONE multiplySum and ONE
         relinearization for all block x giant-power products).  BFV / BGV: integers mod t.  CKKS: real floats; the result's scale is exactly out_scale
         (default: ct.scale).  The result lies polynomialDepth(degree)[0] levels below ct (BFV: at its level)."""
+        self._per_prime_only(relin_keys)
         ctx = self.context
         degree = len(coeffs) - 1
         levels, _ = self.polynomialDepth(degree, baby_steps)
@@ -622,6 +642,10 @@ class Evaluator:
     # -- key switching
     def relinearizeInplace(self, a, relin_keys):
         """relinearizeInternal to size 2 from any size <= 16 (src/evaluator_cuda.cu:703-744): needs the keys of index 0 .. size-3"""
+        if relin_keys.special_primes is not None:
+            if a.size() != 2:
+                a.__dict__.update(self.relinearize(a, relin_keys, destination=a).__dict__)
+            return
         need = max(a.size() - 2, 0)
         for idx in range(need):
             if not relin_keys.hasKey(idx):
@@ -633,7 +657,18 @@ class Evaluator:
 
     def relinearize(self, a, relin_keys, destination=None):
         """relinearize(encrypted, relin_keys, destination): the reference copies and relinearizes in place; from size 3 the library reads the
-        operand where it lies and writes the size-2 result to the destination (troyhip_relinearize_to): no copy of the operand"""
+        operand where it lies and writes the size-2 result to the destination (troyhip_relinearize_to): no copy of the operand.
+        Keys with grouped digits take size 3, and size 2 as a copy (troyhip_relinearize_grouped); destination=a then works in place"""
+        if relin_keys.special_primes is not None:  # size 3 -> 2; a size-2 operand is copied and needs no key, as with per-prime keys
+            if a.size() > 2 and not relin_keys.hasKey(0):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "not enough relinearization keys")
+            out = destination or Ciphertext(a.context, a.batch, 2, a.limbs, capacity=2)
+            si, so = a.struct(), out.struct()
+            key = C.c_void_p(relin_keys.keys[0].ptr) if relin_keys.hasKey(0) else None
+            self._chk(self.lib.troyhip_relinearize_grouped(self.context.h, C.byref(si), C.byref(so), key, relin_keys.special_primes,
+                                                           C.c_uint64(0), C.c_uint64(a.batch), self.stream))
+            out._absorb(so)
+            return out
         need = max(a.size() - 2, 0)
         for idx in range(need):
             if not relin_keys.hasKey(idx):
@@ -655,6 +690,11 @@ class Evaluator:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "kswitch_keys.data().size() != 1")
         key = next(iter(kswitch_keys.keys.values()))
         st = a.struct()
+        if kswitch_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_apply_key_switching_grouped(self.context.h, C.byref(st), C.c_void_p(key.ptr), kswitch_keys.special_primes, C.c_uint64(0),
+                                                                   C.c_uint64(a.batch), self.stream))
+            a._absorb(st)
+            return
         self._chk(self.lib.troyhip_apply_key_switching(self.context.h, C.byref(st), C.c_void_p(key.ptr), C.c_uint64(a.batch), self.stream))
         a._absorb(st)
 
@@ -838,6 +878,7 @@ class Evaluator:
     def packLWEs(self, lwes, galois_keys, scratch_limit_words=0):
         """packLWECiphertexts(lwes, galois_keys), byte for byte, with one merge launch and one key switch per layer of the tree and per round of the field
         trace (BFV / BGV).  lwes: an LWEBatch or a list of LWECiphertext."""
+        self._per_prime_only(galois_keys)
         if not isinstance(lwes, LWEBatch):
             lwes = LWEBatch.from_list(list(lwes))
         ctx = self.context
@@ -876,6 +917,11 @@ class Evaluator:
         if not galois_keys.hasKey(idx):
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Galois key not present")
         st = a.struct()
+        if galois_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_apply_galois_grouped(self.context.h, C.byref(st), C.c_uint32(galois_elt), C.c_void_p(galois_keys.keys[idx].ptr),
+                                                            galois_keys.special_primes, C.c_uint64(0), C.c_uint64(a.batch), self.stream))
+            a._absorb(st)
+            return
         self._chk(self.lib.troyhip_apply_galois(self.context.h, C.byref(st), C.c_uint32(galois_elt), C.c_void_p(galois_keys.keys[idx].ptr), C.c_uint64(a.batch), self.stream))
         a._absorb(st)
 
@@ -883,6 +929,7 @@ class Evaluator:
     def applyGaloisHoisted(self, a, galois_elts, galois_keys, scratch_limit_words=0):
         """[applyGalois(a, g) for g in galois_elts] for roughly the price of one key switch: the digits of c1 are expanded once.  Every result decrypts to
         what applyGalois gives; its limbs differ.  Element 1 is a copy.  Returns a list of len(galois_elts) Ciphertext batches."""
+        self._per_prime_only(galois_keys)
         elts = [int(g) for g in galois_elts]
         if not elts:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "hoisted rotations take at least one Galois element")
@@ -920,6 +967,7 @@ class Evaluator:
         """sum_r plains[r] * applyGalois(a, galois_elts[r]) as ONE call and ONE Ciphertext batch: the plaintexts are applied in the extended basis before
         the single mod-down per item.  plains: DeviceBuffer of K * N words each, NTT form at the KEY level (transformPlainToNtt(plain, K) for BFV / BGV,
         CKKSEncoder.encode(..., limbs=K) for CKKS), shared by the batch.  Element 1 reads no key.  The scale becomes a.scale * plain_scale."""
+        self._per_prime_only(galois_keys)
         elts = [int(g) for g in galois_elts]
         plains = list(plains)
         if not elts or len(plains) != len(elts):
@@ -958,6 +1006,7 @@ class Evaluator:
         """sum_i applyGalois(sum_j plains[i][j] * applyGalois(a, baby_elts[j]), giant_elts[i]) as ONE call: len(baby_elts) + len(giant_elts) keys for
         len(baby_elts) * len(giant_elts) rotations, one mod-down for all giants.  plains: len(giant_elts) lists of len(baby_elts) DeviceBuffer (K * N words,
         NTT form at the KEY level, as applyGaloisPlainSumHoisted) or None for an absent term.  The keys of elements no present plaintext uses are not needed."""
+        self._per_prime_only(galois_keys)
         babies, giants = [int(g) for g in baby_elts], [int(g) for g in giant_elts]
         table = [list(row) for row in plains]
         n1, n2 = len(babies), len(giants)
@@ -1002,7 +1051,29 @@ class Evaluator:
         elt = lambda s: self.context.galois_elt_from_step(int(s)) if int(s) else 1
         return self.applyGaloisPlainSumBsgs(a, [elt(s) for s in baby_steps], [elt(s) for s in giant_steps], plains, galois_keys, plain_scale, scratch_limit_words)
 
+    def _rotate_grouped(self, a, steps, galois_keys):
+        """rotate_internal (capi.cpp; evaluator_cuda.cu:2140-2175) over keys with grouped digits: the key of the step itself, else its NAF terms one by one"""
+        if steps == 0:
+            return
+        elt = self.context.galois_elt_from_step(steps)
+        if galois_keys.hasKey(GaloisKeys.getIndex(elt)):
+            return self.applyGaloisInplace(a, elt, galois_keys)
+        terms, neg, v, i = [], steps < 0, abs(steps), 0
+        while v:  # numth.h:16-36
+            z = 2 - (v & 3) if v & 1 else 0
+            v = (v - z) >> 1
+            if z:
+                terms.append((-z if neg else z) * (1 << i))
+            i += 1
+        if len(terms) == 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "Galois key not present")
+        for t in terms:
+            if abs(t) != self.context.N >> 1:
+                self._rotate_grouped(a, t, galois_keys)
+
     def _rotate(self, a, steps, conjugate, galois_keys):
+        if galois_keys.special_primes is not None:
+            return self.applyGaloisInplace(a, 2 * self.context.N - 1, galois_keys) if conjugate else self._rotate_grouped(a, int(steps), galois_keys)
         elts = [2 * i + 1 for i in galois_keys.keys]
         n = len(elts)
         e = (C.c_uint32 * max(n, 1))(*elts)
@@ -1185,8 +1256,37 @@ class KeyGenerator:
     def _seed_args(self):
         return C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1])
 
-    def createRelinKeys(self, device=False):
-        """the host key array [K-1][2][K][N]; device=True: a RelinKeys whose key was generated on the device"""
+    def _grouped(self, cls, kind, special_primes, device, elts=(0,), new_key=None, seed=None):
+        """keys with grouped digits (no reference counterpart), source kind 1 relin / 2 Galois / 3 key switching: the host
+        arrays [digits][2][K][N], one per element, or with device=True a populated `cls` whose keys were generated on the device in one call"""
+        ctx, alpha = self.context, int(special_primes)
+        digits, _, words = ctx.grouped_key_shape(alpha)
+        lo, hi = seed or self._seed_args()
+        K, N = ctx.key_limbs, ctx.N
+        if device:
+            bufs = [DeviceBuffer(words) for _ in elts]
+            table = (C.c_void_p * max(1, len(bufs)))(*[b.ptr for b in bufs])
+            e = np.ascontiguousarray(elts, dtype=np.uint32)
+            dnew = DeviceBuffer.from_numpy(new_key) if new_key is not None else None
+            capi.check(self.lib, self.lib.troyhip_create_kswitch_keys_grouped(ctx.h, lo, hi, C.c_void_p(self._device_sk().ptr), kind, C.c_void_p(dnew.ptr) if dnew else None,
+                                                                              e.ctypes.data_as(C.c_void_p), C.c_uint64(len(bufs)), alpha, table, None))
+            keys = cls(ctx, special_primes=alpha)
+            for g, b in zip(elts, bufs):
+                keys.set_device(GaloisKeys.getIndex(g) if kind == 2 else 0, b)
+            return keys
+        out = []
+        for g in elts:
+            k = np.zeros((digits, 2, K, N), dtype=np.uint64)
+            capi.check(self.lib, self.lib.troyhip_host_kswitch_key_grouped(ctx.h, lo, hi, _u64p(self._sk), kind, _u64p(new_key) if new_key is not None else None,
+                                                                           C.c_uint32(g), alpha, _u64p(k)))
+            out.append(k)
+        return out
+
+    def createRelinKeys(self, device=False, special_primes=None):
+        """the host key array [K-1][2][K][N]; device=True: a RelinKeys whose key was generated on the device.  special_primes: a key with grouped digits"""
+        if special_primes is not None:
+            r = self._grouped(RelinKeys, 1, special_primes, device)
+            return r if device else r[0]
         if device:
             out = self._device_ksk()
             capi.check(self.lib, self.lib.troyhip_create_relin_key(self.context.h, *self._seed_args(), C.c_void_p(self._device_sk().ptr), C.c_void_p(out.ptr), None))
@@ -1197,7 +1297,7 @@ class KeyGenerator:
         capi.check(self.lib, self.lib.troyhip_host_relin_key(self.context.h, C.c_uint64(self.seed[0]), C.c_uint64(self.seed[1]), _u64p(self._sk), _u64p(out)))
         return out
 
-    def createKeySwitchingKeys(self, new_key, device=False):
+    def createKeySwitchingKeys(self, new_key, device=False, special_primes=None):
         """KeyGenerator::createKeySwitchingKeys (src/keygenerator.cpp:360-366): the host key array that takes a ciphertext under `new_key`
         (another generator's secretKey()) to one under this generator's secret key; KSwitchKeys.set(0, .) + applyKeySwitchingInplace use it.
         device=True: a KSwitchKeys whose key (index 0) was generated on the device.
@@ -1208,6 +1308,9 @@ class KeyGenerator:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "new_key is not valid for encryption parameters")
         lo, hi = C.c_uint64((self.seed[0] + self.kswitch_calls) & (2**64 - 1)), C.c_uint64(self.seed[1])
         self.kswitch_calls += 1
+        if special_primes is not None:  # a key with grouped digits; the calls count together with the per-prime ones
+            r = self._grouped(KSwitchKeys, 3, special_primes, device, new_key=new_key, seed=(lo, hi))
+            return r if device else r[0]
         if device:
             out, dnew = self._device_ksk(), DeviceBuffer.from_numpy(new_key)
             capi.check(self.lib, self.lib.troyhip_create_kswitch_key(self.context.h, lo, hi, C.c_void_p(self._device_sk().ptr), C.c_void_p(dnew.ptr),
@@ -1237,15 +1340,18 @@ class KeyGenerator:
             pos, neg, span = pos * pos % m, neg * neg % m, span << 1
         return elts
 
-    def createAutomorphismKeys(self, device=False):
+    def createAutomorphismKeys(self, device=False, special_primes=None):
         """KeyGenerator::createAutomorphismKeys (src/keygenerator.cpp:350-358): the keys of fieldTraceInplace / packLWECiphertexts,
         X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1; returns {elt: host key array}, or with device=True a GaloisKeys generated on the device"""
-        return self.createGaloisKeys(self.automorphismElts(), device=device)
+        return self.createGaloisKeys(self.automorphismElts(), device=device, special_primes=special_primes)
 
-    def createGaloisKeys(self, galois_elts=None, device=False):
+    def createGaloisKeys(self, galois_elts=None, device=False, special_primes=None):
         """returns {elt: host key array}; galois_elts=None: galoisEltsAll().  device=True: a GaloisKeys whose keys were all generated on the
         device in one call"""
         galois_elts = self.galoisEltsAll() if galois_elts is None else [int(e) for e in galois_elts]
+        if special_primes is not None:  # keys with grouped digits
+            r = self._grouped(GaloisKeys, 2, special_primes, device, elts=galois_elts)
+            return r if device else dict(zip(galois_elts, r))
         if device:
             elts = np.ascontiguousarray(galois_elts, dtype=np.uint32)
             bufs = [self._device_ksk() for _ in galois_elts]

@@ -68,6 +68,8 @@ SYMBOLS = [
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",
     "troyhip_host_noise_budget", "troyhip_noise_budget",
+    "troyhip_grouped_key_shape", "troyhip_host_kswitch_key_grouped", "troyhip_create_kswitch_keys_grouped", "troyhip_switch_key_grouped", "troyhip_relinearize_grouped",
+    "troyhip_apply_galois_grouped", "troyhip_apply_key_switching_grouped", "troyhip_switch_key_grouped_scratch_words",
 ]
 
 _lib = None

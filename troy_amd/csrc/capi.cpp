@@ -709,6 +709,94 @@ int troyhip_create_kswitch_key(troyhip_context *ctx, uint64_t seed_lo, uint64_t 
     });
 }
 
+// ---- key switching with grouped digits (no reference counterpart) ----
+static u64 grouped_stream(int src_kind, uint32_t elt) { // the streams of the per-prime generators: relin 1, Galois (2 << 32) | elt, key switching 5 << 32
+    if (src_kind == 1) return 1;
+    if (src_kind == 2) return ((u64)2 << 32) | elt;
+    if (src_kind == 3) return (u64)5 << 32;
+    throw Error(ST_INVALID_ARGUMENT, "src_kind must be 1 (relinearization), 2 (Galois) or 3 (key switching)");
+}
+int troyhip_grouped_key_shape(const troyhip_context *ctx, int special_primes, int *digits, int *max_limbs, size_t *key_words) {
+    return guard([&] {
+        const Context &c = need(ctx)->ctx;
+        int d = 0, l = 0;
+        c.ksg_shape(special_primes, d, l);
+        if (digits) *digits = d;
+        if (max_limbs) *max_limbs = l;
+        if (key_words) *key_words = (size_t)d * 2 * c.K * c.N;
+    }, false);
+}
+int troyhip_host_kswitch_key_grouped(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, int src_kind, const uint64_t *new_key,
+                                     uint32_t galois_elt, int special_primes, uint64_t *out) {
+    return guard([&] {
+        const Context &c = need(ctx)->ctx;
+        hostcrypto::Rng rng(seed_lo, seed_hi, grouped_stream(src_kind, galois_elt));
+        if (!secret_key || !out || (src_kind == 3 && !new_key)) throw Error(ST_INVALID_ARGUMENT, "null key, element list or key output");
+        std::vector<u64> src;
+        if (src_kind != 3) src.resize((size_t)c.K * c.N);
+        if (src_kind == 1) hostcrypto::relin_source(c, secret_key, src.data());
+        if (src_kind == 2) hostcrypto::galois_source(c, secret_key, galois_elt, src.data());
+        hostcrypto::keygen_kswitch(c, rng, secret_key, src_kind == 3 ? new_key : src.data(), out, special_primes);
+    }, false);
+}
+int troyhip_create_kswitch_keys_grouped(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, int src_kind, const uint64_t *new_key,
+                                        const uint32_t *galois_elts, uint64_t count, int special_primes, uint64_t *const *outs, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        if (src_kind == 2 && !galois_elts) throw Error(ST_INVALID_ARGUMENT, "null key, element list or key output");
+        if (src_kind != 2 && count != 1) throw Error(ST_INVALID_ARGUMENT, "one key per call unless the keys are Galois keys");
+        std::vector<u64> streams((size_t)count);
+        for (size_t i = 0; i < streams.size(); i++) streams[i] = grouped_stream(src_kind, src_kind == 2 ? galois_elts[i] : 0);
+        x->kg.kswitch(seed_lo, seed_hi, secret_key, src_kind, new_key, streams.data(), src_kind == 2 ? galois_elts : nullptr, outs, count, s, special_primes);
+    });
+}
+int troyhip_switch_key_grouped(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *target, uint64_t target_batch_stride, const uint64_t *base, uint64_t base_batch_stride,
+                               int base_polys, const uint64_t *key, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!ct) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        if (base && base_polys != 1 && base_polys != 2) throw Error(ST_INVALID_ARGUMENT, "the base has one or two polynomials");
+        CtBatch x = view(ct);
+        need(ctx)->ev.switch_key_grouped(x, target, target_batch_stride, KsKey{key}, special_primes, batch, scratch_limit_words, on(stream),
+                                         base ? KsBase{base, base_batch_stride, base_polys} : KsBase{});
+        store(x, ct);
+    });
+}
+int troyhip_relinearize_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint64_t *relin_key, int special_primes, uint64_t scratch_limit_words,
+                                uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        CtBatch o = view(out);
+        need(ctx)->ev.relinearize_grouped(view(in), o, KsKey{relin_key}, special_primes, batch, scratch_limit_words, on(stream));
+        store(o, out);
+    });
+}
+int troyhip_apply_galois_grouped(troyhip_context *ctx, troyhip_ct *ct, uint32_t galois_elt, const uint64_t *galois_key, int special_primes, uint64_t scratch_limit_words,
+                                 uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!ct) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        CtBatch x = view(ct);
+        need(ctx)->ev.apply_galois_grouped(x, galois_elt, KsKey{galois_key}, special_primes, batch, scratch_limit_words, on(stream));
+        store(x, ct);
+    });
+}
+int troyhip_apply_key_switching_grouped(troyhip_context *ctx, troyhip_ct *ct, const uint64_t *kswitch_key, int special_primes, uint64_t scratch_limit_words, uint64_t batch,
+                                        void *stream) {
+    return guard([&] {
+        if (!ct) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        CtBatch x = view(ct);
+        need(ctx)->ev.apply_key_switching_grouped(x, KsKey{kswitch_key}, special_primes, batch, scratch_limit_words, on(stream));
+        store(x, ct);
+    });
+}
+int troyhip_switch_key_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.switch_key_grouped_scratch_words(limbs, special_primes, batch);
+    }, false);
+}
+
+
 int troyhip_batch_encode(troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t values_stride, uint64_t *plain_out, uint64_t plain_stride,
                          uint64_t batch, void *stream) {
     return guard([&] {

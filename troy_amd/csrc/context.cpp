@@ -183,6 +183,81 @@ const NoiseDev &Context::noise_level(int limbs) {
     return noise_levels_[limbs] = d;
 }
 
+// ---- key switching with grouped digits ----
+void Context::ksg_shape(int alpha, int &digits, int &max_limbs) const {
+    if (K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    if (alpha < 1 || alpha > std::min(8, K - 1)) throw Error(ST_INVALID_ARGUMENT, "special_primes must lie in 1 .. min(8, key limbs - 1)");
+    const int lmax = K - alpha;
+    digits = (lmax + alpha - 1) / alpha;
+    max_limbs = lmax;
+    if (ksg_admitted_ & (1u << alpha)) return; // the group lengths of this alpha were checked before: every key switch asks
+    const int p_bits = host::bit_length_of_product(std::vector<u64>(primes.begin() + lmax, primes.begin() + K));
+    // one special prime is the reference's key switch, which takes any prime as the special one: nothing to refuse
+    for (int i0 = 0; alpha > 1 && i0 < lmax; i0 += alpha)
+        if (host::bit_length_of_product(std::vector<u64>(primes.begin() + i0, primes.begin() + std::min(i0 + alpha, lmax))) > p_bits)
+            throw Error(ST_INVALID_ARGUMENT, "special modulus is smaller than a digit");
+    ksg_admitted_ |= 1u << alpha;
+}
+const KsgArgs &Context::ksg_level(int alpha, int dl) {
+    int digits = 0, lmax = 0;
+    ksg_shape(alpha, digits, lmax);
+    if (dl < 1 || dl > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    if (!has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    auto it = ksg_levels_.find({alpha, dl});
+    if (it != ksg_levels_.end()) return *it->second;
+    const int rl = dl + alpha, sp0 = K - alpha;
+    auto out_prime = [&](int o) { return primes[o < dl ? o : sp0 + (o - dl)]; };
+    auto others = [&](int lo, int hi, int skip) { // the primes lo .. hi - 1 without `skip`
+        std::vector<u64> v;
+        for (int k = lo; k < hi; k++) if (k != skip) v.push_back(primes[k]);
+        return v;
+    };
+    std::vector<Shoup> ext_pre(dl), md_pre(alpha), inv_p(dl);
+    std::vector<u64> ext_mat((size_t)rl * dl, 0), md_mat((size_t)dl * alpha), md_mat_t(alpha, 0), half_sp(alpha), half_q(dl), p_mod_q(dl);
+    for (int i = 0; i < dl; i++) {
+        const int lo = i / alpha * alpha, hi = std::min(lo + alpha, dl);
+        const std::vector<u64> rest = others(lo, hi, i); // Q_j / p_i
+        ext_pre[i] = make_shoup(host::inv_mod_checked(host::product_mod(rest, primes[i]), primes[i]), primes[i]);
+        for (int o = 0; o < rl; o++) ext_mat[(size_t)o * dl + i] = host::product_mod(rest, out_prime(o));
+    }
+    const std::vector<u64> special = others(sp0, K, -1);
+    auto half_mod = [&](u64 p) { // floor(P / 2) = (P - 1) / 2 modulo an odd prime
+        return host::mul_mod((host::product_mod(special, p) + p - 1) % p, host::inv_mod_checked(2, p), p);
+    };
+    for (int m = 0; m < alpha; m++) {
+        const u64 pm = primes[sp0 + m];
+        const std::vector<u64> rest = others(sp0, K, sp0 + m); // P / p_m
+        md_pre[m] = make_shoup(host::inv_mod_checked(host::product_mod(rest, pm), pm), pm);
+        for (int i = 0; i < dl; i++) md_mat[(size_t)i * alpha + m] = host::product_mod(rest, primes[i]);
+        if (t) md_mat_t[m] = host::product_mod(rest, t);
+        half_sp[m] = half_mod(pm);
+    }
+    for (int i = 0; i < dl; i++) {
+        p_mod_q[i] = host::product_mod(special, primes[i]);
+        inv_p[i] = make_shoup(host::inv_mod_checked(p_mod_q[i], primes[i]), primes[i]);
+        half_q[i] = half_mod(primes[i]);
+    }
+    auto a = std::make_shared<KsgArgs>();
+    std::memset(a.get(), 0, sizeof(KsgArgs));
+    a->primes = d_desc;
+    a->ext_pre = upload(ext_pre, dev_allocs_);
+    a->ext_mat = upload(ext_mat, dev_allocs_);
+    a->md_pre = upload(md_pre, dev_allocs_);
+    a->md_mat = upload(md_mat, dev_allocs_);
+    a->md_mat_t = upload(md_mat_t, dev_allocs_);
+    a->inv_p = upload(inv_p, dev_allocs_);
+    a->half_sp = upload(half_sp, dev_allocs_);
+    a->half_q = upload(half_q, dev_allocs_);
+    a->p_mod_q = upload(p_mod_q, dev_allocs_);
+    if (t) {
+        const Mod tm = make_mod(t);
+        a->t_p = tm.p; a->t_cr0 = tm.cr0; a->t_cr1 = tm.cr1;
+        a->inv_p_mod_t = host::inv_mod_checked(host::product_mod(special, t), t);
+    }
+    a->logn = logn; a->dl = (u32)dl; a->alpha = (u32)alpha; a->d = (u32)((dl + alpha - 1) / alpha); a->K = (u32)K;
+    return *(ksg_levels_[{alpha, dl}] = a);
+}
+
 const Level &Context::level(int limbs) const {
     auto it = levels.find(limbs);
     if (it == levels.end()) throw Error(ST_INVALID_ARGUMENT, "no such level in the modulus chain");

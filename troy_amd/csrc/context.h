@@ -12,6 +12,7 @@
 namespace troyhip {
 
 struct BehzDev; // behz.hip
+struct KsgArgs; // kernels.h
 
 enum Scheme { SCHEME_BFV = 1, SCHEME_CKKS = 2, SCHEME_BGV = 3 };
 
@@ -104,6 +105,11 @@ public:
     LimbMap single_map(int id) const;
     // BFV / BGV: built on the first use of a level and kept for the lifetime of the context (the calling thread's current device must be `device`)
     const NoiseDev &noise_level(int limbs);
+    // Key switching with grouped digits: the last `alpha` key primes serve as special primes.  ksg_shape refuses an alpha outside
+    // 1 .. min(8, K - 1) and, from alpha = 2 on, a digit group whose product is longer than theirs; digits = ceil((K - alpha) / alpha), max_limbs = K - alpha.  Host tables only.
+    void ksg_shape(int alpha, int &digits, int &max_limbs) const;
+    // the constants of one (alpha, data limbs) on the device, built on the first use and kept (as noise_level); batch is left 0
+    const KsgArgs &ksg_level(int alpha, int dl);
 
 private:
     int register_prime(u64 p);
@@ -111,6 +117,8 @@ private:
     void build_level(int limbs);
     std::vector<void *> dev_allocs_;
     std::map<int, NoiseDev> noise_levels_;
+    std::map<std::pair<int, int>, std::shared_ptr<KsgArgs>> ksg_levels_;
+    mutable unsigned ksg_admitted_ = 0; // bit alpha: ksg_shape found every digit group of alpha admissible
     template <class T> T *upload(const std::vector<T> &v, std::vector<void *> &owner);
 };
 

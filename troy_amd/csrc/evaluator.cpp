@@ -1635,6 +1635,148 @@ void Evaluator::apply_key_switching(CtBatch &ct, const KsKey &key, u64 batch, hi
     // ciphertext as (c0, 0): no copy of c1, no zero fill
     switch_key(ct, ct.data + pw, ct.bstride, key, batch, s, KsBase{ct.data, ct.bstride});
 }
+// ---- key switching with grouped digits (no reference counterpart) ----
+// Scratch per item, in units of N words (rl = dl + alpha, d = ceil(dl / alpha)): dl [CKKS: the target in coefficient form] + d rl [D] + 2 rl [acc]
+// + CKKS: 2 alpha [the special limbs in coefficient form] + 2 dl [the correction]
+static u64 ksg_item_words(const Context &c, u64 dl, u64 alpha) {
+    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
+    return c.N * (ckks * dl + d * rl + 2 * rl + ckks * (2 * alpha + 2 * dl));
+}
+static const u64 KSG_BLOCKS = 8;
+u64 Evaluator::switch_key_grouped_scratch_words(int limbs, int alpha, u64 batch) const {
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax);
+    if (limbs < 1 || limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    return batch * ksg_item_words(c, (u64)limbs, (u64)alpha) + slab_slack(KSG_BLOCKS);
+}
+void Evaluator::switch_key_grouped(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s,
+                                   const KsBase &base) {
+    check_ct(ct);
+    if (!target) throw Error(ST_INVALID_ARGUMENT, "target_iter");
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax); // K < 2, alpha out of range
+    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "kswitch_keys is not valid for encryption parameters");
+    check_ks_form(ct.ntt);
+    if (ct.size < 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be at least 2");
+    if (ct.limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    if (!batch) return;
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const u64 N = c.N, dl = ct.limbs, al = alpha, rl = dl + al, d = (dl + al - 1) / al, K = c.K;
+    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_BLOCKS, ksg_item_words(c, dl, al), 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
+    const u64 bs = plan.items;
+    KsgArgs a = c.ksg_level(alpha, (int)dl);
+    std::vector<uint8_t> out_ids, sp_ids;
+    for (u64 o = 0; o < rl; o++) out_ids.push_back((uint8_t)(o < dl ? o : K - al + (o - dl)));
+    for (u64 m = 0; m < al; m++) sp_ids.push_back((uint8_t)(K - al + m));
+    const LimbMap digit_map = c.ids_map(out_ids, (uint32_t)d), acc_map = c.ids_map(out_ids), sp_map = c.ids_map(sp_ids), tmap = c.ct_map((int)dl);
+
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(bs * 2 * rl * N);
+    u64 *last = ckks ? c.arena.take(bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(bs * 2 * dl * N) : nullptr;
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        a.batch = std::min(bs, batch - b0);
+        const u64 nb = a.batch;
+        const u64 *tg = target + b0 * t_bstride;
+        u64 tb = t_bstride;
+        if (ckks) { // the target in coefficient form (ks_coeff_target)
+            launch_copy_strided(tg, tb, tt, dl * N, dl * N, nb, s);
+            launch_ntt(tt, c.d_desc, tmap, nb * dl, c.logn, true, s);
+            tg = tt;
+            tb = dl * N;
+        }
+        // 1. extension of every digit to every output prime, 2. forward transforms and the inner product with the key
+        launch_ksg_extend(tg, tb, D, a, s);
+        launch_ntt(D, c.d_desc, digit_map, nb * rl * d, c.logn, false, s);
+        launch_ksg_mac(D, key.data, acc, a, s);
+        // the base, after the target has been read (apply_key_switching: the target is c1 of ct itself)
+        u64 *dst = ct.data + b0 * ct.bstride;
+        if (base.ptr) {
+            const u64 *bp = base.ptr + b0 * base.bstride;
+            if (bp != dst) launch_copy_strided(bp, base.bstride, dst, ct.bstride, (u64)base.polys * dl * N, nb, s);
+            if (base.polys < 2) launch_zero_strided(dst + dl * N, ct.bstride, dl * N, nb, s);
+        }
+        // 3. mod-down by P
+        if (ckks) {
+            launch_copy_strided(acc + dl * N, rl * N, last, al * N, al * N, nb * 2, s);
+            launch_ntt(last, c.d_desc, sp_map, nb * 2 * al, c.logn, true, s);
+            launch_ksg_moddown(1, nullptr, last, al * N, corr, nullptr, 0, a, s);
+            launch_ntt(corr, c.d_desc, tmap, nb * 2 * dl, c.logn, false, s);
+            launch_ksg_ckks_combine(acc, corr, dst, ct.bstride, a, s);
+        } else {
+            launch_ntt(acc, c.d_desc, acc_map, nb * 2 * rl, c.logn, true, s);
+            launch_ksg_moddown(c.scheme == SCHEME_BFV ? 0 : 2, acc, acc + dl * N, rl * N, nullptr, dst, ct.bstride, a, s);
+        }
+        stats::counter(stats::GROUPED_KS_SLABS)++;
+    }
+}
+void Evaluator::relinearize_grouped(const CtBatch &in, CtBatch &out, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (in.size != 2 && in.size != 3) throw Error(ST_INVALID_ARGUMENT, "grouped relinearization takes a ciphertext of size 2 or 3");
+    const u64 pw = poly_words(c, in.limbs);
+    u64 *dptr = out.data;
+    const u64 bs = out.bstride;
+    if (!dptr || bs < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "relinearize: destination too small");
+    const bool in_place = dptr == in.data;
+    if (in.size == 2) { // nothing to switch, as the per-prime relinearization: a copy (or nothing in place), no key read
+        if (!in_place && batch) {
+            if (batches_overlap(dptr, batch, bs, 2 * pw, in.data, batch, in.bstride, 2 * pw)) throw Error(ST_INVALID_ARGUMENT, "relinearize: destination must be a distinct buffer");
+            launch_copy_strided(in.data, in.bstride, dptr, bs, 2 * pw, batch, s);
+        }
+        out = in;
+        out.data = dptr;
+        out.bstride = bs;
+        return;
+    }
+    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "not enough relinearization keys");
+    if (!in_place && batch && batches_overlap(dptr, batch, bs, 2 * pw, in.data, batch, in.bstride, 3 * pw)) throw Error(ST_INVALID_ARGUMENT, "relinearize: destination must be a distinct buffer");
+    out = in;
+    out.data = dptr;
+    out.bstride = bs;
+    out.size = 2;
+    // in place: accumulates onto (c0, c1) as they lie; else the operand is read where it lies and (c0, c1) reach the destination as the base
+    switch_key_grouped(out, in.data + 2 * pw, in.bstride, key, alpha, batch, scratch_limit_words, s, in_place ? KsBase{} : KsBase{in.data, in.bstride, 2});
+}
+void Evaluator::apply_galois_grouped(CtBatch &ct, uint32_t elt, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(ct);
+    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    if (!(elt & 1) || elt >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
+    if (ct.size > 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax);
+    if (ct.limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    if (!batch) return;
+    const u64 pw = poly_words(c, ct.limbs);
+    const int L = ct.limbs;
+    // sigma(c0), sigma(c1) of a run of items behind the key switch's own scratch, as apply_galois keeps them; the runs are planned here, the key switch
+    // of a run then takes one slab
+    const u64 per_item = ksg_item_words(c, (u64)L, (u64)alpha);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_BLOCKS + 2, per_item + 2 * pw, 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
+    const u64 bs = plan.items, ks = bs * per_item + slab_slack(KSG_BLOCKS);
+    const LimbMap map = c.ct_map(L);
+    const bool ntt_form = c.scheme == SCHEME_CKKS;
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        c.arena.begin(s);
+        c.arena.reserve(plan.words);
+        (void)c.arena.take(ks);
+        u64 *t0 = c.arena.take(bs * pw), *t1 = c.arena.take(bs * pw);
+        CtBatch part = ct;
+        part.data = ct.data + b0 * ct.bstride;
+        launch_galois(ntt_form, part.data, ct.bstride, t0, pw, c.d_desc, map, c.logn, elt, L, nb, s);
+        launch_galois(ntt_form, part.data + pw, ct.bstride, t1, pw, c.d_desc, map, c.logn, elt, L, nb, s);
+        switch_key_grouped(part, t1, pw, key, alpha, nb, ks, s, KsBase{t0, pw});
+    }
+}
+void Evaluator::apply_key_switching_grouped(CtBatch &ct, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(ct);
+    if (!key.data) throw Error(ST_INVALID_ARGUMENT, "kswitch_keys.data().size() != 1");
+    if (ct.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted.size() != 2");
+    const u64 pw = poly_words(c, ct.limbs);
+    switch_key_grouped(ct, ct.data + pw, ct.bstride, key, alpha, batch, scratch_limit_words, s, KsBase{ct.data, ct.bstride});
+}
+
 // negacyclicShift (evaluator_cuda.cu:2342-2351): every limb of every polynomial is multiplied by x^shift
 void Evaluator::negacyclic_shift(CtBatch &ct, u64 shift, u64 batch, hipStream_t s) {
     check_ct(ct);

@@ -83,6 +83,17 @@ public:
     void mod_switch_to_next(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void rescale_to_next(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
     void apply_galois(CtBatch &ct, uint32_t elt, const KsKey &key, u64 batch, hipStream_t s);
+    // Key switching with grouped digits (no reference counterpart): `key` holds ceil((K - alpha) / alpha) digits over the last
+    // alpha key primes as special primes (KeyGenerator, special_primes = alpha); the operand has at most K - alpha limbs.  switch_key_grouped is
+    // switch_key (the same target, base and accumulation), the other three are relinearize_to from size 3 / in place, apply_galois and
+    // apply_key_switching on it.  At alpha == 1 every result equals the per-prime call byte for byte.  The arena request stays under
+    // scratch_limit_words (0: 2^28 words), in slabs of items; the result does not depend on the slabs or the batch size.
+    void switch_key_grouped(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s,
+                            const KsBase &base = {});
+    void relinearize_grouped(const CtBatch &in, CtBatch &out, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s); // out.data == in.data: in place; size 2: a copy
+    void apply_galois_grouped(CtBatch &ct, uint32_t elt, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    void apply_key_switching_grouped(CtBatch &ct, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    u64 switch_key_grouped_scratch_words(int limbs, int alpha, u64 batch) const; // what switch_key_grouped asks of the arena with the whole batch in one slab
     // Hoisted rotations: out item r * batch + b = the Galois automorphism elts[r] of in item b, key-switched with keys[r] (R dense batches back to
     // back; out.data / out.bstride are the caller's, room for R * batch size-2 items, distinct from in).  The digits of c1 are expanded once per
     // item; element 1 is a copy and reads no key.  The arena request stays under scratch_limit_words (0: 2^28 words), in slabs where needed.

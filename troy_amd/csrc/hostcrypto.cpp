@@ -164,18 +164,23 @@ void keygen_public(const Context &c, Rng &rng, const u64 *sk, u64 *pk) { // keyg
     const u64 e_scale = c.scheme == SCHEME_BGV ? c.t : 1; // BGV errors are multiples of t (rlwe.cpp:300-320)
     encrypt_zero_symmetric_ntt(P, rng, sk, c.K, pk, pk + (size_t)c.K * c.N, e_scale);
 }
-// keygenerator.cpp:294-329 generateOneKswitchKey: key j encrypts q_special * new_key in limb j only
-void keygen_kswitch(const Context &c, Rng &rng, const u64 *sk, const u64 *new_key, u64 *out) {
-    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+// keygenerator.cpp:294-329 generateOneKswitchKey: key j encrypts q_special * new_key in limb j only.  alpha > 1 (no reference
+// counterpart): the last alpha primes are special, digit j covers the limbs of group G_j and carries (P mod p_i) * new_key on them; the draws are the same
+void keygen_kswitch(const Context &c, Rng &rng, const u64 *sk, const u64 *new_key, u64 *out, int alpha) {
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax);
     Polys P(c);
     const size_t N = c.N, K = c.K;
     const u64 e_scale = c.scheme == SCHEME_BGV ? c.t : 1;
-    for (size_t j = 0; j + 1 < K; j++) {
+    const std::vector<u64> special(c.primes.begin() + lmax, c.primes.begin() + K);
+    for (size_t j = 0; j < (size_t)digits; j++) {
         u64 *c0 = out + (j * 2) * K * N, *c1 = c0 + K * N;
         encrypt_zero_symmetric_ntt(P, rng, sk, (int)K, c0, c1, e_scale);
-        const Mod m = P.mod((int)j);
-        const u64 factor = c.primes[K - 1] % m.p;
-        for (size_t i = 0; i < N; i++) c0[j * N + i] = addmod(c0[j * N + i], mulmod(new_key[j * N + i], factor, m), m.p);
+        for (size_t l = j * alpha; l < std::min<size_t>((j + 1) * alpha, lmax); l++) {
+            const Mod m = P.mod((int)l);
+            const u64 factor = host::product_mod(special, m.p);
+            for (size_t i = 0; i < N; i++) c0[l * N + i] = addmod(c0[l * N + i], mulmod(new_key[l * N + i], factor, m), m.p);
+        }
     }
 }
 void relin_source(const Context &c, const u64 *sk, u64 *out) { // s^2 (keygenerator.cpp:228-262)

@@ -239,6 +239,37 @@ void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const 
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_combine(const u64 *acc, const u64 *corr, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
+// ---- key switching with grouped digits (no reference counterpart) ----
+// alpha special primes (the last alpha key primes, product P), the data limbs taken alpha at a time as one digit: d = ceil(dl / alpha) digits, output
+// primes o = 0 .. rl - 1 (rl = dl + alpha): the data primes, then the special primes (prime id and key limb K - alpha + o - dl).  The tables are the
+// context's per (alpha, dl), on the device (Context::ksg_level).  A struct of its own: KsArgs means "one digit per limb, one special limb" throughout.
+enum { KSG_MAX_ALPHA = 8 };
+struct KsgArgs {
+    const PrimeDesc *primes;
+    const Shoup *ext_pre;  // [dl]        (Q_j / p_i)^-1 mod p_i, j = i / alpha
+    const u64 *ext_mat;    // [rl][dl]    (Q_j / p_i) mod p_o (unused where o lies in the group of i)
+    const Shoup *md_pre;   // [alpha]     (P / p_m)^-1 mod p_m
+    const u64 *md_mat;     // [dl][alpha] (P / p_m) mod p_i
+    const u64 *md_mat_t;   // [alpha]     (P / p_m) mod t (BGV)
+    const Shoup *inv_p;    // [dl]        P^-1 mod p_i
+    const u64 *half_sp;    // [alpha]     floor(P / 2) mod p_m
+    const u64 *half_q;     // [dl]        floor(P / 2) mod p_i
+    const u64 *p_mod_q;    // [dl]        P mod p_i
+    u64 t_p, t_cr0, t_cr1, inv_p_mod_t;
+    int logn;
+    u32 dl, alpha, d, K;
+    u64 batch;
+};
+// step 1: D[((b * rl + o) * d + j)][n] = the extension of digit j of target[b] ([dl][N] coefficient form, stride t_bstride) to output prime o
+void launch_ksg_extend(const u64 *target, u64 t_bstride, u64 *D, const KsgArgs &a, hipStream_t s);
+// step 2: acc[(b * 2 + c) * rl + o][n] = sum_j D[(b * rl + o) * d + j][n] * key[j][c][limb(o)][n] mod p_o over the transformed rows
+void launch_ksg_mac(const u64 *D, const u64 *key, u64 *acc, const KsgArgs &a, hipStream_t s);
+// step 3, everything in coefficient form.  kind 0 (BFV) / 2 (BGV): ct[b][c][i] += mod-down of acc ([2 batch][rl][N]); kind 1 (CKKS):
+// corr[(b * 2 + c) * dl + i][n] = (r_i - [h]_{p_i}) mod p_i -- acc / ct are not read.  sp: the special limbs, item o = b * 2 + c at sp + o * sp_ostride, [alpha][N]
+void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s);
+// CKKS: ct[b][c][i] += (acc_i - corr_i) P^-1 mod p_i, both in NTT form
+void launch_ksg_ckks_combine(const u64 *acc, const u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s);
+
 // ---- decryption (decryptor_cuda.cu:61-330, rns_cuda.cu:510-621) ----
 struct DecryptArgs {
     const PrimeDesc *primes;
@@ -314,7 +345,8 @@ void launch_enc_sk_combine(u64 *ct, u64 ct_bstride, const u64 *sk, const u64 *e,
                            hipStream_t s);
 
 // ---- keygen.hip (device key generation, keygen.cpp) ----
-// one digit j of a batch of keys: c0 = -(c1 s + e es_l) + [l == j] factor src_j over limbs l < K, c1 = c0 + K N already holds the uniform draws.
+// one digit of a batch of keys: c0 = -(c1 s + e es_l) + [j <= l < j_end] factors_l src_l over limbs l < K, c1 = c0 + K N already holds the uniform draws
+// (the per-prime key: j_end = j + 1; a grouped key, DESIGN.md section 4.16: the limbs of digit group G_j).
 // Item b's key at out_tab[b] (device table) or out + b * out_bstride; its c0 at + c0_off.  src_kind: 0 none (public key), 1 s^2 (relin),
 // 2 sigma_elts[b](s) in NTT form (Galois), 3 src [K][N] (key switching)
 struct KeyCombineArgs {
@@ -324,10 +356,10 @@ struct KeyCombineArgs {
     const u64 *sk;       // [K][N] NTT form; item b's at sk + b * sk_bstride (0: one key for all)
     u64 sk_bstride;
     const u64 *e;        // [items][K][N] NTT form
-    int src_kind, j;
+    int src_kind, j, j_end;
     const u64 *src;
     const u64 *elts;     // [items] Galois elements (src_kind 2)
-    u64 factor;          // q_special mod p_j
+    EncScale factors;    // v[l] = (product of the special primes) mod p_l for j <= l < j_end
     EncScale es;
     const PrimeDesc *primes;
     int logn;

@@ -93,7 +93,7 @@ void DeviceKeygen::keygen(const u64 *seeds, u64 *sk_out, u64 sk_bstride, u64 *pk
 }
 
 void DeviceKeygen::kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind, const u64 *new_key, const u64 *streams, const uint32_t *elts, u64 *const *outs,
-                           u64 count, hipStream_t s) {
+                           u64 count, hipStream_t s, int alpha) {
     // the checks of the host forms, with their statuses and messages (hostcrypto galois_source, keygen_kswitch); every element before anything runs
     if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
     if (!sk || !outs || (src_kind == 3 && !new_key) || (src_kind == 2 && !elts)) throw Error(ST_INVALID_ARGUMENT, "null key, element list or key output");
@@ -102,9 +102,13 @@ void DeviceKeygen::kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind
         if (!outs[i]) throw Error(ST_INVALID_ARGUMENT, "null key, element list or key output");
         if (src_kind == 2 && (!(elts[i] & 1) || elts[i] >= 2 * c.N)) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
     }
-    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax); // alpha == 1: K - 1 digits of one limb, the reference's key
     const int K = c.K;
     const u64 N = c.N, kw = (u64)K * N;
+    EncScale factors; // (product of the special primes) mod p_l
+    std::memset(&factors, 0, sizeof(factors));
+    for (int l = 0; l < lmax; l++) factors.v[l] = host::product_mod(std::vector<u64>(c.primes.begin() + lmax, c.primes.begin() + K), c.primes[l]);
     // the uniform samplers of limbs 0 .. K-1 (one per limb, every digit alike)
     std::vector<SamplerArgs> segs(K);
     size_t blocks = 0;
@@ -138,7 +142,7 @@ void DeviceKeygen::kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind
         u64 *const *d_outs = (u64 *const *)(d_words + 4 * B);
         HIP_CHECK(hipMemsetAsync(pos[0], 0, B * sizeof(u64), s));
         int cur = 0;
-        for (int j = 0; j + 1 < K; j++) {
+        for (int j = 0; j < digits; j++) {
             // c1 of digit j: K uniform samplers straight into the keys; then the noise, its transform and the combine
             for (int l = 0; l < K; l++, cur ^= 1) {
                 SamplerArgs a = segs[l];
@@ -157,7 +161,7 @@ void DeviceKeygen::kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind
             KeyCombineArgs k;
             std::memset(&k, 0, sizeof(k));
             k.out_tab = d_outs; k.c0_off = (u64)(2 * j) * kw; k.sk = sk; k.sk_bstride = 0; k.e = E;
-            k.src_kind = src_kind; k.j = j; k.src = new_key; k.elts = d_elts; k.factor = c.primes[K - 1] % c.primes[j];
+            k.src_kind = src_kind; k.j = j * alpha; k.j_end = std::min((j + 1) * alpha, lmax); k.src = new_key; k.elts = d_elts; k.factors = factors;
             k.es = es; k.primes = c.d_desc; k.logn = c.logn; k.K = (u32)K; k.items = B;
             launch_key_combine(k, s);
         }

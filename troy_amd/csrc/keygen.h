@@ -20,7 +20,7 @@ public:
     // keygen_kswitch of `count` keys with one seed: key i streams from (seed, streams[i]) into outs[i] ([K-1][2][K][N], device).  sk: device [K][N] NTT form.
     // src_kind 1: s^2 (relin), 2: sigma_elts[i](s) (Galois), 3: new_key (device [K][N]).  streams / elts / outs are HOST arrays, read before return
     void kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind, const u64 *new_key, const u64 *streams, const uint32_t *elts, u64 *const *outs, u64 count,
-                 hipStream_t s);
+                 hipStream_t s, int alpha = 1); // alpha special primes: keys of ceil((K - alpha) / alpha) grouped digits
 
 private:
     Context &c;

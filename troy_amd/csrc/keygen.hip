@@ -1,6 +1,6 @@
 // keygen.hip -- the element-wise step of device key generation (keygen.cpp): one digit of a key-switching key, or a public key, over a batch
 // of keys.  The draws come from sampler.hip, the transform of the noise from ntt.hip; this kernel closes hostcrypto.cpp's
-// encrypt_zero_symmetric_ntt and keygen_kswitch:  c0 = -(c1 s + e es_l) + [l == j] (q_special mod p_j) src_j.
+// encrypt_zero_symmetric_ntt and keygen_kswitch:  c0 = -(c1 s + e es_l) + [l in the digit's group] (P mod p_l) src_l, P the product of the special primes.
 #include "kernels.h"
 #include <algorithm>
 
@@ -8,8 +8,8 @@ namespace troyhip {
 
 #define KG_THREADS 256
 
-// grid x: coefficients, y: rows (item, limb) (stride loop).  Consecutive lanes read and write consecutive coefficients of one row; only the row
-// l == j of a Galois key gathers (sigma_elt(s) in NTT form, as galois_ntt_kernel / hostcrypto galois_source)
+// grid x: coefficients, y: rows (item, limb) (stride loop).  Consecutive lanes read and write consecutive coefficients of one row; only the rows
+// of the digit's group of a Galois key gather (sigma_elt(s) in NTT form, as galois_ntt_kernel / hostcrypto galois_source)
 __global__ __launch_bounds__(KG_THREADS) void key_combine_kernel(KeyCombineArgs a) {
     const u64 n = (u64)blockIdx.x * KG_THREADS + threadIdx.x, N = u64(1) << a.logn;
     if (n >= N) return;
@@ -23,7 +23,7 @@ __global__ __launch_bounds__(KG_THREADS) void key_combine_kernel(KeyCombineArgs 
         const u64 c1 = c0[(u64)a.K * N], ev = a.e[((b * a.K + l) << a.logn) + n];
         const u64 ee = a.es.v[l] == 1 ? ev : mulmod(ev, a.es.v[l], m);
         u64 v = negmod(addmod(mulmod(c1, sk[n], m), ee, m.p), m.p);
-        if (a.src_kind && (int)l == a.j) {
+        if (a.src_kind && (int)l >= a.j && (int)l < a.j_end) {
             u64 src;
             if (a.src_kind == 1) {
                 src = mulmod(sk[n], sk[n], m); // relin: s^2
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(KG_THREADS) void key_combine_kernel(KeyCombineArgs 
             } else {
                 src = a.src[(u64)l * N + n];
             }
-            v = addmod(v, mulmod(src, a.factor, m), m.p);
+            v = addmod(v, mulmod(src, a.factors.v[l], m), m.p);
         }
         *c0 = v;
     }

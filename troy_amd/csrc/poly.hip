@@ -1354,6 +1354,166 @@ void launch_ks_ckks_combine(const u64 *acc, const u64 *corr, u64 *ct, u64 ct_bst
     launch_check("ks_ckks_combine_kernel");
 }
 
+// ---------------------------------------------------------------- key switching with grouped digits
+// Element-wise, one coefficient per thread, no LDS; every loop over a group or over the special primes is unrolled under a predicate so that the
+// <= 8 residues of a group stay in registers (no private scratch); consecutive lanes store consecutive n of one row.
+__device__ __forceinline__ u32 ksg_out_id(const KsgArgs &a, u32 o) { return o < a.dl ? o : a.K - a.alpha + (o - a.dl); }
+// step 1.  y_i = [x_i (Q_j / p_i)^-1]_{p_i}; ext_j[p_o] = sum_i y_i [(Q_j / p_i) mod p_o] mod p_o, or x_o itself where p_o lies in the group (read again: it is
+// in the cache, and indexing the registers by o would put them into scratch).  At most 8 products below 2^61 * 2^61: the 128-bit sum stays below 2^125.
+__global__ __launch_bounds__(EW_THREADS) void ksg_extend_kernel(const u64 *target, u64 t_bstride, u64 *D, KsgArgs a) {
+    const u64 idx = (u64)blockIdx.x * EW_THREADS + threadIdx.x; // over batch * d * N
+    const u64 N = u64(1) << a.logn;
+    if (idx >= a.batch * a.d * N) return;
+    const u64 n = idx & (N - 1), bj = idx >> a.logn, j = bj % a.d, b = bj / a.d;
+    const u32 i0 = (u32)j * a.alpha, g = a.dl - i0 < a.alpha ? a.dl - i0 : a.alpha, rl = a.dl + a.alpha;
+    const u64 *x = target + b * t_bstride + (u64)i0 * N + n;
+    u64 y[KSG_MAX_ALPHA];
+#pragma unroll
+    for (u32 t = 0; t < KSG_MAX_ALPHA; t++) {
+        y[t] = 0;
+        if (t < g) y[t] = mul_shoup(x[(u64)t * N], a.ext_pre[i0 + t], a.primes[i0 + t].p);
+    }
+    for (u32 o = 0; o < rl; o++) {
+        u64 v;
+        if (o >= i0 && o < i0 + g) {
+            v = x[(u64)(o - i0) * N];
+        } else {
+            const u64 *row = a.ext_mat + (u64)o * a.dl + i0;
+            U128 sum{0, 0};
+#pragma unroll
+            for (u32 t = 0; t < KSG_MAX_ALPHA; t++)
+                if (t < g) mac128(sum, y[t], row[t]);
+            v = barrett128(sum.lo, sum.hi, mod_of(a.primes[ksg_out_id(a, o)]));
+        }
+        D[((b * rl + o) * a.d + j) * N + n] = v;
+    }
+}
+// step 2: ks_mac_kernel over d digits and rl output primes, four batch items per thread: a key word is read once per four items.
+// The lazy sums hold d products of canonical operands: d * p * p < 2^128 for d <= 63 and p < 2^61 (the launcher refuses more digits).
+__global__ __launch_bounds__(EW_THREADS) void ksg_mac_kernel(const u64 *D, const u64 *key, u64 *acc, KsgArgs a) {
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha;
+    const u64 groups = (a.batch + 3) / 4;
+    const u64 g = blockIdx.x % groups, wi = blockIdx.x / groups; // the batch group fastest, as ks_mac_kernel
+    const u64 idx = wi * EW_THREADS + threadIdx.x;               // over rl * N
+    if (idx >= rl << a.logn) return;
+    const u64 n = idx & (N - 1), o = idx >> a.logn, b0 = g * 4;
+    const u32 id = ksg_out_id(a, (u32)o);
+    const Mod m = mod_of(a.primes[id]);
+    MacAcc s0[4], s1[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); }
+    for (u64 j = 0; j < a.d; j++) {
+        const u64 *kp = key + ((j * 2) * a.K + id) * N + n;
+        const u64 t0 = kp[0], t1 = kp[a.K * N];
+        u64 k0[4], k1[4], x[4];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const u64 bb = b0 + b < a.batch ? b0 + b : a.batch - 1; // ragged last group: recompute the last item, store nothing
+            k0[b] = t0; k1[b] = t1;
+            x[b] = D[((bb * rl + o) * a.d + j) * N + n];
+        }
+        mac4(s0, x, k0);
+        mac4(s1, x, k1);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if (b0 + b >= a.batch) break;
+        const U128 v0 = mac_value(s0[b]), v1 = mac_value(s1[b]);
+        acc[(((b0 + b) * 2 + 0) * rl + o) * N + n] = barrett128(v0.lo, v0.hi, m);
+        acc[(((b0 + b) * 2 + 1) * rl + o) * N + n] = barrett128(v1.lo, v1.hi, m);
+    }
+}
+// step 3, one thread per (item, polynomial, coefficient): z_m (and r_t, k_t) once, then a walk over the data limbs.
+//   BFV / CKKS: z_m = [(a_m + [h]_{p_m}) (P / p_m)^-1]_{p_m};  BGV: z_m = [a_m (P / p_m)^-1]_{p_m};  r_i = sum_m z_m [(P / p_m) mod p_i] mod p_i
+//   KIND 0: ct += (acc_i - r_i + [h]_{p_i}) P^-1;  KIND 2: ct += (acc_i - r_i - [k_t]_{p_i} [P]_{p_i}) P^-1, k_t = [-r_t P^-1]_t;  KIND 1: corr = r_i - [h]_{p_i}
+template <int KIND> __global__ __launch_bounds__(EW_THREADS) void ksg_moddown_kernel(const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, KsgArgs a) {
+    const u64 idx = (u64)blockIdx.x * EW_THREADS + threadIdx.x; // over batch * 2 * N
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha;
+    if (idx >= a.batch * 2 * N) return;
+    const u64 n = idx & (N - 1), o = idx >> a.logn, c = o & 1, b = o >> 1;
+    u64 z[KSG_MAX_ALPHA];
+    U128 st{0, 0};
+#pragma unroll
+    for (u32 mm = 0; mm < KSG_MAX_ALPHA; mm++) {
+        z[mm] = 0;
+        if (mm < a.alpha) {
+            const u64 pm = a.primes[a.K - a.alpha + mm].p;
+            u64 v = sp[o * sp_ostride + (u64)mm * N + n];
+            if (KIND != 2) v = addmod(v, a.half_sp[mm], pm);
+            z[mm] = mul_shoup(v, a.md_pre[mm], pm);
+            if (KIND == 2) mac128(st, z[mm], a.md_mat_t[mm]);
+        }
+    }
+    u64 kt = 0;
+    if (KIND == 2) {
+        const Mod tm{a.t_p, a.t_cr0, a.t_cr1};
+        kt = mulmod(negmod(barrett128(st.lo, st.hi, tm), tm.p), a.inv_p_mod_t, tm);
+    }
+    for (u32 i = 0; i < a.dl; i++) {
+        const Mod m = mod_of(a.primes[i]);
+        const u64 *row = a.md_mat + (u64)i * a.alpha;
+        U128 sum{0, 0};
+#pragma unroll
+        for (u32 mm = 0; mm < KSG_MAX_ALPHA; mm++)
+            if (mm < a.alpha) mac128(sum, z[mm], row[mm]);
+        const u64 ri = barrett128(sum.lo, sum.hi, m);
+        if (KIND == 1) {
+            corr[(o * a.dl + i) * N + n] = submod(ri, a.half_q[i], m.p);
+            continue;
+        }
+        const u64 ai = acc[(o * rl + i) * N + n];
+        u64 v;
+        if (KIND == 0) v = ai + (m.p - ri) + a.half_q[i];
+        else v = ai + 2 * m.p - (ri + mulmod(barrett64(kt, m), a.p_mod_q[i], m));
+        v = mul_shoup(v, a.inv_p[i], m.p);
+        u64 *w = ct + b * ct_bstride + (c * a.dl + i) * N + n;
+        *w = addmod(*w, v, m.p);
+    }
+}
+__global__ __launch_bounds__(EW_THREADS) void ksg_ckks_combine_kernel(const u64 *acc, const u64 *corr, u64 *ct, u64 ct_bstride, KsgArgs a) {
+    const u64 idx = (u64)blockIdx.x * EW_THREADS + threadIdx.x; // over batch * 2 * dl * N
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha;
+    if (idx >= a.batch * 2 * a.dl * N) return;
+    const u64 n = idx & (N - 1), r = idx >> a.logn, i = r % a.dl, o = r / a.dl, c = o & 1, b = o >> 1;
+    const u64 p = a.primes[i].p;
+    const u64 v = mul_shoup(acc[(o * rl + i) * N + n] + p - corr[idx], a.inv_p[i], p);
+    u64 *w = ct + b * ct_bstride + (c * a.dl + i) * N + n;
+    *w = addmod(*w, v, p);
+}
+// every launch is one-dimensional: a grid stays below 2^31 blocks or is refused, no dimension can pass 65535 unnoticed
+static unsigned ksg_grid(u64 blocks, const char *what) {
+    if (!blocks || blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": batch too large for one launch");
+    return (unsigned)blocks;
+}
+static void ksg_check(const KsgArgs &a) {
+    if (!a.alpha || a.alpha > KSG_MAX_ALPHA || !a.dl || a.d != (a.dl + a.alpha - 1) / a.alpha || a.d >= 64 || a.dl + a.alpha > a.K || !a.batch)
+        throw Error(ST_LOGIC_ERROR, "grouped key switch: 1 .. 8 special primes, at most 63 digits, a non-empty batch");
+}
+void launch_ksg_extend(const u64 *target, u64 t_bstride, u64 *D, const KsgArgs &a, hipStream_t s) {
+    ksg_check(a);
+    TROY_LAUNCH(ksg_extend_kernel, dim3(ksg_grid(ceil_div(a.batch * a.d << a.logn, EW_THREADS), "ksg_extend")), dim3(EW_THREADS), 0, s, target, t_bstride, D, a);
+    launch_check("ksg_extend_kernel");
+}
+void launch_ksg_mac(const u64 *D, const u64 *key, u64 *acc, const KsgArgs &a, hipStream_t s) {
+    ksg_check(a);
+    const u64 blocks = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS) * ((a.batch + 3) / 4);
+    TROY_LAUNCH(ksg_mac_kernel, dim3(ksg_grid(blocks, "ksg_mac")), dim3(EW_THREADS), 0, s, D, key, acc, a);
+    launch_check("ksg_mac_kernel");
+}
+void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s) {
+    ksg_check(a);
+    const dim3 grid(ksg_grid(ceil_div(a.batch * 2 << a.logn, EW_THREADS), "ksg_moddown")), blk(EW_THREADS);
+    if (kind == 0) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_moddown_kernel<0>), grid, blk, 0, s, acc, sp, sp_ostride, corr, ct, ct_bstride, a);
+    else if (kind == 2) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_moddown_kernel<2>), grid, blk, 0, s, acc, sp, sp_ostride, corr, ct, ct_bstride, a);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(ksg_moddown_kernel<1>), grid, blk, 0, s, acc, sp, sp_ostride, corr, ct, ct_bstride, a);
+    launch_check("ksg_moddown_kernel");
+}
+void launch_ksg_ckks_combine(const u64 *acc, const u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s) {
+    ksg_check(a);
+    TROY_LAUNCH(ksg_ckks_combine_kernel, dim3(ksg_grid(ceil_div(a.batch * 2 * a.dl << a.logn, EW_THREADS), "ksg_ckks_combine")), dim3(EW_THREADS), 0, s, acc, corr, ct, ct_bstride, a);
+    launch_check("ksg_ckks_combine_kernel");
+}
+
 // ---------------------------------------------------------------- decryption
 // dotProductCtSkArray (decryptor_cuda.cu:284-330): every product reduced, then added modulo p
 __global__ __launch_bounds__(EW_THREADS) void dot_sk_kernel(const u64 *x, const u64 *spow, u64 *acc, DecryptArgs a) {
