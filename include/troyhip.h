@@ -485,6 +485,27 @@ int troyhip_apply_key_switching_grouped(troyhip_context *ctx, troyhip_ct *ct, co
                                         void *stream);
 /* the arena words troyhip_switch_key_grouped asks for with the whole batch in one slab (no reference counterpart); host-only */
 int troyhip_switch_key_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words);
+/* ---- Hoisted calls with grouped keys.  NO REFERENCE COUNTERPART: the result is defined in DESIGN.md section 4.17 on top of
+ * sections 4.10, 4.11 and 4.16.  troyhip_apply_galois_hoisted and troyhip_galois_plain_sum_hoisted keep taking per-prime keys only. ---- */
+/* troyhip_apply_galois_hoisted with grouped keys (no reference counterpart): galois_keys[r] is a grouped key over `special_primes`
+ * special primes ([digits][2][K][N]); the operand has at most K - special_primes limbs ("operand has more limbs than the grouped key serves").  The digits of
+ * c1 are extended and transformed once per item.  special_primes == 1 with per-prime keys: the bytes of troyhip_apply_galois_hoisted.  The result depends on
+ * (ciphertext, element, key, special_primes) only -- not on n_elts, the order, the batch size or the scratch limit.  Counter: "grouped_hoist_slabs". */
+int troyhip_apply_galois_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
+                                         int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* troyhip_galois_plain_sum_hoisted with grouped keys (no reference counterpart): one mod-down by all special primes per item.  The
+ * plaintexts are [K][N] NTT form at the key level, as there.  special_primes == 1 with per-prime keys: the bytes of troyhip_galois_plain_sum_hoisted.  The
+ * result depends on the multiset of (element, key, plaintext) terms only.  Counter: "grouped_hoist_lt_slabs". */
+int troyhip_galois_plain_sum_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                             const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, int special_primes, uint64_t scratch_limit_words,
+                                             uint64_t batch, void *stream);
+/* the arena words the two calls ask for with everything in one slab (no reference counterpart); host-only.  In units of N words, with
+ * dl = limbs, alpha = special_primes, rl = dl + alpha, d = ceil(dl / alpha), plus 384 words of rounding:
+ *   rotations: batch ([CKKS: dl] + d rl) + min(rots, 16) batch (2 rl + dl + [CKKS: 2 alpha + 2 dl])
+ *   linear transform: batch ([CKKS: dl] + d rl + 2 rl + 2 dl + [BFV / BGV: 2 dl] + [CKKS: 2 alpha + 2 dl])
+ * Below the value for (one item, one rotation) the calls refuse with "scratch_limit_words is too small ...". */
+int troyhip_apply_galois_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int rots, uint64_t *words);
+int troyhip_galois_plain_sum_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words);
 
 /* ---- Device encoding, `batch` items per call (BatchEncoder / CKKSEncoder).  Item i is BYTE-IDENTICAL to the host form called with item i
  * (DESIGN.md section 4.7).  Every buffer is device memory; strides are in words (u64 or double) between consecutive items; batch in 1 .. 65535.

@@ -2116,7 +2116,13 @@ public:
     std::vector<Ciphertext> rotateRowsHoisted(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoisted(a, eltsOfSteps(steps), gk); }
     std::vector<Ciphertext> rotateVectorHoisted(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoisted(a, eltsOfSteps(steps), gk); }
     // over a batch: result[r][b] = element r of item b; the R x batch results are members of one slab (R dense batches back to back)
-    std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const {
+    std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return hoistedBatch(a, elts, gk, false); }
+private:
+    // what the hoisted members and their *Grouped twins share; grouped: the key set carries the grouped tag
+    static void needGrouped(const GaloisKeys &gk) { if (!gk.specialPrimes()) throw std::invalid_argument("this call takes keys with grouped digits"); }
+    const uint64_t *hoistKey(const GaloisKeys &gk, uint32_t elt, bool grouped) const { return grouped ? grouped_key_of(gk, GaloisKeys::getIndex(elt)) : key_of(gk, GaloisKeys::getIndex(elt)); }
+    std::vector<std::vector<Ciphertext>> hoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk, bool grouped) const {
+        if (grouped) needGrouped(gk);
         if (elts.empty()) throw std::invalid_argument("hoisted rotations take at least one Galois element");
         if (a.empty()) return std::vector<std::vector<Ciphertext>>(elts.size());
         std::vector<const uint64_t *> keys(elts.size(), nullptr);
@@ -2124,7 +2130,7 @@ public:
             if (elts[r] == 1) continue;
             if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
             if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
-            keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+            keys[r] = hoistKey(gk, elts[r], grouped);
         }
         if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
         std::vector<Ciphertext> pa;
@@ -2132,7 +2138,8 @@ public:
         const size_t batch = a.size(), R = elts.size();
         std::vector<Ciphertext> flat = Ciphertext::allocateBatch(R * batch, *a[0], 2, a[0]->coeffModulusSize());
         troyhip_ct t = *flat[0].raw();
-        check(troyhip_apply_galois_hoisted(h(), &va, &t, elts.data(), keys.data(), (int)R, 0, batch, nullptr));
+        if (grouped) check(troyhip_apply_galois_hoisted_grouped(h(), &va, &t, elts.data(), keys.data(), (int)R, gk.specialPrimes(), 0, batch, nullptr));
+        else check(troyhip_apply_galois_hoisted(h(), &va, &t, elts.data(), keys.data(), (int)R, 0, batch, nullptr));
         std::vector<std::vector<Ciphertext>> out(R);
         for (size_t r = 0; r < R; r++)
             for (size_t b = 0; b < batch; b++) {
@@ -2141,9 +2148,25 @@ public:
             }
         return out;
     }
+    static std::vector<Ciphertext> firstItems(std::vector<std::vector<Ciphertext>> &&r) {
+        std::vector<Ciphertext> out;
+        for (auto &v : r) out.push_back(std::move(v[0]));
+        return out;
+    }
+public:
     std::vector<std::vector<Ciphertext>> applyGaloisHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return applyGaloisHoistedBatch(Ciphertext::pointers(a), elts, gk); }
     std::vector<std::vector<Ciphertext>> rotateRowsHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
     std::vector<std::vector<Ciphertext>> rotateVectorHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoistedBatch(a, eltsOfSteps(steps), gk); }
+    // The hoisted rotations with keys with grouped digits (troyhip_apply_galois_hoisted_grouped; no reference counterpart): gk
+    // comes from KeyGenerator::createGaloisKeys(elts, special_primes), the operand has at most K - special_primes limbs.  A per-prime key set is refused
+    // ("this call takes keys with grouped digits"), as the members above refuse a grouped one.
+    std::vector<Ciphertext> applyGaloisHoistedGrouped(const Ciphertext &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return firstItems(hoistedBatch(std::vector<const Ciphertext *>{&a}, elts, gk, true)); }
+    std::vector<Ciphertext> rotateRowsHoistedGrouped(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoistedGrouped(a, eltsOfSteps(steps), gk); }
+    std::vector<Ciphertext> rotateVectorHoistedGrouped(const Ciphertext &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoistedGrouped(a, eltsOfSteps(steps), gk); }
+    std::vector<std::vector<Ciphertext>> applyGaloisHoistedGroupedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return hoistedBatch(a, elts, gk, true); }
+    std::vector<std::vector<Ciphertext>> applyGaloisHoistedGroupedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const GaloisKeys &gk) const { return hoistedBatch(Ciphertext::pointers(a), elts, gk, true); }
+    std::vector<std::vector<Ciphertext>> rotateRowsHoistedGroupedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisHoistedGroupedBatch(a, eltsOfSteps(steps), gk); }
+    std::vector<std::vector<Ciphertext>> rotateVectorHoistedGroupedBatch(const std::vector<Ciphertext> &a, const std::vector<int> &steps, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisHoistedGroupedBatch(a, eltsOfSteps(steps), gk); }
     // Hoisted linear transform (troyhip_galois_plain_sum_hoisted; the reference has no such call):
     //   sum_r plains[r] * applyGalois(a, elts[r])   as ONE call and ONE ciphertext,
     // the plaintexts applied in the extended basis before the single mod-down.  The plaintexts are in NTT form at the KEY level (transformToNttInplace(plain,
@@ -2156,7 +2179,10 @@ public:
     Ciphertext rotateRowsPlainSumHoisted(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumHoisted(a, eltsOfSteps(steps), plains, gk); }
     Ciphertext rotateVectorPlainSumHoisted(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumHoisted(a, eltsOfSteps(steps), plains, gk); }
     // over a batch (Ciphertext::packBatch members or any ciphertexts of one shape): result[b] for item b, the plaintexts shared; the results are one slab run
-    std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const {
+    std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return plainSumHoistedBatch(a, elts, plains, gk, false); }
+private:
+    std::vector<Ciphertext> plainSumHoistedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk, bool grouped) const {
+        if (grouped) needGrouped(gk);
         if (elts.empty() || plains.size() != elts.size()) throw std::invalid_argument("hoisted linear transform takes at least one Galois element and one plaintext per element");
         std::vector<const uint64_t *> keys(elts.size(), nullptr), pls(elts.size(), nullptr);
         for (size_t r = 0; r < elts.size(); r++) {
@@ -2166,7 +2192,7 @@ public:
             if (elts[r] == 1) continue;
             if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
             if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
-            keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+            keys[r] = hoistKey(gk, elts[r], grouped);
         }
         if (a.empty()) return {};
         if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
@@ -2175,10 +2201,22 @@ public:
         std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, a[0]->coeffModulusSize());
         troyhip_ct t = *out[0].raw();
         const double plain_scale = c_.parms().scheme() == SchemeType::ckks ? plains[0].scale() : 1.0;
-        check(troyhip_galois_plain_sum_hoisted(h(), &va, &t, elts.data(), keys.data(), pls.data(), (int)elts.size(), plain_scale, 0, a.size(), nullptr));
+        if (grouped) check(troyhip_galois_plain_sum_hoisted_grouped(h(), &va, &t, elts.data(), keys.data(), pls.data(), (int)elts.size(), plain_scale, gk.specialPrimes(), 0, a.size(), nullptr));
+        else check(troyhip_galois_plain_sum_hoisted(h(), &va, &t, elts.data(), keys.data(), pls.data(), (int)elts.size(), plain_scale, 0, a.size(), nullptr));
         for (auto &c : out) c.copyMeta(t);
         return out;
     }
+public:
+    // ... with keys with grouped digits (troyhip_galois_plain_sum_hoisted_grouped; no reference counterpart): one mod-down by all
+    // special primes per item; the plaintexts as above
+    Ciphertext applyGaloisPlainSumHoistedGrouped(const Ciphertext &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const {
+        std::vector<Ciphertext> r = plainSumHoistedBatch(std::vector<const Ciphertext *>{&a}, elts, plains, gk, true);
+        return std::move(r[0]);
+    }
+    Ciphertext rotateRowsPlainSumHoistedGrouped(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumHoistedGrouped(a, eltsOfSteps(steps), plains, gk); }
+    Ciphertext rotateVectorPlainSumHoistedGrouped(const Ciphertext &a, const std::vector<int> &steps, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumHoistedGrouped(a, eltsOfSteps(steps), plains, gk); }
+    std::vector<Ciphertext> applyGaloisPlainSumHoistedGroupedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return plainSumHoistedBatch(a, elts, plains, gk, true); }
+    std::vector<Ciphertext> applyGaloisPlainSumHoistedGroupedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return plainSumHoistedBatch(Ciphertext::pointers(a), elts, plains, gk, true); }
     std::vector<Ciphertext> applyGaloisPlainSumHoistedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &elts, const std::vector<Plaintext> &plains, const GaloisKeys &gk) const { return applyGaloisPlainSumHoistedBatch(Ciphertext::pointers(a), elts, plains, gk); }
     // Baby-step / giant-step linear transform (troyhip_galois_plain_sum_bsgs; the reference has no such call):
     //   sum_i applyGalois( sum_j plains[i][j] * applyGalois(a, babies[j]), giants[i] )   as ONE call and ONE ciphertext,

@@ -930,6 +930,10 @@ class Evaluator:
         """[applyGalois(a, g) for g in galois_elts] for roughly the price of one key switch: the digits of c1 are expanded once.  Every result decrypts to
         what applyGalois gives; its limbs differ.  Element 1 is a copy.  Returns a list of len(galois_elts) Ciphertext batches."""
         self._per_prime_only(galois_keys)
+        return self._apply_galois_hoisted(a, galois_elts, galois_keys, scratch_limit_words)
+
+    def _apply_galois_hoisted(self, a, galois_elts, galois_keys, scratch_limit_words):
+        """applyGaloisHoisted / applyGaloisHoistedGrouped behind their check of the key set's kind"""
         elts = [int(g) for g in galois_elts]
         if not elts:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "hoisted rotations take at least one Galois element")
@@ -943,8 +947,12 @@ class Evaluator:
         buf = DeviceBuffer(R * a.batch * item)
         so = CtStruct(buf.ptr, item, 2, a.limbs, int(a.is_ntt_form), a.scale, a.correction_factor)
         si = a.struct()
-        self._chk(self.lib.troyhip_apply_galois_hoisted(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), R,
-                                                        C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        head = (self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), R)
+        tail = (C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream)
+        if galois_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_apply_galois_hoisted_grouped(*head, galois_keys.special_primes, *tail))
+        else:
+            self._chk(self.lib.troyhip_apply_galois_hoisted(*head, *tail))
         out = []
         for r in range(R):  # the results are windows of the one allocation the call filled: no copies; it is freed with the last of them
             ct = Ciphertext(self.context, a.batch, 2, a.limbs, buf=_BufferWindow(buf, r * a.batch * item, a.batch * item))
@@ -962,12 +970,51 @@ class Evaluator:
             raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
         return self.applyGaloisHoisted(a, [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps], galois_keys, scratch_limit_words)
 
+    # -- the hoisted calls with grouped keys (troyhip_*_hoisted_grouped: no reference counterpart).  The members above keep refusing
+    # a grouped key set; these refuse a per-prime one
+    @staticmethod
+    def _grouped_only(keys):
+        if getattr(keys, "special_primes", None) is None:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "this call takes keys with grouped digits")
+
+    def _steps_to_elts(self, steps, schemes):
+        if self.context.scheme not in schemes:
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        return [self.context.galois_elt_from_step(int(s)) if int(s) else 1 for s in steps]
+
+    def applyGaloisHoistedGrouped(self, a, galois_elts, galois_keys, scratch_limit_words=0):
+        """applyGaloisHoisted with a GaloisKeys(special_primes=alpha) set: the digits of c1 are extended and transformed once, every element then costs a
+        gathered inner product over ceil(limbs / alpha) digits.  `a` has at most K - alpha limbs."""
+        self._grouped_only(galois_keys)
+        return self._apply_galois_hoisted(a, galois_elts, galois_keys, scratch_limit_words)
+
+    def rotateRowsHoistedGrouped(self, a, steps, galois_keys, scratch_limit_words=0):
+        return self.applyGaloisHoistedGrouped(a, self._steps_to_elts(steps, (BFV, BGV)), galois_keys, scratch_limit_words)
+
+    def rotateVectorHoistedGrouped(self, a, steps, galois_keys, scratch_limit_words=0):
+        return self.applyGaloisHoistedGrouped(a, self._steps_to_elts(steps, (CKKS,)), galois_keys, scratch_limit_words)
+
+    def applyGaloisPlainSumHoistedGrouped(self, a, galois_elts, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        """applyGaloisPlainSumHoisted with a GaloisKeys(special_primes=alpha) set: one mod-down by all special primes per item"""
+        self._grouped_only(galois_keys)
+        return self._apply_galois_plain_sum_hoisted(a, galois_elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def rotateRowsPlainSumHoistedGrouped(self, a, steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        return self.applyGaloisPlainSumHoistedGrouped(a, self._steps_to_elts(steps, (BFV, BGV)), plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def rotateVectorPlainSumHoistedGrouped(self, a, steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        return self.applyGaloisPlainSumHoistedGrouped(a, self._steps_to_elts(steps, (CKKS,)), plains, galois_keys, plain_scale, scratch_limit_words)
+
     # -- hoisted linear transform (troyhip_galois_plain_sum_hoisted: no reference counterpart, DESIGN.md section 4.11)
     def applyGaloisPlainSumHoisted(self, a, galois_elts, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
         """sum_r plains[r] * applyGalois(a, galois_elts[r]) as ONE call and ONE Ciphertext batch: the plaintexts are applied in the extended basis before
         the single mod-down per item.  plains: DeviceBuffer of K * N words each, NTT form at the KEY level (transformPlainToNtt(plain, K) for BFV / BGV,
         CKKSEncoder.encode(..., limbs=K) for CKKS), shared by the batch.  Element 1 reads no key.  The scale becomes a.scale * plain_scale."""
         self._per_prime_only(galois_keys)
+        return self._apply_galois_plain_sum_hoisted(a, galois_elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def _apply_galois_plain_sum_hoisted(self, a, galois_elts, plains, galois_keys, plain_scale, scratch_limit_words):
+        """applyGaloisPlainSumHoisted / applyGaloisPlainSumHoistedGrouped behind their check of the key set's kind"""
         elts = [int(g) for g in galois_elts]
         plains = list(plains)
         if not elts or len(plains) != len(elts):
@@ -984,8 +1031,12 @@ class Evaluator:
         R = len(elts)
         out = Ciphertext(self.context, a.batch, 2, a.limbs, a.is_ntt_form, a.scale, a.correction_factor)
         si, so = a.struct(), out.struct()
-        self._chk(self.lib.troyhip_galois_plain_sum_hoisted(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), (C.c_void_p * R)(*pls),
-                                                            R, C.c_double(plain_scale), C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        head = (self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * R)(*elts), (C.c_void_p * R)(*ptrs), (C.c_void_p * R)(*pls), R, C.c_double(plain_scale))
+        tail = (C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream)
+        if galois_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_galois_plain_sum_hoisted_grouped(*head, galois_keys.special_primes, *tail))
+        else:
+            self._chk(self.lib.troyhip_galois_plain_sum_hoisted(*head, *tail))
         out._absorb(so)
         return out
 

@@ -70,6 +70,8 @@ SYMBOLS = [
     "troyhip_host_noise_budget", "troyhip_noise_budget",
     "troyhip_grouped_key_shape", "troyhip_host_kswitch_key_grouped", "troyhip_create_kswitch_keys_grouped", "troyhip_switch_key_grouped", "troyhip_relinearize_grouped",
     "troyhip_apply_galois_grouped", "troyhip_apply_key_switching_grouped", "troyhip_switch_key_grouped_scratch_words",
+    "troyhip_apply_galois_hoisted_grouped", "troyhip_galois_plain_sum_hoisted_grouped", "troyhip_apply_galois_hoisted_grouped_scratch_words",
+    "troyhip_galois_plain_sum_hoisted_grouped_scratch_words",
 ]
 
 _lib = None

@@ -795,6 +795,49 @@ int troyhip_switch_key_grouped_scratch_words(const troyhip_context *ctx, int lim
         *words = need(ctx)->ev.switch_key_grouped_scratch_words(limbs, special_primes, batch);
     }, false);
 }
+// ---- hoisted calls with grouped keys (no reference counterpart) ----
+static std::vector<KsKey> ks_keys(const uint64_t *const *keys, int n) {
+    std::vector<KsKey> v((size_t)n);
+    for (int i = 0; i < n; i++) v[(size_t)i] = KsKey{keys[i]};
+    return v;
+}
+int troyhip_apply_galois_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
+                                         int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_elts < 1 || !galois_elts || !galois_keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
+        CtBatch o = view(out);
+        need(ctx)->ev.apply_galois_hoisted_grouped(view(in), o, galois_elts, keys.data(), n_elts, special_primes, batch, scratch_limit_words, on(stream));
+        store(o, out);
+    });
+}
+int troyhip_galois_plain_sum_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                             const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, int special_primes, uint64_t scratch_limit_words,
+                                             uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_elts < 1 || !galois_elts || !galois_keys || !plains_ntt_keylevel) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
+        CtBatch o = view(out);
+        need(ctx)->ev.galois_plain_sum_hoisted_grouped(view(in), o, galois_elts, keys.data(), plains_ntt_keylevel, n_elts, plain_scale, special_primes, batch, scratch_limit_words,
+                                                       on(stream));
+        store(o, out);
+    });
+}
+int troyhip_apply_galois_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int rots, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        if (rots < 1) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+        *words = need(ctx)->ev.apply_galois_hoisted_grouped_scratch_words(limbs, special_primes, batch, (u64)rots);
+    }, false);
+}
+int troyhip_galois_plain_sum_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.galois_plain_sum_hoisted_grouped_scratch_words(limbs, special_primes, batch);
+    }, false);
+}
 
 
 int troyhip_batch_encode(troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t values_stride, uint64_t *plain_out, uint64_t plain_stride,

@@ -736,16 +736,17 @@ void Evaluator::hoist_c0_to_ntt(const u64 *c0, u64 bstride, u64 *c0n, const KsAr
     launch_ntt(c0n, c.d_desc, c.ct_map((int)a.dl), a.batch * a.dl, c.logn, false, s);
 }
 // every present term, HOIST_MAX_ROT per launch: c0 is read through the index map of the element (element 1: in place) and, polys == 2, c1 for element 1.
-// CKKS reads the operand where it lies (c1 follows c0); BFV / BGV read c0n (hoist_c0_to_ntt) and c1's own limbs in D
-void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const u64 *D, int polys, u64 *dst,
+// CKKS reads the operand where it lies (c1 follows c0); BFV / BGV read c0n (hoist_c0_to_ntt) and c1's limbs in NTT form where c1n says (the per-prime
+// calls: c1's own limbs in D, hoist_c1_in_digits)
+void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const HoistC1 &c1n, int polys, u64 *dst,
                               const KsArgs &a, hipStream_t s) {
-    const u64 N = c.N, dl = a.dl, rl = dl + 1, pw = dl * N;
+    const u64 N = c.N, dl = a.dl, pw = dl * N;
     HoistLtArgs h;
     std::memset(&h, 0, sizeof(h));
     auto flush = [&] {
         if (!h.rots) return;
         if (c.scheme == SCHEME_CKKS) launch_hoist_lt_base(c0, bstride, c0 + pw, bstride, N, dst, (u64)polys * pw, polys, a, h, s);
-        else launch_hoist_lt_base(c0n, pw, D, rl * dl * N, rl * N, dst, (u64)polys * pw, polys, a, h, s);
+        else launch_hoist_lt_base(c0n, pw, c1n.ptr, c1n.bstride, c1n.lstride, dst, (u64)polys * pw, polys, a, h, s);
         std::memset(&h, 0, sizeof(h));
         h.accumulate = 1; // later launches add to what this one stored
     };
@@ -756,6 +757,8 @@ void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, in
         }
     flush();
 }
+// D[b][j][j] of the per-prime digits is limb j of c1 in NTT form: item b at + b rl dl N, limb j at + j rl N
+static HoistC1 hoist_c1_in_digits(const u64 *D, u64 dl, u64 N) { return HoistC1{D, (dl + 1) * dl * N, (dl + 1) * N}; }
 void Evaluator::hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s) {
     const u64 pw = k.a.dl * c.N;
     CtBatch o = out;
@@ -765,6 +768,51 @@ void Evaluator::hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *
         c.arena.rewind(mark);
         ks_acc_to_ct(o, acc, k, s, KsBase{base, (u64)polys * pw, polys});
     }
+}
+
+// The rotations of the items b0 .. b0 + nb - 1 of a hoisted call, in chunks of at most `rs` consecutive elements other than 1: sigma_r(c0) of a chunk goes
+// to sig0 (item r * nb + b), then chunk(h, o) runs with o at the chunk's first output item.  Element 1 is a copy of the operand and reads no key.
+template <class F> static void hoist_rotation_chunks(Context &c, const CtBatch &in, const CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 b0, u64 nb,
+                                                     u64 rs, u64 *sig0, hipStream_t s, F chunk) {
+    const u64 pw = poly_words(c, in.limbs);
+    const u64 *c0 = in.data + b0 * in.bstride;
+    const LimbMap map = c.ct_map(in.limbs);
+    for (int r0 = 0; r0 < R;) {
+        CtBatch o = out;
+        o.data = out.data + ((u64)r0 * batch + b0) * out.bstride;
+        if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
+            launch_copy_strided(c0, in.bstride, o.data, out.bstride, 2 * pw, nb, s);
+            r0++;
+            continue;
+        }
+        HoistArgs h;
+        std::memset(&h, 0, sizeof(h));
+        while (r0 + (int)h.rots < R && h.rots < rs && elts[r0 + h.rots] != 1) {
+            h.elt[h.rots] = elts[r0 + h.rots];
+            h.key[h.rots] = keys[r0 + h.rots].data;
+            h.rots++;
+        }
+        for (u32 r = 0; r < h.rots; r++) launch_galois(c.scheme == SCHEME_CKKS, c0, in.bstride, sig0 + (u64)r * nb * pw, pw, c.d_desc, map, c.logn, h.elt[r], (u64)in.limbs, nb, s);
+        chunk(h, o);
+        r0 += (int)h.rots;
+    }
+}
+// The terms of a hoisted linear transform whose element is not 1, HOIST_MAX_ROT per launch(h); launches after the first accumulate onto what the first stored
+template <class F> static void hoist_lt_chunks(const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, F launch) {
+    HoistLtArgs h;
+    std::memset(&h, 0, sizeof(h));
+    auto flush = [&] {
+        if (!h.rots) return;
+        launch(h);
+        std::memset(&h, 0, sizeof(h));
+        h.accumulate = 1;
+    };
+    for (int r = 0; r < R; r++) {
+        if (elts[r] == 1) continue;
+        h.key[h.rots] = keys[r].data; h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
+        if (++h.rots == HOIST_MAX_ROT) flush();
+    }
+    flush();
 }
 
 // Hoisted rotations (Halevi-Shoup; no reference counterpart): the digits of c1 are decomposed, extended and transformed ONCE
@@ -791,38 +839,21 @@ void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint
     u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
     u64 *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
     const size_t mark = c.arena.mark();
-    const LimbMap map = c.ct_map(L);
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
         const u64 nb = std::min(bs, batch - b0);
-        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        const u64 *c1 = in.data + b0 * in.bstride + pw;
         KsPlan k = ks_plan(L, nb);
         KsArgs &a = k.a;
         hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
-        for (int r0 = 0; r0 < R;) {
-            if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
-                launch_copy_strided(c0, in.bstride, out.data + ((u64)r0 * batch + b0) * out.bstride, out.bstride, 2 * pw, nb, s);
-                r0++;
-                continue;
-            }
-            HoistArgs h;
-            std::memset(&h, 0, sizeof(h));
-            while (r0 + (int)h.rots < R && h.rots < rs && elts[r0 + h.rots] != 1) {
-                h.elt[h.rots] = elts[r0 + h.rots];
-                h.key[h.rots] = keys[r0 + h.rots].data;
-                h.rots++;
-            }
-            for (u32 r = 0; r < h.rots; r++) launch_galois(ckks, c0, in.bstride, sig0 + (u64)r * nb * pw, pw, c.d_desc, map, c.logn, h.elt[r], dl, nb, s);
+        hoist_rotation_chunks(c, in, out, elts, keys, R, batch, b0, nb, rs, sig0, s, [&](const HoistArgs &h, CtBatch &o) {
             launch_hoist_mac(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
             // the second half of the key switch over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
-            CtBatch o = out;
-            o.data = out.data + ((u64)r0 * batch + b0) * out.bstride;
             a.batch = (u64)h.rots * nb;
             c.arena.rewind(mark);
             ks_acc_to_ct(o, acc, k, s, KsBase{sig0, pw});
             a.batch = nb;
             stats::counter(stats::HOIST_SLABS)++;
-            r0 += (int)h.rots;
-        }
+        });
     }
 }
 
@@ -866,23 +897,10 @@ void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const 
         const KsArgs &a = k.a;
         hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
         // the extended-basis accumulators: every element other than 1, HOIST_MAX_ROT per launch
-        HoistLtArgs h;
-        std::memset(&h, 0, sizeof(h));
-        auto flush = [&] {
-            if (!h.rots) return;
-            launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
-            std::memset(&h, 0, sizeof(h));
-            h.accumulate = 1; // later launches add to what this one stored
-        };
-        for (int r = 0; r < R; r++) {
-            if (elts[r] == 1) continue;
-            h.key[h.rots] = keys[r].data; h.pt[h.rots] = plains[r]; h.elt[h.rots] = elts[r];
-            if (++h.rots == HOIST_MAX_ROT) flush();
-        }
-        flush();
+        hoist_lt_chunks(elts, keys, plains, R, [&](const HoistLtArgs &h) { launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s); });
         // the base in NTT form: every element
         if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, a, s);
-        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, D, polys, base, a, s);
+        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, hoist_c1_in_digits(D, dl, N), polys, base, a, s);
         if (!ckks) launch_ntt(base, c.d_desc, map, nb * polys * dl, c.logn, true, s);
         hoist_lt_finish(any_rot, out, b0, acc, base, polys, mark, k, s); // every element is 1 (polys == 2): the base
         stats::counter(stats::HOIST_LT_SLABS)++;
@@ -973,7 +991,7 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
         for (u64 i0 = 0; i0 < n2; i0 += gc) {
             const u64 gn = std::min(gc, n2 - i0);
             // the bases of the rows, in NTT form, as galois_plain_sum_hoisted makes them: every present pair of the row, both polynomials
-            for (u64 ii = 0; ii < gn; ii++) hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, D, 2, baseU + ii * nb * 2 * pw, a, s);
+            for (u64 ii = 0; ii < gn; ii++) hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, hoist_c1_in_digits(D, dl, N), 2, baseU + ii * nb * 2 * pw, a, s);
             if (!ckks) launch_ntt(baseU, c.d_desc, map, gn * nb * 2 * dl, c.logn, true, s);
             // u_i of the chunk: ONE second half over rows x items
             if (nrb) {
@@ -1649,6 +1667,59 @@ u64 Evaluator::switch_key_grouped_scratch_words(int limbs, int alpha, u64 batch)
     if (limbs < 1 || limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
     return batch * ksg_item_words(c, (u64)limbs, (u64)alpha) + slab_slack(KSG_BLOCKS);
 }
+// the limbs a grouped key over `alpha` special primes serves (refuses K < 2 and an alpha out of range first)
+void Evaluator::ksg_check_limbs(int alpha, int limbs) const {
+    int digits = 0, lmax = 0;
+    c.ksg_shape(alpha, digits, lmax);
+    if (limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+}
+KsgPlan Evaluator::ksg_plan(int alpha, int limbs) {
+    const u64 dl = limbs, al = alpha, rl = dl + al, d = (dl + al - 1) / al, K = c.K;
+    KsgPlan k;
+    k.a = c.ksg_level(alpha, limbs);
+    std::vector<uint8_t> out_ids, sp_ids;
+    for (u64 o = 0; o < rl; o++) out_ids.push_back((uint8_t)(o < dl ? o : K - al + (o - dl)));
+    for (u64 m = 0; m < al; m++) sp_ids.push_back((uint8_t)(K - al + m));
+    k.digit_map = c.ids_map(out_ids, (uint32_t)d);
+    k.acc_map = c.ids_map(out_ids);
+    k.sp_map = c.ids_map(sp_ids);
+    k.tmap = c.ct_map(limbs);
+    return k;
+}
+// The two halves of switch_key_grouped (the split section 4.10 made of switch_key), over k.a.batch items.  First half, 1.: the extension of every digit of
+// the target to every output prime and the forward transforms (tt: CKKS, room for the target in coefficient form, ks_coeff_target); 2.: the inner product
+void Evaluator::ksg_target_to_digits(const u64 *target, u64 t_bstride, u64 *tt, u64 *D, const KsgPlan &k, hipStream_t s) {
+    const KsgArgs &a = k.a;
+    const u64 N = c.N, dl = a.dl, nb = a.batch;
+    if (c.scheme == SCHEME_CKKS) {
+        launch_copy_strided(target, t_bstride, tt, dl * N, dl * N, nb, s);
+        launch_ntt(tt, c.d_desc, k.tmap, nb * dl, c.logn, true, s);
+        target = tt;
+        t_bstride = dl * N;
+    }
+    launch_ksg_extend(target, t_bstride, D, a, s);
+    launch_ntt(D, c.d_desc, k.digit_map, nb * (dl + a.alpha) * a.d, c.logn, false, s);
+}
+// Second half: dst (item stride ct_bstride) = base, or what it holds, + the mod-down by P of acc.  The base is copied after the first half has read the
+// target (apply_key_switching: the target is c1 of the destination).  last / corr: CKKS, room for 2 alpha and 2 dl limbs per item
+void Evaluator::ksg_acc_to_ct(u64 *dst, u64 ct_bstride, u64 *acc, u64 *last, u64 *corr, const KsgPlan &k, hipStream_t s, const KsBase &base) {
+    const KsgArgs &a = k.a;
+    const u64 N = c.N, dl = a.dl, al = a.alpha, rl = dl + al, nb = a.batch;
+    if (base.ptr) {
+        if (base.ptr != dst) launch_copy_strided(base.ptr, base.bstride, dst, ct_bstride, (u64)base.polys * dl * N, nb, s);
+        if (base.polys < 2) launch_zero_strided(dst + dl * N, ct_bstride, dl * N, nb, s);
+    }
+    if (c.scheme == SCHEME_CKKS) {
+        launch_copy_strided(acc + dl * N, rl * N, last, al * N, al * N, nb * 2, s);
+        launch_ntt(last, c.d_desc, k.sp_map, nb * 2 * al, c.logn, true, s);
+        launch_ksg_moddown(1, nullptr, last, al * N, corr, nullptr, 0, a, s);
+        launch_ntt(corr, c.d_desc, k.tmap, nb * 2 * dl, c.logn, false, s);
+        launch_ksg_ckks_combine(acc, corr, dst, ct_bstride, a, s);
+    } else {
+        launch_ntt(acc, c.d_desc, k.acc_map, nb * 2 * rl, c.logn, true, s);
+        launch_ksg_moddown(c.scheme == SCHEME_BFV ? 0 : 2, acc, acc + dl * N, rl * N, nullptr, dst, ct_bstride, a, s);
+    }
+}
 void Evaluator::switch_key_grouped(CtBatch &ct, const u64 *target, u64 t_bstride, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s,
                                    const KsBase &base) {
     check_ct(ct);
@@ -1661,14 +1732,10 @@ void Evaluator::switch_key_grouped(CtBatch &ct, const u64 *target, u64 t_bstride
     if (ct.limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
     if (!batch) return;
     const bool ckks = c.scheme == SCHEME_CKKS;
-    const u64 N = c.N, dl = ct.limbs, al = alpha, rl = dl + al, d = (dl + al - 1) / al, K = c.K;
+    const u64 N = c.N, dl = ct.limbs, al = alpha, rl = dl + al, d = (dl + al - 1) / al;
     const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_BLOCKS, ksg_item_words(c, dl, al), 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
     const u64 bs = plan.items;
-    KsgArgs a = c.ksg_level(alpha, (int)dl);
-    std::vector<uint8_t> out_ids, sp_ids;
-    for (u64 o = 0; o < rl; o++) out_ids.push_back((uint8_t)(o < dl ? o : K - al + (o - dl)));
-    for (u64 m = 0; m < al; m++) sp_ids.push_back((uint8_t)(K - al + m));
-    const LimbMap digit_map = c.ids_map(out_ids, (uint32_t)d), acc_map = c.ids_map(out_ids), sp_map = c.ids_map(sp_ids), tmap = c.ct_map((int)dl);
+    KsgPlan k = ksg_plan(alpha, (int)dl);
 
     c.arena.begin(s);
     c.arena.reserve(plan.words);
@@ -1676,38 +1743,10 @@ void Evaluator::switch_key_grouped(CtBatch &ct, const u64 *target, u64 t_bstride
     u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(bs * 2 * rl * N);
     u64 *last = ckks ? c.arena.take(bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(bs * 2 * dl * N) : nullptr;
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
-        a.batch = std::min(bs, batch - b0);
-        const u64 nb = a.batch;
-        const u64 *tg = target + b0 * t_bstride;
-        u64 tb = t_bstride;
-        if (ckks) { // the target in coefficient form (ks_coeff_target)
-            launch_copy_strided(tg, tb, tt, dl * N, dl * N, nb, s);
-            launch_ntt(tt, c.d_desc, tmap, nb * dl, c.logn, true, s);
-            tg = tt;
-            tb = dl * N;
-        }
-        // 1. extension of every digit to every output prime, 2. forward transforms and the inner product with the key
-        launch_ksg_extend(tg, tb, D, a, s);
-        launch_ntt(D, c.d_desc, digit_map, nb * rl * d, c.logn, false, s);
-        launch_ksg_mac(D, key.data, acc, a, s);
-        // the base, after the target has been read (apply_key_switching: the target is c1 of ct itself)
-        u64 *dst = ct.data + b0 * ct.bstride;
-        if (base.ptr) {
-            const u64 *bp = base.ptr + b0 * base.bstride;
-            if (bp != dst) launch_copy_strided(bp, base.bstride, dst, ct.bstride, (u64)base.polys * dl * N, nb, s);
-            if (base.polys < 2) launch_zero_strided(dst + dl * N, ct.bstride, dl * N, nb, s);
-        }
-        // 3. mod-down by P
-        if (ckks) {
-            launch_copy_strided(acc + dl * N, rl * N, last, al * N, al * N, nb * 2, s);
-            launch_ntt(last, c.d_desc, sp_map, nb * 2 * al, c.logn, true, s);
-            launch_ksg_moddown(1, nullptr, last, al * N, corr, nullptr, 0, a, s);
-            launch_ntt(corr, c.d_desc, tmap, nb * 2 * dl, c.logn, false, s);
-            launch_ksg_ckks_combine(acc, corr, dst, ct.bstride, a, s);
-        } else {
-            launch_ntt(acc, c.d_desc, acc_map, nb * 2 * rl, c.logn, true, s);
-            launch_ksg_moddown(c.scheme == SCHEME_BFV ? 0 : 2, acc, acc + dl * N, rl * N, nullptr, dst, ct.bstride, a, s);
-        }
+        k.a.batch = std::min(bs, batch - b0);
+        ksg_target_to_digits(target + b0 * t_bstride, t_bstride, tt, D, k, s);
+        launch_ksg_mac(D, key.data, acc, k.a, s);
+        ksg_acc_to_ct(ct.data + b0 * ct.bstride, ct.bstride, acc, last, corr, k, s, base.ptr ? KsBase{base.ptr + b0 * base.bstride, base.bstride, base.polys} : KsBase{});
         stats::counter(stats::GROUPED_KS_SLABS)++;
     }
 }
@@ -1743,9 +1782,7 @@ void Evaluator::apply_galois_grouped(CtBatch &ct, uint32_t elt, const KsKey &key
     if (!key.data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
     if (!(elt & 1) || elt >= 2 * c.N) throw Error(ST_INVALID_ARGUMENT, "Galois element is not valid");
     if (ct.size > 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
-    int digits = 0, lmax = 0;
-    c.ksg_shape(alpha, digits, lmax);
-    if (ct.limbs > lmax) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, ct.limbs);
     if (!batch) return;
     const u64 pw = poly_words(c, ct.limbs);
     const int L = ct.limbs;
@@ -1775,6 +1812,115 @@ void Evaluator::apply_key_switching_grouped(CtBatch &ct, const KsKey &key, int a
     if (ct.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted.size() != 2");
     const u64 pw = poly_words(c, ct.limbs);
     switch_key_grouped(ct, ct.data + pw, ct.bstride, key, alpha, batch, scratch_limit_words, s, KsBase{ct.data, ct.bstride});
+}
+
+// ---- hoisted calls with grouped keys (no reference counterpart) ----
+// Scratch in units of N words (rl = dl + alpha, d = ceil(dl / alpha)).  Rotations, per item: dl [CKKS: c1 in coefficient form] + d rl [D]; per (rotation,
+// item): 2 rl [acc] + dl [sigma(c0)] + CKKS: 2 alpha [the special limbs in coefficient form] + 2 dl [the correction]
+static void ksg_hoist_words(const Context &c, u64 dl, u64 alpha, u64 &per_item, u64 &per_rot_item) {
+    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
+    per_item = c.N * (ckks * dl + d * rl);
+    per_rot_item = c.N * (2 * rl + dl + ckks * (2 * alpha + 2 * dl));
+}
+// Linear transform, per item only: dl [CKKS: c1 in coefficient form] + d rl [D] + 2 rl [acc] + 2 dl [base] + BFV / BGV: 2 dl [c0 and c1 in NTT form]
+// + CKKS: 2 alpha + 2 dl [as above]
+static u64 ksg_hoist_lt_words(const Context &c, u64 dl, u64 alpha) {
+    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
+    return c.N * (ckks * dl + d * rl + 2 * rl + 2 * dl + (1 - ckks) * 2 * dl + ckks * (2 * alpha + 2 * dl));
+}
+static const u64 KSG_HOIST_BLOCKS = 8;
+u64 Evaluator::apply_galois_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rots) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    u64 per_item, per_rot_item;
+    ksg_hoist_words(c, (u64)limbs, (u64)alpha, per_item, per_rot_item);
+    return batch * per_item + std::min<u64>(rots, HOIST_MAX_ROT) * batch * per_rot_item + slab_slack(KSG_HOIST_BLOCKS);
+}
+u64 Evaluator::galois_plain_sum_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    return batch * ksg_hoist_lt_words(c, (u64)limbs, (u64)alpha) + slab_slack(KSG_HOIST_BLOCKS);
+}
+void Evaluator::apply_galois_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, int alpha, u64 batch, u64 scratch_limit_words,
+                                             hipStream_t s) {
+    check_ct(in);
+    if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+    check_galois_elts(c, elts, keys, R, every_key);
+    ksg_check_limbs(alpha, in.limbs);
+    if (!hoist_operands("hoisted rotations", in, out, nullptr, (u64)R * batch, batch)) return; // the destination holds R batches back to back
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    u64 per_item, per_rot_item;
+    ksg_hoist_words(c, dl, al, per_item, per_rot_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_HOIST_BLOCKS, per_item, per_rot_item, batch, std::min<u64>(R, HOIST_MAX_ROT),
+                                     "scratch_limit_words is too small for one rotation of one ciphertext");
+    const u64 bs = plan.items, rs = plan.units;
+    if (rs > 1 && bs != batch) throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch"); // the widened second half below
+    KsgPlan k = ksg_plan(alpha, L);
+
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
+    u64 *last = ckks ? c.arena.take(rs * bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(rs * bs * 2 * dl * N) : nullptr;
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        k.a.batch = nb;
+        ksg_target_to_digits(in.data + b0 * in.bstride + pw, in.bstride, tt, D, k, s); // the digit prologue of this run of items, once
+        hoist_rotation_chunks(c, in, out, elts, keys, R, batch, b0, nb, rs, sig0, s, [&](const HoistArgs &h, CtBatch &o) {
+            launch_ksg_hoist_mac(D, acc, k.a, h, s);
+            // the second half over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
+            k.a.batch = (u64)h.rots * nb;
+            ksg_acc_to_ct(o.data, out.bstride, acc, last, corr, k, s, KsBase{sig0, pw});
+            k.a.batch = nb;
+            stats::counter(stats::GROUPED_HOIST_SLABS)++;
+        });
+    }
+}
+void Evaluator::galois_plain_sum_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale,
+                                                 int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (R < 1 || !elts || !keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
+    bool any_rot = false, any_one = false;
+    for (int r = 0; r < R; r++) { // one term at a time, as galois_plain_sum_hoisted
+        check_galois_elts(c, elts + r, keys + r, 1, every_key);
+        if (!plains[r]) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
+        (elts[r] == 1 ? any_one : any_rot) = true;
+    }
+    ksg_check_limbs(alpha, in.limbs);
+    if (!hoist_operands("hoisted linear transform", in, out, &plain_scale, batch, batch)) return;
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const int polys = any_one ? 2 : 1;
+    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_HOIST_BLOCKS, ksg_hoist_lt_words(c, dl, al), 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
+    const u64 bs = plan.items;
+    KsgPlan k = ksg_plan(alpha, L);
+
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks ? nullptr : c.arena.take(bs * pw);
+    u64 *last = ckks ? c.arena.take(bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(bs * 2 * dl * N) : nullptr;
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        k.a.batch = nb;
+        const KsPlan kp = ks_plan(L, nb); // what the base of section 4.11 reads: the data primes
+        ksg_target_to_digits(c1, in.bstride, tt, D, k, s); // the digit prologue of this run of items, once
+        hoist_lt_chunks(elts, keys, plains, R, [&](const HoistLtArgs &h) { launch_ksg_hoist_lt(D, acc, k.a, h, s); });
+        // the base in NTT form, over the data limbs: every element.  The rows of D are grouped, so c1 in NTT form (element 1 only) is made next to c0
+        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, kp.a, s);
+        if (!ckks && any_one) hoist_c0_to_ntt(c1, in.bstride, c1n, kp.a, s);
+        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, HoistC1{c1n, pw, N}, polys, base, kp.a, s);
+        if (!ckks) launch_ntt(base, c.d_desc, k.tmap, nb * polys * dl, c.logn, true, s);
+        u64 *dst = out.data + b0 * out.bstride;
+        if (!any_rot) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, s); // every element is 1 (polys == 2): the result is the base, no key read
+        else ksg_acc_to_ct(dst, out.bstride, acc, last, corr, k, s, KsBase{base, (u64)polys * pw, polys});
+        stats::counter(stats::GROUPED_HOIST_LT_SLABS)++;
+    }
 }
 
 // negacyclicShift (evaluator_cuda.cu:2342-2351): every limb of every polynomial is multiplied by x^shift

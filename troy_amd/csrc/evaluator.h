@@ -34,6 +34,16 @@ struct KsPlan {
     KsArgs a;
     LimbMap digit_map, acc_map;
 };
+// The same for a key switch with grouped digits: the rows of D and acc over the output primes, the special limbs, the data limbs
+struct KsgPlan {
+    KsgArgs a;
+    LimbMap digit_map, acc_map, sp_map, tmap;
+};
+// where a hoisted linear transform finds c1 in NTT form: item b at ptr + b * bstride, limb j at + j * lstride
+struct HoistC1 {
+    const u64 *ptr;
+    u64 bstride, lstride;
+};
 
 // The plan of a polynomial evaluation, a function of (degree, baby steps) alone.  Levels count the primes consumed below the operand.
 struct PolyPlan {
@@ -94,6 +104,17 @@ public:
     void apply_galois_grouped(CtBatch &ct, uint32_t elt, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s);
     void apply_key_switching_grouped(CtBatch &ct, const KsKey &key, int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s);
     u64 switch_key_grouped_scratch_words(int limbs, int alpha, u64 batch) const; // what switch_key_grouped asks of the arena with the whole batch in one slab
+    // The hoisted calls below with grouped keys (no reference counterpart): keys[r] holds grouped digits over `alpha` special primes,
+    // the operand has at most K - alpha limbs.  The digits of c1 are extended and transformed once per item (the first half of switch_key_grouped up to
+    // its inner product); a rotation costs a gathered inner product over d = ceil(limbs / alpha) digits.  At alpha == 1 both equal the per-prime calls
+    // byte for byte; the result does not depend on R, the order of the elements, the batch size or the slabs.  Scratch: evaluator.cpp.
+    void apply_galois_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, int alpha, u64 batch, u64 scratch_limit_words,
+                                      hipStream_t s);
+    void galois_plain_sum_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale,
+                                          int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    // what they ask of the arena with everything in one slab (at most HOIST_MAX_ROT rotations are held at a time)
+    u64 apply_galois_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rots) const;
+    u64 galois_plain_sum_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch) const;
     // Hoisted rotations: out item r * batch + b = the Galois automorphism elts[r] of in item b, key-switched with keys[r] (R dense batches back to
     // back; out.data / out.bstride are the caller's, room for R * batch size-2 items, distinct from in).  The digits of c1 are expanded once per
     // item; element 1 is a copy and reads no key.  The arena request stays under scratch_limit_words (0: 2^28 words), in slabs where needed.
@@ -172,6 +193,11 @@ private:
     void ks_expand_digits(const u64 *coeff, u64 coeff_bstride, u64 *D, const KsPlan &k, hipStream_t s);
     void ks_target_to_acc(const u64 *target, u64 t_bstride, const KsKey &key, u64 *D, u64 *acc, const KsPlan &k, hipStream_t s);
     void ks_acc_to_ct(CtBatch &ct, u64 *acc, const KsPlan &k, hipStream_t s, KsBase base);
+    // the two halves of switch_key_grouped, which the hoisted calls with grouped keys share: target -> D (the caller forms the inner product), acc (+ base) -> ct
+    void ksg_check_limbs(int alpha, int limbs) const;
+    KsgPlan ksg_plan(int alpha, int limbs);
+    void ksg_target_to_digits(const u64 *target, u64 t_bstride, u64 *tt, u64 *D, const KsgPlan &k, hipStream_t s);
+    void ksg_acc_to_ct(u64 *dst, u64 ct_bstride, u64 *acc, u64 *last, u64 *corr, const KsgPlan &k, hipStream_t s, const KsBase &base);
     // what the hoisted calls share, each next to its first user in evaluator.cpp:
     // the digits of the c1 of k.a.batch items (stride bstride) into D; tt: room for c1 in coefficient form (CKKS)
     void hoist_digits(const u64 *c1, u64 bstride, u64 *D, u64 *tt, const KsPlan &k, hipStream_t s);
@@ -180,7 +206,7 @@ private:
     bool hoist_operands(const char *what, const CtBatch &in, CtBatch &out, const double *plain_scale, u64 out_items, u64 batch) const;
     void hoist_c0_to_ntt(const u64 *c0, u64 bstride, u64 *c0n, const KsArgs &a, hipStream_t s); // BFV / BGV: a dense copy of c0, transformed forward
     // dst [k.a.batch][polys][dl][N] = sum over the non-null plains[i] of plains[i] * galois_{elts[i]}(c0 and, polys == 2, c1), in NTT form
-    void hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const u64 *D, int polys, u64 *dst, const KsArgs &a,
+    void hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const HoistC1 &c1n, int polys, u64 *dst, const KsArgs &a,
                        hipStream_t s);
     // the result of a slab of a linear transform from item b0 of out on: the base itself (no element other than 1) or the second half over acc onto the base
     void hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s);

@@ -264,6 +264,11 @@ struct KsgArgs {
 void launch_ksg_extend(const u64 *target, u64 t_bstride, u64 *D, const KsgArgs &a, hipStream_t s);
 // step 2: acc[(b * 2 + c) * rl + o][n] = sum_j D[(b * rl + o) * d + j][n] * key[j][c][limb(o)][n] mod p_o over the transformed rows
 void launch_ksg_mac(const u64 *D, const u64 *key, u64 *acc, const KsgArgs &a, hipStream_t s);
+// hoisted calls with grouped keys: launch_hoist_mac / launch_hoist_lt over the rows D of step 1 (transformed), no CKKS special case
+//   acc[(r * batch + b) * 2 + c][o][n] = sum_j D[(b * rl + o) * d + j][pi_r(n)] * key[r][j][c][limb(o)][n] mod p_o
+void launch_ksg_hoist_mac(const u64 *D, u64 *acc, const KsgArgs &a, const HoistArgs &h, hipStream_t s);
+//   acc[b * 2 + c][o][n] (+)= sum_r pt[r][limb(o)][n] * (the inner product above of rotation r) mod p_o
+void launch_ksg_hoist_lt(const u64 *D, u64 *acc, const KsgArgs &a, const HoistLtArgs &h, hipStream_t s);
 // step 3, everything in coefficient form.  kind 0 (BFV) / 2 (BGV): ct[b][c][i] += mod-down of acc ([2 batch][rl][N]); kind 1 (CKKS):
 // corr[(b * 2 + c) * dl + i][n] = (r_i - [h]_{p_i}) mod p_i -- acc / ct are not read.  sp: the special limbs, item o = b * 2 + c at sp + o * sp_ostride, [alpha][N]
 void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s);

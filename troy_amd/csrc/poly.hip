@@ -1480,6 +1480,150 @@ __global__ __launch_bounds__(EW_THREADS) void ksg_ckks_combine_kernel(const u64 
     u64 *w = ct + b * ct_bstride + (c * a.dl + i) * N + n;
     *w = addmod(*w, v, p);
 }
+// Hoisted calls with grouped keys: hoist_mac_kernel / hoist_lt_kernel over d digits and rl = dl + alpha output primes, D and the
+// key indexed as ksg_mac_kernel indexes them.  D holds every row (the in-group rows are the target's own limbs), so there is no CKKS special case.
+// The loop over the digits is short (d = 3 .. 7 where it matters) and the per-prime kernels are latency-bound with one digit in flight: here the key and
+// digit words of U <= 2 digits are all loaded before the first multiply-accumulate.  ksg_gather_mac walks d in steps of U, then a last single digit: no
+// predicated load, no padding product.  xrow[t]: row of digit 0 of accumulator t's item at its gathered coefficient (digit j at + j N); krow[t]:
+// word of digit 0, component 0 of accumulator t's key (digit j at + j 2 K N, component 1 at + K N).  SHARED: krow[0] serves all four accumulators.
+template <int U, bool SHARED>
+__device__ __forceinline__ void ksg_gather_step(MacAcc (&s0)[4], MacAcc (&s1)[4], const u64 *(&xrow)[4], const u64 *(&krow)[4], u64 j, u64 N, u64 KN) {
+    u64 k0[U][4], k1[U][4], x[U][4];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (!SHARED || t == 0) { const u64 *kp = krow[t] + (j + u) * 2 * KN; k0[u][t] = kp[0]; k1[u][t] = kp[KN]; }
+            else { k0[u][t] = k0[u][0]; k1[u][t] = k1[u][0]; }
+            x[u][t] = xrow[t][(j + u) * N];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        mac4(s0, x[u], k0[u]);
+        mac4(s1, x[u], k1[u]);
+    }
+}
+template <int U, bool SHARED>
+__device__ __forceinline__ void ksg_gather_mac(MacAcc (&s0)[4], MacAcc (&s1)[4], const u64 *(&xrow)[4], const u64 *(&krow)[4], u32 d, u64 N, u64 KN) {
+#pragma unroll
+    for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); }
+    static_assert(U == 1 || U == 2, "one or two digits in flight");
+    u32 j = 0;
+    for (; j + U <= d; j += U) ksg_gather_step<U, SHARED>(s0, s1, xrow, krow, j, N, KN);
+    if (U == 2 && j < d) ksg_gather_step<1, SHARED>(s0, s1, xrow, krow, j, N, KN);
+}
+// digits in flight: two where a thread holds four items of one rotation (6 words per digit), one where it holds four rotations (12 words per digit and
+// nothing shared).  Measured against 1, 2 and 4 in either instance (docs/LAB_NOTEBOOK.md): no setting moved a kernel by more than 7 %; these keep every
+// instance at three waves per SIMD (DESIGN.md section 4.17 has the compiler's resource report)
+template <bool ROT4> struct KsgHoistUnroll { static constexpr int U = ROT4 ? 1 : 2; };
+//   acc[(r * batch + b) * 2 + c][o][n] = sum_{j < d} D[(b * rl + o) * d + j][pi_r(n)] * key_r[j][c][limb(o)][n] mod p_o
+// The two instances and the block order (rotation or group of four, output prime and coefficient window, batch group fastest) are hoist_mac_kernel's.
+// The lazy sums hold d <= 63 products of canonical operands (the launcher refuses more digits).
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void ksg_hoist_mac_kernel(const u64 *D, u64 *acc, KsgArgs a, HoistArgs h) {
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha, KN = (u64)a.K << a.logn;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4), windows = (u32)(((rl << a.logn) + EW_THREADS - 1) / EW_THREADS);
+    const u32 g = blockIdx.x % groups, rest = blockIdx.x / groups, wi = rest % windows, rg = rest / windows;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over rl * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 o = idx >> a.logn;
+    const u32 id = ksg_out_id(a, (u32)o);
+    const Mod m = mod_of(a.primes[id]);
+    // accumulator t: (rotation, item); a ragged last group recomputes its last member and stores nothing for it
+    const u64 *xrow[4], *krow[4];
+    u32 src0 = 0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u32 r = ROT4 ? rg * 4 + t : rg;
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        const u32 rr = r < h.rots ? r : h.rots - 1;
+        const u64 bb = b < a.batch ? b : a.batch - 1;
+        const u32 src = (ROT4 || t == 0) ? galois_ntt_index(n, h.elt[rr], a.logn) : src0;
+        if (t == 0) src0 = src;
+        xrow[t] = D + ((bb * rl + o) * a.d) * N + src;
+        krow[t] = h.key[rr] + (u64)id * N + n;
+    }
+    MacAcc s0[4], s1[4];
+    ksg_gather_mac<KsgHoistUnroll<ROT4>::U, !ROT4>(s0, s1, xrow, krow, a.d, N, KN);
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u32 r = ROT4 ? rg * 4 + t : rg;
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (r >= h.rots || b >= a.batch) break;
+        const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+        const u64 w = (u64)r * a.batch + b;
+        acc[((w * 2 + 0) * rl + o) * N + n] = barrett128(v0.lo, v0.hi, m);
+        acc[((w * 2 + 1) * rl + o) * N + n] = barrett128(v1.lo, v1.hi, m);
+    }
+}
+//   acc[b * 2 + c][o][n] (+)= sum_r pt_r[limb(o)][n] * (the inner product above of rotation r) mod p_o
+// hoist_lt_kernel's shape: its two instances, its outer accumulators and their bounds (at most HOIST_MAX_ROT terms per launch: 128-bit sums of products
+// of canonical words below 2^124 for four rotations of one item; 64-bit sums of reduced products below 2^64 for four items of one rotation), and
+// `accumulate` for the launches after the first.
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void ksg_hoist_lt_kernel(const u64 *D, u64 *acc, KsgArgs a, HoistLtArgs h) {
+    constexpr int NO = ROT4 ? 1 : 4; // items per thread
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha, KN = (u64)a.K << a.logn;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4);
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over rl * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 o = idx >> a.logn;
+    const u32 id = ksg_out_id(a, (u32)o);
+    const Mod m = mod_of(a.primes[id]);
+    const u64 *xbase[4]; // digit 0 of the item of accumulator t at output prime o, coefficient 0
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        xbase[t] = D + (((b < a.batch ? b : a.batch - 1) * rl + o) * a.d) * N;
+    }
+    U128 o0[NO], o1[NO];
+#pragma unroll
+    for (int t = 0; t < NO; t++) o0[t] = o1[t] = U128{0, 0};
+    const u32 steps = ROT4 ? (h.rots + 3) / 4 : h.rots;
+    for (u32 st = 0; st < steps; st++) {
+        u32 rr[4];
+        const u64 *xrow[4], *krow[4];
+        u32 src0 = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const u32 r = ROT4 ? st * 4 + t : st;
+            rr[t] = r < h.rots ? r : h.rots - 1;
+            const u32 src = (ROT4 || t == 0) ? galois_ntt_index(n, h.elt[rr[t]], a.logn) : src0;
+            if (t == 0) src0 = src;
+            xrow[t] = xbase[t] + src;
+            krow[t] = h.key[rr[t]] + (u64)id * N + n;
+        }
+        MacAcc s0[4], s1[4];
+        ksg_gather_mac<KsgHoistUnroll<ROT4>::U, !ROT4>(s0, s1, xrow, krow, a.d, N, KN);
+        // the inner sums of this rotation (of these four), reduced, times the rotation's plaintext word, onto the outer accumulators
+        u64 w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (ROT4 && st * 4 + t >= h.rots) break;
+            if (ROT4 || t == 0) w = h.pt[rr[t]][(u64)id * N + n];
+            const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+            if (ROT4) {
+                mac128(o0[0], barrett128(v0.lo, v0.hi, m), w);
+                mac128(o1[0], barrett128(v1.lo, v1.hi, m), w);
+            } else {
+                o0[t].lo += mulmod(barrett128(v0.lo, v0.hi, m), w, m);
+                o1[t].lo += mulmod(barrett128(v1.lo, v1.hi, m), w, m);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NO; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (b >= a.batch) break;
+        u64 *p0 = acc + ((b * 2 + 0) * rl + o) * N + n, *p1 = acc + ((b * 2 + 1) * rl + o) * N + n;
+        u64 r0 = barrett128(o0[t].lo, o0[t].hi, m), r1 = barrett128(o1[t].lo, o1[t].hi, m);
+        if (h.accumulate) { r0 = addmod(r0, *p0, m.p); r1 = addmod(r1, *p1, m.p); } // the canonical words an earlier launch of this call stored
+        *p0 = r0;
+        *p1 = r1;
+    }
+}
 // every launch is one-dimensional: a grid stays below 2^31 blocks or is refused, no dimension can pass 65535 unnoticed
 static unsigned ksg_grid(u64 blocks, const char *what) {
     if (!blocks || blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": batch too large for one launch");
@@ -1499,6 +1643,31 @@ void launch_ksg_mac(const u64 *D, const u64 *key, u64 *acc, const KsgArgs &a, hi
     const u64 blocks = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS) * ((a.batch + 3) / 4);
     TROY_LAUNCH(ksg_mac_kernel, dim3(ksg_grid(blocks, "ksg_mac")), dim3(EW_THREADS), 0, s, D, key, acc, a);
     launch_check("ksg_mac_kernel");
+}
+static bool ksg_hoist_check(const KsgArgs &a, u32 rots, const char *what) {
+    ksg_check(a);
+    if (!rots || rots > HOIST_MAX_ROT) throw Error(ST_LOGIC_ERROR, std::string(what) + ": 1 .. 16 rotations per launch");
+    return a.batch <= 2 && rots > 1; // one or two ciphertexts: four rotations per thread, as launch_hoist_mac
+}
+void launch_ksg_hoist_mac(const u64 *D, u64 *acc, const KsgArgs &a, const HoistArgs &h, hipStream_t s) {
+    const bool rot4 = ksg_hoist_check(a, h.rots, "ksg_hoist_mac");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.key[r] || h.elt[r] == 1) throw Error(ST_LOGIC_ERROR, "ksg_hoist_mac: every rotation takes a key; element 1 is a copy");
+    const u64 windows = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS);
+    const unsigned grid = ksg_grid(rot4 ? (u64)((h.rots + 3) / 4) * windows * a.batch : (u64)h.rots * windows * ((a.batch + 3) / 4), "ksg_hoist_mac");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_mac_kernel<true>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_mac_kernel<false>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    launch_check("ksg_hoist_mac_kernel");
+}
+void launch_ksg_hoist_lt(const u64 *D, u64 *acc, const KsgArgs &a, const HoistLtArgs &h, hipStream_t s) {
+    const bool rot4 = ksg_hoist_check(a, h.rots, "ksg_hoist_lt");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.key[r] || !h.pt[r] || h.elt[r] == 1) throw Error(ST_LOGIC_ERROR, "ksg_hoist_lt: every rotation takes a key and a plaintext; element 1 belongs to the base");
+    const u64 windows = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS);
+    const unsigned grid = ksg_grid(windows * (rot4 ? a.batch : (a.batch + 3) / 4), "ksg_hoist_lt");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_lt_kernel<true>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_lt_kernel<false>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    launch_check("ksg_hoist_lt_kernel");
 }
 void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s) {
     ksg_check(a);
