@@ -506,6 +506,29 @@ int troyhip_galois_plain_sum_hoisted_grouped(troyhip_context *ctx, const troyhip
  * Below the value for (one item, one rotation) the calls refuse with "scratch_limit_words is too small ...". */
 int troyhip_apply_galois_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int rots, uint64_t *words);
 int troyhip_galois_plain_sum_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, uint64_t *words);
+/* ---- Baby-step / giant-step linear transform with grouped keys.  NO REFERENCE COUNTERPART: the result is defined in DESIGN.md
+ * section 4.18 on top of sections 4.12, 4.16 and 4.17.  troyhip_galois_plain_sum_bsgs keeps taking per-prime keys only. ---- */
+/* troyhip_galois_plain_sum_bsgs with grouped keys: every baby and giant key is a grouped key over `special_primes` special primes ([digits][2][K][N]); the
+ * operand has at most K - special_primes limbs ("operand has more limbs than the grouped key serves").  The table, the null entries, the skipped babies
+ * and rows, the limits (1 <= n_baby, n_giant <= 64), the destination and the result form are those of troyhip_galois_plain_sum_bsgs, and so are its
+ * refusals and their messages.  u_i is byte for byte what troyhip_galois_plain_sum_hoisted_grouped returns for the present babies and plaintexts of row
+ * i; the giant stage extends the digits of each u_i.c1, sums the gathered inner products of all giants over the dl + special_primes output primes and
+ * runs ONE mod-down by all special primes.  The limbs are a function of the ciphertext, special_primes and the SET of rows alone (not of the order of
+ * the babies or rows, the chunking, the batch size or the scratch limit).  special_primes == 1 with per-prime keys: the bytes of
+ * troyhip_galois_plain_sum_bsgs.  n_giant == 1 with giant element 1: the bytes of troyhip_galois_plain_sum_hoisted_grouped.
+ * scratch_limit_words bounds the arena request (0: 2^28 words): the whole batch with as many rows per chunk as fit (16 at the most), else slabs of
+ * items with one row per chunk; below one item with one row it is refused ("scratch_limit_words is too small for one giant step of one ciphertext").
+ * Counter "grouped_bsgs_slabs" (troyhip_stat): slabs run so far.  Stream-ordered. */
+int troyhip_galois_plain_sum_bsgs_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                          const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel,
+                                          double plain_scale, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* the arena words the call asks for with the whole batch in one slab and min(rows_per_chunk, used_rows, 16) rows per chunk; host-only.  used_babies: the
+ * babies other than 1 with a present plaintext (0 .. 64); used_rows: the rows with a present plaintext (1 .. 64).  In units of N words, with dl = limbs,
+ * alpha = special_primes, rl = dl + alpha, d = ceil(dl / alpha), w = min(16, used_babies), gc = min(rows_per_chunk, used_rows, 16), plus 640 words of rounding:
+ *   batch ([CKKS: dl] + d rl + w 2 rl + used_rows 2 rl + [BFV / BGV: 2 dl] + 2 rl + 2 dl)  +  gc batch (4 dl + d rl + [CKKS: 3 dl + 2 alpha])
+ * The value for (batch 1, rows_per_chunk 1) is the least scratch_limit_words the call accepts. */
+int troyhip_galois_plain_sum_bsgs_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int used_babies, int used_rows,
+                                                        int rows_per_chunk, uint64_t *words);
 
 /* ---- Device encoding, `batch` items per call (BatchEncoder / CKKSEncoder).  Item i is BYTE-IDENTICAL to the host form called with item i
  * (DESIGN.md section 4.7).  Every buffer is device memory; strides are in words (u64 or double) between consecutive items; batch in 1 .. 65535.

@@ -2230,7 +2230,10 @@ public:
     }
     Ciphertext rotateRowsPlainSumBsgs(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumBsgs(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
     Ciphertext rotateVectorPlainSumBsgs(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumBsgs(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
-    std::vector<Ciphertext> applyGaloisPlainSumBsgsBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const {
+    std::vector<Ciphertext> applyGaloisPlainSumBsgsBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const { return plainSumBsgsBatch(a, babies, giants, plains, gk, false); }
+private:
+    std::vector<Ciphertext> plainSumBsgsBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk, bool grouped) const {
+        if (grouped) needGrouped(gk);
         const size_t n1 = babies.size(), n2 = giants.size();
         if (!n1 || !n2) throw std::invalid_argument("baby-step / giant-step transform takes at least one baby and one giant element");
         if (plains.size() != n2) throw std::invalid_argument("baby-step / giant-step transform takes one row of plaintexts per giant and one entry (or null) per baby");
@@ -2255,7 +2258,7 @@ public:
                 if (!(elts[r] & 1)) throw std::invalid_argument("Galois element is not valid");
                 if (elts[r] == 1 || !used[r]) continue;
                 if (!gk.hasKey(elts[r])) throw std::invalid_argument("Galois key not present");
-                keys[r] = key_of(gk, GaloisKeys::getIndex(elts[r]));
+                keys[r] = hoistKey(gk, elts[r], grouped);
             }
         };
         look_up(babies, baby_used, bk);
@@ -2267,10 +2270,23 @@ public:
         std::vector<Ciphertext> out = Ciphertext::allocateBatch(a.size(), *a[0], 2, a[0]->coeffModulusSize());
         troyhip_ct t = *out[0].raw();
         const double plain_scale = c_.parms().scheme() == SchemeType::ckks ? first->scale() : 1.0;
-        check(troyhip_galois_plain_sum_bsgs(h(), &va, &t, babies.data(), bk.data(), (int)n1, giants.data(), gkeys.data(), (int)n2, pls.data(), plain_scale, 0, a.size(), nullptr));
+        if (grouped) check(troyhip_galois_plain_sum_bsgs_grouped(h(), &va, &t, babies.data(), bk.data(), (int)n1, giants.data(), gkeys.data(), (int)n2, pls.data(), plain_scale, gk.specialPrimes(), 0, a.size(), nullptr));
+        else check(troyhip_galois_plain_sum_bsgs(h(), &va, &t, babies.data(), bk.data(), (int)n1, giants.data(), gkeys.data(), (int)n2, pls.data(), plain_scale, 0, a.size(), nullptr));
         for (auto &c : out) c.copyMeta(t);
         return out;
     }
+public:
+    // ... with keys with grouped digits (troyhip_galois_plain_sum_bsgs_grouped; no reference counterpart): every baby and giant
+    // costs a gathered inner product over ceil(limbs / special_primes) digits, the giants share one mod-down by all special primes; the table as above.
+    // A per-prime key set is refused ("this call takes keys with grouped digits"), as the members above refuse a grouped one.
+    Ciphertext applyGaloisPlainSumBsgsGrouped(const Ciphertext &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const {
+        std::vector<Ciphertext> r = plainSumBsgsBatch(std::vector<const Ciphertext *>{&a}, babies, giants, plains, gk, true);
+        return std::move(r[0]);
+    }
+    Ciphertext rotateRowsPlainSumBsgsGrouped(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, false); return applyGaloisPlainSumBsgsGrouped(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
+    Ciphertext rotateVectorPlainSumBsgsGrouped(const Ciphertext &a, const std::vector<int> &baby_steps, const std::vector<int> &giant_steps, const PlainTable &plains, const GaloisKeys &gk) const { need(SchemeType::ckks, true); return applyGaloisPlainSumBsgsGrouped(a, eltsOfSteps(baby_steps), eltsOfSteps(giant_steps), plains, gk); }
+    std::vector<Ciphertext> applyGaloisPlainSumBsgsGroupedBatch(const std::vector<const Ciphertext *> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const { return plainSumBsgsBatch(a, babies, giants, plains, gk, true); }
+    std::vector<Ciphertext> applyGaloisPlainSumBsgsGroupedBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const { return plainSumBsgsBatch(Ciphertext::pointers(a), babies, giants, plains, gk, true); }
     std::vector<Ciphertext> applyGaloisPlainSumBsgsBatch(const std::vector<Ciphertext> &a, const std::vector<uint32_t> &babies, const std::vector<uint32_t> &giants, const PlainTable &plains, const GaloisKeys &gk) const { return applyGaloisPlainSumBsgsBatch(Ciphertext::pointers(a), babies, giants, plains, gk); }
     void transformToNttInplace(Ciphertext &a) const { check(troyhip_transform_to_ntt(h(), a.raw(), 1, nullptr)); }
     void transformFromNttInplace(Ciphertext &a) const { check(troyhip_transform_from_ntt(h(), a.raw(), 1, nullptr)); }

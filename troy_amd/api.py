@@ -1058,6 +1058,10 @@ class Evaluator:
         len(baby_elts) * len(giant_elts) rotations, one mod-down for all giants.  plains: len(giant_elts) lists of len(baby_elts) DeviceBuffer (K * N words,
         NTT form at the KEY level, as applyGaloisPlainSumHoisted) or None for an absent term.  The keys of elements no present plaintext uses are not needed."""
         self._per_prime_only(galois_keys)
+        return self._apply_galois_plain_sum_bsgs(a, baby_elts, giant_elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def _apply_galois_plain_sum_bsgs(self, a, baby_elts, giant_elts, plains, galois_keys, plain_scale, scratch_limit_words):
+        """applyGaloisPlainSumBsgs / applyGaloisPlainSumBsgsGrouped behind their check of the key set's kind"""
         babies, giants = [int(g) for g in baby_elts], [int(g) for g in giant_elts]
         table = [list(row) for row in plains]
         n1, n2 = len(babies), len(giants)
@@ -1084,11 +1088,31 @@ class Evaluator:
         gk = key_ptrs(giants, [any(p is not None for p in row) for row in table])
         out = Ciphertext(self.context, a.batch, 2, a.limbs, a.is_ntt_form, a.scale, a.correction_factor)
         si, so = a.struct(), out.struct()
-        self._chk(self.lib.troyhip_galois_plain_sum_bsgs(self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * n1)(*babies), (C.c_void_p * n1)(*bk), n1,
-                                                         (C.c_uint32 * n2)(*giants), (C.c_void_p * n2)(*gk), n2, (C.c_void_p * (n1 * n2))(*pls),
-                                                         C.c_double(plain_scale), C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream))
+        head = (self.context.h, C.byref(si), C.byref(so), (C.c_uint32 * n1)(*babies), (C.c_void_p * n1)(*bk), n1, (C.c_uint32 * n2)(*giants), (C.c_void_p * n2)(*gk), n2,
+                (C.c_void_p * (n1 * n2))(*pls), C.c_double(plain_scale))
+        tail = (C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream)
+        if galois_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_galois_plain_sum_bsgs_grouped(*head, galois_keys.special_primes, *tail))
+        else:
+            self._chk(self.lib.troyhip_galois_plain_sum_bsgs(*head, *tail))
         out._absorb(so)
         return out
+
+    # -- ... with keys with grouped digits (troyhip_galois_plain_sum_bsgs_grouped: no reference counterpart).  The members above keep
+    # refusing a grouped key set; these refuse a per-prime one
+    def applyGaloisPlainSumBsgsGrouped(self, a, baby_elts, giant_elts, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        """applyGaloisPlainSumBsgs with a GaloisKeys(special_primes=alpha) set: every baby and giant costs a gathered inner product over
+        ceil(limbs / alpha) digits, the giants share one mod-down by all special primes.  `a` has at most K - alpha limbs."""
+        self._grouped_only(galois_keys)
+        return self._apply_galois_plain_sum_bsgs(a, baby_elts, giant_elts, plains, galois_keys, plain_scale, scratch_limit_words)
+
+    def rotateRowsPlainSumBsgsGrouped(self, a, baby_steps, giant_steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        return self.applyGaloisPlainSumBsgsGrouped(a, self._steps_to_elts(baby_steps, (BFV, BGV)), self._steps_to_elts(giant_steps, (BFV, BGV)), plains, galois_keys,
+                                                   plain_scale, scratch_limit_words)
+
+    def rotateVectorPlainSumBsgsGrouped(self, a, baby_steps, giant_steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
+        return self.applyGaloisPlainSumBsgsGrouped(a, self._steps_to_elts(baby_steps, (CKKS,)), self._steps_to_elts(giant_steps, (CKKS,)), plains, galois_keys,
+                                                   plain_scale, scratch_limit_words)
 
     def rotateRowsPlainSumBsgs(self, a, baby_steps, giant_steps, plains, galois_keys, plain_scale=1.0, scratch_limit_words=0):
         if self.context.scheme not in (BFV, BGV):

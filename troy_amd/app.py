@@ -441,5 +441,7 @@ class DiagonalMatvecBSGS:
             raise capi.LogicError(capi.LOGIC_ERROR, "encodeDiagonals has not been called")
         if not self.steps:
             raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the matrix is zero")
-        fn = evaluator.rotateVectorPlainSumBsgs if self.context.scheme == capi.CKKS else evaluator.rotateRowsPlainSumBsgs
+        # a key set with grouped digits goes to the members that take one
+        name = ("rotateVector" if self.context.scheme == capi.CKKS else "rotateRows") + "PlainSumBsgs" + ("Grouped" if galois_keys.special_primes is not None else "")
+        fn = getattr(evaluator, name)
         return fn(ct, self.baby_steps, self.giant_steps, self.plains, galois_keys, self.plain_scale)

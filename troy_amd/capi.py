@@ -72,6 +72,7 @@ SYMBOLS = [
     "troyhip_apply_galois_grouped", "troyhip_apply_key_switching_grouped", "troyhip_switch_key_grouped_scratch_words",
     "troyhip_apply_galois_hoisted_grouped", "troyhip_galois_plain_sum_hoisted_grouped", "troyhip_apply_galois_hoisted_grouped_scratch_words",
     "troyhip_galois_plain_sum_hoisted_grouped_scratch_words",
+    "troyhip_galois_plain_sum_bsgs_grouped", "troyhip_galois_plain_sum_bsgs_grouped_scratch_words",
 ]
 
 _lib = None

@@ -838,6 +838,33 @@ int troyhip_galois_plain_sum_hoisted_grouped_scratch_words(const troyhip_context
         *words = need(ctx)->ev.galois_plain_sum_hoisted_grouped_scratch_words(limbs, special_primes, batch);
     }, false);
 }
+// ---- baby-step / giant-step linear transform with grouped keys (no reference counterpart) ----
+int troyhip_galois_plain_sum_bsgs_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                          const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel,
+                                          double plain_scale, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains_ntt_keylevel)
+            throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
+        if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx); // the context is bound before the stream is looked at, as troyhip_galois_plain_sum_bsgs
+        hipStream_t s = on(stream);
+        const std::vector<KsKey> bk = ks_keys(baby_keys, n_baby), gk = ks_keys(giant_keys, n_giant);
+        CtBatch o = view(out);
+        handle->ev.galois_plain_sum_bsgs_grouped(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains_ntt_keylevel, plain_scale, special_primes, batch,
+                                                 scratch_limit_words, s);
+        store(o, out);
+    });
+}
+int troyhip_galois_plain_sum_bsgs_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int used_babies, int used_rows,
+                                                        int rows_per_chunk, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        if (used_babies < 0 || used_babies > 64 || used_rows < 1 || used_rows > 64 || rows_per_chunk < 1)
+            throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+        *words = need(ctx)->ev.galois_plain_sum_bsgs_grouped_scratch_words(limbs, special_primes, batch, (u64)used_babies, (u64)used_rows, (u64)rows_per_chunk);
+    }, false);
+}
 
 
 int troyhip_batch_encode(troyhip_context *ctx, const uint64_t *values, uint64_t count, uint64_t values_stride, uint64_t *plain_out, uint64_t plain_stride,

@@ -1923,6 +1923,163 @@ void Evaluator::galois_plain_sum_hoisted_grouped(const CtBatch &in, CtBatch &out
     }
 }
 
+// ---- baby-step / giant-step linear transform with grouped keys (no reference counterpart) ----
+// The walk of galois_plain_sum_bsgs over the grouped halves of section 4.16: u_i is byte for byte what galois_plain_sum_hoisted_grouped returns for the
+// present babies of row i; the giants cost one digit prologue per row, one gathered inner product over d digits and -- all of them together -- one
+// mod-down by the alpha special primes.  Scratch in units of N words (rl = dl + alpha, d = ceil(dl / alpha), w = min(16, used babies other than 1),
+// n2' = used rows, gc = rows per chunk).  Per item of a slab:
+//   dl [CKKS: c1 in coefficient form] + d rl [D] + w 2 rl [W] + n2' 2 rl [accU] + 2 dl [BFV / BGV: c0 and c1 in NTT form] + 2 rl [acc] + 2 dl [base]
+// and per (row of a chunk, item):
+//   2 dl [baseU] + 2 dl [u] + d rl [the digits of u.c1] + CKKS: dl [u.c1 in coefficient form] + 2 alpha [the special limbs] + 2 dl [the correction]
+// The units of plan_slabs are the rows (16 per chunk at the most).
+static void ksg_bsgs_words(const Context &c, u64 dl, u64 alpha, u64 rot_babies, u64 rows, u64 &per_item, u64 &per_row_item) {
+    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS, w = std::min<u64>(rot_babies, HOIST_MAX_ROT);
+    per_item = c.N * (ckks * dl + d * rl + w * 2 * rl + rows * 2 * rl + (1 - ckks) * 2 * dl + 2 * rl + 2 * dl);
+    per_row_item = c.N * (2 * dl + 2 * dl + d * rl + ckks * (dl + 2 * alpha + 2 * dl));
+}
+static const u64 KSG_BSGS_BLOCKS = 16;
+u64 Evaluator::galois_plain_sum_bsgs_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rot_babies, u64 rows, u64 rows_per_chunk) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    if (rot_babies > 64 || rows < 1 || rows > 64 || rows_per_chunk < 1)
+        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+    u64 per_item, per_row_item;
+    ksg_bsgs_words(c, (u64)limbs, (u64)alpha, rot_babies, rows, per_item, per_row_item);
+    const u64 gc = std::min<u64>(std::min<u64>(rows_per_chunk, rows), HOIST_MAX_ROT);
+    return batch * per_item + gc * batch * per_row_item + slab_slack(KSG_BSGS_BLOCKS);
+}
+void Evaluator::galois_plain_sum_bsgs_grouped(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                                              const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, int alpha, u64 batch,
+                                              u64 scratch_limit_words, hipStream_t s) {
+    check_ct(in);
+    if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
+        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
+    if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+    // as galois_plain_sum_bsgs: every element of both lists before any key, the keys of the used elements only
+    check_galois_elts(c, baby_elts, nullptr, n_baby, every_key);
+    check_galois_elts(c, giant_elts, nullptr, n_giant, every_key);
+    u64 used_babies = 0, used_rows = 0; // bit j / bit i: some plaintext of the column / of the row is present
+    for (int i = 0; i < n_giant; i++)
+        for (int j = 0; j < n_baby; j++)
+            if (plains[(size_t)i * n_baby + j]) { used_babies |= u64(1) << j; used_rows |= u64(1) << i; }
+    check_galois_elts(c, baby_elts, baby_keys, n_baby, [&](int j) { return used_babies >> j & 1; });
+    if (!used_babies) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
+    check_galois_elts(c, giant_elts, giant_keys, n_giant, [&](int i) { return used_rows >> i & 1; });
+    std::vector<int> rot_babies, rows;
+    bool any_one = false; // some used baby is 1: the bases read c1
+    for (int j = 0; j < n_baby; j++)
+        if (used_babies >> j & 1) {
+            if (baby_elts[j] != 1) rot_babies.push_back(j);
+            else any_one = true;
+        }
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n_giant; i++)
+            if ((used_rows >> i & 1) && (giant_elts[i] == 1) == (pass == 1)) rows.push_back(i);
+    const u64 n_rot_rows = (u64)std::count_if(rows.begin(), rows.end(), [&](int i) { return giant_elts[i] != 1; });
+    std::vector<char> row_rot(rows.size(), 0); // the row has a present baby other than 1
+    for (size_t r = 0; r < rows.size(); r++)
+        for (int j : rot_babies)
+            if (plains[(size_t)rows[r] * n_baby + j]) row_rot[r] = 1;
+    ksg_check_limbs(alpha, in.limbs);
+    if (!hoist_operands("baby-step / giant-step transform", in, out, &plain_scale, batch, batch)) return;
+    const int L = in.limbs;
+    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
+    const bool ckks = c.scheme == SCHEME_CKKS;
+    const u64 n2 = rows.size(), nrb = rot_babies.size(), wb = std::min<u64>(nrb, HOIST_MAX_ROT);
+    u64 per_item, per_row_item;
+    ksg_bsgs_words(c, dl, al, nrb, n2, per_item, per_row_item);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_BSGS_BLOCKS, per_item, per_row_item, batch, std::min<u64>(n2, HOIST_MAX_ROT),
+                                     "scratch_limit_words is too small for one giant step of one ciphertext");
+    const u64 bs = plan.items, gc = plan.units;
+    KsgPlan k = ksg_plan(alpha, L);
+
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
+    u64 *D = c.arena.take(bs * d * rl * N);
+    u64 *W = nrb ? c.arena.take(wb * bs * 2 * rl * N) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * 2 * rl * N) : nullptr;
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks ? nullptr : c.arena.take(bs * pw);
+    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
+    u64 *baseU = c.arena.take(gc * bs * 2 * pw), *U = nrb ? c.arena.take(gc * bs * 2 * pw) : baseU; // no baby other than 1: u is its base
+    u64 *DG = n_rot_rows ? c.arena.take(gc * bs * d * rl * N) : nullptr, *ttG = n_rot_rows && ckks ? c.arena.take(gc * bs * dl * N) : nullptr;
+    u64 *last = ckks ? c.arena.take(gc * bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(gc * bs * 2 * dl * N) : nullptr; // of a chunk's rows, then of the result
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        const KsPlan kp = ks_plan(L, nb); // what the bases read: the data primes
+        k.a.batch = nb;
+        ksg_target_to_digits(c1, in.bstride, tt, D, k, s); // stage 1: the digit prologue of this run of items, once
+        // stages 2 and 3: the baby inner products, HOIST_MAX_ROT at a time, kept only until every row has taken its plaintext-weighted share of them
+        for (u64 j0 = 0; j0 < nrb; j0 += HOIST_MAX_ROT) {
+            HoistArgs hm;
+            std::memset(&hm, 0, sizeof(hm));
+            hm.rots = (u32)std::min<u64>(HOIST_MAX_ROT, nrb - j0);
+            for (u32 j = 0; j < hm.rots; j++) { hm.elt[j] = baby_elts[rot_babies[j0 + j]]; hm.key[j] = baby_keys[rot_babies[j0 + j]].data; }
+            launch_ksg_hoist_mac(D, W, k.a, hm, s);
+            for (u64 r0 = 0; r0 < n2; r0 += BSGS_MAX_ROWS) {
+                BsgsInnerArgs hi;
+                std::memset(&hi, 0, sizeof(hi));
+                hi.rows = (u32)std::min<u64>(BSGS_MAX_ROWS, n2 - r0);
+                hi.babies = hm.rots; hi.row0 = (u32)r0; hi.accumulate = j0 ? 1 : 0;
+                bool any = false;
+                for (u32 r = 0; r < hi.rows; r++)
+                    for (u32 j = 0; j < hm.rots; j++)
+                        if (const u64 *p = plains[(size_t)rows[r0 + r] * n_baby + rot_babies[j0 + j]]) { hi.pt[r][j] = p; hi.mask[r] |= 1u << j; any = true; }
+                if (any || !hi.accumulate) launch_ksg_bsgs_inner(W, accU, k.a, hi, s);
+            }
+        }
+        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, kp.a, s);
+        if (!ckks && any_one) hoist_c0_to_ntt(c1, in.bstride, c1n, kp.a, s);
+        bool acc_started = false;
+        for (u64 i0 = 0; i0 < n2; i0 += gc) {
+            const u64 gn = std::min(gc, n2 - i0);
+            // the bases of the rows, as galois_plain_sum_hoisted_grouped makes them: every present pair of the row, both polynomials
+            for (u64 ii = 0; ii < gn; ii++)
+                hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, HoistC1{c1n, pw, N}, 2, baseU + ii * nb * 2 * pw, kp.a, s);
+            if (!ckks) launch_ntt(baseU, c.d_desc, k.tmap, gn * nb * 2 * dl, c.logn, true, s);
+            // u_i of the chunk: ONE second half over rows x items.  A row whose only present babies are 1 takes none: its u_i is its base, as
+            // galois_plain_sum_hoisted_grouped returns it (the grouped mod-down of a zero accumulator is minus its overshoot, not zero: section 4.18),
+            // so the second half runs over the runs of rows that have a baby other than 1 -- one run, unless such a row lies between them
+            for (u64 r0 = 0; nrb && r0 < gn;) {
+                const bool rot = row_rot[i0 + r0];
+                u64 r1 = r0 + 1;
+                while (r1 < gn && row_rot[i0 + r1] == rot) r1++;
+                const u64 off = r0 * nb * 2 * pw;
+                if (rot) {
+                    k.a.batch = (r1 - r0) * nb;
+                    ksg_acc_to_ct(U + off, 2 * pw, accU + (i0 + r0) * nb * 2 * rl * N, last, corr, k, s, KsBase{baseU + off, 2 * pw, 2});
+                    k.a.batch = nb;
+                } else launch_copy_strided(baseU + off, 2 * pw, U + off, 2 * pw, 2 * pw, (r1 - r0) * nb, s);
+                r0 = r1;
+            }
+            // stage 4: the digits of the u_i.c1 whose giant is not 1 (they lead the chunk), each giant its own block; the giant sum and its base
+            u64 gr = 0;
+            while (gr < gn && giant_elts[rows[i0 + gr]] != 1) gr++;
+            if (gr) {
+                k.a.batch = gr * nb;
+                ksg_target_to_digits(U + pw, 2 * pw, ttG, DG, k, s);
+                k.a.batch = nb;
+                HoistSumArgs hs;
+                std::memset(&hs, 0, sizeof(hs));
+                hs.rots = (u32)gr; hs.accumulate = acc_started ? 1 : 0;
+                hs.d_rstride = nb * d * rl * N;
+                for (u64 r = 0; r < gr; r++) { hs.elt[r] = giant_elts[rows[i0 + r]]; hs.key[r] = giant_keys[rows[i0 + r]].data; }
+                launch_ksg_hoist_sum(DG, acc, k.a, hs, s);
+                acc_started = true;
+            }
+            BsgsBaseArgs hb;
+            std::memset(&hb, 0, sizeof(hb));
+            hb.rots = (u32)gn; hb.accumulate = i0 ? 1 : 0;
+            for (u64 r = 0; r < gn; r++) hb.elt[r] = giant_elts[rows[i0 + r]];
+            launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, kp.a, hb, s);
+        }
+        u64 *dst = out.data + b0 * out.bstride;
+        if (!acc_started) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, s); // every used giant is 1: the sum of the u_i, no second mod-down
+        else ksg_acc_to_ct(dst, out.bstride, acc, last, corr, k, s, KsBase{base, 2 * pw, 2}); // ONE mod-down by all special primes for all giants
+        stats::counter(stats::GROUPED_BSGS_SLABS)++;
+    }
+}
+
 // negacyclicShift (evaluator_cuda.cu:2342-2351): every limb of every polynomial is multiplied by x^shift
 void Evaluator::negacyclic_shift(CtBatch &ct, u64 shift, u64 batch, hipStream_t s) {
     check_ct(ct);

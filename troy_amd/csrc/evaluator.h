@@ -134,6 +134,19 @@ public:
     // the arena request stays under scratch_limit_words (0: 2^28 words), in slabs of items and chunks of rows.  DESIGN.md section 4.12.
     void galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
                                const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    // The same transform with grouped keys (no reference counterpart): every key holds grouped digits over `alpha` special primes,
+    // the operand has at most K - alpha limbs.  u_i is byte for byte what galois_plain_sum_hoisted_grouped returns for row i; the giants share one mod-down
+    // by all special primes.  Refuses what galois_plain_sum_bsgs refuses, with its messages, and what the grouped calls refuse.  The result depends on
+    // the set of rows only (not on their order, the order of the babies, the batch size or the scratch limit); at alpha == 1 with the per-prime keys it
+    // stores the bytes of galois_plain_sum_bsgs.  Scratch, in units of N words (rl = limbs + alpha, d = ceil(limbs / alpha), w = min(16, rot_babies)):
+    //   per item:          limbs [CKKS] + d rl + w 2 rl + rows 2 rl + 2 limbs [BFV / BGV] + 2 rl + 2 limbs
+    //   per (row, item):   4 limbs + d rl + CKKS: 3 limbs + 2 alpha
+    // The query returns batch (per item + min(rows_per_chunk, rows, 16) per (row, item)) + slack: what the call asks of the arena with the whole batch in
+    // one slab and that many rows per chunk (rot_babies: the used babies other than 1; rows: the rows with a present plaintext).  Counter: GROUPED_BSGS_SLABS.
+    void galois_plain_sum_bsgs_grouped(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                                       const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, int alpha, u64 batch,
+                                       u64 scratch_limit_words, hipStream_t s);
+    u64 galois_plain_sum_bsgs_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rot_babies, u64 rows, u64 rows_per_chunk) const;
     void transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void transform_from_ntt(CtBatch &ct, u64 batch, hipStream_t s);
     void multiply_plain_ntt(CtBatch &ct, const u64 *plain, double plain_scale, u64 batch, hipStream_t s);

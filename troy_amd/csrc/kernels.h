@@ -269,6 +269,13 @@ void launch_ksg_mac(const u64 *D, const u64 *key, u64 *acc, const KsgArgs &a, hi
 void launch_ksg_hoist_mac(const u64 *D, u64 *acc, const KsgArgs &a, const HoistArgs &h, hipStream_t s);
 //   acc[b * 2 + c][o][n] (+)= sum_r pt[r][limb(o)][n] * (the inner product above of rotation r) mod p_o
 void launch_ksg_hoist_lt(const u64 *D, u64 *acc, const KsgArgs &a, const HoistLtArgs &h, hipStream_t s);
+// baby-step / giant-step linear transform with grouped keys: launch_bsgs_inner / launch_hoist_sum over the grouped output primes
+//   accU[((row0 + r) * batch + b) * 2 + c][o][n] (+)= sum_{j: bit j of mask[r]} pt[r][j][limb(o)][n] * W[(j * batch + b) * 2 + c][o][n] mod p_o
+// W: what launch_ksg_hoist_mac wrote for `babies` elements
+void launch_ksg_bsgs_inner(const u64 *W, u64 *accU, const KsgArgs &a, const BsgsInnerArgs &h, hipStream_t s);
+//   acc[b * 2 + c][o][n] (+)= sum_r (sum_j D_r[(b * rl + o) * d + j][pi_r(n)] * key[r][j][c][limb(o)][n] mod p_o) mod p_o, D_r = D + r * h.d_rstride
+// (the transformed rows of step 1 for u_r.c1; h.t_rstride is not read: D holds every row)
+void launch_ksg_hoist_sum(const u64 *D, u64 *acc, const KsgArgs &a, const HoistSumArgs &h, hipStream_t s);
 // step 3, everything in coefficient form.  kind 0 (BFV) / 2 (BGV): ct[b][c][i] += mod-down of acc ([2 batch][rl][N]); kind 1 (CKKS):
 // corr[(b * 2 + c) * dl + i][n] = (r_i - [h]_{p_i}) mod p_i -- acc / ct are not read.  sp: the special limbs, item o = b * 2 + c at sp + o * sp_ostride, [alpha][N]
 void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s);

@@ -1624,6 +1624,97 @@ template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void ksg_hoist_lt_
         *p1 = r1;
     }
 }
+// Baby-step / giant-step linear transform with grouped keys.  Stage 3, bsgs_inner_kernel over the rl = dl + alpha grouped
+// output primes:  accU[((row0 + r) * batch + b) * 2 + c][o][n] (+)= sum_{j in mask[r]} pt[r][j][limb(o)][n] * W[(j * batch + b) * 2 + c][o][n] mod p_o.
+// Its mapping (a thread owns one (item, c, o, n), (item, c) fastest among the workgroups), its 16 W words in registers, its workgroup-uniform row masks,
+// its 128-bit lazy row sum (at most 16 products of canonical words below 2^60, below 2^124) and its `accumulate`.
+__global__ __launch_bounds__(EW_THREADS) void ksg_bsgs_inner_kernel(const u64 *W, u64 *accU, KsgArgs a, BsgsInnerArgs h) {
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha;
+    const u32 groups = (u32)a.batch * 2;
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over rl * N
+    if (idx >= rl << a.logn) return;
+    const u64 n = idx & (N - 1), o = idx >> a.logn;
+    const u32 id = ksg_out_id(a, (u32)o);
+    const Mod m = mod_of(a.primes[id]);
+    const u64 bk = g; // (item, c): b * 2 + c
+    u64 w[HOIST_MAX_ROT];
+#pragma unroll
+    for (int j = 0; j < HOIST_MAX_ROT; j++) w[j] = (u32)j < h.babies ? W[((((u64)j * a.batch) * 2 + bk) * rl + o) * N + n] : 0;
+    for (u32 r = 0; r < h.rows; r++) {
+        const u32 mask = h.mask[r];
+        if (h.accumulate && !mask) continue;
+        U128 sum{0, 0};
+#pragma unroll
+        for (int j = 0; j < HOIST_MAX_ROT; j++) {
+            if (!((mask >> j) & 1)) continue;
+            mac128(sum, w[j], h.pt[r][j][(u64)id * N + n]);
+        }
+        u64 *dst = accU + ((((u64)(h.row0 + r) * a.batch) * 2 + bk) * rl + o) * N + n;
+        u64 v = barrett128(sum.lo, sum.hi, m);
+        if (h.accumulate) v = addmod(v, *dst, m.p);
+        *dst = v;
+    }
+}
+// Stage 4, the giant sum: hoist_sum_kernel over d digits and rl output primes -- its two instances, its block order (batch group fastest), its ragged-group
+// rule and its `accumulate` -- with giant r reading its own digit block D + r * d_rstride, indexed as ksg_hoist_mac_kernel indexes D:
+//   acc[b * 2 + c][o][n] (+)= sum_r (sum_{j < d} D_r[(b * rl + o) * d + j][pi_r(n)] * key_r[j][c][limb(o)][n] mod p_o) mod p_o.
+// One Barrett step per giant; the outer sums hold at most HOIST_MAX_ROT = 16 canonical words below 2^60 in 64 bits, below 2^64, and are reduced once
+// per launch.  The inner sums hold d <= 63 products of canonical operands (the launcher refuses more digits).  D holds every row: no CKKS special case.
+template <bool ROT4> __global__ __launch_bounds__(EW_THREADS) void ksg_hoist_sum_kernel(const u64 *D, u64 *acc, KsgArgs a, HoistSumArgs h) {
+    constexpr int NO = ROT4 ? 1 : 4; // items per thread
+    const u64 N = u64(1) << a.logn, rl = a.dl + a.alpha, KN = (u64)a.K << a.logn;
+    const u32 groups = ROT4 ? (u32)a.batch : (u32)((a.batch + 3) / 4);
+    const u32 g = blockIdx.x % groups, wi = blockIdx.x / groups;
+    const u64 idx = (u64)wi * EW_THREADS + threadIdx.x; // over rl * N
+    if (idx >= rl << a.logn) return;
+    const u32 n = (u32)(idx & (N - 1));
+    const u64 o = idx >> a.logn;
+    const u32 id = ksg_out_id(a, (u32)o);
+    const Mod m = mod_of(a.primes[id]);
+    u64 xoff[4]; // digit 0 of the item of accumulator t at output prime o, coefficient 0, within a giant's block; a ragged last group recomputes its last member
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        xoff[t] = (((b < a.batch ? b : a.batch - 1) * rl + o) * a.d) * N;
+    }
+    u64 o0[NO], o1[NO];
+#pragma unroll
+    for (int t = 0; t < NO; t++) o0[t] = o1[t] = 0;
+    const u32 steps = ROT4 ? (h.rots + 3) / 4 : h.rots;
+    for (u32 st = 0; st < steps; st++) {
+        const u64 *xrow[4], *krow[4];
+        u32 src0 = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const u32 r = ROT4 ? st * 4 + t : st;
+            const u32 rr = r < h.rots ? r : h.rots - 1;
+            const u32 src = (ROT4 || t == 0) ? galois_ntt_index(n, h.elt[rr], a.logn) : src0;
+            if (t == 0) src0 = src;
+            xrow[t] = D + (u64)rr * h.d_rstride + xoff[t] + src;
+            krow[t] = h.key[rr] + (u64)id * N + n;
+        }
+        MacAcc s0[4], s1[4];
+        ksg_gather_mac<KsgHoistUnroll<ROT4>::U, !ROT4>(s0, s1, xrow, krow, a.d, N, KN);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (ROT4 && st * 4 + t >= h.rots) break;
+            const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+            o0[ROT4 ? 0 : t] += barrett128(v0.lo, v0.hi, m);
+            o1[ROT4 ? 0 : t] += barrett128(v1.lo, v1.hi, m);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NO; t++) {
+        const u64 b = ROT4 ? g : (u64)g * 4 + t;
+        if (b >= a.batch) break;
+        u64 *p0 = acc + ((b * 2 + 0) * rl + o) * N + n, *p1 = acc + ((b * 2 + 1) * rl + o) * N + n;
+        u64 r0 = barrett64(o0[t], m), r1 = barrett64(o1[t], m);
+        if (h.accumulate) { r0 = addmod(r0, *p0, m.p); r1 = addmod(r1, *p1, m.p); } // the canonical words an earlier launch of this call stored
+        *p0 = r0;
+        *p1 = r1;
+    }
+}
 // every launch is one-dimensional: a grid stays below 2^31 blocks or is refused, no dimension can pass 65535 unnoticed
 static unsigned ksg_grid(u64 blocks, const char *what) {
     if (!blocks || blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": batch too large for one launch");
@@ -1668,6 +1759,28 @@ void launch_ksg_hoist_lt(const u64 *D, u64 *acc, const KsgArgs &a, const HoistLt
     if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_lt_kernel<true>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
     else TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_lt_kernel<false>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
     launch_check("ksg_hoist_lt_kernel");
+}
+void launch_ksg_bsgs_inner(const u64 *W, u64 *accU, const KsgArgs &a, const BsgsInnerArgs &h, hipStream_t s) {
+    ksg_check(a);
+    if (!h.rows || h.rows > BSGS_MAX_ROWS || !h.babies || h.babies > HOIST_MAX_ROT) throw Error(ST_LOGIC_ERROR, "ksg_bsgs_inner: 1 .. 8 rows over 1 .. 16 babies of a non-empty batch per launch");
+    for (u32 r = 0; r < h.rows; r++) {
+        if (h.mask[r] >> h.babies) throw Error(ST_LOGIC_ERROR, "ksg_bsgs_inner: a row names a baby the launch does not hold");
+        for (u32 j = 0; j < h.babies; j++)
+            if (((h.mask[r] >> j) & 1) && !h.pt[r][j]) throw Error(ST_LOGIC_ERROR, "ksg_bsgs_inner: every present pair takes a plaintext");
+    }
+    const u64 windows = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS);
+    TROY_LAUNCH(ksg_bsgs_inner_kernel, dim3(ksg_grid(windows * a.batch * 2, "ksg_bsgs_inner")), dim3(EW_THREADS), 0, s, W, accU, a, h);
+    launch_check("ksg_bsgs_inner_kernel");
+}
+void launch_ksg_hoist_sum(const u64 *D, u64 *acc, const KsgArgs &a, const HoistSumArgs &h, hipStream_t s) {
+    const bool rot4 = ksg_hoist_check(a, h.rots, "ksg_hoist_sum");
+    for (u32 r = 0; r < h.rots; r++)
+        if (!h.key[r] || h.elt[r] == 1) throw Error(ST_LOGIC_ERROR, "ksg_hoist_sum: every giant takes a key; element 1 belongs to the base");
+    const u64 windows = ceil_div((u64)(a.dl + a.alpha) << a.logn, EW_THREADS);
+    const unsigned grid = ksg_grid(windows * (rot4 ? a.batch : (a.batch + 3) / 4), "ksg_hoist_sum");
+    if (rot4) TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_sum_kernel<true>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(ksg_hoist_sum_kernel<false>), dim3(grid), dim3(EW_THREADS), 0, s, D, acc, a, h);
+    launch_check("ksg_hoist_sum_kernel");
 }
 void launch_ksg_moddown(int kind, const u64 *acc, const u64 *sp, u64 sp_ostride, u64 *corr, u64 *ct, u64 ct_bstride, const KsgArgs &a, hipStream_t s) {
     ksg_check(a);
