@@ -15,8 +15,11 @@
 // per output instead of ~85; the kernels are VALU-issue bound (profiles/r01_behz_probe.txt), so that is where the time goes.
 // The per-coefficient correction terms are extra INPUT columns of the product: the centred m_tilde residue r against
 // q m_tilde^-1 (extension), the centred alpha against -(B mod q_l) (Shenoy-Kumaresan), at limb position L (nB) of the digit
-// matrix -- patched into the B fragment in registers, whatever L mod 4 is.  B^-1 mod m_sk is folded into the m_sk rows of both
-// stages, so alpha is one modular subtraction.
+// matrix, whatever L mod 4 is -- r patched into the B fragment in registers, alpha written to the digit buffer in LDS by the one wave that
+// evaluates the m_sk row of a sub-tile.  B^-1 mod m_sk is folded into the m_sk rows of both stages, so alpha is one modular subtraction.
+// Neither correction term is computed more than once per coefficient: r comes from a 32-bit sum that the four waves share through LDS (no
+// matrix product), alpha from one m_sk product per sub-tile.  An int8 MFMA and 64-bit VALU work do not overlap on gfx950, so a repeated
+// product is paid in full.
 #include "kernels.h"
 #include <cstdlib>
 
@@ -28,9 +31,11 @@ namespace troyhip {
 #ifdef TROYHIP_CPU_EMUL
 #define B2_UNIFORM(x) (x)
 typedef const u64 *b2_cu64;
+typedef const u32 *b2_cu32;
 #else
 #define B2_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 typedef const __attribute__((address_space(4))) u64 *b2_cu64; // wave-uniform addresses: scalar loads
+typedef const __attribute__((address_space(4))) u32 *b2_cu32;
 #endif
 
 __device__ __forceinline__ long long b2_mad(int a, int b, long long c) { // c + sext(a) * b in one instruction
@@ -106,12 +111,17 @@ __device__ __forceinline__ void b2_patch(MfmaFrag &f, const B2Patch w, u64 digit
 
 // ---------------------------------------------------------------- extension q -> Bsk (fastbconvmTilde + smMrq)
 // in [polys][L][N] -> out [polys][nBsk][N].  A 256-thread workgroup walks `tiles_per_wg` tiles of 64 coefficients of one polynomial;
-// wave w converts limbs w, w+4, .. to digits (LDS, double-buffered: one barrier per tile), evaluates the m_tilde row for its own
-// lanes and owns row-block w = outputs 4w .. 4w+3: a lane finishes outputs 4w + half (accumulators 0-7) and 4w + 2 + half (8-15).
+// wave w converts limbs w, w+4, .. to digits (LDS, double-buffered: one barrier per tile) and owns row-block w = outputs 4w .. 4w+3:
+// a lane finishes outputs 4w + half (accumulators 0-7) and 4w + 2 + half (8-15).
+// The m_tilde residue needs no matrix product: m_tilde is 2^32, so sum_l y_l (q/q_l) mod 2^32 is a sum of 32-bit products of the low words.
+// A wave adds up its own limbs while it still holds y_l (one multiply-add each) and leaves the partial sum beside the digits; after
+// the barrier a lane adds the four partials of its coefficient.  (On gfx950 an int8 MFMA does not overlap 64-bit VALU work, so the
+// four MFMAs per sub-tile that every wave spent on this row -- for four useful rows of 32 -- were paid in full, four times over.)
 // polynomials from `split` on are read from in2 (the second operand of a product: both go through one launch when it is small)
 template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_kernel(const u64 *in, u64 in_pstride, u64 *out, u64 out_pstride, const PrimeDesc *primes, BehzDev c,
                                                                                    u64 N, unsigned tiles_per_wg, const u64 *in2, unsigned split) {
     __shared__ __attribute__((aligned(16))) u64 ydig[2][2 * KB * B2_TILE * 2]; // [buffer][limb pair][coefficient] 16-byte units
+    __shared__ u32 rpart[2][4][B2_TILE];                                       // [buffer][wave][coefficient] partial sums of the m_tilde row
     const unsigned lane = threadIdx.x & 63, half = lane >> 5, cl = lane & 31;
     const int w = B2_UNIFORM((int)(threadIdx.x >> 6));
     const u64 poly = blockIdx.y;
@@ -119,12 +129,9 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
     const BufRsrc rout = make_rsrc(out + poly * out_pstride, (u32)((u64)c.nBsk * N * 8));
     const u32 n32 = (u32)N;
     const bool owner = w < ((c.nBsk + 3) >> 2);
-    MfmaFrag af[KB], am[KB];
+    MfmaFrag af[KB];
 #pragma unroll
-    for (int kb = 0; kb < KB; kb++) {
-        af[kb] = b2_frag(c.x_frag, ((size_t)(owner ? w : 0) * KB + kb) * 64 + lane);
-        am[kb] = b2_frag(c.x_mt_frag, (size_t)kb * 64 + lane);
-    }
+    for (int kb = 0; kb < KB; kb++) af[kb] = b2_frag(c.x_frag, ((size_t)(owner ? w : 0) * KB + kb) * 64 + lane);
     BehzK2 k2[2];
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -134,6 +141,7 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
     const B2Patch where = b2_patch_where(c.L, half);
     u64 qp[KB];
     Shoup qpre[KB];
+    u32 qmt[KB]; // (q/q_l) mod 2^32 of this wave's limbs; 0 for a padding slot
 #pragma unroll
     for (int i = 0; i < KB; i++) {
         const int l = w + 4 * i;
@@ -141,6 +149,7 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
         const unsigned id = B2_UNIFORM((unsigned)c.q_id[lc]);
         qp[i] = ((b2_cu64)&primes[id])[0];
         qpre[i] = Shoup{((b2_cu64)(c.ext_pre + lc))[0], ((b2_cu64)(c.ext_pre + lc))[1]};
+        qmt[i] = l < c.L ? ((b2_cu32)c.ext_mt_row)[lc] : 0u;
     }
     u64 xr[KB];
     auto fetch = [&](unsigned t) { // a tile beyond N, a padding limb: offset out of range, the load returns 0
@@ -160,12 +169,16 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
         if (n0 >= n32) break;
         u64 *yd = ydig[t & 1];
         // y_l = x_l m_tilde (q/q_l)^-1 mod q_l as balanced digits; limbs L .. 4 KB - 1 (the extra input's slot and padding) are zero
+        u32 rs = 0;
 #pragma unroll
         for (int i = 0; i < KB; i++) {
             const int l = w + 4 * i;
             // a padding slot (wave-uniform; only the last k-block has any) skips the multiplication: its residue was loaded as 0, whose digits are 0
-            yd[(((l >> 1) * B2_TILE) + lane) * 2 + (l & 1)] = l < c.L ? b2_digits(mul_shoup(xr[i], qpre[i].op, qpre[i].quo, qp[i])) : 0;
+            const u64 y = l < c.L ? mul_shoup(xr[i], qpre[i].op, qpre[i].quo, qp[i]) : 0;
+            yd[(((l >> 1) * B2_TILE) + lane) * 2 + (l & 1)] = b2_digits(y);
+            rs += (u32)y * qmt[i];
         }
+        rpart[t & 1][w][lane] = rs;
         fetch(t + 1 < tiles_per_wg ? t + 1 : 0x7FFFFFu); // past the last tile: out of range
         __syncthreads();
 #pragma unroll
@@ -174,12 +187,9 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
             MfmaFrag bf[KB];
 #pragma unroll
             for (int kb = 0; kb < KB; kb++) bf[kb] = b2_frag(yd, (size_t)(2 * kb + half) * B2_TILE + cc);
-            // r = -(sum_l y_l (q/q_l)) q^-1 mod 2^32 from the four shift rows of the m_tilde block (both halves hold them)
+            // r = -(sum_l y_l (q/q_l)) q^-1 mod 2^32 from the four waves' partial sums
+            const u32 rsum = rpart[t & 1][0][cc] + rpart[t & 1][1][cc] + rpart[t & 1][2][cc] + rpart[t & 1][3][cc];
             MfmaAcc acc;
-            b2_zero(acc);
-#pragma unroll
-            for (int kb = 0; kb < KB; kb++) TROY_MFMA_I8(am[kb], bf[kb], acc);
-            const u32 rsum = (u32)acc.v[0] + ((u32)acc.v[1] << 8) + ((u32)acc.v[2] << 16) + ((u32)acc.v[3] << 24);
             const u64 r_mt = ((u64)rsum * c.neg_inv_q_mod_mt) & 0xFFFFFFFFull;
             // centred representative of r (rns.cpp:966-975) as one more input: out = (sum + r q) m_tilde^-1
             b2_patch(bf[KB - 1], where, b2_digits((u64)((long long)r_mt - (long long)((r_mt >> 31) << 32))));
@@ -205,8 +215,9 @@ template <int KB> __global__ __launch_bounds__(B2_THREADS) void behz2_extend_ker
 // y [polys][L][N], dbt [polys][nBsk][N] -> out [polys][L][N], inputs PRE-SCALED and canonical: y_l = t dq_l (q/q_l)^-1 mod q_l and
 // dbt_o = db_o T_o mod Bsk_o, which the inverse transforms in front deliver for free (BehzDev::floor_desc).  Two chained products per tile:
 //   (1) rows of f1_frag x digits(y), + dbt_o  ->  u_b (digits, LDS) for o < nB, and z' = z_sk B^-1 mod m_sk
-//   (2) the m_sk row x digits(u) -> alpha = conv' - z' (every wave, for its own lanes), then rows of f2_frag x [digits(u), alpha] -> out_l
-// All A fragments stay in registers (one row-block per wave and stage); two barriers per tile.
+//   (2) the m_sk row x digits(u) -> alpha = conv' - z' (ONE wave per sub-tile; its digits go to LDS as limb nB of u), then rows of
+//       f2_frag x [digits(u), alpha] -> out_l
+// All A fragments stay in registers (one row-block per wave and stage); three barriers per tile.
 template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS) void behz2_floor_sk_kernel(const u64 *dq, u64 dq_pstride, const u64 *db, u64 db_pstride,
                                                                                                            u64 *out, u64 out_pstride, const PrimeDesc *primes, BehzDev c,
                                                                                                            u64 N, unsigned tiles_per_wg) {
@@ -221,7 +232,7 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
     const BufRsrc rout = make_rsrc(out + poly * out_pstride, (u32)((u64)c.L * N * 8));
     const u32 n32 = (u32)N;
     const bool owner1 = w < ((c.nBsk + 3) >> 2), owner2 = w < ((c.L + 3) >> 2);
-    for (unsigned i = threadIdx.x; i < 2 * KB2 * B2_TILE * 2; i += B2_THREADS) udig[i] = 0; // limbs nB .. stay zero
+    for (unsigned i = threadIdx.x; i < 2 * KB2 * B2_TILE * 2; i += B2_THREADS) udig[i] = 0; // limbs above nB stay zero
     MfmaFrag af1[KB1], af2[KB2], amsk[KB2];
 #pragma unroll
     for (int kb = 0; kb < KB1; kb++) af1[kb] = b2_frag(c.f1_frag, ((size_t)(owner1 ? w : 0) * KB1 + kb) * 64 + lane);
@@ -244,7 +255,6 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
         }
     }
     const BehzK2 msk = c.msk_k; // kernel argument: scalar registers
-    const B2Patch where = b2_patch_where(c.nB, half);
     // both operands of a tile are fetched while the previous tile is computed: the q residues of this wave's limbs (xr) and the Bsk
     // residues this lane adds in the stage-1 epilogue, (sub, j) -> db[o = 4w + 2j + half][n0 + 32 sub + cl] (dbn)
     u64 xr[KB1], dbn[2][2];
@@ -301,6 +311,24 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
             }
         }
         __syncthreads();
+        // ---- the m_sk row, once per tile: wave 2 (t mod 2) + sub takes sub-tile sub (the pair alternates from tile to tile, so the four
+        // waves -- one per SIMD -- carry the same load) and leaves the digits of the centred alpha in the slot of limb nB of udig, where
+        // stage 2 of every wave reads them as one more input.  The m_sk row has no weight at limb nB: the previous tile's alpha there is inert
+        const int rsub = w - 2 * (int)(t & 1);
+        if (rsub == 0 || rsub == 1) {
+            const unsigned cc = (unsigned)rsub * 32 + cl;
+            MfmaAcc acc;
+            b2_zero(acc);
+#pragma unroll
+            for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(amsk[kb], b2_frag(udig, (size_t)(2 * kb + half) * B2_TILE + cc), acc);
+            // alpha = (conv_{B->m_sk}(z) - z_sk) B^-1 mod m_sk; above m_sk / 2 it stands for a negative value (rns.cpp:905-930)
+            const u64 conv = b2_finish<0>(acc, msk.biaslo, msk); // both halves of the wave hold the row
+            const u64 z = zsk[cc];
+            const u64 alpha = conv >= z ? conv - z : conv + msk.p - z;
+            const bool neg = alpha > (msk.p >> 1);
+            if (half == 0) udig[(((c.nB >> 1) * B2_TILE) + cc) * 2 + (c.nB & 1)] = b2_digits(neg ? alpha - msk.p : alpha); // out_l = sum - alpha (B mod q_l)
+        }
+        __syncthreads();
         // ---- stage 2: Shenoy-Kumaresan
 #pragma unroll
         for (int sub = 0; sub < 2; sub++) {
@@ -309,15 +337,6 @@ template <int KB1, int KB2, bool FAST2> __global__ __launch_bounds__(B2_THREADS)
 #pragma unroll
             for (int kb = 0; kb < KB2; kb++) bf[kb] = b2_frag(udig, (size_t)(2 * kb + half) * B2_TILE + cc);
             MfmaAcc acc;
-            b2_zero(acc);
-#pragma unroll
-            for (int kb = 0; kb < KB2; kb++) TROY_MFMA_I8(amsk[kb], bf[kb], acc);
-            // alpha = (conv_{B->m_sk}(z) - z_sk) B^-1 mod m_sk; above m_sk / 2 it stands for a negative value (rns.cpp:905-930)
-            const u64 conv = b2_finish<0>(acc, msk.biaslo, msk);
-            const u64 z = zsk[cc];
-            const u64 alpha = conv >= z ? conv - z : conv + msk.p - z;
-            const bool neg = alpha > (msk.p >> 1);
-            b2_patch(bf[KB2 - 1], where, b2_digits(neg ? alpha - msk.p : alpha)); // out_l = sum - alpha (B mod q_l)
             u64 r[2] = {0, 0};
             if (owner2) {
                 b2_zero(acc);

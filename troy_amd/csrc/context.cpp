@@ -459,6 +459,8 @@ void Context::upload_tables() {
                 f2w[l].push_back(pb ? r.q[l] - pb : 0);                                             // the centred alpha against -(B mod q_l)
                 f2k[l] = make_k2(r.q[l]);
             }
+            // mskw has exactly nB columns: pack_rows8 leaves the weight of limb nB and above at zero, and behz2_floor_sk_kernel relies on it -- the m_sk
+            // product of a tile reads the slot of limb nB while it still holds the previous tile's alpha.  Append no column here
             for (int h = 0; h < 2; h++) {
                 for (int l = 0; l < L; l++) mtw[h].push_back(mt_row[l]);
                 for (int b = 0; b < nB; b++) mskw[h].push_back(host::mul_mod(r.B_to_msk.mat[0][b], r.inv_prod_B_mod_msk, r.m_sk));
