@@ -795,34 +795,82 @@ int troyhip_switch_key_grouped_scratch_words(const troyhip_context *ctx, int lim
         *words = need(ctx)->ev.switch_key_grouped_scratch_words(limbs, special_primes, batch);
     }, false);
 }
-// ---- hoisted calls with grouped keys (no reference counterpart) ----
+// ---- the hoisted calls (DESIGN.md sections 4.10 - 4.12) and their twins with grouped keys (4.17, 4.18): one body per pair.  special_primes == null:
+// the per-prime call.  The context is bound before the stream is looked at: argument evaluation order is unspecified ----
 static std::vector<KsKey> ks_keys(const uint64_t *const *keys, int n) {
     std::vector<KsKey> v((size_t)n);
     for (int i = 0; i < n; i++) v[(size_t)i] = KsKey{keys[i]};
     return v;
 }
+static void hoisted_rotations(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *elts, const uint64_t *const *galois_keys, int n_elts,
+                              const int *special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    if (n_elts < 1 || !elts || !galois_keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
+    if (special_primes && (!in || !out)) throw Error(ST_INVALID_ARGUMENT, "null ciphertext"); // the per-prime call leaves it to view()
+    const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
+    CtBatch o = view(out);
+    Evaluator &ev = need(ctx)->ev;
+    const hipStream_t s = on(stream);
+    if (special_primes) ev.apply_galois_hoisted_grouped(view(in), o, elts, keys.data(), n_elts, *special_primes, batch, scratch_limit_words, s);
+    else ev.apply_galois_hoisted(view(in), o, elts, keys.data(), n_elts, batch, scratch_limit_words, s);
+    store(o, out);
+}
+static void hoisted_linear(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
+                           int n_elts, double plain_scale, const int *special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    if (n_elts < 1 || !elts || !galois_keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
+    if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+    const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
+    CtBatch o = view(out);
+    Evaluator &ev = need(ctx)->ev;
+    const hipStream_t s = on(stream);
+    if (special_primes) ev.galois_plain_sum_hoisted_grouped(view(in), o, elts, keys.data(), plains, n_elts, plain_scale, *special_primes, batch, scratch_limit_words, s);
+    else ev.galois_plain_sum_hoisted(view(in), o, elts, keys.data(), plains, n_elts, plain_scale, batch, scratch_limit_words, s);
+    store(o, out);
+}
+static void hoisted_bsgs(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                         const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains, double plain_scale, const int *special_primes,
+                         uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
+        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
+    if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+    if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+    Evaluator &ev = need(ctx)->ev;
+    const hipStream_t s = on(stream);
+    const std::vector<KsKey> bk = ks_keys(baby_keys, n_baby), gk = ks_keys(giant_keys, n_giant);
+    CtBatch o = view(out);
+    if (special_primes)
+        ev.galois_plain_sum_bsgs_grouped(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains, plain_scale, *special_primes, batch, scratch_limit_words, s);
+    else ev.galois_plain_sum_bsgs(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains, plain_scale, batch, scratch_limit_words, s);
+    store(o, out);
+}
+int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
+                                 uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] { hoisted_rotations(ctx, in, out, galois_elts, galois_keys, n_elts, nullptr, scratch_limit_words, batch, stream); });
+}
 int troyhip_apply_galois_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
                                          int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
-    return guard([&] {
-        if (n_elts < 1 || !galois_elts || !galois_keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
-        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
-        const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
-        CtBatch o = view(out);
-        need(ctx)->ev.apply_galois_hoisted_grouped(view(in), o, galois_elts, keys.data(), n_elts, special_primes, batch, scratch_limit_words, on(stream));
-        store(o, out);
-    });
+    return guard([&] { hoisted_rotations(ctx, in, out, galois_elts, galois_keys, n_elts, &special_primes, scratch_limit_words, batch, stream); });
+}
+int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                     const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] { hoisted_linear(ctx, in, out, galois_elts, galois_keys, plains_ntt_keylevel, n_elts, plain_scale, nullptr, scratch_limit_words, batch, stream); });
 }
 int troyhip_galois_plain_sum_hoisted_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
                                              const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, int special_primes, uint64_t scratch_limit_words,
                                              uint64_t batch, void *stream) {
+    return guard([&] { hoisted_linear(ctx, in, out, galois_elts, galois_keys, plains_ntt_keylevel, n_elts, plain_scale, &special_primes, scratch_limit_words, batch, stream); });
+}
+int troyhip_galois_plain_sum_bsgs(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                  const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel, double plain_scale,
+                                  uint64_t scratch_limit_words, uint64_t batch, void *stream) {
     return guard([&] {
-        if (n_elts < 1 || !galois_elts || !galois_keys || !plains_ntt_keylevel) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
-        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
-        const std::vector<KsKey> keys = ks_keys(galois_keys, n_elts);
-        CtBatch o = view(out);
-        need(ctx)->ev.galois_plain_sum_hoisted_grouped(view(in), o, galois_elts, keys.data(), plains_ntt_keylevel, n_elts, plain_scale, special_primes, batch, scratch_limit_words,
-                                                       on(stream));
-        store(o, out);
+        hoisted_bsgs(ctx, in, out, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant, plains_ntt_keylevel, plain_scale, nullptr, scratch_limit_words, batch, stream);
+    });
+}
+int troyhip_galois_plain_sum_bsgs_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
+                                          const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel,
+                                          double plain_scale, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        hoisted_bsgs(ctx, in, out, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant, plains_ntt_keylevel, plain_scale, &special_primes, scratch_limit_words, batch, stream);
     });
 }
 int troyhip_apply_galois_hoisted_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int rots, uint64_t *words) {
@@ -837,24 +885,6 @@ int troyhip_galois_plain_sum_hoisted_grouped_scratch_words(const troyhip_context
         if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
         *words = need(ctx)->ev.galois_plain_sum_hoisted_grouped_scratch_words(limbs, special_primes, batch);
     }, false);
-}
-// ---- baby-step / giant-step linear transform with grouped keys (no reference counterpart) ----
-int troyhip_galois_plain_sum_bsgs_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
-                                          const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel,
-                                          double plain_scale, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
-    return guard([&] {
-        if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains_ntt_keylevel)
-            throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
-        if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
-        auto *handle = need(ctx); // the context is bound before the stream is looked at, as troyhip_galois_plain_sum_bsgs
-        hipStream_t s = on(stream);
-        const std::vector<KsKey> bk = ks_keys(baby_keys, n_baby), gk = ks_keys(giant_keys, n_giant);
-        CtBatch o = view(out);
-        handle->ev.galois_plain_sum_bsgs_grouped(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains_ntt_keylevel, plain_scale, special_primes, batch,
-                                                 scratch_limit_words, s);
-        store(o, out);
-    });
 }
 int troyhip_galois_plain_sum_bsgs_grouped_scratch_words(const troyhip_context *ctx, int limbs, int special_primes, uint64_t batch, int used_babies, int used_rows,
                                                         int rows_per_chunk, uint64_t *words) {
@@ -968,48 +998,6 @@ int troyhip_rescale_to_next(troyhip_context *ctx, const troyhip_ct *in, troyhip_
 int troyhip_apply_galois(troyhip_context *ctx, troyhip_ct *ct, uint32_t galois_elt, const uint64_t *galois_key, uint64_t batch, void *stream) {
     return guard([&] { CtBatch x = view(ct); need(ctx)->ev.apply_galois(x, galois_elt, KsKey{galois_key}, batch, on(stream)); store(x, ct); });
 }
-int troyhip_apply_galois_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int n_elts,
-                                 uint64_t scratch_limit_words, uint64_t batch, void *stream) {
-    return guard([&] {
-        if (n_elts < 1 || !galois_elts || !galois_keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
-        std::vector<KsKey> keys((size_t)n_elts);
-        for (int i = 0; i < n_elts; i++) keys[(size_t)i] = KsKey{galois_keys[i]};
-        CtBatch o = view(out);
-        need(ctx)->ev.apply_galois_hoisted(view(in), o, galois_elts, keys.data(), n_elts, batch, scratch_limit_words, on(stream));
-        store(o, out);
-    });
-}
-int troyhip_galois_plain_sum_hoisted(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
-                                     const uint64_t *const *plains_ntt_keylevel, int n_elts, double plain_scale, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
-    return guard([&] {
-        if (n_elts < 1 || !galois_elts || !galois_keys || !plains_ntt_keylevel) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
-        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
-        std::vector<KsKey> keys((size_t)n_elts);
-        for (int i = 0; i < n_elts; i++) keys[(size_t)i] = KsKey{galois_keys[i]};
-        CtBatch o = view(out);
-        need(ctx)->ev.galois_plain_sum_hoisted(view(in), o, galois_elts, keys.data(), plains_ntt_keylevel, n_elts, plain_scale, batch, scratch_limit_words, on(stream));
-        store(o, out);
-    });
-}
-int troyhip_galois_plain_sum_bsgs(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, const uint32_t *baby_elts, const uint64_t *const *baby_keys, int n_baby,
-                                  const uint32_t *giant_elts, const uint64_t *const *giant_keys, int n_giant, const uint64_t *const *plains_ntt_keylevel, double plain_scale,
-                                  uint64_t scratch_limit_words, uint64_t batch, void *stream) {
-    return guard([&] {
-        if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains_ntt_keylevel)
-            throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
-        if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
-        auto *handle = need(ctx); // the context is bound before the stream is looked at: argument evaluation order is unspecified
-        hipStream_t s = on(stream);
-        std::vector<KsKey> bk((size_t)n_baby), gk((size_t)n_giant);
-        for (int i = 0; i < n_baby; i++) bk[(size_t)i] = KsKey{baby_keys[i]};
-        for (int i = 0; i < n_giant; i++) gk[(size_t)i] = KsKey{giant_keys[i]};
-        CtBatch o = view(out);
-        handle->ev.galois_plain_sum_bsgs(view(in), o, baby_elts, bk.data(), n_baby, giant_elts, gk.data(), n_giant, plains_ntt_keylevel, plain_scale, batch, scratch_limit_words, s);
-        store(o, out);
-    });
-}
-
 static void rotate_internal(troyhip_context *ctx, CtBatch &x, int steps, const uint32_t *elts, const uint64_t *const *keys, int n_keys, u64 batch, hipStream_t s) {
     if (steps == 0) return; // evaluator_cuda.cu:2140-2143
     const u64 N = need(ctx)->ctx.N;

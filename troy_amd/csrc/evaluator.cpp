@@ -726,18 +726,13 @@ bool Evaluator::hoist_operands(const char *what, const CtBatch &in, CtBatch &out
         throw Error(ST_INVALID_ARGUMENT, std::string(what) + ": destination must be a distinct buffer");
     return batch != 0;
 }
-// D[b][i][j] = NTT_{p_i}(d_j mod p_i) of c1's digits d_j; D[b][j][j] is c1's own limb j in NTT form
-void Evaluator::hoist_digits(const u64 *c1, u64 bstride, u64 *D, u64 *tt, const KsPlan &k, hipStream_t s) {
-    if (c.scheme == SCHEME_CKKS) c1 = ks_coeff_target(c1, bstride, tt, k, s);
-    ks_expand_digits(c1, bstride, D, k, s);
-}
 void Evaluator::hoist_c0_to_ntt(const u64 *c0, u64 bstride, u64 *c0n, const KsArgs &a, hipStream_t s) {
     launch_copy_strided(c0, bstride, c0n, a.dl * c.N, a.dl * c.N, a.batch, s);
     launch_ntt(c0n, c.d_desc, c.ct_map((int)a.dl), a.batch * a.dl, c.logn, false, s);
 }
 // every present term, HOIST_MAX_ROT per launch: c0 is read through the index map of the element (element 1: in place) and, polys == 2, c1 for element 1.
-// CKKS reads the operand where it lies (c1 follows c0); BFV / BGV read c0n (hoist_c0_to_ntt) and c1's limbs in NTT form where c1n says (the per-prime
-// calls: c1's own limbs in D, hoist_c1_in_digits)
+// CKKS reads the operand where it lies (c1 follows c0); BFV / BGV read c0n (hoist_c0_to_ntt) and c1's limbs in NTT form where c1n says (HoistKs::c1_ntt:
+// the per-prime calls find c1's own limbs in D)
 void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const HoistC1 &c1n, int polys, u64 *dst,
                               const KsArgs &a, hipStream_t s) {
     const u64 N = c.N, dl = a.dl, pw = dl * N;
@@ -757,46 +752,141 @@ void Evaluator::hoist_lt_base(const u64 *const *plains, const uint32_t *elts, in
         }
     flush();
 }
-// D[b][j][j] of the per-prime digits is limb j of c1 in NTT form: item b at + b rl dl N, limb j at + j rl N
-static HoistC1 hoist_c1_in_digits(const u64 *D, u64 dl, u64 N) { return HoistC1{D, (dl + 1) * dl * N, (dl + 1) * N}; }
-void Evaluator::hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s) {
-    const u64 pw = k.a.dl * c.N;
-    CtBatch o = out;
-    o.data = out.data + b0 * out.bstride;
-    if (!switched) launch_copy_strided(base, 2 * pw, o.data, out.bstride, 2 * pw, k.a.batch, s); // the result is the base: no key read, no mod-down
-    else {
-        c.arena.rewind(mark);
-        ks_acc_to_ct(o, acc, k, s, KsBase{base, (u64)polys * pw, polys});
-    }
+
+// ---- one flavour of key switching, as the hoisted walks see it ----
+// What a flavour holds in scratch, in words per item: the digits of a target (D), a CKKS target in coefficient form (tt), an accumulator pair in the
+// extended basis (acc) and what its second half needs (finish).  c1n: the BFV / BGV bases read c1 in NTT form from a block next to c0's
+struct HoistWords { u64 D, tt, acc, finish; bool c1n; };
+// per-prime (rl = dl + 1), in units of N words: rl dl [D], dl [tt], 2 rl [acc], 2 dl + 4 [what ks_acc_to_ct carves]; c1's limbs in NTT form lie in D
+static HoistWords ks_hoist_words(const Context &c, u64 dl) {
+    const u64 N = c.N, rl = dl + 1, ckks = c.scheme == SCHEME_CKKS;
+    return HoistWords{N * rl * dl, N * ckks * dl, N * 2 * rl, N * (2 * dl + 4), false};
+}
+// grouped (rl = dl + alpha, d = ceil(dl / alpha)): d rl [D], dl [tt], 2 rl [acc], CKKS: 2 alpha [the special limbs in coefficient form] + 2 dl [the correction]
+static HoistWords ksg_hoist_words(const Context &c, u64 dl, u64 alpha) {
+    const u64 N = c.N, rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
+    return HoistWords{N * d * rl, N * ckks * dl, N * 2 * rl, N * ckks * (2 * alpha + 2 * dl), true};
+}
+// The scratch of the three walks from those words: per item and per (unit, item) of a slab (plan_slabs; pw = dl N, ntt = BFV / BGV: pw [c0 in NTT form],
+// 2 pw with c1n).  The same functions serve the walks and the *_scratch_words queries.
+struct SlabWords { u64 per_item, per_unit_item; };
+static const u64 HOIST_BLOCKS = 8, BSGS_BLOCKS = 16; // what a walk and its second half carve at the most
+static u64 hoist_ntt_words(const Context &c, const HoistWords &w, u64 pw) { return c.scheme == SCHEME_CKKS ? 0 : (w.c1n ? 2 : 1) * pw; }
+// rotations (the units are the rotations; the digits of a run of items are made once for all of them): D + tt, and acc + pw [sigma(c0)] + finish
+static SlabWords hoist_rot_words(const HoistWords &w, u64 pw) { return SlabWords{w.D + w.tt, w.acc + pw + w.finish}; }
+// linear transform (no factor R, nothing per unit): D + tt + acc + 2 pw [base] + ntt + finish
+static SlabWords hoist_lt_words(const Context &c, const HoistWords &w, u64 pw) { return SlabWords{w.D + w.tt + w.acc + 2 * pw + hoist_ntt_words(c, w, pw) + w.finish, 0}; }
+// BSGS (the units are the rows; wb = min(16, used babies other than 1), n2 = used rows): D + tt + wb acc [W] + n2 acc [accU] + ntt + acc + 2 pw [base], and
+// per row of a chunk 2 pw [baseU] + 2 pw [u] + D + tt [the digits of u.c1] + finish
+static SlabWords bsgs_words(const Context &c, const HoistWords &w, u64 pw, u64 rot_babies, u64 rows) {
+    const u64 wb = std::min<u64>(rot_babies, HOIST_MAX_ROT);
+    return SlabWords{w.D + w.tt + (wb + rows + 1) * w.acc + hoist_ntt_words(c, w, pw) + 2 * pw, 4 * pw + w.D + w.tt + w.finish};
 }
 
-// The rotations of the items b0 .. b0 + nb - 1 of a hoisted call, in chunks of at most `rs` consecutive elements other than 1: sigma_r(c0) of a chunk goes
-// to sig0 (item r * nb + b), then chunk(h, o) runs with o at the chunk's first output item.  Element 1 is a copy of the operand and reads no key.
-template <class F> static void hoist_rotation_chunks(Context &c, const CtBatch &in, const CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 b0, u64 nb,
-                                                     u64 rs, u64 *sig0, hipStream_t s, F chunk) {
-    const u64 pw = poly_words(c, in.limbs);
-    const u64 *c0 = in.data + b0 * in.bstride;
-    const LimbMap map = c.ct_map(in.limbs);
-    for (int r0 = 0; r0 < R;) {
-        CtBatch o = out;
-        o.data = out.data + ((u64)r0 * batch + b0) * out.bstride;
-        if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
-            launch_copy_strided(c0, in.bstride, o.data, out.bstride, 2 * pw, nb, s);
-            r0++;
-            continue;
-        }
-        HoistArgs h;
-        std::memset(&h, 0, sizeof(h));
-        while (r0 + (int)h.rots < R && h.rots < rs && elts[r0 + h.rots] != 1) {
-            h.elt[h.rots] = elts[r0 + h.rots];
-            h.key[h.rots] = keys[r0 + h.rots].data;
-            h.rots++;
-        }
-        for (u32 r = 0; r < h.rots; r++) launch_galois(c.scheme == SCHEME_CKKS, c0, in.bstride, sig0 + (u64)r * nb * pw, pw, c.d_desc, map, c.logn, h.elt[r], (u64)in.limbs, nb, s);
-        chunk(h, o);
-        r0 += (int)h.rots;
+// The two halves of a key switch and the four gathered inner products between them.  A walk carves D, tt, acc and the bases; the flavour says how many
+// words they take and fills them.  kp: the key switch over the data primes at the operand's level, which the base kernels read whatever the flavour.
+struct Evaluator::HoistKs {
+    enum Call { ROTATIONS, LINEAR, BSGS };
+    Evaluator &ev;
+    Context &c;
+    const hipStream_t s;
+    const int *const slab_ids; // the flavour's slab counter of each call
+    KsPlan kp;
+    u64 nb = 0; // the items of the slab
+    HoistKs(Evaluator &e, hipStream_t st, const int *ids) : ev(e), c(e.c), s(st), slab_ids(ids) {}
+    virtual ~HoistKs() {}
+    virtual void admit(int limbs) const = 0; // after the element / key / plaintext checks, before hoist_operands
+    virtual HoistWords words(u64 dl) const = 0;
+    virtual void open(int limbs) { kp = ev.ks_plan(limbs, 0); } // behind every check: the plans
+    virtual void carved(u64 items) = 0; // the walk has carved its blocks; its widest second half runs over `items` items
+    virtual void slab(u64 items) { nb = kp.a.batch = items; }
+    // first half up to the inner product: the digits of `items` targets (stride bstride) into D
+    virtual void digits(const u64 *target, u64 bstride, u64 *tt, u64 *D, u64 items) = 0;
+    // the inner products over the slab's items; t: the target in the form the ciphertext is in (the per-prime CKKS kernels read its own limb there)
+    virtual void mac(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistArgs &h) = 0;
+    virtual void lt(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistLtArgs &h) = 0;
+    virtual void inner(const u64 *W, u64 *accU, const BsgsInnerArgs &h) = 0;
+    virtual void sum(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistSumArgs &h) = 0;
+    // BFV / BGV: where the bases find c1 in NTT form (needed: some term reads it); c1n: the walk's block for it, where words().c1n
+    virtual HoistC1 c1_ntt(const u64 *c1, u64 bstride, const u64 *D, u64 *c1n, bool needed) = 0;
+    // second half over `items` items: dst (item stride `stride`) = base + the mod-down of acc
+    virtual void finish(u64 *dst, u64 stride, u64 *acc, const KsBase &base, u64 items) = 0;
+    virtual bool zero_acc_is_base() const = 0; // finish() over an accumulator of zeros stores the base, byte for byte, on every route it takes
+    void count_slab(Call w) const { stats::counter(slab_ids[w])++; }
+};
+// per-prime: ks_coeff_target + ks_expand_digits (D[b][i][j] = NTT_{p_i}(d_j mod p_i); D[b][j][j] is c1's own limb j in NTT form) and ks_acc_to_ct, which
+// carves what it needs behind the walk's blocks and picks its fused epilogues
+struct Evaluator::HoistPerPrime final : Evaluator::HoistKs {
+    size_t mark = 0;
+    HoistPerPrime(Evaluator &e, hipStream_t st) : HoistKs(e, st, ids()) {}
+    static const int *ids() { static const int v[] = {stats::HOIST_SLABS, stats::HOIST_LT_SLABS, stats::BSGS_SLABS}; return v; }
+    const u64 *own(const u64 *t) const { return c.scheme == SCHEME_CKKS ? t : nullptr; }
+    void admit(int) const override {}
+    HoistWords words(u64 dl) const override { return ks_hoist_words(c, dl); }
+    void carved(u64) override { mark = c.arena.mark(); }
+    bool zero_acc_is_base() const override { return true; } // the mod-down and the CKKS correction of zero are zero
+    void digits(const u64 *target, u64 bstride, u64 *tt, u64 *D, u64 items) override {
+        kp.a.batch = items;
+        if (c.scheme == SCHEME_CKKS) target = ev.ks_coeff_target(target, bstride, tt, kp, s);
+        ev.ks_expand_digits(target, bstride, D, kp, s);
+        kp.a.batch = nb;
     }
-}
+    void mac(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistArgs &h) override { launch_hoist_mac(D, own(t), t_bstride, acc, kp.a, h, s); }
+    void lt(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistLtArgs &h) override { launch_hoist_lt(D, own(t), t_bstride, acc, kp.a, h, s); }
+    void inner(const u64 *W, u64 *accU, const BsgsInnerArgs &h) override { launch_bsgs_inner(W, accU, kp.a, h, s); }
+    void sum(const u64 *D, const u64 *t, u64 t_bstride, u64 *acc, const HoistSumArgs &h) override { launch_hoist_sum(D, own(t), t_bstride, acc, kp.a, h, s); }
+    HoistC1 c1_ntt(const u64 *, u64, const u64 *D, u64 *, bool) override { // the diagonal of D: item b at + b rl dl N, limb j at + j rl N
+        const u64 dl = kp.a.dl;
+        return HoistC1{D, (dl + 1) * dl * c.N, (dl + 1) * c.N};
+    }
+    void finish(u64 *dst, u64 stride, u64 *acc, const KsBase &base, u64 items) override {
+        CtBatch o;
+        o.data = dst; o.bstride = stride;
+        kp.a.batch = items;
+        c.arena.rewind(mark);
+        ev.ks_acc_to_ct(o, acc, kp, s, base);
+        kp.a.batch = nb;
+    }
+};
+// grouped over alpha special primes (section 4.16): ksg_target_to_digits and ksg_acc_to_ct, which is handed its CKKS blocks, sized for the widest use
+struct Evaluator::HoistGrouped final : Evaluator::HoistKs {
+    const int alpha;
+    KsgPlan k;
+    u64 *last = nullptr, *corr = nullptr;
+    HoistGrouped(Evaluator &e, int al, hipStream_t st) : HoistKs(e, st, ids()), alpha(al) {}
+    static const int *ids() { static const int v[] = {stats::GROUPED_HOIST_SLABS, stats::GROUPED_HOIST_LT_SLABS, stats::GROUPED_BSGS_SLABS}; return v; }
+    void admit(int limbs) const override { ev.ksg_check_limbs(alpha, limbs); }
+    HoistWords words(u64 dl) const override { return ksg_hoist_words(c, dl, (u64)alpha); }
+    void open(int limbs) override { HoistKs::open(limbs); k = ev.ksg_plan(alpha, limbs); }
+    void carved(u64 items) override {
+        if (c.scheme != SCHEME_CKKS) return;
+        last = c.arena.take(items * 2 * alpha * c.N);
+        corr = c.arena.take(items * 2 * k.a.dl * c.N);
+    }
+    void slab(u64 items) override { HoistKs::slab(items); k.a.batch = items; }
+    bool zero_acc_is_base() const override { return false; } // the mod-down of a zero accumulator is minus its overshoot (section 4.18)
+    void digits(const u64 *target, u64 bstride, u64 *tt, u64 *D, u64 items) override {
+        k.a.batch = items;
+        ev.ksg_target_to_digits(target, bstride, tt, D, k, s);
+        k.a.batch = nb;
+    }
+    // the rows of D hold every digit at every output prime: no CKKS special case
+    void mac(const u64 *D, const u64 *, u64, u64 *acc, const HoistArgs &h) override { launch_ksg_hoist_mac(D, acc, k.a, h, s); }
+    void lt(const u64 *D, const u64 *, u64, u64 *acc, const HoistLtArgs &h) override { launch_ksg_hoist_lt(D, acc, k.a, h, s); }
+    void inner(const u64 *W, u64 *accU, const BsgsInnerArgs &h) override { launch_ksg_bsgs_inner(W, accU, k.a, h, s); }
+    void sum(const u64 *D, const u64 *, u64, u64 *acc, const HoistSumArgs &h) override { launch_ksg_hoist_sum(D, acc, k.a, h, s); }
+    HoistC1 c1_ntt(const u64 *c1, u64 bstride, const u64 *, u64 *c1n, bool needed) override { // the rows of D are grouped: c1 is transformed as c0 is
+        if (needed) ev.hoist_c0_to_ntt(c1, bstride, c1n, kp.a, s);
+        return HoistC1{c1n, kp.a.dl * c.N, c.N};
+    }
+    void finish(u64 *dst, u64 stride, u64 *acc, const KsBase &base, u64 items) override {
+        k.a.batch = items;
+        ev.ksg_acc_to_ct(dst, stride, acc, last, corr, k, s, base);
+        k.a.batch = nb;
+    }
+};
+
+// ---- the three hoisted walks (DESIGN.md sections 4.10 - 4.12; no reference counterpart), each over either flavour ----
 // The terms of a hoisted linear transform whose element is not 1, HOIST_MAX_ROT per launch(h); launches after the first accumulate onto what the first stored
 template <class F> static void hoist_lt_chunks(const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, F launch) {
     HoistLtArgs h;
@@ -815,56 +905,65 @@ template <class F> static void hoist_lt_chunks(const uint32_t *elts, const KsKey
     flush();
 }
 
-// Hoisted rotations (Halevi-Shoup; no reference counterpart): the digits of c1 are decomposed, extended and transformed ONCE
-// per item; every Galois element then costs a gathered inner product over them (the automorphism is a permutation in NTT form), sigma(c0) and the
-// second half of the key switch.  Scratch per slab of `bs` items and `rs` rotations (plan_slabs; the digits of a run of items are made once for all
-// its rotations):
-//   bs N (rl dl [D] + dl [CKKS: c1 in coefficient form]) + rs bs N (2 rl [acc] + dl [sigma(c0)] + 2 dl + 4 [what the second half carves])
-void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+// Hoisted rotations (Halevi-Shoup): the digits of c1 are decomposed, extended and transformed ONCE per item; every Galois element then costs a gathered
+// inner product over them (the automorphism is a permutation in NTT form), sigma(c0) and the second half of the key switch.  The rotations of a slab run
+// in chunks of at most `rs` consecutive elements other than 1: sigma_r(c0) of a chunk goes to sig0 (item r * nb + b), and ONE second half runs over
+// rots * nb items, item r * nb + b accumulating onto (sigma_r(c0_b), 0).  Element 1 is a copy of the operand and reads no key.
+void Evaluator::hoist_rotations(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words) {
     check_ct(in);
     if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
     check_galois_elts(c, elts, keys, R, every_key);
+    f.admit(in.limbs);
     if (!hoist_operands("hoisted rotations", in, out, nullptr, (u64)R * batch, batch)) return; // the destination holds R batches back to back
     const int L = in.limbs;
-    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
-    const bool ckks = c.scheme == SCHEME_CKKS;
-    const u64 per_item = N * (rl * dl + (ckks ? dl : 0)), per_rot_item = N * (2 * rl + dl + 2 * dl + 4);
-    const SlabPlan plan = plan_slabs(scratch_limit_words, 8, per_item, per_rot_item, batch, std::min<u64>(R, HOIST_MAX_ROT), "scratch_limit_words is too small for one rotation of one ciphertext");
+    const u64 pw = poly_words(c, L);
+    const HoistWords w = f.words((u64)L);
+    const SlabWords sw = hoist_rot_words(w, pw);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, HOIST_BLOCKS, sw.per_item, sw.per_unit_item, batch, std::min<u64>(R, HOIST_MAX_ROT),
+                                     "scratch_limit_words is too small for one rotation of one ciphertext");
     const u64 bs = plan.items, rs = plan.units;
     if (rs > 1 && bs != batch) throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch"); // the widened second half below
+    f.open(L);
 
-    c.arena.begin(s);
+    c.arena.begin(f.s);
     c.arena.reserve(plan.words);
-    u64 *D = c.arena.take(bs * rl * dl * N);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
-    const size_t mark = c.arena.mark();
+    u64 *D = c.arena.take(bs * w.D), *tt = w.tt ? c.arena.take(bs * w.tt) : nullptr;
+    u64 *acc = c.arena.take(rs * bs * w.acc), *sig0 = c.arena.take(rs * bs * pw);
+    f.carved(rs * bs);
+    const LimbMap map = c.ct_map(L);
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
         const u64 nb = std::min(bs, batch - b0);
-        const u64 *c1 = in.data + b0 * in.bstride + pw;
-        KsPlan k = ks_plan(L, nb);
-        KsArgs &a = k.a;
-        hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
-        hoist_rotation_chunks(c, in, out, elts, keys, R, batch, b0, nb, rs, sig0, s, [&](const HoistArgs &h, CtBatch &o) {
-            launch_hoist_mac(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s);
-            // the second half of the key switch over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
-            a.batch = (u64)h.rots * nb;
-            c.arena.rewind(mark);
-            ks_acc_to_ct(o, acc, k, s, KsBase{sig0, pw});
-            a.batch = nb;
-            stats::counter(stats::HOIST_SLABS)++;
-        });
+        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
+        f.slab(nb);
+        f.digits(c1, in.bstride, tt, D, nb); // of this run of items, once
+        for (int r0 = 0; r0 < R;) {
+            u64 *dst = out.data + ((u64)r0 * batch + b0) * out.bstride;
+            if (elts[r0] == 1) { // the identity: a copy of the operand, no key read
+                launch_copy_strided(c0, in.bstride, dst, out.bstride, 2 * pw, nb, f.s);
+                r0++;
+                continue;
+            }
+            HoistArgs h;
+            std::memset(&h, 0, sizeof(h));
+            while (r0 + (int)h.rots < R && h.rots < rs && elts[r0 + h.rots] != 1) {
+                h.elt[h.rots] = elts[r0 + h.rots];
+                h.key[h.rots] = keys[r0 + h.rots].data;
+                h.rots++;
+            }
+            for (u32 r = 0; r < h.rots; r++) launch_galois(c.scheme == SCHEME_CKKS, c0, in.bstride, sig0 + (u64)r * nb * pw, pw, c.d_desc, map, c.logn, h.elt[r], (u64)L, nb, f.s);
+            f.mac(D, c1, in.bstride, acc, h);
+            f.finish(dst, out.bstride, acc, KsBase{sig0, pw}, (u64)h.rots * nb);
+            f.count_slab(HoistKs::ROTATIONS);
+            r0 += (int)h.rots;
+        }
     }
 }
 
-// Hoisted linear transform (no reference counterpart): sum_r plains[r] * (Galois element elts[r] of the operand), the plaintexts
-// applied in the extended basis BEFORE the mod-down, so that the sum over the rotations is formed inside the gathered inner product: one accumulator and
-// one mod-down per item whatever R is, nothing of size R in memory.  Scratch per item (no factor R):
-//   N (rl dl [D] + dl [CKKS: c1 in coefficient form] + 2 rl [acc] + 2 dl [base] + dl [BFV / BGV: c0 in NTT form] + 2 dl + 4 [what the second half carves])
-// A slab is a run of items that fits under the limit (plan_slabs, nothing per unit); the rotations of a slab run HOIST_MAX_ROT per launch, later launches
-// accumulating.
-void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
-                                         u64 scratch_limit_words, hipStream_t s) {
+// Hoisted linear transform: sum_r plains[r] * (Galois element elts[r] of the operand), the plaintexts applied in the extended basis BEFORE the mod-down, so
+// that the sum over the rotations is formed inside the gathered inner product: one accumulator and one mod-down per item whatever R is, nothing of size R
+// in memory.  A slab is a run of items that fits under the limit; its rotations run HOIST_MAX_ROT per launch, later launches accumulating.
+void Evaluator::hoist_linear(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
+                             u64 scratch_limit_words) {
     check_ct(in);
     if (R < 1 || !elts || !keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
     bool any_rot = false, any_one = false;
@@ -873,56 +972,59 @@ void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const 
         if (!plains[r]) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
         (elts[r] == 1 ? any_one : any_rot) = true;
     }
+    f.admit(in.limbs);
     if (!hoist_operands("hoisted linear transform", in, out, &plain_scale, batch, batch)) return;
     const int L = in.limbs;
-    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
+    const u64 pw = poly_words(c, L);
     const bool ckks = c.scheme == SCHEME_CKKS;
     const int polys = any_one ? 2 : 1;
-    const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + 2 * rl + 2 * dl + (ckks ? 0 : dl) + 2 * dl + 4);
-    const SlabPlan plan = plan_slabs(scratch_limit_words, 8, per_item, 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
+    const HoistWords w = f.words((u64)L);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, HOIST_BLOCKS, hoist_lt_words(c, w, pw).per_item, 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
     const u64 bs = plan.items;
+    f.open(L);
 
-    c.arena.begin(s);
+    c.arena.begin(f.s);
     c.arena.reserve(plan.words);
-    u64 *D = c.arena.take(bs * rl * dl * N);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
-    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw);
-    const size_t mark = c.arena.mark();
-    const LimbMap map = c.ct_map(L);
+    u64 *D = c.arena.take(bs * w.D), *tt = w.tt ? c.arena.take(bs * w.tt) : nullptr;
+    u64 *acc = c.arena.take(bs * w.acc), *base = c.arena.take(bs * 2 * pw);
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks || !w.c1n ? nullptr : c.arena.take(bs * pw);
+    f.carved(bs);
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
         const u64 nb = std::min(bs, batch - b0);
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
-        const KsPlan k = ks_plan(L, nb);
-        const KsArgs &a = k.a;
-        hoist_digits(c1, in.bstride, D, tt, k, s); // of this run of items, once
+        f.slab(nb);
+        f.digits(c1, in.bstride, tt, D, nb); // of this run of items, once
         // the extended-basis accumulators: every element other than 1, HOIST_MAX_ROT per launch
-        hoist_lt_chunks(elts, keys, plains, R, [&](const HoistLtArgs &h) { launch_hoist_lt(D, ckks ? c1 : nullptr, in.bstride, acc, a, h, s); });
-        // the base in NTT form: every element
-        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, a, s);
-        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, hoist_c1_in_digits(D, dl, N), polys, base, a, s);
-        if (!ckks) launch_ntt(base, c.d_desc, map, nb * polys * dl, c.logn, true, s);
-        hoist_lt_finish(any_rot, out, b0, acc, base, polys, mark, k, s); // every element is 1 (polys == 2): the base
-        stats::counter(stats::HOIST_LT_SLABS)++;
+        hoist_lt_chunks(elts, keys, plains, R, [&](const HoistLtArgs &h) { f.lt(D, c1, in.bstride, acc, h); });
+        // the base in NTT form, over the data limbs: every element
+        HoistC1 c1at{};
+        if (!ckks) {
+            hoist_c0_to_ntt(c0, in.bstride, c0n, f.kp.a, f.s);
+            c1at = f.c1_ntt(c1, in.bstride, D, c1n, any_one);
+        }
+        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, c1at, polys, base, f.kp.a, f.s);
+        if (!ckks) launch_ntt(base, c.d_desc, c.ct_map(L), nb * polys * L, c.logn, true, f.s);
+        u64 *dst = out.data + b0 * out.bstride;
+        if (!any_rot) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, f.s); // every element is 1 (polys == 2): the result is the base, no key read
+        else f.finish(dst, out.bstride, acc, KsBase{base, (u64)polys * pw, polys}, nb);
+        f.count_slab(HoistKs::LINEAR);
     }
 }
 
-// Baby-step / giant-step linear transform (no reference counterpart):
-//   out = sum_i galois_{G_i}(u_i),   u_i = sum_{j: plains[i * n_baby + j] != null} plains[i * n_baby + j] * galois_{g_j}(in)
-// u_i is what galois_plain_sum_hoisted returns for the present babies of row i (the same kernels and the same second half, run once over all the rows
-// of a chunk); the giants then cost one digit expansion, one key stream and -- all of them together -- one mod-down.  Babies and rows with no present
-// plaintext are skipped and their keys are not read.  The used rows run with the giants other than 1 first (the result does not depend on the order).
-// Scratch per item of a slab, in units of N words (dl = limbs, rl = dl + 1, w = min(16, used babies other than 1), n2' = used rows, gc = rows per chunk):
-//   rl dl [D] + dl [CKKS: c1 in coefficient form] + w 2 rl [W] + n2' 2 rl [accU] + dl [BFV / BGV: c0 in NTT form] + 2 rl [acc] + 2 dl [base]
-//   + gc (2 dl [baseU] + 2 dl [u] + rl dl [digits of u.c1] + dl [CKKS: u.c1 in coefficient form] + 2 dl + 4 [what a second half carves])
-// The units of plan_slabs are the rows (16 per chunk at the most).
-void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
-                                      const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s) {
-    check_ct(in);
+// The terms of a baby-step / giant-step transform: what is used and in which order.  Babies and rows with no present plaintext are skipped and their keys
+// are not read; the babies that are 1 enter the bases only; the used rows run with the giants other than 1 first (the result does not depend on the order)
+struct BsgsTerms {
+    std::vector<int> rot_babies, rows; // the used babies other than 1; the used rows
+    std::vector<char> row_rot;         // per entry of rows: the row has a present baby other than 1
+    u64 n_rot_rows = 0;                // the rows whose giant is not 1: they lead `rows`
+    bool any_one = false;              // some used baby is 1: the bases read c1
+};
+static BsgsTerms bsgs_terms(const Context &c, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts, const KsKey *giant_keys, int n_giant,
+                            const u64 *const *plains) {
     if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
         throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
     if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-    // unlike the other two calls: every element of both lists before any key
+    // unlike the other two calls: every element of both lists before any key, then the keys of the used elements only
     check_galois_elts(c, baby_elts, nullptr, n_baby, every_key);
     check_galois_elts(c, giant_elts, nullptr, n_giant, every_key);
     u64 used_babies = 0, used_rows = 0; // bit j / bit i: some plaintext of the column / of the row is present
@@ -932,48 +1034,68 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
     check_galois_elts(c, baby_elts, baby_keys, n_baby, [&](int j) { return used_babies >> j & 1; });
     if (!used_babies) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
     check_galois_elts(c, giant_elts, giant_keys, n_giant, [&](int i) { return used_rows >> i & 1; });
-    // what is used: the babies other than 1 (inner products; the babies that are 1 enter the base only), the rows with the giants other than 1 first
-    std::vector<int> rot_babies, rows;
+    BsgsTerms t;
     for (int j = 0; j < n_baby; j++)
-        if ((used_babies >> j & 1) && baby_elts[j] != 1) rot_babies.push_back(j);
+        if (used_babies >> j & 1) {
+            if (baby_elts[j] != 1) t.rot_babies.push_back(j);
+            else t.any_one = true;
+        }
     for (int pass = 0; pass < 2; pass++)
         for (int i = 0; i < n_giant; i++)
-            if ((used_rows >> i & 1) && (giant_elts[i] == 1) == (pass == 1)) rows.push_back(i);
-    const u64 n_rot_rows = (u64)std::count_if(rows.begin(), rows.end(), [&](int i) { return giant_elts[i] != 1; });
+            if ((used_rows >> i & 1) && (giant_elts[i] == 1) == (pass == 1)) {
+                t.rows.push_back(i);
+                t.n_rot_rows += pass == 0;
+            }
+    t.row_rot.assign(t.rows.size(), 0);
+    for (size_t r = 0; r < t.rows.size(); r++)
+        for (int j : t.rot_babies)
+            if (plains[(size_t)t.rows[r] * n_baby + j]) t.row_rot[r] = 1;
+    return t;
+}
+
+// Baby-step / giant-step linear transform:
+//   out = sum_i galois_{G_i}(u_i),   u_i = sum_{j: plains[i * n_baby + j] != null} plains[i * n_baby + j] * galois_{g_j}(in)
+// u_i is what the hoisted linear transform of the flavour returns for the present babies of row i (the same kernels and the same second half, run once over
+// the rows of a chunk); the giants then cost one digit expansion per row, one key stream and -- all of them together -- one mod-down.
+void Evaluator::hoist_bsgs(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                           const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words) {
+    check_ct(in);
+    const BsgsTerms t = bsgs_terms(c, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant, plains);
+    const std::vector<int> &rot_babies = t.rot_babies, &rows = t.rows;
+    f.admit(in.limbs);
     if (!hoist_operands("baby-step / giant-step transform", in, out, &plain_scale, batch, batch)) return;
     const int L = in.limbs;
-    const u64 N = c.N, dl = L, rl = dl + 1, pw = poly_words(c, L);
+    const u64 pw = poly_words(c, L);
     const bool ckks = c.scheme == SCHEME_CKKS;
     const u64 n2 = rows.size(), nrb = rot_babies.size(), wb = std::min<u64>(nrb, HOIST_MAX_ROT);
-    const u64 per_item = N * (rl * dl + (ckks ? dl : 0) + wb * 2 * rl + n2 * 2 * rl + (ckks ? 0 : dl) + 2 * rl + 2 * dl);
-    const u64 per_row_item = N * (2 * dl + 2 * dl + rl * dl + (ckks ? dl : 0) + 2 * dl + 4);
-    const SlabPlan plan = plan_slabs(scratch_limit_words, 16, per_item, per_row_item, batch, std::min<u64>(n2, HOIST_MAX_ROT), "scratch_limit_words is too small for one giant step of one ciphertext");
+    const HoistWords w = f.words((u64)L);
+    const SlabWords sw = bsgs_words(c, w, pw, nrb, n2);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, BSGS_BLOCKS, sw.per_item, sw.per_unit_item, batch, std::min<u64>(n2, HOIST_MAX_ROT),
+                                     "scratch_limit_words is too small for one giant step of one ciphertext");
     const u64 bs = plan.items, gc = plan.units;
+    f.open(L);
 
-    c.arena.begin(s);
+    c.arena.begin(f.s);
     c.arena.reserve(plan.words);
-    u64 *D = c.arena.take(bs * rl * dl * N);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *W = nrb ? c.arena.take(wb * bs * 2 * rl * N) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * 2 * rl * N) : nullptr;
-    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw);
-    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
+    u64 *D = c.arena.take(bs * w.D), *tt = w.tt ? c.arena.take(bs * w.tt) : nullptr;
+    u64 *W = nrb ? c.arena.take(wb * bs * w.acc) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * w.acc) : nullptr;
+    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks || !w.c1n ? nullptr : c.arena.take(bs * pw);
+    u64 *acc = c.arena.take(bs * w.acc), *base = c.arena.take(bs * 2 * pw);
     u64 *baseU = c.arena.take(gc * bs * 2 * pw), *U = nrb ? c.arena.take(gc * bs * 2 * pw) : baseU; // no baby other than 1: u is its base
-    u64 *DG = n_rot_rows ? c.arena.take(gc * bs * rl * dl * N) : nullptr, *ttG = n_rot_rows && ckks ? c.arena.take(gc * bs * dl * N) : nullptr;
-    const size_t mark = c.arena.mark();
-    const LimbMap map = c.ct_map(L);
+    u64 *DG = t.n_rot_rows ? c.arena.take(gc * bs * w.D) : nullptr, *ttG = t.n_rot_rows && w.tt ? c.arena.take(gc * bs * w.tt) : nullptr;
+    f.carved(gc * bs); // the rows of a chunk, then the result
     for (u64 b0 = 0; b0 < batch; b0 += bs) {
         const u64 nb = std::min(bs, batch - b0);
         const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
-        KsPlan k = ks_plan(L, nb);
-        KsArgs &a = k.a;
-        hoist_digits(c1, in.bstride, D, tt, k, s); // stage 1: of this run of items, once
+        f.slab(nb);
+        f.digits(c1, in.bstride, tt, D, nb); // stage 1: of this run of items, once
         // stages 2 and 3: the baby inner products, HOIST_MAX_ROT at a time, kept only until every row has taken its plaintext-weighted share of them
         for (u64 j0 = 0; j0 < nrb; j0 += HOIST_MAX_ROT) {
             HoistArgs hm;
             std::memset(&hm, 0, sizeof(hm));
             hm.rots = (u32)std::min<u64>(HOIST_MAX_ROT, nrb - j0);
             for (u32 j = 0; j < hm.rots; j++) { hm.elt[j] = baby_elts[rot_babies[j0 + j]]; hm.key[j] = baby_keys[rot_babies[j0 + j]].data; }
-            launch_hoist_mac(D, ckks ? c1 : nullptr, in.bstride, W, a, hm, s);
+            f.mac(D, c1, in.bstride, W, hm);
             for (u64 r0 = 0; r0 < n2; r0 += BSGS_MAX_ROWS) {
                 BsgsInnerArgs hi;
                 std::memset(&hi, 0, sizeof(hi));
@@ -983,47 +1105,110 @@ void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uin
                 for (u32 r = 0; r < hi.rows; r++)
                     for (u32 j = 0; j < hm.rots; j++)
                         if (const u64 *p = plains[(size_t)rows[r0 + r] * n_baby + rot_babies[j0 + j]]) { hi.pt[r][j] = p; hi.mask[r] |= 1u << j; any = true; }
-                if (any || !hi.accumulate) launch_bsgs_inner(W, accU, a, hi, s);
+                if (any || !hi.accumulate) f.inner(W, accU, hi);
             }
         }
-        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, a, s);
+        HoistC1 c1at{};
+        if (!ckks) {
+            hoist_c0_to_ntt(c0, in.bstride, c0n, f.kp.a, f.s);
+            c1at = f.c1_ntt(c1, in.bstride, D, c1n, t.any_one);
+        }
         bool acc_started = false;
         for (u64 i0 = 0; i0 < n2; i0 += gc) {
             const u64 gn = std::min(gc, n2 - i0);
-            // the bases of the rows, in NTT form, as galois_plain_sum_hoisted makes them: every present pair of the row, both polynomials
-            for (u64 ii = 0; ii < gn; ii++) hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, hoist_c1_in_digits(D, dl, N), 2, baseU + ii * nb * 2 * pw, a, s);
-            if (!ckks) launch_ntt(baseU, c.d_desc, map, gn * nb * 2 * dl, c.logn, true, s);
-            // u_i of the chunk: ONE second half over rows x items
-            if (nrb) {
-                CtBatch o = out;
-                o.data = U; o.bstride = 2 * pw;
-                a.batch = gn * nb;
-                c.arena.rewind(mark);
-                ks_acc_to_ct(o, accU + i0 * nb * 2 * rl * N, k, s, KsBase{baseU, 2 * pw, 2});
-                a.batch = nb;
+            // the bases of the rows, in NTT form, as the linear transform makes them: every present pair of the row, both polynomials
+            for (u64 ii = 0; ii < gn; ii++) hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, c1at, 2, baseU + ii * nb * 2 * pw, f.kp.a, f.s);
+            if (!ckks) launch_ntt(baseU, c.d_desc, c.ct_map(L), gn * nb * 2 * L, c.logn, true, f.s);
+            // u_i of the chunk: ONE second half over rows x items.  The u_i of a row whose only present babies are 1 is its base, as the linear transform
+            // returns it.  Where the flavour's second half over a zero accumulator stores the base, such a row rides along in the one wide launch; else
+            // (grouped: minus the overshoot, section 4.18) it is a copy, and the second half runs over the runs of rows between such rows
+            auto switched = [&](u64 r) { return f.zero_acc_is_base() || t.row_rot[r]; };
+            for (u64 r0 = 0; nrb && r0 < gn;) {
+                const bool rot = switched(i0 + r0);
+                u64 r1 = r0 + 1;
+                while (r1 < gn && switched(i0 + r1) == rot) r1++;
+                const u64 off = r0 * nb * 2 * pw;
+                if (rot) f.finish(U + off, 2 * pw, accU + (i0 + r0) * nb * w.acc, KsBase{baseU + off, 2 * pw, 2}, (r1 - r0) * nb);
+                else launch_copy_strided(baseU + off, 2 * pw, U + off, 2 * pw, 2 * pw, (r1 - r0) * nb, f.s);
+                r0 = r1;
             }
-            // stage 4: the digits of the u_i.c1 whose giant is not 1 (they lead the chunk), the giant sum and its base
+            // stage 4: the digits of the u_i.c1 whose giant is not 1 (they lead the chunk), each giant its own block; the giant sum and its base
             u64 gr = 0;
             while (gr < gn && giant_elts[rows[i0 + gr]] != 1) gr++;
             if (gr) {
-                hoist_digits(U + pw, 2 * pw, DG, ttG, ks_plan(L, gr * nb), s);
+                f.digits(U + pw, 2 * pw, ttG, DG, gr * nb);
                 HoistSumArgs hs;
                 std::memset(&hs, 0, sizeof(hs));
                 hs.rots = (u32)gr; hs.accumulate = acc_started ? 1 : 0;
-                hs.d_rstride = nb * rl * dl * N; hs.t_rstride = nb * 2 * pw;
+                hs.d_rstride = nb * w.D; hs.t_rstride = nb * 2 * pw;
                 for (u64 r = 0; r < gr; r++) { hs.elt[r] = giant_elts[rows[i0 + r]]; hs.key[r] = giant_keys[rows[i0 + r]].data; }
-                launch_hoist_sum(DG, ckks ? U + pw : nullptr, 2 * pw, acc, a, hs, s);
+                f.sum(DG, U + pw, 2 * pw, acc, hs);
                 acc_started = true;
             }
             BsgsBaseArgs hb;
             std::memset(&hb, 0, sizeof(hb));
             hb.rots = (u32)gn; hb.accumulate = i0 ? 1 : 0;
             for (u64 r = 0; r < gn; r++) hb.elt[r] = giant_elts[rows[i0 + r]];
-            launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, a, hb, s);
+            launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, f.kp.a, hb, f.s);
         }
-        hoist_lt_finish(acc_started, out, b0, acc, base, 2, mark, k, s); // every used giant is 1: the sum of the u_i, no second mod-down
-        stats::counter(stats::BSGS_SLABS)++;
+        u64 *dst = out.data + b0 * out.bstride;
+        if (!acc_started) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, f.s); // every used giant is 1: the sum of the u_i, no second mod-down
+        else f.finish(dst, out.bstride, acc, KsBase{base, 2 * pw, 2}, nb); // ONE mod-down for all giants
+        f.count_slab(HoistKs::BSGS);
     }
+}
+
+// the six calls: a flavour and its walk
+void Evaluator::apply_galois_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    HoistPerPrime f(*this, s);
+    hoist_rotations(f, in, out, elts, keys, R, batch, scratch_limit_words);
+}
+void Evaluator::apply_galois_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, int alpha, u64 batch, u64 scratch_limit_words,
+                                             hipStream_t s) {
+    HoistGrouped f(*this, alpha, s);
+    hoist_rotations(f, in, out, elts, keys, R, batch, scratch_limit_words);
+}
+void Evaluator::galois_plain_sum_hoisted(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
+                                         u64 scratch_limit_words, hipStream_t s) {
+    HoistPerPrime f(*this, s);
+    hoist_linear(f, in, out, elts, keys, plains, R, plain_scale, batch, scratch_limit_words);
+}
+void Evaluator::galois_plain_sum_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale,
+                                                 int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    HoistGrouped f(*this, alpha, s);
+    hoist_linear(f, in, out, elts, keys, plains, R, plain_scale, batch, scratch_limit_words);
+}
+void Evaluator::galois_plain_sum_bsgs(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                                      const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words, hipStream_t s) {
+    HoistPerPrime f(*this, s);
+    hoist_bsgs(f, in, out, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant, plains, plain_scale, batch, scratch_limit_words);
+}
+void Evaluator::galois_plain_sum_bsgs_grouped(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
+                                              const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, int alpha, u64 batch,
+                                              u64 scratch_limit_words, hipStream_t s) {
+    HoistGrouped f(*this, alpha, s);
+    hoist_bsgs(f, in, out, baby_elts, baby_keys, n_baby, giant_elts, giant_keys, n_giant, plains, plain_scale, batch, scratch_limit_words);
+}
+// what the grouped calls ask of the arena with everything in one slab (at most HOIST_MAX_ROT rotations / rows are held at a time)
+u64 Evaluator::apply_galois_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rots) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    const SlabWords sw = hoist_rot_words(ksg_hoist_words(c, (u64)limbs, (u64)alpha), poly_words(c, limbs));
+    return batch * sw.per_item + std::min<u64>(rots, HOIST_MAX_ROT) * batch * sw.per_unit_item + slab_slack(HOIST_BLOCKS);
+}
+u64 Evaluator::galois_plain_sum_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    return batch * hoist_lt_words(c, ksg_hoist_words(c, (u64)limbs, (u64)alpha), poly_words(c, limbs)).per_item + slab_slack(HOIST_BLOCKS);
+}
+u64 Evaluator::galois_plain_sum_bsgs_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rot_babies, u64 rows, u64 rows_per_chunk) const {
+    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
+    ksg_check_limbs(alpha, limbs);
+    if (rot_babies > 64 || rows < 1 || rows > 64 || rows_per_chunk < 1)
+        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
+    const SlabWords sw = bsgs_words(c, ksg_hoist_words(c, (u64)limbs, (u64)alpha), poly_words(c, limbs), rot_babies, rows);
+    const u64 gc = std::min<u64>(std::min<u64>(rows_per_chunk, rows), HOIST_MAX_ROT);
+    return batch * sw.per_item + gc * batch * sw.per_unit_item + slab_slack(BSGS_BLOCKS);
 }
 
 void Evaluator::transform_to_ntt(CtBatch &ct, u64 batch, hipStream_t s) { // evaluator_cuda.cu:1950-1985
@@ -1812,272 +1997,6 @@ void Evaluator::apply_key_switching_grouped(CtBatch &ct, const KsKey &key, int a
     if (ct.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted.size() != 2");
     const u64 pw = poly_words(c, ct.limbs);
     switch_key_grouped(ct, ct.data + pw, ct.bstride, key, alpha, batch, scratch_limit_words, s, KsBase{ct.data, ct.bstride});
-}
-
-// ---- hoisted calls with grouped keys (no reference counterpart) ----
-// Scratch in units of N words (rl = dl + alpha, d = ceil(dl / alpha)).  Rotations, per item: dl [CKKS: c1 in coefficient form] + d rl [D]; per (rotation,
-// item): 2 rl [acc] + dl [sigma(c0)] + CKKS: 2 alpha [the special limbs in coefficient form] + 2 dl [the correction]
-static void ksg_hoist_words(const Context &c, u64 dl, u64 alpha, u64 &per_item, u64 &per_rot_item) {
-    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
-    per_item = c.N * (ckks * dl + d * rl);
-    per_rot_item = c.N * (2 * rl + dl + ckks * (2 * alpha + 2 * dl));
-}
-// Linear transform, per item only: dl [CKKS: c1 in coefficient form] + d rl [D] + 2 rl [acc] + 2 dl [base] + BFV / BGV: 2 dl [c0 and c1 in NTT form]
-// + CKKS: 2 alpha + 2 dl [as above]
-static u64 ksg_hoist_lt_words(const Context &c, u64 dl, u64 alpha) {
-    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS;
-    return c.N * (ckks * dl + d * rl + 2 * rl + 2 * dl + (1 - ckks) * 2 * dl + ckks * (2 * alpha + 2 * dl));
-}
-static const u64 KSG_HOIST_BLOCKS = 8;
-u64 Evaluator::apply_galois_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rots) const {
-    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
-    ksg_check_limbs(alpha, limbs);
-    u64 per_item, per_rot_item;
-    ksg_hoist_words(c, (u64)limbs, (u64)alpha, per_item, per_rot_item);
-    return batch * per_item + std::min<u64>(rots, HOIST_MAX_ROT) * batch * per_rot_item + slab_slack(KSG_HOIST_BLOCKS);
-}
-u64 Evaluator::galois_plain_sum_hoisted_grouped_scratch_words(int limbs, int alpha, u64 batch) const {
-    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
-    ksg_check_limbs(alpha, limbs);
-    return batch * ksg_hoist_lt_words(c, (u64)limbs, (u64)alpha) + slab_slack(KSG_HOIST_BLOCKS);
-}
-void Evaluator::apply_galois_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, int alpha, u64 batch, u64 scratch_limit_words,
-                                             hipStream_t s) {
-    check_ct(in);
-    if (R < 1 || !elts || !keys) throw Error(ST_INVALID_ARGUMENT, "hoisted rotations take at least one Galois element");
-    check_galois_elts(c, elts, keys, R, every_key);
-    ksg_check_limbs(alpha, in.limbs);
-    if (!hoist_operands("hoisted rotations", in, out, nullptr, (u64)R * batch, batch)) return; // the destination holds R batches back to back
-    const int L = in.limbs;
-    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
-    const bool ckks = c.scheme == SCHEME_CKKS;
-    u64 per_item, per_rot_item;
-    ksg_hoist_words(c, dl, al, per_item, per_rot_item);
-    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_HOIST_BLOCKS, per_item, per_rot_item, batch, std::min<u64>(R, HOIST_MAX_ROT),
-                                     "scratch_limit_words is too small for one rotation of one ciphertext");
-    const u64 bs = plan.items, rs = plan.units;
-    if (rs > 1 && bs != batch) throw Error(ST_LOGIC_ERROR, "hoisted rotations: a slab of several rotations must span the batch"); // the widened second half below
-    KsgPlan k = ksg_plan(alpha, L);
-
-    c.arena.begin(s);
-    c.arena.reserve(plan.words);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(rs * bs * 2 * rl * N), *sig0 = c.arena.take(rs * bs * pw);
-    u64 *last = ckks ? c.arena.take(rs * bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(rs * bs * 2 * dl * N) : nullptr;
-    for (u64 b0 = 0; b0 < batch; b0 += bs) {
-        const u64 nb = std::min(bs, batch - b0);
-        k.a.batch = nb;
-        ksg_target_to_digits(in.data + b0 * in.bstride + pw, in.bstride, tt, D, k, s); // the digit prologue of this run of items, once
-        hoist_rotation_chunks(c, in, out, elts, keys, R, batch, b0, nb, rs, sig0, s, [&](const HoistArgs &h, CtBatch &o) {
-            launch_ksg_hoist_mac(D, acc, k.a, h, s);
-            // the second half over rots * nb items at once: item r * nb + b accumulates onto (sigma_r(c0_b), 0)
-            k.a.batch = (u64)h.rots * nb;
-            ksg_acc_to_ct(o.data, out.bstride, acc, last, corr, k, s, KsBase{sig0, pw});
-            k.a.batch = nb;
-            stats::counter(stats::GROUPED_HOIST_SLABS)++;
-        });
-    }
-}
-void Evaluator::galois_plain_sum_hoisted_grouped(const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale,
-                                                 int alpha, u64 batch, u64 scratch_limit_words, hipStream_t s) {
-    check_ct(in);
-    if (R < 1 || !elts || !keys || !plains) throw Error(ST_INVALID_ARGUMENT, "hoisted linear transform takes at least one Galois element");
-    bool any_rot = false, any_one = false;
-    for (int r = 0; r < R; r++) { // one term at a time, as galois_plain_sum_hoisted
-        check_galois_elts(c, elts + r, keys + r, 1, every_key);
-        if (!plains[r]) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
-        (elts[r] == 1 ? any_one : any_rot) = true;
-    }
-    ksg_check_limbs(alpha, in.limbs);
-    if (!hoist_operands("hoisted linear transform", in, out, &plain_scale, batch, batch)) return;
-    const int L = in.limbs;
-    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
-    const bool ckks = c.scheme == SCHEME_CKKS;
-    const int polys = any_one ? 2 : 1;
-    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_HOIST_BLOCKS, ksg_hoist_lt_words(c, dl, al), 0, batch, 1, "scratch_limit_words is too small for one ciphertext");
-    const u64 bs = plan.items;
-    KsgPlan k = ksg_plan(alpha, L);
-
-    c.arena.begin(s);
-    c.arena.reserve(plan.words);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *D = c.arena.take(bs * d * rl * N), *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
-    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks ? nullptr : c.arena.take(bs * pw);
-    u64 *last = ckks ? c.arena.take(bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(bs * 2 * dl * N) : nullptr;
-    for (u64 b0 = 0; b0 < batch; b0 += bs) {
-        const u64 nb = std::min(bs, batch - b0);
-        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
-        k.a.batch = nb;
-        const KsPlan kp = ks_plan(L, nb); // what the base of section 4.11 reads: the data primes
-        ksg_target_to_digits(c1, in.bstride, tt, D, k, s); // the digit prologue of this run of items, once
-        hoist_lt_chunks(elts, keys, plains, R, [&](const HoistLtArgs &h) { launch_ksg_hoist_lt(D, acc, k.a, h, s); });
-        // the base in NTT form, over the data limbs: every element.  The rows of D are grouped, so c1 in NTT form (element 1 only) is made next to c0
-        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, kp.a, s);
-        if (!ckks && any_one) hoist_c0_to_ntt(c1, in.bstride, c1n, kp.a, s);
-        hoist_lt_base(plains, elts, R, c0, in.bstride, c0n, HoistC1{c1n, pw, N}, polys, base, kp.a, s);
-        if (!ckks) launch_ntt(base, c.d_desc, k.tmap, nb * polys * dl, c.logn, true, s);
-        u64 *dst = out.data + b0 * out.bstride;
-        if (!any_rot) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, s); // every element is 1 (polys == 2): the result is the base, no key read
-        else ksg_acc_to_ct(dst, out.bstride, acc, last, corr, k, s, KsBase{base, (u64)polys * pw, polys});
-        stats::counter(stats::GROUPED_HOIST_LT_SLABS)++;
-    }
-}
-
-// ---- baby-step / giant-step linear transform with grouped keys (no reference counterpart) ----
-// The walk of galois_plain_sum_bsgs over the grouped halves of section 4.16: u_i is byte for byte what galois_plain_sum_hoisted_grouped returns for the
-// present babies of row i; the giants cost one digit prologue per row, one gathered inner product over d digits and -- all of them together -- one
-// mod-down by the alpha special primes.  Scratch in units of N words (rl = dl + alpha, d = ceil(dl / alpha), w = min(16, used babies other than 1),
-// n2' = used rows, gc = rows per chunk).  Per item of a slab:
-//   dl [CKKS: c1 in coefficient form] + d rl [D] + w 2 rl [W] + n2' 2 rl [accU] + 2 dl [BFV / BGV: c0 and c1 in NTT form] + 2 rl [acc] + 2 dl [base]
-// and per (row of a chunk, item):
-//   2 dl [baseU] + 2 dl [u] + d rl [the digits of u.c1] + CKKS: dl [u.c1 in coefficient form] + 2 alpha [the special limbs] + 2 dl [the correction]
-// The units of plan_slabs are the rows (16 per chunk at the most).
-static void ksg_bsgs_words(const Context &c, u64 dl, u64 alpha, u64 rot_babies, u64 rows, u64 &per_item, u64 &per_row_item) {
-    const u64 rl = dl + alpha, d = (dl + alpha - 1) / alpha, ckks = c.scheme == SCHEME_CKKS, w = std::min<u64>(rot_babies, HOIST_MAX_ROT);
-    per_item = c.N * (ckks * dl + d * rl + w * 2 * rl + rows * 2 * rl + (1 - ckks) * 2 * dl + 2 * rl + 2 * dl);
-    per_row_item = c.N * (2 * dl + 2 * dl + d * rl + ckks * (dl + 2 * alpha + 2 * dl));
-}
-static const u64 KSG_BSGS_BLOCKS = 16;
-u64 Evaluator::galois_plain_sum_bsgs_grouped_scratch_words(int limbs, int alpha, u64 batch, u64 rot_babies, u64 rows, u64 rows_per_chunk) const {
-    if (limbs < 1) throw Error(ST_INVALID_ARGUMENT, "operand has more limbs than the grouped key serves");
-    ksg_check_limbs(alpha, limbs);
-    if (rot_babies > 64 || rows < 1 || rows > 64 || rows_per_chunk < 1)
-        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-    u64 per_item, per_row_item;
-    ksg_bsgs_words(c, (u64)limbs, (u64)alpha, rot_babies, rows, per_item, per_row_item);
-    const u64 gc = std::min<u64>(std::min<u64>(rows_per_chunk, rows), HOIST_MAX_ROT);
-    return batch * per_item + gc * batch * per_row_item + slab_slack(KSG_BSGS_BLOCKS);
-}
-void Evaluator::galois_plain_sum_bsgs_grouped(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
-                                              const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, int alpha, u64 batch,
-                                              u64 scratch_limit_words, hipStream_t s) {
-    check_ct(in);
-    if (n_baby < 1 || n_giant < 1 || !baby_elts || !baby_keys || !giant_elts || !giant_keys || !plains)
-        throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one baby and one giant element");
-    if (n_baby > 64 || n_giant > 64) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at most 64 baby and 64 giant elements");
-    // as galois_plain_sum_bsgs: every element of both lists before any key, the keys of the used elements only
-    check_galois_elts(c, baby_elts, nullptr, n_baby, every_key);
-    check_galois_elts(c, giant_elts, nullptr, n_giant, every_key);
-    u64 used_babies = 0, used_rows = 0; // bit j / bit i: some plaintext of the column / of the row is present
-    for (int i = 0; i < n_giant; i++)
-        for (int j = 0; j < n_baby; j++)
-            if (plains[(size_t)i * n_baby + j]) { used_babies |= u64(1) << j; used_rows |= u64(1) << i; }
-    check_galois_elts(c, baby_elts, baby_keys, n_baby, [&](int j) { return used_babies >> j & 1; });
-    if (!used_babies) throw Error(ST_INVALID_ARGUMENT, "baby-step / giant-step transform takes at least one plaintext");
-    check_galois_elts(c, giant_elts, giant_keys, n_giant, [&](int i) { return used_rows >> i & 1; });
-    std::vector<int> rot_babies, rows;
-    bool any_one = false; // some used baby is 1: the bases read c1
-    for (int j = 0; j < n_baby; j++)
-        if (used_babies >> j & 1) {
-            if (baby_elts[j] != 1) rot_babies.push_back(j);
-            else any_one = true;
-        }
-    for (int pass = 0; pass < 2; pass++)
-        for (int i = 0; i < n_giant; i++)
-            if ((used_rows >> i & 1) && (giant_elts[i] == 1) == (pass == 1)) rows.push_back(i);
-    const u64 n_rot_rows = (u64)std::count_if(rows.begin(), rows.end(), [&](int i) { return giant_elts[i] != 1; });
-    std::vector<char> row_rot(rows.size(), 0); // the row has a present baby other than 1
-    for (size_t r = 0; r < rows.size(); r++)
-        for (int j : rot_babies)
-            if (plains[(size_t)rows[r] * n_baby + j]) row_rot[r] = 1;
-    ksg_check_limbs(alpha, in.limbs);
-    if (!hoist_operands("baby-step / giant-step transform", in, out, &plain_scale, batch, batch)) return;
-    const int L = in.limbs;
-    const u64 N = c.N, dl = L, al = alpha, rl = dl + al, d = (dl + al - 1) / al, pw = poly_words(c, L);
-    const bool ckks = c.scheme == SCHEME_CKKS;
-    const u64 n2 = rows.size(), nrb = rot_babies.size(), wb = std::min<u64>(nrb, HOIST_MAX_ROT);
-    u64 per_item, per_row_item;
-    ksg_bsgs_words(c, dl, al, nrb, n2, per_item, per_row_item);
-    const SlabPlan plan = plan_slabs(scratch_limit_words, KSG_BSGS_BLOCKS, per_item, per_row_item, batch, std::min<u64>(n2, HOIST_MAX_ROT),
-                                     "scratch_limit_words is too small for one giant step of one ciphertext");
-    const u64 bs = plan.items, gc = plan.units;
-    KsgPlan k = ksg_plan(alpha, L);
-
-    c.arena.begin(s);
-    c.arena.reserve(plan.words);
-    u64 *tt = ckks ? c.arena.take(bs * dl * N) : nullptr;
-    u64 *D = c.arena.take(bs * d * rl * N);
-    u64 *W = nrb ? c.arena.take(wb * bs * 2 * rl * N) : nullptr, *accU = nrb ? c.arena.take(n2 * bs * 2 * rl * N) : nullptr;
-    u64 *c0n = ckks ? nullptr : c.arena.take(bs * pw), *c1n = ckks ? nullptr : c.arena.take(bs * pw);
-    u64 *acc = c.arena.take(bs * 2 * rl * N), *base = c.arena.take(bs * 2 * pw);
-    u64 *baseU = c.arena.take(gc * bs * 2 * pw), *U = nrb ? c.arena.take(gc * bs * 2 * pw) : baseU; // no baby other than 1: u is its base
-    u64 *DG = n_rot_rows ? c.arena.take(gc * bs * d * rl * N) : nullptr, *ttG = n_rot_rows && ckks ? c.arena.take(gc * bs * dl * N) : nullptr;
-    u64 *last = ckks ? c.arena.take(gc * bs * 2 * al * N) : nullptr, *corr = ckks ? c.arena.take(gc * bs * 2 * dl * N) : nullptr; // of a chunk's rows, then of the result
-    for (u64 b0 = 0; b0 < batch; b0 += bs) {
-        const u64 nb = std::min(bs, batch - b0);
-        const u64 *c0 = in.data + b0 * in.bstride, *c1 = c0 + pw;
-        const KsPlan kp = ks_plan(L, nb); // what the bases read: the data primes
-        k.a.batch = nb;
-        ksg_target_to_digits(c1, in.bstride, tt, D, k, s); // stage 1: the digit prologue of this run of items, once
-        // stages 2 and 3: the baby inner products, HOIST_MAX_ROT at a time, kept only until every row has taken its plaintext-weighted share of them
-        for (u64 j0 = 0; j0 < nrb; j0 += HOIST_MAX_ROT) {
-            HoistArgs hm;
-            std::memset(&hm, 0, sizeof(hm));
-            hm.rots = (u32)std::min<u64>(HOIST_MAX_ROT, nrb - j0);
-            for (u32 j = 0; j < hm.rots; j++) { hm.elt[j] = baby_elts[rot_babies[j0 + j]]; hm.key[j] = baby_keys[rot_babies[j0 + j]].data; }
-            launch_ksg_hoist_mac(D, W, k.a, hm, s);
-            for (u64 r0 = 0; r0 < n2; r0 += BSGS_MAX_ROWS) {
-                BsgsInnerArgs hi;
-                std::memset(&hi, 0, sizeof(hi));
-                hi.rows = (u32)std::min<u64>(BSGS_MAX_ROWS, n2 - r0);
-                hi.babies = hm.rots; hi.row0 = (u32)r0; hi.accumulate = j0 ? 1 : 0;
-                bool any = false;
-                for (u32 r = 0; r < hi.rows; r++)
-                    for (u32 j = 0; j < hm.rots; j++)
-                        if (const u64 *p = plains[(size_t)rows[r0 + r] * n_baby + rot_babies[j0 + j]]) { hi.pt[r][j] = p; hi.mask[r] |= 1u << j; any = true; }
-                if (any || !hi.accumulate) launch_ksg_bsgs_inner(W, accU, k.a, hi, s);
-            }
-        }
-        if (!ckks) hoist_c0_to_ntt(c0, in.bstride, c0n, kp.a, s);
-        if (!ckks && any_one) hoist_c0_to_ntt(c1, in.bstride, c1n, kp.a, s);
-        bool acc_started = false;
-        for (u64 i0 = 0; i0 < n2; i0 += gc) {
-            const u64 gn = std::min(gc, n2 - i0);
-            // the bases of the rows, as galois_plain_sum_hoisted_grouped makes them: every present pair of the row, both polynomials
-            for (u64 ii = 0; ii < gn; ii++)
-                hoist_lt_base(plains + (size_t)rows[i0 + ii] * n_baby, baby_elts, n_baby, c0, in.bstride, c0n, HoistC1{c1n, pw, N}, 2, baseU + ii * nb * 2 * pw, kp.a, s);
-            if (!ckks) launch_ntt(baseU, c.d_desc, k.tmap, gn * nb * 2 * dl, c.logn, true, s);
-            // u_i of the chunk: ONE second half over rows x items.  A row whose only present babies are 1 takes none: its u_i is its base, as
-            // galois_plain_sum_hoisted_grouped returns it (the grouped mod-down of a zero accumulator is minus its overshoot, not zero: section 4.18),
-            // so the second half runs over the runs of rows that have a baby other than 1 -- one run, unless such a row lies between them
-            for (u64 r0 = 0; nrb && r0 < gn;) {
-                const bool rot = row_rot[i0 + r0];
-                u64 r1 = r0 + 1;
-                while (r1 < gn && row_rot[i0 + r1] == rot) r1++;
-                const u64 off = r0 * nb * 2 * pw;
-                if (rot) {
-                    k.a.batch = (r1 - r0) * nb;
-                    ksg_acc_to_ct(U + off, 2 * pw, accU + (i0 + r0) * nb * 2 * rl * N, last, corr, k, s, KsBase{baseU + off, 2 * pw, 2});
-                    k.a.batch = nb;
-                } else launch_copy_strided(baseU + off, 2 * pw, U + off, 2 * pw, 2 * pw, (r1 - r0) * nb, s);
-                r0 = r1;
-            }
-            // stage 4: the digits of the u_i.c1 whose giant is not 1 (they lead the chunk), each giant its own block; the giant sum and its base
-            u64 gr = 0;
-            while (gr < gn && giant_elts[rows[i0 + gr]] != 1) gr++;
-            if (gr) {
-                k.a.batch = gr * nb;
-                ksg_target_to_digits(U + pw, 2 * pw, ttG, DG, k, s);
-                k.a.batch = nb;
-                HoistSumArgs hs;
-                std::memset(&hs, 0, sizeof(hs));
-                hs.rots = (u32)gr; hs.accumulate = acc_started ? 1 : 0;
-                hs.d_rstride = nb * d * rl * N;
-                for (u64 r = 0; r < gr; r++) { hs.elt[r] = giant_elts[rows[i0 + r]]; hs.key[r] = giant_keys[rows[i0 + r]].data; }
-                launch_ksg_hoist_sum(DG, acc, k.a, hs, s);
-                acc_started = true;
-            }
-            BsgsBaseArgs hb;
-            std::memset(&hb, 0, sizeof(hb));
-            hb.rots = (u32)gn; hb.accumulate = i0 ? 1 : 0;
-            for (u64 r = 0; r < gn; r++) hb.elt[r] = giant_elts[rows[i0 + r]];
-            launch_bsgs_base(ckks, U, nb * 2 * pw, 2 * pw, base, 2 * pw, kp.a, hb, s);
-        }
-        u64 *dst = out.data + b0 * out.bstride;
-        if (!acc_started) launch_copy_strided(base, 2 * pw, dst, out.bstride, 2 * pw, nb, s); // every used giant is 1: the sum of the u_i, no second mod-down
-        else ksg_acc_to_ct(dst, out.bstride, acc, last, corr, k, s, KsBase{base, 2 * pw, 2}); // ONE mod-down by all special primes for all giants
-        stats::counter(stats::GROUPED_BSGS_SLABS)++;
-    }
 }
 
 // negacyclicShift (evaluator_cuda.cu:2342-2351): every limb of every polynomial is multiplied by x^shift

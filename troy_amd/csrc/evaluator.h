@@ -138,11 +138,9 @@ public:
     // the operand has at most K - alpha limbs.  u_i is byte for byte what galois_plain_sum_hoisted_grouped returns for row i; the giants share one mod-down
     // by all special primes.  Refuses what galois_plain_sum_bsgs refuses, with its messages, and what the grouped calls refuse.  The result depends on
     // the set of rows only (not on their order, the order of the babies, the batch size or the scratch limit); at alpha == 1 with the per-prime keys it
-    // stores the bytes of galois_plain_sum_bsgs.  Scratch, in units of N words (rl = limbs + alpha, d = ceil(limbs / alpha), w = min(16, rot_babies)):
-    //   per item:          limbs [CKKS] + d rl + w 2 rl + rows 2 rl + 2 limbs [BFV / BGV] + 2 rl + 2 limbs
-    //   per (row, item):   4 limbs + d rl + CKKS: 3 limbs + 2 alpha
-    // The query returns batch (per item + min(rows_per_chunk, rows, 16) per (row, item)) + slack: what the call asks of the arena with the whole batch in
-    // one slab and that many rows per chunk (rot_babies: the used babies other than 1; rows: the rows with a present plaintext).  Counter: GROUPED_BSGS_SLABS.
+    // stores the bytes of galois_plain_sum_bsgs.  Scratch: bsgs_words over the grouped flavour's words (evaluator.cpp).  The query returns
+    // batch (per item + min(rows_per_chunk, rows, 16) per (row, item)) + slack: what the call asks of the arena with the whole batch in one slab and that
+    // many rows per chunk (rot_babies: the used babies other than 1; rows: the rows with a present plaintext).  Counter: GROUPED_BSGS_SLABS.
     void galois_plain_sum_bsgs_grouped(const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts,
                                        const KsKey *giant_keys, int n_giant, const u64 *const *plains, double plain_scale, int alpha, u64 batch,
                                        u64 scratch_limit_words, hipStream_t s);
@@ -211,9 +209,16 @@ private:
     KsgPlan ksg_plan(int alpha, int limbs);
     void ksg_target_to_digits(const u64 *target, u64 t_bstride, u64 *tt, u64 *D, const KsgPlan &k, hipStream_t s);
     void ksg_acc_to_ct(u64 *dst, u64 ct_bstride, u64 *acc, u64 *last, u64 *corr, const KsgPlan &k, hipStream_t s, const KsBase &base);
-    // what the hoisted calls share, each next to its first user in evaluator.cpp:
-    // the digits of the c1 of k.a.batch items (stride bstride) into D; tt: room for c1 in coefficient form (CKKS)
-    void hoist_digits(const u64 *c1, u64 bstride, u64 *D, u64 *tt, const KsPlan &k, hipStream_t s);
+    // The hoisted calls: one host-side walk per call, written once over a flavour of key switching (HoistKs, evaluator.cpp) --
+    // per-prime, over the halves of switch_key, or grouped, over those of switch_key_grouped.  The six public calls build their flavour and run the walk.
+    struct HoistKs;
+    struct HoistPerPrime;
+    struct HoistGrouped;
+    void hoist_rotations(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, int R, u64 batch, u64 scratch_limit_words);
+    void hoist_linear(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *elts, const KsKey *keys, const u64 *const *plains, int R, double plain_scale, u64 batch,
+                      u64 scratch_limit_words);
+    void hoist_bsgs(HoistKs &f, const CtBatch &in, CtBatch &out, const uint32_t *baby_elts, const KsKey *baby_keys, int n_baby, const uint32_t *giant_elts, const KsKey *giant_keys,
+                    int n_giant, const u64 *const *plains, double plain_scale, u64 batch, u64 scratch_limit_words);
     // the checks of a size-2 operand and its destination of out_items items, and the output's metadata; plain_scale: null for plain rotations.
     // `what` names the call in the messages.  False: the batch is empty, nothing to do
     bool hoist_operands(const char *what, const CtBatch &in, CtBatch &out, const double *plain_scale, u64 out_items, u64 batch) const;
@@ -221,8 +226,6 @@ private:
     // dst [k.a.batch][polys][dl][N] = sum over the non-null plains[i] of plains[i] * galois_{elts[i]}(c0 and, polys == 2, c1), in NTT form
     void hoist_lt_base(const u64 *const *plains, const uint32_t *elts, int n, const u64 *c0, u64 bstride, const u64 *c0n, const HoistC1 &c1n, int polys, u64 *dst, const KsArgs &a,
                        hipStream_t s);
-    // the result of a slab of a linear transform from item b0 of out on: the base itself (no element other than 1) or the second half over acc onto the base
-    void hoist_lt_finish(bool switched, const CtBatch &out, u64 b0, u64 *acc, u64 *base, int polys, size_t mark, const KsPlan &k, hipStream_t s);
     void check_product_form(bool a_ntt, bool b_ntt) const; // the form a product of the scheme takes its two operands in
     bool scale_ok(double scale, int limbs) const;
     void mod_switch_scale(const CtBatch &in, CtBatch &out, u64 batch, hipStream_t s);
