@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -399,6 +399,32 @@ int troyhip_pack_lwes(troyhip_context *ctx, const uint64_t *c1, const uint64_t *
                       const uint32_t *key_elts, const uint64_t *const *keys, int n_keys, troyhip_ct *out, uint64_t batch, uint64_t scratch_limit_words, void *stream);
 /* the arena words troyhip_pack_lwes asks for when every step runs as one chunk: a host-only function of (limbs, count, batch) */
 int troyhip_pack_lwes_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, uint64_t *words);
+/* ---- Oblivious expansion, the opposite direction of troyhip_pack_lwes (no reference counterpart).  BFV / BGV, size 2, coefficient
+ * form, any data level.  Stream-ordered; nothing is read back. ---- */
+/* One batch of ciphertexts, item b encrypting a_0 + a_1 x + .. + a_(N-1) x^(N-1), into `count` batches: with m = 2^ceil(log2 count), out item r * batch + b
+ * (r < count) decrypts to sum_k a_(r + k m) x^(k m) of in item b -- a_r in its constant coefficient, and a_r alone at count == N.  The operand is multiplied by
+ * m^-1 mod q first, so its own noise is not amplified; the key-switch noise of a layer is doubled by each later layer.  Level, scale and correction factor
+ * are the operand's; count == 1 is a copy.  Every limb equals the composition of troyhip_divide_by_poly_modulus_degree (mul = N / m) and, per layer
+ * j = 0 .. log2 m - 1 with s = 2^j and g = (N >> j) + 1, K = troyhip_apply_galois(c, g), c + K (troyhip_add) and x^(2N - s) (c - K) (troyhip_sub,
+ * troyhip_negacyclic_shift) for every node c -- with ONE pre-pass launch, ONE key switch and ONE post-pass launch per layer over all (node, item) units, so
+ * the key of a layer is streamed once; a node past the count is never formed.  keys[i] is the Galois key of element key_elts[i]; the elements 2^k + 1,
+ * k = log2 N - log2 m + 1 .. log2 N, are looked up ("Galois key not present").  out->data, ->batch_stride are INPUTS: count dense batches back to back, item
+ * r * batch + b at out->data + (r * batch + b) * batch_stride, sharing no word with the operand; the call sets the other fields of *out.  The destination is
+ * the only node store: no second buffer of its size is taken.  The arena request stays under scratch_limit_words (0: 2^28 words): a layer that does not fit
+ * runs in chunks of units, and the result does not depend on the limit or on the batch size; below one unit
+ * (troyhip_expand_coefficients_scratch_words(.., 1, 1, ..)) the call is refused.  1 <= count <= N.  CKKS is TROYHIP_LOGIC_ERROR "unsupported scheme"; an
+ * operand in NTT form or of another size is refused.  Counters "expand_key_switches", "expand_chunks". */
+int troyhip_expand_coefficients(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, uint64_t count, const uint32_t *key_elts, const uint64_t *const *keys,
+                                int n_keys, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* troyhip_expand_coefficients with grouped keys (no reference counterpart; DESIGN.md sections 4.16 and 4.19): every key holds grouped digits over
+ * `special_primes` special primes and the operand has at most K - special_primes limbs ("operand has more limbs than the grouped key serves").  The same
+ * decryption law -- out item r * batch + b decrypts to sum_k a_(r + k m) x^(k m) -- and the same composition, limb for limb, with
+ * troyhip_apply_galois_grouped in the place of troyhip_apply_galois.  special_primes == 1 with per-prime keys: the bytes of troyhip_expand_coefficients. */
+int troyhip_expand_coefficients_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, uint64_t count, const uint32_t *key_elts, const uint64_t *const *keys,
+                                        int n_keys, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* the arena words the two calls above ask for when every layer runs as one chunk (no reference counterpart): a host-only function of (limbs, count, batch)
+ * and the kind of key -- special_primes == 0: per-prime keys.  (limbs, 1, 1) is one unit, the least a call accepts as its limit. */
+int troyhip_expand_coefficients_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, int special_primes, uint64_t *words);
 /* ---- DecryptorCuda::decrypt (src/decryptor_cuda.cu:61-330; dotProductCtSkArray + decryptScaleAndRound / decryptModt,
  * src/utils/rns_cuda.cu:510-621), SURVEY 8-f3.  secret_key: device [K][N] (NTT form, src/secretkey.h).  plain_out (device):
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */

@@ -1156,6 +1156,14 @@ public:
         for (size_t n = c_.polyModulusDegree(); n >= 2; n >>= 1) elts.push_back((uint32_t)(n + 1));
         return elts;
     }
+    // the ceil(log2 count) keys Evaluator::expandCoefficients(.., count, ..) needs: X -> X^((N >> j) + 1) for the layers j = 0, 1, ..
+    std::vector<uint32_t> expansionElts(size_t count) const {
+        const size_t N = c_.polyModulusDegree();
+        if (count < 1 || count > N) throw std::invalid_argument("expand_coefficients: count must be 1 .. N");
+        std::vector<uint32_t> elts;
+        for (size_t j = 0; (size_t(1) << j) < count; j++) elts.push_back((uint32_t)((N >> j) + 1));
+        return elts;
+    }
 private:
     std::vector<uint32_t> eltsOfSteps(const std::vector<int> &steps) const {
         std::vector<uint32_t> elts;
@@ -2708,6 +2716,50 @@ public:
         check(troyhip_copy_h2d(b.c0_.get(), c0.data(), c0.size() * 8, nullptr));
         check(troyhip_stream_synchronize(nullptr)); // c0 is a local: the copy has read it before it goes
         return packLWEs(b, automorphism_keys);
+    }
+    // Oblivious expansion, the opposite direction (troyhip_expand_coefficients / _grouped; the reference has no such call): result r,
+    // r < count, encrypts coefficient r of `a` in its constant coefficient -- it decrypts to sum_k a_(r + k m) x^(k m), m = 2^ceil(log2 count), a_r alone at
+    // count == N.  One key switch per layer of the tree.  BFV / BGV, size 2; gk holds the keys of KeyGenerator::expansionElts(count), per-prime or with
+    // grouped digits (gk.specialPrimes()); the library names a missing one.  Every limb equals the composition of divideByPolyModulusDegreeInplace,
+    // applyGalois, add, sub and negacyclicShift.
+    std::vector<Ciphertext> expandCoefficients(const Ciphertext &a, size_t count, const GaloisKeys &gk) const {
+        std::vector<std::vector<Ciphertext>> r = expandCoefficientsBatch(std::vector<const Ciphertext *>{&a}, count, gk);
+        std::vector<Ciphertext> out;
+        for (auto &v : r) out.push_back(std::move(v[0]));
+        return out;
+    }
+    // over a batch: result[r][b] = coefficient r of item b; the count x batch results are members of one slab (count dense batches back to back)
+    std::vector<std::vector<Ciphertext>> expandCoefficientsBatch(const std::vector<const Ciphertext *> &a, size_t count, const GaloisKeys &gk) const {
+        const size_t N = c_.polyModulusDegree();
+        if (count < 1 || count > N) throw std::invalid_argument("expand_coefficients: count must be 1 .. N");
+        if (a.empty()) return std::vector<std::vector<Ciphertext>>(count);
+        const bool grouped = gk.specialPrimes() != 0;
+        std::vector<uint32_t> elts;
+        std::vector<const uint64_t *> keys;
+        for (size_t d = 2; d <= N; d <<= 1) {
+            const uint32_t elt = (uint32_t)(d + 1);
+            if (!gk.hasKey(elt)) continue;
+            elts.push_back(elt);
+            keys.push_back(grouped ? grouped_key_of(gk, GaloisKeys::getIndex(elt)) : key_of(gk, GaloisKeys::getIndex(elt)));
+        }
+        if (a[0]->size() != 2) throw std::invalid_argument("encrypted size must be 2");
+        std::vector<Ciphertext> pa;
+        const troyhip_ct va = runOf(a, pa);
+        const size_t batch = a.size();
+        std::vector<Ciphertext> flat = Ciphertext::allocateBatch(count * batch, *a[0], 2, a[0]->coeffModulusSize());
+        troyhip_ct t = *flat[0].raw();
+        if (grouped) check(troyhip_expand_coefficients_grouped(h(), &va, &t, count, elts.data(), keys.data(), (int)elts.size(), gk.specialPrimes(), 0, batch, nullptr));
+        else check(troyhip_expand_coefficients(h(), &va, &t, count, elts.data(), keys.data(), (int)elts.size(), 0, batch, nullptr));
+        std::vector<std::vector<Ciphertext>> out(count);
+        for (size_t r = 0; r < count; r++)
+            for (size_t b = 0; b < batch; b++) {
+                flat[r * batch + b].copyMeta(t);
+                out[r].push_back(std::move(flat[r * batch + b]));
+            }
+        return out;
+    }
+    std::vector<std::vector<Ciphertext>> expandCoefficientsBatch(const std::vector<Ciphertext> &a, size_t count, const GaloisKeys &gk) const {
+        return expandCoefficientsBatch(Ciphertext::pointers(a), count, gk);
     }
 
 private:

@@ -899,6 +899,42 @@ class Evaluator:
         self._chk(self.lib.troyhip_pack_lwes_scratch_words(self.context.h, int(limbs), C.c_uint64(count), C.c_uint64(batch), C.byref(w)))
         return w.value
 
+    # -- oblivious expansion, the opposite direction (troyhip_expand_coefficients: no reference counterpart)
+    def expandCoefficients(self, a, count, galois_keys, scratch_limit_words=0):
+        """`count` Ciphertext batches, the r-th encrypting coefficient r of `a` in its constant coefficient: it decrypts to sum_k a_(r + k m) x^(k m),
+        m = 2^ceil(log2 count) -- a_r alone at count == N.  One key switch per layer of the tree (BFV / BGV, coefficient form); per-prime or grouped
+        keys of the elements KeyGenerator.expansionElts(count).  The results are windows of one buffer."""
+        count = int(count)
+        ctx, N = self.context, self.context.N
+        if count < 1 or count > N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "expand_coefficients: count must be 1 .. N")
+        elts = [2 * i + 1 for i in galois_keys.keys]
+        e = (C.c_uint32 * max(len(elts), 1))(*elts)
+        k = (C.c_void_p * max(len(elts), 1))(*[galois_keys.keys[i].ptr for i in galois_keys.keys])
+        item = 2 * a.limbs * N
+        buf = DeviceBuffer(count * a.batch * item)
+        so = CtStruct(buf.ptr, item, 2, a.limbs, int(a.is_ntt_form), a.scale, a.correction_factor)
+        si = a.struct()
+        head = (ctx.h, C.byref(si), C.byref(so), C.c_uint64(count), e, k, len(elts))
+        tail = (C.c_uint64(scratch_limit_words), C.c_uint64(a.batch), self.stream)
+        if galois_keys.special_primes is not None:
+            self._chk(self.lib.troyhip_expand_coefficients_grouped(*head, galois_keys.special_primes, *tail))
+        else:
+            self._chk(self.lib.troyhip_expand_coefficients(*head, *tail))
+        out = []
+        for r in range(count):  # windows of the one allocation the call filled, as applyGaloisHoisted returns its results
+            ct = Ciphertext(ctx, a.batch, 2, a.limbs, buf=_BufferWindow(buf, r * a.batch * item, a.batch * item))
+            ct._absorb(so)
+            out.append(ct)
+        return out
+
+    def expandCoefficientsScratchWords(self, limbs, count, batch, special_primes=None):
+        """the arena words expandCoefficients asks for with every layer in one chunk (troyhip_expand_coefficients_scratch_words); special_primes: of a
+        grouped key set, None for per-prime keys"""
+        w = C.c_uint64(0)
+        self._chk(self.lib.troyhip_expand_coefficients_scratch_words(self.context.h, int(limbs), C.c_uint64(count), C.c_uint64(batch), int(special_primes or 0), C.byref(w)))
+        return w.value
+
     def _copy_then(self, fn, a, *args):
         r = a.copy()
         fn(r, *args)
@@ -1404,6 +1440,13 @@ class KeyGenerator:
             elts.append(n + 1)
             n >>= 1
         return elts
+
+    def expansionElts(self, count):
+        """the ceil(log2 count) elements Evaluator.expandCoefficients(.., count, ..) needs: (N >> j) + 1 for the layers j = 0, 1, .."""
+        count, N = int(count), self.context.N
+        if count < 1 or count > N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "expand_coefficients: count must be 1 .. N")
+        return [(N >> j) + 1 for j in range((count - 1).bit_length())]
 
     def galoisEltsAll(self):
         """every element rotate / conjugate can ask for: X -> X^(2N-1) and X -> X^(3^(2^i)), X^(3^-(2^i)) (GaloisTool::getEltsAll,

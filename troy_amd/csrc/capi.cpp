@@ -1160,6 +1160,36 @@ int troyhip_pack_lwes_scratch_words(const troyhip_context *ctx, int limbs, uint6
         *words = need(ctx)->ev.pack_lwes_scratch_words(limbs, count, batch);
     }, false);
 }
+/* oblivious expansion (no reference counterpart) */
+static void expand_coefficients(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, uint64_t count, const uint32_t *key_elts, const uint64_t *const *keys, int n_keys,
+                                int alpha, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+    if (n_keys < 0 || (n_keys && (!key_elts || !keys))) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    auto *handle = need(ctx);
+    const hipStream_t s = on(stream);
+    const std::vector<KsKey> k = ks_keys(keys, n_keys);
+    CtBatch o = view(out);
+    handle->ev.expand_coefficients(view(in), o, count, key_elts, k.data(), n_keys, alpha, batch, scratch_limit_words, s);
+    store(o, out);
+}
+int troyhip_expand_coefficients(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, uint64_t count, const uint32_t *key_elts, const uint64_t *const *keys, int n_keys,
+                                uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] { expand_coefficients(ctx, in, out, count, key_elts, keys, n_keys, 0, scratch_limit_words, batch, stream); });
+}
+int troyhip_expand_coefficients_grouped(troyhip_context *ctx, const troyhip_ct *in, troyhip_ct *out, uint64_t count, const uint32_t *key_elts, const uint64_t *const *keys,
+                                        int n_keys, int special_primes, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (special_primes < 1) throw Error(ST_INVALID_ARGUMENT, "special_primes must lie in 1 .. min(8, key limbs - 1)");
+        expand_coefficients(ctx, in, out, count, key_elts, keys, n_keys, special_primes, scratch_limit_words, batch, stream);
+    });
+}
+int troyhip_expand_coefficients_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, int special_primes, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        if (special_primes < 0) throw Error(ST_INVALID_ARGUMENT, "special_primes must lie in 1 .. min(8, key limbs - 1)");
+        *words = need(ctx)->ev.expand_coefficients_scratch_words(limbs, count, batch, special_primes);
+    }, false);
+}
 int troyhip_random_bytes(void *out, size_t n) { // the reference seeds its PRNG from std::random_device (src/randomgen.cpp:23,72)
     return guard([&] {
         unsigned char *p = static_cast<unsigned char *>(out);

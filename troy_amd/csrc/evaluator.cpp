@@ -2142,6 +2142,91 @@ void Evaluator::pack_lwes(const u64 *c1, const u64 *c0, u64 count, int limbs, do
     }
 }
 
+// ---- oblivious expansion (no reference counterpart) ----
+// Layer j (s = 2^j, g = (N >> j) + 1) turns every node c of index a < s into node a, c + K, and node a + s, x^(2N - s) (c - K), where
+// K = (sigma_g(c0), 0) + the key switch of sigma_g(c1): ONE key switch per node, since sigma_g(x^-s c) = -x^-s sigma_g(c).  The destination is the node store:
+// unit u = a * batch + b lives in item u of `out`, its odd child in item u + s * batch, present for the prefix u < (count - s) * batch.  A unit's chunk runs
+//   1. expand_pre:  base = (c0 + sigma(c0), c1) and target = sigma(c1) into the arena, W = x^(2N - s) 2c into the odd slot (no node of this layer);
+//   2. the key switch: E = base + ks(target) over the node, which nothing reads after 1.;
+//   3. expand_post: odd slot = W - x^(2N - s) E, a gather from the node, over the units of the chunk that have an odd child.
+// Arena per unit: the key switch's own scratch (per-prime or grouped) and 3 dl N words (base, target) behind it, as pack_lwes keeps them.
+static u64 expand_unit_words(const Context &c, int limbs, int alpha) {
+    return alpha ? ksg_item_words(c, (u64)limbs, (u64)alpha) + 3 * poly_words(c, limbs) : lwe_pack_unit_words(c, limbs);
+}
+static u64 expand_blocks(int alpha) { return alpha ? KSG_BLOCKS + 3 : LWE_PACK_BLOCKS; }
+u64 Evaluator::expand_coefficients_scratch_words(int limbs, u64 count, u64 batch, int alpha) const {
+    if (count < 1 || count > c.N) throw Error(ST_INVALID_ARGUMENT, "expand_coefficients: count must be 1 .. N");
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (alpha) ksg_check_limbs(alpha, limbs);
+    const int l = lwe_pack_layers(count);
+    const u64 widest = l ? u64(1) << (l - 1) : 1;
+    return widest * std::max<u64>(batch, 1) * expand_unit_words(c, limbs, alpha) + slab_slack(expand_blocks(alpha));
+}
+void Evaluator::expand_coefficients(const CtBatch &in, CtBatch &out, u64 count, const uint32_t *key_elts, const KsKey *keys, int n_keys, int alpha, u64 batch,
+                                    u64 scratch_limit_words, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: coefficients are expanded under BFV and BGV");
+    if (!in.data || !out.data || n_keys < 0 || (n_keys && (!key_elts || !keys))) throw Error(ST_INVALID_ARGUMENT, "expand_coefficients: null pointer");
+    check_ct(in);
+    if (count < 1 || count > c.N) throw Error(ST_INVALID_ARGUMENT, "expand_coefficients: count must be 1 .. N");
+    const bool any = hoist_operands("expand_coefficients", in, out, nullptr, count * batch, batch); // size 2, K >= 2, the form, the destination
+    if (alpha) ksg_check_limbs(alpha, in.limbs);
+    const int limbs = in.limbs, logn = c.logn, l = lwe_pack_layers(count);
+    const u64 pw = poly_words(c, limbs);
+    std::vector<KsKey> layer_key((size_t)l); // of element (N >> j) + 1
+    for (int j = 0; j < l; j++) {
+        const uint32_t elt = (uint32_t)((c.N >> j) + 1);
+        for (int i = 0; i < n_keys; i++)
+            if (key_elts[i] == elt && keys[i].data) layer_key[(size_t)j] = keys[i];
+        if (!layer_key[(size_t)j].data) throw Error(ST_INVALID_ARGUMENT, "Galois key not present");
+    }
+    const u64 widest = (l ? u64(1) << (l - 1) : 1) * std::max<u64>(batch, 1); // units of the last layer
+    const u64 ks_item = expand_unit_words(c, limbs, alpha) - 3 * pw;
+    const SlabPlan plan = plan_slabs(scratch_limit_words, expand_blocks(alpha), ks_item + 3 * pw, 0, widest, 1, "scratch_limit_words is too small for one node of one ciphertext");
+    if (!any) return;
+    if (!l) { // count == 1: m = 1, the operand itself
+        launch_copy_strided(in.data, in.bstride, out.data, out.bstride, 2 * pw, batch, s);
+        return;
+    }
+    ExpandArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int i = 0; i < limbs; i++) { // m^-1 mod p, the residue divideByPolyModulusDegreeInplace(mul = N / m) multiplies by
+        const u64 p = c.primes[(size_t)i];
+        a.minv[i] = make_shoup(host::inv_mod_checked((u64(1) << l) % p, p), p);
+    }
+    a.base = a.target = nullptr;
+    a.limbs = (u64)limbs; a.logn = logn; a.odd_stride = out.bstride;
+    const LimbMap map = c.ct_map(limbs);
+    for (int j = 0; j < l; j++) {
+        const u64 sn = u64(1) << j, units = sn * batch, u_odd = std::min(sn, count - sn) * batch;
+        a.leaf = j == 0;
+        a.src = j ? out.data : in.data;
+        a.src_stride = j ? out.bstride : in.bstride;
+        a.odd = out.data + units * out.bstride;
+        a.u_odd = u_odd; a.shift = sn; a.elt = (uint32_t)((c.N >> j) + 1);
+        for (u64 u0 = 0; u0 < units; u0 += plan.items) {
+            const u64 nu = std::min(plan.items, units - u0);
+            // the key switch resets the arena and carves its working set from the front; what follows stays intact
+            const u64 ks = alpha ? plan.items * ks_item + slab_slack(KSG_BLOCKS) : scratch_switch_key(limbs, nu);
+            c.arena.begin(s);
+            c.arena.reserve(plan.words);
+            (void)c.arena.take(ks);
+            a.base = c.arena.take(nu * 2 * pw);
+            a.target = c.arena.take(nu * pw);
+            a.u0 = u0; a.units = nu;
+            launch_expand_pre(a, c.d_desc, map, s);
+            CtBatch node = out;
+            node.data = out.data + u0 * out.bstride;
+            if (alpha) switch_key_grouped(node, a.target, pw, layer_key[(size_t)j], alpha, nu, ks, s, KsBase{a.base, 2 * pw, 2});
+            else switch_key(node, a.target, pw, layer_key[(size_t)j], nu, s, KsBase{a.base, 2 * pw, 2});
+            if (u0 < u_odd)
+                launch_expand_post(node.data, out.bstride, a.odd + u0 * out.bstride, out.bstride, c.d_desc, map, logn, sn, (u64)limbs, std::min(nu, u_odd - u0), s);
+            stats::counter(stats::EXPAND_KEY_SWITCHES)++;
+            stats::counter(stats::EXPAND_CHUNKS)++;
+        }
+    }
+}
+
 // ---- decryption ----
 u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
     const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;

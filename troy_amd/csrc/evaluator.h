@@ -180,6 +180,17 @@ public:
     void pack_lwes(const u64 *c1, const u64 *c0, u64 count, int limbs, double scale, u64 cf, const uint32_t *key_elts, const KsKey *keys, int n_keys, CtBatch &out, u64 batch,
                    u64 scratch_limit_words, const DeviceAlloc &mem, hipStream_t s);
     u64 pack_lwes_scratch_words(int limbs, u64 count, u64 batch) const; // what pack_lwes asks of the arena with every layer in one chunk
+    // Oblivious expansion (no reference counterpart): out item r * batch + b, r < count, encrypts coefficient r of in item b in its
+    // constant coefficient -- it decrypts to sum_k a_(r + k m) x^(k m), m = 2^ceil(log2 count), which is a_r alone at count == N.  BFV / BGV, size 2,
+    // coefficient form, any data level; level, scale and correction factor are the operand's; count == 1 is a copy.  ONE pre-pass launch, ONE key switch and ONE
+    // post-pass launch per layer over all its (node, item) units -- or per chunk of units where a layer does not fit under scratch_limit_words (0: 2^28
+    // words).  keys[i]: the Galois key of element key_elts[i]; needed: 2^k + 1, k = log2 N - ceil(log2 count) + 1 .. log2 N.  alpha == 0: per-prime keys;
+    // alpha >= 1: keys with grouped digits over alpha special primes (at most K - alpha limbs); alpha == 1 with the per-prime keys stores the per-prime
+    // bytes.  out.data / out.bstride are the caller's: count dense batches back to back, distinct from in; the destination is the only node store.  Every
+    // limb equals the composition of divide_by_degree, apply_galois, add_sub and negacyclic_shift; the result does not depend on the limit or the batch size.
+    void expand_coefficients(const CtBatch &in, CtBatch &out, u64 count, const uint32_t *key_elts, const KsKey *keys, int n_keys, int alpha, u64 batch, u64 scratch_limit_words,
+                             hipStream_t s);
+    u64 expand_coefficients_scratch_words(int limbs, u64 count, u64 batch, int alpha) const; // what it asks of the arena with every layer in one chunk
     // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
     // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
     static PolyPlan plan_polynomial(int degree, int baby_steps);

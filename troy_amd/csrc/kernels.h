@@ -175,6 +175,23 @@ struct LweMergeArgs {
     int logn;
 };
 void launch_lwe_merge(const LweMergeArgs &a, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
+// Oblivious expansion, coefficient form.  One layer over the units u0 .. u0 + units - 1 (a unit: one node c of one item, [2][limbs][N]
+// at src + u * src_stride): with sigma the automorphism elt and s = shift,
+//   base[u - u0] = (c0 + sigma(c0), c1)  [2][limbs][N],  target[u - u0] = sigma(c1)  [limbs][N],  and where u < u_odd:  odd + u * odd_stride = x^(2N - s) 2c.
+// leaf: c is the node at src times minv (m^-1 mod p per limb, from the host).  After the key switch has stored E = base + ks(target) over the node,
+// launch_expand_post turns the odd slot into x^(2N - s) 2c - x^(2N - s) E, the odd child, over `units` units from the pointers it is given.
+struct ExpandArgs {
+    const u64 *src; u64 src_stride;
+    u64 *odd; u64 odd_stride;
+    u64 *base, *target;
+    u64 u0, units, u_odd, shift, limbs;
+    uint32_t elt;
+    int logn, leaf;
+    Shoup minv[64];
+};
+void launch_expand_pre(const ExpandArgs &a, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
+void launch_expand_post(const u64 *even, u64 even_stride, u64 *odd, u64 odd_stride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 shift, u64 limbs, u64 units,
+                        hipStream_t s);
 
 struct ModSwitchArgs {
     const PrimeDesc *primes;

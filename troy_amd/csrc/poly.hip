@@ -603,6 +603,76 @@ void launch_lwe_merge(const LweMergeArgs &a, const PrimeDesc *primes, const Limb
     launch_check("lwe_merge_kernel");
 }
 
+// ---------------------------------------------------------------- oblivious expansion
+// One layer of the expansion tree up to the key switch, over the units u0 .. u0 + units - 1 (a unit: one node c of one item), as a GATHER for the reason
+// given at galois_coeff_kernel: output coefficient j reads c at j, at n0 = j g^-1 mod 2N (the automorphism, negated where n0 >= N) and at j + s
+// (x^(2N - s) moves coefficient j + s to j, negated past N); every store is a whole line.  LEAF: c is the operand times m^-1, multiplied on the fly (what
+// divideByPolyModulusDegreeInplace stores).  The node is only read; the odd slot and the scratch are only written, and the odd slot is no node of this layer.
+template <bool LEAF> __global__ __launch_bounds__(EW_THREADS) void expand_pre_kernel(ExpandArgs a, const PrimeDesc *primes, LimbMap map, uint32_t elt_inv, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << a.logn, row = i >> a.logn, j = i & (N - 1), l = row % a.limbs, ul = row / a.limbs, u = a.u0 + ul, pw = a.limbs << a.logn;
+    const u64 p = primes[map.id[l]].p;
+    const u64 n0 = (j * elt_inv) & (2 * N - 1), jn = n0 & (N - 1), raw = j + a.shift, js = raw & (N - 1);
+    const u64 *c = a.src + u * a.src_stride + (l << a.logn);
+    auto at = [&](int k, u64 idx) -> u64 { // polynomial k of the node at coefficient idx
+        const u64 v = c[(u64)k * pw + idx];
+        return LEAF ? mul_shoup(v, a.minv[l], p) : v;
+    };
+    u64 g0 = at(0, jn), g1 = at(1, jn);
+    if (n0 >> a.logn) { g0 = negmod(g0, p); g1 = negmod(g1, p); }
+    u64 *base = a.base + ul * 2 * pw + (l << a.logn) + j;
+    base[0] = addmod(at(0, j), g0, p);
+    base[pw] = at(1, j);
+    a.target[ul * pw + (l << a.logn) + j] = g1;
+    if (u < a.u_odd) { // W = x^(2N - s) 2c into the odd child's slot
+        u64 w0 = at(0, js), w1 = at(1, js);
+        w0 = addmod(w0, w0, p);
+        w1 = addmod(w1, w1, p);
+        if (raw & N) { w0 = negmod(w0, p); w1 = negmod(w1, p); }
+        u64 *o = a.odd + u * a.odd_stride + (l << a.logn) + j;
+        o[0] = w0;
+        o[pw] = w1;
+    }
+}
+void launch_expand_pre(const ExpandArgs &a, const PrimeDesc *primes, const LimbMap &map, hipStream_t s) {
+    const u64 total = (a.units * a.limbs) << a.logn;
+    if (!total) return;
+    const u64 item = 2 * a.limbs << a.logn;
+    if (!a.src || !a.base || !a.target || a.limbs > 64 || !(a.elt & 1) || a.elt >> (a.logn + 1) || a.shift >> a.logn || a.src_stride < item ||
+        (a.u_odd > a.u0 && (!a.odd || a.odd_stride < item)))
+        throw Error(ST_LOGIC_ERROR, "expand_pre: operands");
+    uint32_t inv = 1; // g^-1 mod 2N, as launch_galois finds it
+    for (int it = 0; it < 5; it++) inv *= 2u - a.elt * inv;
+    inv &= (uint32_t)((2u << a.logn) - 1);
+    const dim3 grid = flat_grid(total, "expand_pre_kernel");
+    if (a.leaf) TROY_LAUNCH(HIP_KERNEL_NAME(expand_pre_kernel<true>), grid, dim3(EW_THREADS), 0, s, a, primes, map, inv, total);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(expand_pre_kernel<false>), grid, dim3(EW_THREADS), 0, s, a, primes, map, inv, total);
+    launch_check("expand_pre_kernel");
+}
+// After the key switch has written E = c + K over the node: the odd child W - x^(2N - s) E = x^(2N - s) (c - K).  A gather from the even slot (read only);
+// the odd slot is read and written at the thread's own index.
+__global__ __launch_bounds__(EW_THREADS) void expand_post_kernel(const u64 *__restrict__ even, u64 even_stride, u64 *__restrict__ odd, u64 odd_stride, const PrimeDesc *primes,
+                                                                LimbMap map, int logn, u64 shift, u64 limbs, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << logn, row = i >> logn, j = i & (N - 1), r = row % (2 * limbs), u = row / (2 * limbs);
+    const u64 p = primes[map.id[r % limbs]].p;
+    const u64 raw = j + shift;
+    u64 e = even[u * even_stride + (r << logn) + (raw & (N - 1))];
+    if (raw & N) e = negmod(e, p);
+    u64 *o = odd + u * odd_stride + (r << logn) + j;
+    *o = submod(*o, e, p);
+}
+void launch_expand_post(const u64 *even, u64 even_stride, u64 *odd, u64 odd_stride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 shift, u64 limbs, u64 units,
+                        hipStream_t s) {
+    const u64 total = (units * 2 * limbs) << logn;
+    if (!total) return;
+    if (!even || !odd || shift >> logn || even_stride < (2 * limbs << logn) || odd_stride < (2 * limbs << logn)) throw Error(ST_LOGIC_ERROR, "expand_post: operands");
+    TROY_LAUNCH(expand_post_kernel, flat_grid(total, "expand_post_kernel"), dim3(EW_THREADS), 0, s, even, even_stride, odd, odd_stride, primes, map, logn, shift, limbs, total);
+    launch_check("expand_post_kernel");
+}
+
 // ---------------------------------------------------------------- mod-switch / rescale (a-4 / A.10)
 // kind 0: BFV divideAndRoundqLastInplace (rns.cpp:805-830); kind 2: BGV modTAndDivideqLastInplace (rns.cpp:1097-1140).
 // in [polys][limbs][N] -> out [polys][limbs-1][N]
