@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "extprod_slabs", "extprod_chunks": slabs and chunks of troyhip_external_product_sum, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -425,6 +425,37 @@ int troyhip_expand_coefficients_grouped(troyhip_context *ctx, const troyhip_ct *
 /* the arena words the two calls above ask for when every layer runs as one chunk (no reference counterpart): a host-only function of (limbs, count, batch)
  * and the kind of key -- special_primes == 0: per-prime keys.  (limbs, 1, 1) is one unit, the least a call accepts as its limit. */
 int troyhip_expand_coefficients_scratch_words(const troyhip_context *ctx, int limbs, uint64_t count, uint64_t batch, int special_primes, uint64_t *words);
+/* ---- External product with RGSW ciphertexts (no reference counterpart).  BFV / BGV, size 2, coefficient form, any data level,
+ * per-prime keys.  Stream-ordered; nothing is read back. ---- */
+/* An RGSW ciphertext of a small signed polynomial m is a device array [2][K-1][2][K][N] (NTT form): two key-switching keys in the layout of
+ * troyhip_create_kswitch_key, half 0 for the "secret" m (it multiplies the digits of c0), half 1 for the "secret" m (.) s (the digits of c1).
+ * out item b = base item b (NULL: zero) + sum_r rgsw[r] (.) in_descs[r] item b, which decrypts to base + sum_r m_r mu_r in R_t: per term the digits of c0
+ * and c1 are extended and transformed (step 1 of troyhip_switch_key at element 1, both polynomials), ONE inner product runs over all 2 count limbs digits in
+ * the extended basis, and ONE mod-down -- troyhip_switch_key's, with its arithmetic -- and one rounding happen per item, however large count is.  The noise
+ * is additive: sum_r m_r e_r, the key-switch noise of 2 count limbs digits and one rounding.  rgsw[r] is shared by the batch.  Anchors: (A1) count == 1,
+ * base NULL and the operand (0, c1): the bytes of troyhip_switch_key onto a zeroed ciphertext with target c1 and key rgsw[0] + (K-1) 2 K N -- and likewise
+ * (c0, 0) with half 0; (A2) in general no composition of public calls has these bytes (the mod-down is not additive); every limb equals the exact model
+ * of section 4.20, and depends on the multiset of (operand, RGSW) pairs and the base only: not on the order of the terms, the batch size or the limit.
+ * out->data, ->batch_stride are INPUTS, as in troyhip_multiply_sum; the call sets the other fields of *out from the operands, which agree with each other
+ * and the base in limbs, scale and correction factor ("encrypted1 and encrypted2 parameter mismatch", "scale mismatch", "correction factor mismatch").
+ * The arena request stays under scratch_limit_words (0: 2^28 words): slabs of items, chunks of at most 16 terms; below one term of one item
+ * (troyhip_external_product_sum_scratch_words(.., 1, 1, ..)) the call is refused.  1 <= count <= 64.  CKKS is TROYHIP_LOGIC_ERROR "unsupported scheme";
+ * an operand in NTT form or of another size, a null descriptor or RGSW, a context with K < 2 or without a device, and a destination that shares words with
+ * an operand or the base or whose stride is too small are refused.  Grouped RGSWs are out of scope.  Counters "extprod_slabs", "extprod_chunks". */
+int troyhip_external_product_sum(troyhip_context *ctx, const troyhip_ct *const *in_descs, const uint64_t *const *rgsw, int count, const troyhip_ct *base /* may be NULL */,
+                                 troyhip_ct *out, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* the arena words the call above asks for with the batch in one slab and min(count, 16) terms per chunk (no reference counterpart): a host-only function
+ * of (limbs, count, batch).  (limbs, 1, 1) is the least a call accepts as its limit. */
+int troyhip_external_product_sum_scratch_words(const troyhip_context *ctx, int limbs, int count, uint64_t batch, uint64_t *words);
+/* RGSW generation (no reference counterpart).  plain_ntt_keylevel: [K][N], what troyhip_plain_to_ntt(limbs = K) writes (the centred lift of multiplyPlain).
+ * Host form: half 0 == troyhip_host_kswitch_key(seed_lo, seed_hi, sk, m), half 1 == troyhip_host_kswitch_key(seed_lo + 1, seed_hi, sk, m (.) sk), byte for
+ * byte.  As with troyhip_host_kswitch_key, ONE SEED NEVER SERVES TWO KEYS: an RGSW consumes the seeds seed_lo and seed_lo + 1, and a caller that makes
+ * several gives each a pair of its own (the generators of troy_amd.api and troyn.hpp advance their counter by 2 per RGSW). */
+int troyhip_host_rgsw(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *plain_ntt_keylevel, uint64_t *out);
+/* its device twin: item i (plains[i] -> outs[i], HOST arrays of device pointers) uses the seeds (seed_lo + 2 i, seed_hi) and (seed_lo + 2 i + 1, seed_hi) and
+ * is byte-identical to troyhip_host_rgsw with (seed_lo + 2 i, seed_hi); m (.) sk is a dyadic product on the device.  1 <= count <= 65535. */
+int troyhip_create_rgsw(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *const *plains, uint64_t *const *outs,
+                        uint64_t count, void *stream);
 /* ---- DecryptorCuda::decrypt (src/decryptor_cuda.cu:61-330; dotProductCtSkArray + decryptScaleAndRound / decryptModt,
  * src/utils/rns_cuda.cu:510-621), SURVEY 8-f3.  secret_key: device [K][N] (NTT form, src/secretkey.h).  plain_out (device):
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */

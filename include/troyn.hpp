@@ -976,6 +976,35 @@ public:
     static size_t getIndex(uint32_t galois_elt) { return (galois_elt - 1) >> 1; } // src/utils/galois_cuda.cuh:45-48
     bool hasKey(uint32_t galois_elt) const { return hasKeyIndex(getIndex(galois_elt)); }
 };
+// An RGSW ciphertext of a small signed polynomial m (the reference has none): device words [2][K-1][2][K][N], NTT form -- two
+// key-switching keys in KSwitchKeys' layout, half 0 for m, half 1 for m (.) s.  KeyGenerator::createRGSW makes one, Evaluator::externalProduct applies it.
+class RGSWCiphertext {
+public:
+    // what an evaluator hands to the kernels: generated (or uploaded) under the SAME context, or the kernels would read past it
+    const uint64_t *device(const ParmsID &key_parms_id, size_t key_limbs, size_t poly_modulus_degree) const {
+        if (!words_ || parms_id_ != key_parms_id || key_limbs < 2 || words_->size() != 2 * (key_limbs - 1) * 2 * key_limbs * poly_modulus_degree)
+            throw std::invalid_argument("rgsw is not valid for encryption parameters");
+        return words_->get();
+    }
+    void adopt(const ParmsID &key_parms_id, std::shared_ptr<DeviceArray> words) { parms_id_ = key_parms_id; words_ = std::move(words); }
+    void upload(const ParmsID &key_parms_id, const std::vector<uint64_t> &host) {
+        auto a = std::make_shared<DeviceArray>(host.size());
+        check(troyhip_copy_h2d(a->get(), host.data(), host.size() * 8, nullptr));
+        adopt(key_parms_id, a);
+    }
+    std::vector<uint64_t> toHost() const {
+        std::vector<uint64_t> v(words_ ? words_->size() : 0);
+        if (!v.empty()) {
+            check(troyhip_copy_d2h(v.data(), words_->get(), v.size() * 8, nullptr));
+            check(troyhip_stream_synchronize(nullptr));
+        }
+        return v;
+    }
+    const ParmsID &parmsID() const noexcept { return parms_id_; }
+private:
+    std::shared_ptr<DeviceArray> words_;
+    ParmsID parms_id_;
+};
 
 // LWECiphertextCuda (src/lwe_cuda.cuh): the LWE sample (c1: one polynomial [limbs][N] in coefficient form, c0: one word per limb)
 // that extractLWE cuts out of an RLWE ciphertext
@@ -1156,6 +1185,40 @@ public:
         for (size_t n = c_.polyModulusDegree(); n >= 2; n >>= 1) elts.push_back((uint32_t)(n + 1));
         return elts;
     }
+    // ---- RGSW ciphertexts (troyhip_host_rgsw / troyhip_create_rgsw; the reference has none).  `plain`: coefficients mod t,
+    // lifted as multiplyPlain lifts them; the polynomial should be small (a bit, a monomial, coefficients in {-1, 0, 1}): its size multiplies the noise of
+    // the ciphertext it is applied to.  An RGSW is two key-switching keys and takes TWO of the generator's seeds (lo + k, hi), (lo + k + 1, hi): one
+    // seed never serves two keys (createKeySwitchingKeys above), and these members count together with it.  The device forms are byte-identical.
+    RGSWCiphertext createRGSW(const Plaintext &plain) const {
+        const auto m = plainAtKeyLevel(plain);
+        std::vector<uint64_t> mh(m->size()), h(2 * ksk_words());
+        check(troyhip_copy_d2h(mh.data(), m->get(), mh.size() * 8, nullptr));
+        check(troyhip_stream_synchronize(nullptr));
+        check(troyhip_host_rgsw(c_.handle(), lo_ + kswitch_calls_, hi_, sk_.data.data(), mh.data(), h.data()));
+        kswitch_calls_ += 2;
+        RGSWCiphertext g;
+        g.upload(c_.keyParmsID(), h);
+        return g;
+    }
+    std::vector<RGSWCiphertext> createRGSWOnDevice(const std::vector<Plaintext> &plains) const {
+        std::vector<std::shared_ptr<DeviceArray>> ms, outs;
+        std::vector<const uint64_t *> pm;
+        std::vector<uint64_t *> po;
+        for (const Plaintext &p : plains) {
+            ms.push_back(plainAtKeyLevel(p));
+            outs.push_back(std::make_shared<DeviceArray>(2 * ksk_words()));
+            pm.push_back(ms.back()->get());
+            po.push_back(outs.back()->get());
+        }
+        std::vector<RGSWCiphertext> out(plains.size());
+        if (plains.empty()) return out;
+        check(troyhip_create_rgsw(c_.handle(), lo_ + kswitch_calls_, hi_, deviceSecretKey(), pm.data(), po.data(), plains.size(), nullptr));
+        kswitch_calls_ += 2 * plains.size();
+        check(troyhip_stream_synchronize(nullptr)); // the transformed plaintexts are freed on return
+        for (size_t i = 0; i < plains.size(); i++) out[i].adopt(c_.keyParmsID(), outs[i]);
+        return out;
+    }
+    RGSWCiphertext createRGSWOnDevice(const Plaintext &plain) const { return std::move(createRGSWOnDevice(std::vector<Plaintext>{plain})[0]); }
     // the ceil(log2 count) keys Evaluator::expandCoefficients(.., count, ..) needs: X -> X^((N >> j) + 1) for the layers j = 0, 1, ..
     std::vector<uint32_t> expansionElts(size_t count) const {
         const size_t N = c_.polyModulusDegree();
@@ -1188,6 +1251,15 @@ private:
         pk_.coeff_modulus_size = K;
     }
     size_t ksk_words() const { const size_t K = c_.keyLimbs(); return (K - 1) * 2 * K * c_.polyModulusDegree(); }
+    // [K][N]: the plaintext in NTT form at the key level, what troyhip_plain_to_ntt(limbs = K) writes
+    std::shared_ptr<DeviceArray> plainAtKeyLevel(const Plaintext &plain) const {
+        const size_t K = c_.keyLimbs(), N = c_.polyModulusDegree();
+        if (K < 2) throw std::logic_error("keyswitching is not supported by the context");
+        if (!plain.coeffCount() || plain.coeffCount() > N) throw std::invalid_argument("plain is not valid for encryption parameters");
+        auto m = std::make_shared<DeviceArray>(K * N);
+        check(troyhip_plain_to_ntt(c_.handle(), plain.device(), plain.coeffCount(), 0, (int)K, m->get(), 1, nullptr));
+        return m;
+    }
     // keys with grouped digits: source kind 1 relin / 2 Galois (one key per element) / 3 key switching, on the host or in one call on the device
     template <class Keys> void grouped(Keys &out, int kind, int special_primes, bool on_device, const std::vector<uint32_t> &elts, const SecretKey *new_key, uint64_t lo) const {
         size_t words = 0;
@@ -2760,6 +2832,61 @@ public:
     }
     std::vector<std::vector<Ciphertext>> expandCoefficientsBatch(const std::vector<Ciphertext> &a, size_t count, const GaloisKeys &gk) const {
         return expandCoefficientsBatch(Ciphertext::pointers(a), count, gk);
+    }
+    // External product with RGSW ciphertexts (troyhip_external_product_sum; the reference has no such call): base + sum_r g[r] (.)
+    // cts[r], which decrypts to base + sum_r m_r mu_r.  BFV / BGV, size 2, coefficient form, one level; 1 .. 64 terms.  The sum is formed in the extended
+    // basis: one mod-down and one rounding whatever the number of terms, additive noise.  cmux(sel, ct0, ct1) = ct0 + sel (.) (ct1 - ct0): ct1 where the
+    // RGSW encrypts 1, ct0 where it encrypts 0.
+    const uint64_t *rgsw_of(const RGSWCiphertext &g) const { return g.device(c_.keyParmsID(), c_.keyLimbs(), c_.polyModulusDegree()); }
+    void externalProductSum(const std::vector<const Ciphertext *> &cts, const std::vector<const RGSWCiphertext *> &g, Ciphertext &dst, const Ciphertext *base = nullptr) const {
+        std::vector<std::vector<const Ciphertext *>> runs;
+        for (const Ciphertext *c : cts) runs.push_back({c});
+        const std::vector<const Ciphertext *> b{base};
+        dst = std::move(externalProductSumBatch(runs, g, base ? &b : nullptr)[0]);
+    }
+    void externalProduct(const Ciphertext &a, const RGSWCiphertext &g, Ciphertext &dst) const { externalProductSum({&a}, {&g}, dst); }
+    void cmux(const RGSWCiphertext &sel, const Ciphertext &ct0, const Ciphertext &ct1, Ciphertext &dst) const {
+        Ciphertext d;
+        sub(ct1, ct0, d);
+        externalProductSum({&d}, {&sel}, dst, &ct0);
+    }
+    // over batches: cts[r] is a run of `count` slab members (anything else is packed first), g[r] multiplies every item of it; item i of the result =
+    // base[i] + sum_r g[r] (.) cts[r][i].  ONE library call for the whole batch.
+    std::vector<Ciphertext> externalProductSumBatch(const std::vector<std::vector<const Ciphertext *>> &cts, const std::vector<const RGSWCiphertext *> &g,
+                                                    const std::vector<const Ciphertext *> *base = nullptr) const {
+        if (cts.empty() || cts.size() > 64 || cts.size() != g.size()) throw std::invalid_argument("external_product_sum takes 1 to 64 terms");
+        const size_t R = cts.size(), count = cts[0].size();
+        if (!count) return {};
+        std::vector<std::vector<Ciphertext>> packed(R + 1);
+        std::vector<troyhip_ct> views(R + 1);
+        std::vector<const troyhip_ct *> pa(R);
+        std::vector<const uint64_t *> pg(R);
+        for (size_t r = 0; r < R; r++) {
+            if (cts[r].size() != count) throw std::invalid_argument("externalProductSumBatch: operand counts differ");
+            if (!g[r]) throw std::invalid_argument("rgsw is not valid for encryption parameters");
+            views[r] = runOf(cts[r], packed[r]);
+            pa[r] = &views[r];
+            pg[r] = rgsw_of(*g[r]);
+        }
+        if (base) {
+            if (base->size() != count) throw std::invalid_argument("externalProductSumBatch: operand counts differ");
+            views[R] = runOf(*base, packed[R]);
+        }
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(count, *cts[0][0], 2, cts[0][0]->coeffModulusSize());
+        troyhip_ct t = *out[0].raw();
+        check(troyhip_external_product_sum(h(), pa.data(), pg.data(), (int)R, base ? &views[R] : nullptr, &t, 0, count, nullptr));
+        for (auto &c : out) c.copyMeta(t);
+        return out;
+    }
+    std::vector<Ciphertext> externalProductBatch(const std::vector<const Ciphertext *> &a, const RGSWCiphertext &g) const { return externalProductSumBatch({a}, {&g}); }
+    std::vector<Ciphertext> externalProductBatch(const std::vector<Ciphertext> &a, const RGSWCiphertext &g) const { return externalProductBatch(Ciphertext::pointers(a), g); }
+    std::vector<Ciphertext> cmuxBatch(const RGSWCiphertext &sel, const std::vector<Ciphertext> &ct0, const std::vector<Ciphertext> &ct1) const {
+        if (ct0.size() != ct1.size()) throw std::invalid_argument("cmuxBatch: operand counts differ");
+        std::vector<Ciphertext> d(ct0.size());
+        for (size_t i = 0; i < ct0.size(); i++) sub(ct1[i], ct0[i], d[i]);
+        const std::vector<Ciphertext> &diff = d;
+        const std::vector<const Ciphertext *> b = Ciphertext::pointers(ct0);
+        return externalProductSumBatch({Ciphertext::pointers(diff)}, {&sel}, &b);
     }
 
 private:

@@ -444,6 +444,29 @@ class GaloisKeys(KSwitchKeys):  # src/galoiskeys_cuda.cuh:74-77
         self.set(self.getIndex(galois_elt), host_array)
 
 
+class RGSWCiphertext:
+    """An RGSW ciphertext of a small signed polynomial m (no reference counterpart): device words [2][K-1][2][K][N], NTT form --
+    two key-switching keys in KSwitchKeys' layout, half 0 for m, half 1 for m (.) s.  Evaluator.externalProduct multiplies a ciphertext by it."""
+
+    def __init__(self, context, buf):
+        K, N = context.key_limbs, context.N
+        if not isinstance(buf, DeviceBuffer) or K < 2 or buf.words != 2 * (K - 1) * 2 * K * N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "rgsw is not valid for encryption parameters")
+        self.context, self.buf = context, buf
+
+    @classmethod
+    def from_numpy(cls, context, host_array):
+        a = np.ascontiguousarray(host_array, dtype=np.uint64)
+        K, N = context.key_limbs, context.N
+        if a.shape != (2, K - 1, 2, K, N):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "rgsw is not valid for encryption parameters")
+        return cls(context, DeviceBuffer.from_numpy(a))
+
+    def cpu(self):
+        K, N = self.context.key_limbs, self.context.N
+        return self.buf.to_numpy().reshape(2, K - 1, 2, K, N)
+
+
 class Evaluator:
     """EvaluatorCuda (src/evaluator_cuda.cuh:13-361) over batches."""
 
@@ -933,6 +956,44 @@ class Evaluator:
         grouped key set, None for per-prime keys"""
         w = C.c_uint64(0)
         self._chk(self.lib.troyhip_expand_coefficients_scratch_words(self.context.h, int(limbs), C.c_uint64(count), C.c_uint64(batch), int(special_primes or 0), C.byref(w)))
+        return w.value
+
+    # -- external product with RGSW ciphertexts (troyhip_external_product_sum: no reference counterpart, DESIGN.md section 4.20)
+    def externalProductSum(self, cts, rgsws, base=None, scratch_limit_words=0):
+        """base + sum_r rgsws[r] (.) cts[r] as ONE size-2 batch, which decrypts to base + sum_r m_r mu_r: 1 .. 64 size-2 batches of one level and item
+        count in coefficient form (BFV / BGV), each with the RGSWCiphertext that multiplies every item of it.  The sum is formed in the extended basis:
+        one mod-down and one rounding per item, additive noise."""
+        if not 1 <= len(cts) <= 64 or len(cts) != len(rgsws):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "external_product_sum takes 1 to 64 terms")
+        for g in rgsws:
+            if not isinstance(g, RGSWCiphertext) or g.context is not self.context:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "rgsw is not valid for encryption parameters")
+        a0 = cts[0]
+        if any(a.batch != a0.batch for a in cts) or (base is not None and base.batch != a0.batch):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "external_product_sum: the operands and the base hold one number of items")
+        out = Ciphertext(a0.context, a0.batch, 2, a0.limbs)
+        sa = [a.struct() for a in cts]
+        pa = (C.POINTER(CtStruct) * len(sa))(*[C.pointer(st) for st in sa])
+        pg = (C.c_void_p * len(rgsws))(*[g.buf.ptr for g in rgsws])
+        sb = base.struct() if base is not None else None
+        so = out.struct()
+        self._chk(self.lib.troyhip_external_product_sum(self.context.h, pa, pg, len(sa), C.byref(sb) if sb is not None else None, C.byref(so),
+                                                        C.c_uint64(scratch_limit_words), C.c_uint64(a0.batch), self.stream))
+        out._absorb(so)
+        return out
+
+    def externalProduct(self, ct, rgsw):
+        """rgsw (.) ct: decrypts to m mu"""
+        return self.externalProductSum([ct], [rgsw])
+
+    def cmux(self, sel_rgsw, ct0, ct1):
+        """ct0 + sel (.) (ct1 - ct0): ct1 where the RGSW encrypts 1, ct0 where it encrypts 0"""
+        return self.externalProductSum([self.sub(ct1, ct0)], [sel_rgsw], base=ct0)
+
+    def externalProductSumScratchWords(self, limbs, count, batch):
+        """the arena words externalProductSum asks for with the batch in one slab and min(count, 16) terms per chunk (troyhip_external_product_sum_scratch_words)"""
+        w = C.c_uint64(0)
+        self._chk(self.lib.troyhip_external_product_sum_scratch_words(self.context.h, int(limbs), int(count), C.c_uint64(batch), C.byref(w)))
         return w.value
 
     def _copy_then(self, fn, a, *args):
@@ -1432,6 +1493,67 @@ class KeyGenerator:
         out = self._ksk()
         capi.check(self.lib, self.lib.troyhip_host_kswitch_key(self.context.h, lo, hi, _u64p(self._sk), _u64p(new_key), _u64p(out)))
         return out
+
+    # ---- RGSW ciphertexts (troyhip_host_rgsw / troyhip_create_rgsw: no reference counterpart, DESIGN.md section 4.20)
+    def _rgsw_plain(self, plain):
+        """[K][N] NTT form at the key level: a DeviceBuffer or array of that shape as it is; coefficients mod t (at most N) through troyhip_plain_to_ntt"""
+        ctx = self.context
+        K, N = ctx.key_limbs, ctx.N
+        if isinstance(plain, DeviceBuffer):
+            if plain.words != K * N:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "plain is not valid for encryption parameters")
+            return plain
+        a = np.ascontiguousarray(plain, dtype=np.uint64)
+        if a.shape == (K, N):
+            return DeviceBuffer.from_numpy(a)
+        if a.ndim != 1 or not 1 <= a.size <= N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "plain is not valid for encryption parameters")
+        out = DeviceBuffer(K * N)
+        capi.check(self.lib, self.lib.troyhip_plain_to_ntt(ctx.h, C.c_void_p(DeviceBuffer.from_numpy(a).ptr), C.c_uint64(a.size), C.c_uint64(0), K, C.c_void_p(out.ptr),
+                                                           C.c_uint64(1), None))
+        return out
+
+    def _rgsw_seed(self, count):
+        """an RGSW is two key-switching keys: it takes two of the generator's seeds (lo + k, hi), (lo + k + 1, hi); one seed never serves two keys"""
+        lo = C.c_uint64((self.seed[0] + self.kswitch_calls) & (2**64 - 1))
+        self.kswitch_calls += 2 * count
+        return lo, C.c_uint64(self.seed[1])
+
+    def createRGSW(self, plain, device=False):
+        """the RGSW ciphertext of the plaintext `plain` (coefficients mod t, lifted as multiplyPlain lifts them; or [K][N] in NTT form at the key level):
+        the host array [2][K-1][2][K][N], or with device=True an RGSWCiphertext generated on the device, byte-identical.  The polynomial should be small
+        (a bit, a monomial, coefficients in {-1, 0, 1}): its size multiplies the noise of the ciphertext it is applied to."""
+        if device:
+            return self.createRGSWBatch([plain])[0]
+        ctx = self.context
+        K, N = ctx.key_limbs, ctx.N
+        if K < 2:
+            raise capi.LogicError(capi.LOGIC_ERROR, "keyswitching is not supported by the context")
+        if not isinstance(plain, DeviceBuffer) and np.shape(plain) == (K, N):  # already at the key level: no device is needed
+            m = np.ascontiguousarray(plain, dtype=np.uint64)
+        else:
+            m = self._rgsw_plain(plain).to_numpy().reshape(K, N)
+        out = np.zeros((2, K - 1, 2, K, N), dtype=np.uint64)
+        lo, hi = self._rgsw_seed(1)
+        capi.check(self.lib, self.lib.troyhip_host_rgsw(ctx.h, lo, hi, _u64p(self._sk), _u64p(m), _u64p(out)))
+        return out
+
+    def createRGSWBatch(self, plains):
+        """one RGSWCiphertext per plaintext, generated on the device in one call: item i from the generator's next seeds 2 i and 2 i + 1"""
+        ctx = self.context
+        K, N = ctx.key_limbs, ctx.N
+        if K < 2:
+            raise capi.LogicError(capi.LOGIC_ERROR, "keyswitching is not supported by the context")
+        if not len(plains):
+            return []
+        ms = [self._rgsw_plain(p) for p in plains]
+        bufs = [DeviceBuffer(2 * (K - 1) * 2 * K * N) for _ in ms]
+        pm = (C.c_void_p * len(ms))(*[m.ptr for m in ms])
+        po = (C.c_void_p * len(ms))(*[b.ptr for b in bufs])
+        lo, hi = self._rgsw_seed(len(ms))
+        capi.check(self.lib, self.lib.troyhip_create_rgsw(ctx.h, lo, hi, C.c_void_p(self._device_sk().ptr), pm, po, C.c_uint64(len(ms)), None))
+        synchronize()  # the plaintext buffers made here are released on return
+        return [RGSWCiphertext(ctx, b) for b in bufs]
 
     def automorphismElts(self):
         """X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)"""

@@ -65,6 +65,7 @@ SYMBOLS = [
     "troyhip_stat", "troyhip_build_id", "troyhip_host_batch_encode", "troyhip_host_batch_decode", "troyhip_plain_to_ntt", "troyhip_decrypt", "troyhip_apply_key_switching", "troyhip_negacyclic_shift", "troyhip_divide_by_poly_modulus_degree",
     "troyhip_extract_lwes", "troyhip_pack_lwes", "troyhip_pack_lwes_scratch_words",
     "troyhip_expand_coefficients", "troyhip_expand_coefficients_grouped", "troyhip_expand_coefficients_scratch_words",
+    "troyhip_external_product_sum", "troyhip_external_product_sum_scratch_words", "troyhip_host_rgsw", "troyhip_create_rgsw",
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",

@@ -1190,6 +1190,54 @@ int troyhip_expand_coefficients_scratch_words(const troyhip_context *ctx, int li
         *words = need(ctx)->ev.expand_coefficients_scratch_words(limbs, count, batch, special_primes);
     }, false);
 }
+/* external product with RGSW ciphertexts (no reference counterpart) */
+int troyhip_external_product_sum(troyhip_context *ctx, const troyhip_ct *const *in_descs, const uint64_t *const *rgsw, int count, const troyhip_ct *base, troyhip_ct *out,
+                                 uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (count < 1 || count > 64) throw Error(ST_INVALID_ARGUMENT, "external_product_sum takes 1 to 64 terms");
+        if (!in_descs || !rgsw || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        for (int i = 0; i < count; i++) {
+            if (!in_descs[i]) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+            if (!rgsw[i]) throw Error(ST_INVALID_ARGUMENT, "external_product_sum: null RGSW ciphertext");
+        }
+        auto *handle = need(ctx); // the context is bound before the stream is looked at
+        const hipStream_t s = on(stream);
+        CtBatch v[64], vb;
+        for (int i = 0; i < count; i++) v[i] = view(in_descs[i]);
+        if (base) vb = view(base);
+        CtBatch o = view(out);
+        handle->ev.external_product_sum(v, rgsw, count, base ? &vb : nullptr, o, batch, scratch_limit_words, s);
+        store(o, out);
+    });
+}
+int troyhip_external_product_sum_scratch_words(const troyhip_context *ctx, int limbs, int count, uint64_t batch, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.external_product_sum_scratch_words(limbs, count, batch);
+    }, false);
+}
+int troyhip_host_rgsw(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *plain_ntt_keylevel, uint64_t *out) {
+    return guard([&] {
+        if (!secret_key || !plain_ntt_keylevel || !out) throw Error(ST_INVALID_ARGUMENT, "null key, plaintext list or RGSW output");
+        hostcrypto::keygen_rgsw(need(ctx)->ctx, seed_lo, seed_hi, secret_key, plain_ntt_keylevel, out);
+    }, false);
+}
+int troyhip_create_rgsw(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *const *plains, uint64_t *const *outs,
+                        uint64_t count, void *stream) {
+    return guard([&] {
+        troyhip_context *x = need(ctx);
+        const hipStream_t s = on(stream);
+        // the dyadic product m (.) s outlives each key generation's use of the context arena: the caching pool, as troyhip_pack_lwes
+        u64 *tmp = (u64 *)DevicePool::instance().get((size_t)x->ctx.K * x->ctx.N * sizeof(u64));
+        try {
+            x->kg.rgsw(seed_lo, seed_hi, secret_key, plains, outs, count, tmp, s);
+        } catch (...) {
+            DevicePool::instance().put(tmp);
+            throw;
+        }
+        DevicePool::instance().put(tmp);
+    });
+}
 int troyhip_random_bytes(void *out, size_t n) { // the reference seeds its PRNG from std::random_device (src/randomgen.cpp:23,72)
     return guard([&] {
         unsigned char *p = static_cast<unsigned char *>(out);

@@ -2227,6 +2227,107 @@ void Evaluator::expand_coefficients(const CtBatch &in, CtBatch &out, u64 count, 
     }
 }
 
+// ---- external product with RGSW ciphertexts (no reference counterpart) ----
+// out item b = base item b + the mod-down of  sum_r sum_h sum_j digits(c_h of ins[r] item b)[j] * rgsw[r][h][j]:  the first half of switch_key over
+// BOTH polynomials of every term (ks_expand_digits; the operand is in coefficient form), ONE inner product over all 2 R dl digits
+// (launch_extprod_mac, at most HOIST_MAX_ROT terms per launch, later launches accumulating) and ONE second half (ks_acc_to_ct) per item.
+// Scratch in words, the units of plan_slabs being the terms: per item 2 rl N [acc] + (2 dl + 4) N [what ks_acc_to_ct carves], per (term, item)
+// 2 rl dl N [the digits of c0 and c1].
+static const u64 EXTPROD_BLOCKS = 8; // D, acc and what ks_acc_to_ct carves
+static const int EXTPROD_MAX_TERMS = 64;
+static SlabWords extprod_words(const Context &c, u64 dl) {
+    const HoistWords w = ks_hoist_words(c, dl);
+    return SlabWords{w.acc + w.finish, 2 * w.D};
+}
+u64 Evaluator::external_product_sum_scratch_words(int limbs, int count, u64 batch) const {
+    if (count < 1 || count > EXTPROD_MAX_TERMS) throw Error(ST_INVALID_ARGUMENT, "external_product_sum takes 1 to 64 terms");
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    const SlabWords sw = extprod_words(c, (u64)limbs);
+    const u64 nb = std::max<u64>(batch, 1);
+    return nb * sw.per_item + std::min<u64>((u64)count, HOIST_MAX_ROT) * nb * sw.per_unit_item + slab_slack(EXTPROD_BLOCKS);
+}
+void Evaluator::external_product_sum(const CtBatch *ins, const u64 *const *rgsw, int count, const CtBatch *base, CtBatch &out, u64 batch, u64 scratch_limit_words,
+                                     hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: the external product is defined under BFV and BGV");
+    if (count < 1 || count > EXTPROD_MAX_TERMS) throw Error(ST_INVALID_ARGUMENT, "external_product_sum takes 1 to 64 terms");
+    if (!ins || !rgsw) throw Error(ST_INVALID_ARGUMENT, "external_product_sum: null pointer");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    const CtBatch &first = ins[0];
+    for (int r = 0; r <= count; r++) { // the terms, then the base
+        if (r == count && !base) break;
+        const CtBatch &x = r < count ? ins[r] : *base;
+        if (!x.data) throw Error(ST_INVALID_ARGUMENT, "external_product_sum: null pointer");
+        if (r < count && !rgsw[r]) throw Error(ST_INVALID_ARGUMENT, "external_product_sum: null RGSW ciphertext");
+        check_ct(x);
+        if (x.size != 2) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2");
+        check_ks_form(x.ntt);
+        if (x.limbs != first.limbs) throw Error(ST_INVALID_ARGUMENT, "encrypted1 and encrypted2 parameter mismatch");
+        if (x.scale != first.scale) throw Error(ST_INVALID_ARGUMENT, "scale mismatch");
+        if (c.scheme == SCHEME_BGV && x.cf != first.cf) throw Error(ST_INVALID_ARGUMENT, "correction factor mismatch");
+    }
+    const int L = first.limbs;
+    if (L >= 64) throw Error(ST_LOGIC_ERROR, "external_product_sum: more than 63 digits");
+    const u64 N = c.N, dl = (u64)L, rl = dl + 1, pw = poly_words(c, L), dw = rl * dl * N;
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    for (int r = 0; batch && r <= count; r++) { // the destination is written slab by slab while later slabs still read their operands and base
+        if (r == count && !base) break;
+        const CtBatch &x = r < count ? ins[r] : *base;
+        if (x.bstride < 2 * pw && batch > 1) throw Error(ST_INVALID_ARGUMENT, "encrypted batch stride too small for its size");
+        if (batches_overlap(out.data, batch, out.bstride, 2 * pw, x.data, batch, x.bstride, 2 * pw))
+            throw Error(ST_INVALID_ARGUMENT, "external_product_sum: destination must be a distinct buffer");
+    }
+    out.size = 2; out.limbs = L; out.ntt = first.ntt; out.scale = first.scale; out.cf = first.cf;
+    const SlabWords sw = extprod_words(c, dl);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, EXTPROD_BLOCKS, sw.per_item, sw.per_unit_item, std::max<u64>(batch, 1), std::min<u64>((u64)count, HOIST_MAX_ROT),
+                                     "scratch_limit_words is too small for one term of one ciphertext");
+    if (!batch) return;
+    const u64 bs = plan.items, rs = plan.units;
+    KsPlan k = ks_plan(L, 0);
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *D = c.arena.take(rs * bs * 2 * dw), *acc = c.arena.take(bs * 2 * rl * N);
+    const size_t mark = c.arena.mark();
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        for (int r0 = 0; r0 < count; r0 += (int)rs) {
+            ExtProdArgs h;
+            std::memset(&h, 0, sizeof(h));
+            h.terms = (u32)std::min<u64>(rs, (u64)(count - r0));
+            h.accumulate = r0 ? 1 : 0; // later chunks add to the canonical words the first one stored
+            for (u32 t = 0; t < h.terms; t++) {
+                const CtBatch &x = ins[r0 + (int)t];
+                const u64 *src = x.data + b0 * x.bstride;
+                u64 *Dt = D + (u64)t * nb * 2 * dw;
+                if (nb == 1 || x.bstride == 2 * pw) { // c0 and c1 of the run lie back to back: 2 nb polynomials in one call, item b's two sets side by side
+                    k.a.batch = 2 * nb;
+                    ks_expand_digits(src, pw, Dt, k, s);
+                    h.d_bstride[t] = 2 * dw; h.d_hstride[t] = dw;
+                } else { // a strided operand: c0 of every item, then c1 of every item
+                    k.a.batch = nb;
+                    ks_expand_digits(src, x.bstride, Dt, k, s);
+                    ks_expand_digits(src + pw, x.bstride, Dt + nb * dw, k, s);
+                    h.d_bstride[t] = dw; h.d_hstride[t] = nb * dw;
+                }
+                h.D[t] = Dt;
+                h.rgsw[t] = rgsw[r0 + (int)t];
+            }
+            k.a.batch = nb;
+            launch_extprod_mac(acc, k.a, h, s);
+            stats::counter(stats::EXTPROD_CHUNKS)++;
+        }
+        CtBatch o;
+        o.data = out.data + b0 * out.bstride; o.bstride = out.bstride;
+        c.arena.rewind(mark);
+        if (base) ks_acc_to_ct(o, acc, k, s, KsBase{base->data + b0 * base->bstride, base->bstride, 2});
+        else { // no base: the mod-down accumulates onto zeros, as switch_key does onto a zeroed ciphertext
+            launch_zero_strided(o.data, o.bstride, 2 * pw, nb, s);
+            ks_acc_to_ct(o, acc, k, s, KsBase{});
+        }
+        stats::counter(stats::EXTPROD_SLABS)++;
+    }
+}
+
 // ---- decryption ----
 u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
     const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;

@@ -191,6 +191,16 @@ public:
     void expand_coefficients(const CtBatch &in, CtBatch &out, u64 count, const uint32_t *key_elts, const KsKey *keys, int n_keys, int alpha, u64 batch, u64 scratch_limit_words,
                              hipStream_t s);
     u64 expand_coefficients_scratch_words(int limbs, u64 count, u64 batch, int alpha) const; // what it asks of the arena with every layer in one chunk
+    // External product with RGSW ciphertexts, summed before one mod-down (no reference counterpart): out item b = base item b (or
+    // zero) + sum_r rgsw[r] (.) ins[r] item b, which decrypts to base + sum_r m_r mu_r.  rgsw[r]: device [2][K-1][2][K][N], two key-switching keys (half 0
+    // for the digits of c0, half 1 for those of c1), shared by the batch.  BFV / BGV, size 2, coefficient form, any data level, per-prime keys; limbs,
+    // scale and correction factor are the operands', which all agree with each other and the base.  The digits of both polynomials of every term are
+    // expanded (ks_expand_digits), ONE inner product runs over all 2 R dl of them (at most 16 terms per launch, later launches accumulating) and
+    // ks_acc_to_ct runs ONCE per item.  out.data / out.bstride are the caller's, distinct from every operand and the base.  1 <= count <= 64.  The arena
+    // request stays under scratch_limit_words (0: 2^28 words): slabs of items, chunks of terms; the limbs depend on the multiset of (operand, RGSW)
+    // pairs and the base only -- not on the order of the terms, the chunks, the batch size or the limit.
+    void external_product_sum(const CtBatch *ins, const u64 *const *rgsw, int count, const CtBatch *base, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s);
+    u64 external_product_sum_scratch_words(int limbs, int count, u64 batch) const; // what it asks of the arena with the batch in one slab, min(count, 16) terms a chunk
     // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
     // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
     static PolyPlan plan_polynomial(int degree, int baby_steps);

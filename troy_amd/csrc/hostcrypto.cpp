@@ -183,6 +183,18 @@ void keygen_kswitch(const Context &c, Rng &rng, const u64 *sk, const u64 *new_ke
         }
     }
 }
+void keygen_rgsw(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, const u64 *m, u64 *out) {
+    const size_t N = c.N, K = c.K;
+    if (K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    Rng r0(seed_lo, seed_hi, (u64)5 << 32), r1(seed_lo + 1, seed_hi, (u64)5 << 32); // one seed never serves two keys
+    keygen_kswitch(c, r0, sk, m, out);
+    std::vector<u64> ms(K * N);
+    for (size_t l = 0; l < K; l++) {
+        const Mod md = make_mod(c.primes[l]);
+        for (size_t i = 0; i < N; i++) ms[l * N + i] = mulmod(m[l * N + i], sk[l * N + i], md);
+    }
+    keygen_kswitch(c, r1, sk, ms.data(), out + (K - 1) * 2 * K * N);
+}
 void relin_source(const Context &c, const u64 *sk, u64 *out) { // s^2 (keygenerator.cpp:228-262)
     for (int l = 0; l < c.K; l++) {
         const Mod m = make_mod(c.primes[l]);

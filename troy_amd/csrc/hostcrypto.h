@@ -22,6 +22,9 @@ void ntt_inverse(u64 *a, const host::NttTable &t);
 void keygen_secret(const Context &c, Rng &rng, u64 *sk);                                   // [K][N] NTT form
 void keygen_public(const Context &c, Rng &rng, const u64 *sk, u64 *pk);                    // [2][K][N] NTT form
 void keygen_kswitch(const Context &c, Rng &rng, const u64 *sk, const u64 *new_key, u64 *out, int alpha = 1); // [K-1][2][K][N]; alpha special primes: [ceil((K - alpha) / alpha)][2][K][N]
+// RGSW ciphertext of the plaintext m ([K][N], NTT form at the key level): out [2][K-1][2][K][N], half 0 = keygen_kswitch of m from
+// the stream (seed_lo, seed_hi, 5 << 32), half 1 = keygen_kswitch of m (.) sk from (seed_lo + 1, seed_hi, 5 << 32)
+void keygen_rgsw(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, const u64 *m, u64 *out);
 void relin_source(const Context &c, const u64 *sk, u64 *out);
 void galois_source(const Context &c, const u64 *sk, uint32_t elt, u64 *out);
 void encrypt(const Context &c, Rng &rng, const u64 *pk, const u64 *plain, size_t n_coeffs, int limbs, u64 *ct);

@@ -252,6 +252,13 @@ void launch_hoist_sum(const u64 *D, const u64 *ckks_target, u64 t_bstride, u64 *
 // at u + r * u_rstride + b * u_bstride; elt_inv is filled by the launcher
 struct BsgsBaseArgs { uint32_t elt[HOIST_MAX_ROT], elt_inv[HOIST_MAX_ROT]; u32 rots, accumulate; };
 void launch_bsgs_base(bool ntt_form, const u64 *u, u64 u_rstride, u64 u_bstride, u64 *base, u64 base_bstride, const KsArgs &a, BsgsBaseArgs h, hipStream_t s);
+// external product with RGSW ciphertexts: the inner product of launch_ks_mac over TWO digit sets per term (those of c0 and of c1)
+// against the two keys of the term's RGSW ([2][K-1][2][K][N], half h at + h (K-1) 2 K N), summed over the terms of the launch:
+//   acc[b * 2 + k][i][n] (+)= sum_r sum_h sum_j D_r[b, h][i][j][n] * rgsw[r][h][j][k][limb(i)][n] mod p_i
+// D_r[b, h]: the digits ks_expand_digits wrote for polynomial h of item b of term r, [dl + 1][dl][N] at D[r] + b * d_bstride[r] + h * d_hstride[r];
+// accumulate: start from the canonical words acc holds.  One RGSW per term, shared by the batch.
+struct ExtProdArgs { const u64 *rgsw[HOIST_MAX_ROT]; const u64 *D[HOIST_MAX_ROT]; u64 d_bstride[HOIST_MAX_ROT], d_hstride[HOIST_MAX_ROT]; u32 terms, accumulate; };
+void launch_extprod_mac(u64 *acc, const KsArgs &a, const ExtProdArgs &h, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

@@ -168,4 +168,21 @@ void DeviceKeygen::kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind
     }
 }
 
+void DeviceKeygen::rgsw(u64 seed_lo, u64 seed_hi, const u64 *sk, const u64 *const *plains, u64 *const *outs, u64 count, u64 *tmp, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    if (!sk || !plains || !outs || !tmp) throw Error(ST_INVALID_ARGUMENT, "null key, plaintext list or RGSW output");
+    if (!count || count > 65535) throw Error(ST_INVALID_ARGUMENT, "batch must lie in 1 .. 65535");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    for (u64 i = 0; i < count; i++)
+        if (!plains[i] || !outs[i]) throw Error(ST_INVALID_ARGUMENT, "null key, plaintext list or RGSW output");
+    const u64 K = (u64)c.K, kw = K * c.N, half = (K - 1) * 2 * kw, sid = (u64)5 << 32; // the stream of troyhip_host_kswitch_key
+    for (u64 i = 0; i < count; i++) {
+        u64 *h0 = outs[i], *h1 = outs[i] + half;
+        kswitch(seed_lo + 2 * i, seed_hi, sk, 3, plains[i], &sid, nullptr, &h0, 1, s);
+        launch_copy_strided(plains[i], kw, tmp, kw, kw, 1, s); // m (.) s, a dyadic product in NTT form
+        launch_mul_plain(tmp, sk, c.d_desc, c.ct_map((int)K), c.logn, K, K, s);
+        kswitch(seed_lo + 2 * i + 1, seed_hi, sk, 3, tmp, &sid, nullptr, &h1, 1, s);
+    }
+}
+
 } // namespace troyhip

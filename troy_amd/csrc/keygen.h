@@ -21,6 +21,10 @@ public:
     // src_kind 1: s^2 (relin), 2: sigma_elts[i](s) (Galois), 3: new_key (device [K][N]).  streams / elts / outs are HOST arrays, read before return
     void kswitch(u64 seed_lo, u64 seed_hi, const u64 *sk, int src_kind, const u64 *new_key, const u64 *streams, const uint32_t *elts, u64 *const *outs, u64 count,
                  hipStream_t s, int alpha = 1); // alpha special primes: keys of ceil((K - alpha) / alpha) grouped digits
+    // `count` RGSW ciphertexts: outs[i] ([2][K-1][2][K][N], device) = the key-switching keys of plains[i] (device [K][N], NTT form
+    // at the key level) from seed (seed_lo + 2 i, seed_hi) and of plains[i] (.) sk from seed (seed_lo + 2 i + 1, seed_hi), both on the stream of
+    // troyhip_host_kswitch_key: byte for byte hostcrypto::keygen_rgsw.  tmp: device [K][N], for the dyadic product.  plains / outs are HOST arrays
+    void rgsw(u64 seed_lo, u64 seed_hi, const u64 *sk, const u64 *const *plains, u64 *const *outs, u64 count, u64 *tmp, hipStream_t s);
 
 private:
     Context &c;

@@ -1245,6 +1245,107 @@ template <bool NTT> __global__ __launch_bounds__(EW_THREADS) void bsgs_base_kern
         *o = res;
     }
 }
+// External product with RGSW ciphertexts: ks_mac_kernel's inner product over TWO digit sets per term -- the digits of c0 against
+// half 0 of the term's RGSW, those of c1 against half 1 -- summed over the terms of the launch inside the thread,
+//   acc[b * 2 + k][i][n] (+)= sum_r sum_h sum_j D_r[b, h][i][j][n] * rgsw_r[h][j][k][limb(i)][n] mod p_i,
+// so one accumulator per item reaches memory whatever the number of terms.  Thread-to-(i, n) mapping and block order (batch group fastest: the workgroups
+// in flight share a narrow window of the RGSWs) are ks_mac_kernel's, and so are the two instances, NB * V == 4 accumulators per key component:
+//   NB == 4, V == 1: four batch items of one coefficient -- every key word is used four times (the batched caller: one RGSW multiplies every column);
+//   NB == 1, V == 4: four consecutive coefficients of ONE item with 16-byte loads -- no accumulator idles (one or two ciphertexts).
+// Bounds.  A MacAcc sum holds fewer than 64 products of operands below 2^61: a run of products ends (one Barrett step per accumulator) before it would pass
+// 63.  A half is dl <= 63 products, so for dl <= 31 a run holds at least one whole term and a launch of at most HOIST_MAX_ROT = 16 terms ends at most 16
+// runs: their canonical words, below 2^60, are summed in 64 bits, below 2^64, and reduced ONCE at the end.  For dl >= 32 every half is a run of its own
+// (32 per launch), and each is added canonically (addmod) instead.  `accumulate` adds the launch's canonical sum to the canonical word acc holds.
+__device__ __forceinline__ void extprod_end_run(MacAcc (&s0)[4], MacAcc (&s1)[4], u64 (&o0)[4], u64 (&o1)[4], const Mod &m, bool canonical) {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const U128 v0 = mac_value(s0[t]), v1 = mac_value(s1[t]);
+        const u64 r0 = barrett128(v0.lo, v0.hi, m), r1 = barrett128(v1.lo, v1.hi, m);
+        o0[t] = canonical ? addmod(o0[t], r0, m.p) : o0[t] + r0;
+        o1[t] = canonical ? addmod(o1[t], r1, m.p) : o1[t] + r1;
+        mac_zero(s0[t]);
+        mac_zero(s1[t]);
+    }
+}
+template <int NB, int V> __global__ __launch_bounds__(EW_THREADS) void extprod_mac_kernel(u64 *acc, KsArgs a, ExtProdArgs h) {
+    static_assert(NB * V == 4 && (V == 1 || V == 4), "mac4 works on four accumulators");
+    const u64 N = u64(1) << a.logn, rl = a.dl + 1, KN = a.K * N;
+    constexpr int logv = V == 4 ? 2 : 0;
+    const u64 groups = (a.batch + NB - 1) / NB;
+    const u64 g = blockIdx.x % groups, wi = blockIdx.x / groups;         // wi = i * windows + window
+    const u64 idx = wi * EW_THREADS + threadIdx.x;                       // over (dl + 1) * (N / V)
+    if (idx >= rl << (a.logn - logv)) return;
+    const u64 n = (idx & ((N >> logv) - 1)) << logv, i = idx >> (a.logn - logv), b0 = g * NB;
+    const Mod m = mod_of(a.primes[a.key_id[i]]);
+    const u64 row = (a.key_limb[i] << a.logn) + n, drow = ((i * a.dl) << a.logn) + n;
+    u64 bb[NB]; // a ragged last group recomputes its last item and stores nothing for it
+#pragma unroll
+    for (int b = 0; b < NB; b++) bb[b] = b0 + b < a.batch ? b0 + b : a.batch - 1;
+    const bool canonical = a.dl > 31;
+    MacAcc s0[4], s1[4];
+    u64 o0[4], o1[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) { mac_zero(s0[t]); mac_zero(s1[t]); o0[t] = o1[t] = 0; }
+    u32 run = 0; // products in the open run
+    const u32 halves = 2 * h.terms;
+#pragma unroll 1
+    for (u32 q = 0; q <= halves; q++) { // half q = (term q / 2, polynomial q & 1); the pass q == halves only ends the last run
+        if (q == halves || run + (u32)a.dl > 63) {
+            extprod_end_run(s0, s1, o0, o1, m, canonical);
+            run = 0;
+            if (q == halves) break;
+        }
+        const u32 r = q >> 1, hh = q & 1;
+        const u64 *key = h.rgsw[r] + hh * (a.K - 1) * 2 * KN + row;
+        const u64 *dig = h.D[r] + hh * h.d_hstride[r] + drow;
+        const u64 dbs = h.d_bstride[r];
+        for (u64 j = 0; j < a.dl; j++) {
+            const u64 *kp = key + j * 2 * KN;
+            u64 k0[4], k1[4], x[4];
+            if (V == 4) {
+                const ulonglong2 t0 = *reinterpret_cast<const ulonglong2 *>(kp), t1 = *reinterpret_cast<const ulonglong2 *>(kp + 2);
+                const ulonglong2 u0 = *reinterpret_cast<const ulonglong2 *>(kp + KN), u1 = *reinterpret_cast<const ulonglong2 *>(kp + KN + 2);
+                const u64 *xp = dig + bb[0] * dbs + (j << a.logn);
+                const ulonglong2 x0 = *reinterpret_cast<const ulonglong2 *>(xp), x1 = *reinterpret_cast<const ulonglong2 *>(xp + 2);
+                k0[0] = t0.x; k0[1] = t0.y; k0[2] = t1.x; k0[3] = t1.y;
+                k1[0] = u0.x; k1[1] = u0.y; k1[2] = u1.x; k1[3] = u1.y;
+                x[0] = x0.x; x[1] = x0.y; x[2] = x1.x; x[3] = x1.y;
+            } else {
+                const u64 t0 = kp[0], t1 = kp[KN];
+#pragma unroll
+                for (int b = 0; b < NB; b++) {
+                    k0[b] = t0; k1[b] = t1;
+                    x[b] = dig[bb[b] * dbs + (j << a.logn)];
+                }
+            }
+            mac4(s0, x, k0);
+            mac4(s1, x, k1);
+        }
+        run += (u32)a.dl;
+    }
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        if (b0 + b >= a.batch) break;
+        u64 *p0 = acc + (((b0 + b) * 2 + 0) * rl + i) * N + n, *p1 = acc + (((b0 + b) * 2 + 1) * rl + i) * N + n;
+        u64 r0[V], r1[V];
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+            r0[v] = barrett64(o0[b * V + v], m);
+            r1[v] = barrett64(o1[b * V + v], m);
+            if (h.accumulate) { r0[v] = addmod(r0[v], p0[v], m.p); r1[v] = addmod(r1[v], p1[v], m.p); } // the canonical words an earlier launch of this call stored
+        }
+        if (V == 4) {
+            constexpr int c1 = V == 4 ? 1 : 0, c2 = V == 4 ? 2 : 0, c3 = V == 4 ? 3 : 0; // V == 1 never comes here; its arrays hold one word
+            ulonglong2 t;
+            t.x = r0[0]; t.y = r0[c1]; *reinterpret_cast<ulonglong2 *>(p0) = t;
+            t.x = r0[c2]; t.y = r0[c3]; *reinterpret_cast<ulonglong2 *>(p0 + 2) = t;
+            t.x = r1[0]; t.y = r1[c1]; *reinterpret_cast<ulonglong2 *>(p1) = t;
+            t.x = r1[c2]; t.y = r1[c3]; *reinterpret_cast<ulonglong2 *>(p1 + 2) = t;
+        } else {
+            p0[0] = r0[0]; p1[0] = r1[0];
+        }
+    }
+}
 // BFV (kind 0) / BGV (kind 2) mod-down, everything in coefficient form (evaluator.cpp:2528-2648):
 //   ct[b][k][j][n] += (acc_j - [t']_{q_j} + [half]_{q_j}) * qk^-1 mod q_j, t' = (acc_last + half) mod qk       (BFV)
 //   ct[b][k][j][n] += (acc_j - [acc_last]_{q_j} - [k_t]_{q_j} * qk) * qk^-1,  k_t = -acc_last * qk^-1 mod t     (BGV)
@@ -1400,6 +1501,24 @@ void launch_bsgs_base(bool ntt_form, const u64 *u, u64 u_rstride, u64 u_bstride,
     if (ntt_form) TROY_LAUNCH(HIP_KERNEL_NAME(bsgs_base_kernel<true>), grid, dim3(EW_THREADS), 0, s, u, u_rstride, u_bstride, base, base_bstride, a, h);
     else TROY_LAUNCH(HIP_KERNEL_NAME(bsgs_base_kernel<false>), grid, dim3(EW_THREADS), 0, s, u, u_rstride, u_bstride, base, base_bstride, a, h);
     launch_check("bsgs_base_kernel");
+}
+void launch_extprod_mac(u64 *acc, const KsArgs &a, const ExtProdArgs &h, hipStream_t s) {
+    if (a.dl >= 64) throw Error(ST_LOGIC_ERROR, "extprod_mac: more than 63 digits");
+    if (!acc || !h.terms || h.terms > HOIST_MAX_ROT || !a.batch) throw Error(ST_LOGIC_ERROR, "extprod_mac: 1 .. 16 terms of a non-empty batch per launch");
+    const u64 dw = ((a.dl + 1) * a.dl) << a.logn; // the digits of one polynomial
+    // one or two ciphertexts: four coefficients per thread, every accumulator useful; a batch: four items per thread share each key word.  The
+    // 16-byte loads need 16-byte rows: every offset is a multiple of N words, so the pointers decide
+    bool vec = a.batch <= 2 && a.logn >= 2 && !((uintptr_t)acc & 15);
+    for (u32 r = 0; r < h.terms; r++) {
+        if (!h.rgsw[r] || !h.D[r] || h.d_hstride[r] < dw || h.d_bstride[r] < dw) throw Error(ST_LOGIC_ERROR, "extprod_mac: every term takes an RGSW and two digit sets per item");
+        vec = vec && !(((uintptr_t)h.rgsw[r] | (uintptr_t)h.D[r]) & 15);
+    }
+    const u64 windows = ceil_div((a.dl + 1) << (a.logn - (vec ? 2 : 0)), EW_THREADS);
+    const u64 blocks = windows * (vec ? a.batch : (a.batch + 3) / 4); // a flat x grid: nothing else grows with the batch, and the terms are walked inside
+    if (blocks > 0x7fffffffull) throw Error(ST_INVALID_ARGUMENT, "extprod_mac: batch too large for one launch");
+    if (vec) TROY_LAUNCH(HIP_KERNEL_NAME(extprod_mac_kernel<1, 4>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, acc, a, h);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(extprod_mac_kernel<4, 1>), dim3((unsigned)blocks), dim3(EW_THREADS), 0, s, acc, a, h);
+    launch_check("extprod_mac_kernel");
 }
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s) {
     u64 total = a.batch * 2 * a.dl << a.logn;
