@@ -446,7 +446,9 @@ def test_cfgE_ckks_matmul_semantics(gpu, oracle_lib):
 @pytest.mark.parametrize("name", ["cfgA_bfv_n4096_k3", "bgv_n4096_k3", "cfgB_bfv_n8192_k5"])
 def test_plain_operands_monomial_and_per_item(name, gpu, oracle_lib):
     """addPlain / subPlain / multiplyPlain (coefficient form) / transformToNtt(Plaintext) with one plaintext per
-    batch row, and the one-coefficient plaintext under the CUDA evaluator's semantics; vs the CPU oracle, bit-exact"""
+    batch row, and the one-coefficient plaintext under the CUDA evaluator's semantics; vs the CPU oracle, bit-exact.  Uniform plaintexts under a 20-bit
+    batching prime, first level: the rounding, lift and correction-factor boundaries, the lower levels and the wide plain moduli are
+    tests/test_gpu_plain.py's (tests/plain_cases.py)"""
     cases.check_plain_monomial_and_batch(name)
 
 
