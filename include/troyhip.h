@@ -315,6 +315,21 @@ int troyhip_multiply_plain_ntt(troyhip_context *ctx, troyhip_ct *ct, const uint6
  * (app/LinearHelperCKKS.cuh:227-248 MatmulHelper::matmul, :536-556 Conv2dHelper::conv2d): same residues, every operand read once. */
 int troyhip_multiply_plain_accumulate(troyhip_context *ctx, const troyhip_ct *const *cts, const uint64_t *const *plains, int count, double plain_scale, troyhip_ct *out,
                                       uint64_t batch, void *stream);
+/* Plaintext matrix times ciphertext vector in ONE launch (no reference counterpart): for every column c < cols
+ *   out[c] item b = sum_{r < rows} in[r] item b (x) plains[r][c],   out[c][b][k][l][n] = sum_r in[r][b][k][l][n] * plains[r][c][l][n] mod p_l,
+ * the database scan of a PIR server (out_c = sum_r db[r][c] * query_r) and the coefficient-packed linear layer.  Every stored word is canonical.
+ * Operand r, item b lies at in->data + r * in_row_stride + b * in->batch_stride ([size][limbs][N], NTT form, size 2 or 3, any data level, every scheme):
+ * the layout troyhip_expand_coefficients returns is in_row_stride = batch * 2 * limbs * N; items that leave room for a third polynomial are accepted.
+ * plains[r][c], [limbs][N] in NTT form, lies at plains + r * plain_row_stride + c * plain_col_stride.  Result c, item b goes to out->data + c * out_col_stride +
+ * b * out->batch_stride; out->data and ->batch_stride are INPUTS, the call sets size, limbs, form (NTT), scale = in->scale * plain_scale (CKKS: "scale out of
+ * bounds" as troyhip_multiply_plain_ntt) and the operand's correction factor.  1 <= rows <= 4096, 1 <= cols <= 2^20; batch == 0 does nothing.
+ * Strides are even (16-byte accesses), no smaller than the item they address, and the (column, item) results share no word; the destination's extent
+ * shares no word with the operand's or the plaintexts' ("destination must be a distinct buffer").  A refused call writes nothing.
+ * The bytes are those of troyhip_multiply_plain_accumulate over chunks of the rows followed by troyhip_add, and do not depend on the batch size, the
+ * number of columns or the order of the rows.  No scratch; stream-ordered.  Counters (troyhip_stat): "plainmat_launches", launches so far;
+ * "plainmat_workgroups", the workgroups of their grids.  Strides are at most 2^36 words and batch * batch_stride at most 2^56. */
+int troyhip_multiply_plain_matrix(troyhip_context *ctx, const troyhip_ct *in, uint64_t in_row_stride, int rows, const uint64_t *plains, uint64_t plain_row_stride,
+                                  uint64_t plain_col_stride, int cols, double plain_scale, troyhip_ct *out, uint64_t out_col_stride, uint64_t batch, void *stream);
 /* Sum of ciphertext products, relinearized once (lazy relinearization and lazy scale-down; no reference counterpart):
  *   out item i = sum_{r < count} a_descs[r] item i (x) b_descs[r] item i,   a size-3 ciphertext; ONE troyhip_relinearize (CKKS: and one rescale) follows.
  * 1 <= count <= 16 pairs of batches of size-2 ciphertexts, all at one level, in the form troyhip_multiply takes for the scheme, `batch` items each.  An

@@ -1006,6 +1006,26 @@ private:
     ParmsID parms_id_;
 };
 
+// A rows x cols matrix of NTT-form plaintexts of one level and one scale in ONE device array [rows][cols][limbs][N] (the reference has none; DESIGN.md
+// section 4.21): what Evaluator::multiplyPlainMatrix streams.  Evaluator::packPlainMatrix makes one; a database that is scanned many times is packed once.
+class PlainMatrix {
+public:
+    PlainMatrix() = default;
+    PlainMatrix(size_t rows, size_t cols, size_t plain_words, double scale, const ParmsID &parms_id, std::shared_ptr<DeviceArray> words)
+        : rows_(rows), cols_(cols), plain_words_(plain_words), scale_(scale), parms_id_(parms_id), words_(std::move(words)) {}
+    size_t rows() const noexcept { return rows_; }
+    size_t cols() const noexcept { return cols_; }
+    size_t plainWords() const noexcept { return plain_words_; } // limbs * N
+    double scale() const noexcept { return scale_; }
+    const ParmsID &parmsID() const noexcept { return parms_id_; }
+    const uint64_t *device() const { return words_ ? words_->get() : nullptr; }
+private:
+    size_t rows_ = 0, cols_ = 0, plain_words_ = 0;
+    double scale_ = 1.0;
+    ParmsID parms_id_;
+    std::shared_ptr<DeviceArray> words_;
+};
+
 // LWECiphertextCuda (src/lwe_cuda.cuh): the LWE sample (c1: one polynomial [limbs][N] in coefficient form, c0: one word per limb)
 // that extractLWE cuts out of an RLWE ciphertext
 class LWECiphertext {
@@ -2422,6 +2442,74 @@ public:
         check(troyhip_multiply_plain_accumulate(h(), ct_ptrs.data(), pl_ptrs.data(), (int)count, plains[0]->scale(), &t, batch, nullptr));
         for (auto &c : out) c.copyMeta(t);
         return out;
+    }
+    // Plaintext matrix times ciphertext vector (troyhip_multiply_plain_matrix; the reference has no such call):
+    //   out[c] = sum_r cts[r] (x) plains[r][c]   for every column c, in ONE launch --
+    // the database scan of a PIR server (cts = the expanded query), a coefficient-packed linear layer without its cap of 16 input blocks.  Same residues as
+    // the multiplyPlainAccumulate + addInplace loop per column.  NTT-form operands of one level, NTT-form plaintexts of that level and one scale.
+    PlainMatrix packPlainMatrix(const std::vector<std::vector<const Plaintext *>> &plains) const {
+        if (plains.empty() || plains[0].empty()) throw std::invalid_argument("packPlainMatrix: at least one row and one column");
+        const size_t R = plains.size(), C = plains[0].size();
+        const Plaintext &head = *plains[0][0];
+        const size_t pw = head.coeffCount();
+        auto words = std::make_shared<DeviceArray>(R * C * pw);
+        for (size_t r = 0; r < R; r++) {
+            if (plains[r].size() != C) throw std::invalid_argument("packPlainMatrix: rows of different length");
+            for (size_t c = 0; c < C; c++) {
+                const Plaintext &p = *plains[r][c];
+                if (!p.isNttForm()) throw std::invalid_argument("NTT form mismatch");
+                if (p.parmsID() != head.parmsID() || p.coeffCount() != pw) throw std::invalid_argument("encrypted_ntt and plain_ntt parameter mismatch");
+                if (p.scale() != head.scale()) throw std::invalid_argument("scale mismatch");
+                check(troyhip_copy_d2d(words->get() + (r * C + c) * pw, p.device(), pw * 8, nullptr));
+            }
+        }
+        return PlainMatrix(R, C, pw, head.scale(), head.parmsID(), words);
+    }
+    // over batches: rows[r] is a run of `batch` ciphertexts; item i of out[c] = sum_r rows[r][i] (x) m[r][c].  Rows that are consecutive runs of ONE slab
+    // (Ciphertext::allocateBatch(rows * batch, ..), row after row) are used where they lie; anything else is packed first (one copy per ciphertext).
+    std::vector<std::vector<Ciphertext>> multiplyPlainMatrixBatch(const std::vector<std::vector<const Ciphertext *>> &rows, const PlainMatrix &m) const {
+        if (rows.empty() || rows.size() != m.rows() || rows.size() > 4096) throw std::invalid_argument("multiplyPlainMatrixBatch: one run of ciphertexts per row of the matrix, 1 to 4096");
+        const size_t R = rows.size(), C = m.cols(), batch = rows[0].size();
+        if (!batch) return std::vector<std::vector<Ciphertext>>(C);
+        std::vector<const Ciphertext *> all;
+        for (const auto &row : rows) {
+            if (row.size() != batch) throw std::invalid_argument("multiplyPlainMatrixBatch: operand counts differ");
+            all.insert(all.end(), row.begin(), row.end());
+        }
+        const Ciphertext &head = *all[0];
+        if (!head.isNttForm()) throw std::invalid_argument("NTT form mismatch");
+        if (head.parmsID() != m.parmsID() || m.plainWords() != head.coeffModulusSize() * head.polyModulusDegree()) throw std::invalid_argument("encrypted_ntt and plain_ntt parameter mismatch");
+        std::vector<Ciphertext> packed;
+        if (!Ciphertext::isBatch(all)) {
+            packed = Ciphertext::packBatch(all);
+            all = Ciphertext::pointers(static_cast<const std::vector<Ciphertext> &>(packed));
+        }
+        const troyhip_ct in = *all[0]->raw();
+        std::vector<Ciphertext> flat = Ciphertext::allocateBatch(C * batch, *all[0]);
+        troyhip_ct t = *flat[0].raw();
+        check(troyhip_multiply_plain_matrix(h(), &in, batch * in.batch_stride, (int)R, m.device(), C * m.plainWords(), m.plainWords(), (int)C, m.scale(), &t,
+                                            batch * t.batch_stride, batch, nullptr));
+        std::vector<std::vector<Ciphertext>> out(C);
+        for (size_t c = 0; c < C; c++)
+            for (size_t b = 0; b < batch; b++) {
+                flat[c * batch + b].copyMeta(t);
+                out[c].push_back(std::move(flat[c * batch + b]));
+            }
+        return out;
+    }
+    std::vector<std::vector<Ciphertext>> multiplyPlainMatrixBatch(const std::vector<std::vector<const Ciphertext *>> &rows, const std::vector<std::vector<const Plaintext *>> &plains) const {
+        return multiplyPlainMatrixBatch(rows, packPlainMatrix(plains));
+    }
+    // one ciphertext per row -> one ciphertext per column
+    std::vector<Ciphertext> multiplyPlainMatrix(const std::vector<const Ciphertext *> &cts, const PlainMatrix &m) const {
+        std::vector<std::vector<const Ciphertext *>> rows;
+        for (const Ciphertext *c : cts) rows.push_back({c});
+        std::vector<Ciphertext> out;
+        for (auto &col : multiplyPlainMatrixBatch(rows, m)) out.push_back(std::move(col[0]));
+        return out;
+    }
+    std::vector<Ciphertext> multiplyPlainMatrix(const std::vector<const Ciphertext *> &cts, const std::vector<std::vector<const Plaintext *>> &plains) const {
+        return multiplyPlainMatrix(cts, packPlainMatrix(plains));
     }
     void addInplaceBatch(std::vector<Ciphertext> &acc, const std::vector<Ciphertext> &x) const {
         if (acc.size() != x.size()) throw std::invalid_argument("Size incorrect.");

@@ -1327,6 +1327,53 @@ class Evaluator:
         out._absorb(st)
         return out
 
+    # -- plaintext matrix times ciphertext vector (troyhip_multiply_plain_matrix: no reference counterpart)
+    def multiplyPlainMatrix(self, cts, plains, rows, cols, plain_scale=1.0, plain_row_stride=None, plain_col_stride=None, out_col_stride=None):
+        """out[c] = sum_{r < rows} cts[r] (x) plains[r][c] for every column c in ONE launch: the database scan of a PIR server, a coefficient-packed
+        linear layer.  cts: a list of `rows` NTT-form Ciphertext batches of one shape that are windows of one buffer a constant stride apart (what
+        expandCoefficients returns), or ONE Ciphertext whose rows * B items lie row after row.  plains: DeviceBuffer [rows][cols][limbs][N] in NTT
+        form (other strides in words: plain_row_stride, plain_col_stride).  Returns `cols` Ciphertext batches of B items, windows of one buffer
+        (out_col_stride words apart; the default is dense)."""
+        rows, cols = int(rows), int(cols)
+        bad = lambda msg: capi.InvalidArgument(capi.INVALID_ARGUMENT, "multiplyPlainMatrix: " + msg)  # noqa: E731
+        if isinstance(cts, Ciphertext):
+            a0 = cts
+            if rows < 1 or a0.batch % rows:
+                raise bad("the items of the operand are not `rows` rows of one batch")
+            B = a0.batch // rows
+            row_stride = B * a0.bstride
+        else:
+            cts = list(cts)
+            if rows < 1 or len(cts) != rows:
+                raise bad("one operand per row")
+            a0 = cts[0]
+            B = a0.batch
+            shape = lambda a: (a.batch, a.size(), a.limbs, a.capacity, a.is_ntt_form, a.scale, a.correction_factor)  # noqa: E731
+            steps = {b.buf.ptr - a.buf.ptr for a, b in zip(cts, cts[1:])}
+            if any(shape(a) != shape(a0) for a in cts) or len(steps) > 1 or any(d <= 0 or d % 8 for d in steps):
+                raise bad("the operands are not windows of one buffer with a common stride")
+            row_stride = steps.pop() // 8 if steps else B * a0.bstride
+        N, limbs, size = self.context.N, a0.limbs, a0.size()
+        item = size * limbs * N
+        prs = cols * limbs * N if plain_row_stride is None else int(plain_row_stride)
+        pcs = limbs * N if plain_col_stride is None else int(plain_col_stride)
+        ocs = B * item if out_col_stride is None else int(out_col_stride)
+        if ocs < B * item or cols < 1:
+            raise bad("the column stride is smaller than one batch" if cols >= 1 else "at least one column")
+        if plains.words < (rows - 1) * prs + (cols - 1) * pcs + limbs * N:
+            raise bad("the plaintext buffer is smaller than rows x cols plaintexts")
+        buf = DeviceBuffer(cols * ocs)
+        si = CtStruct(a0.buf.ptr, a0.bstride, size, limbs, int(a0.is_ntt_form), a0.scale, a0.correction_factor)
+        so = CtStruct(buf.ptr, item, 0, 0, 0, 0.0, 0)
+        self._chk(self.lib.troyhip_multiply_plain_matrix(self.context.h, C.byref(si), C.c_uint64(row_stride), rows, C.c_void_p(plains.ptr), C.c_uint64(prs), C.c_uint64(pcs), cols,
+                                                         C.c_double(plain_scale), C.byref(so), C.c_uint64(ocs), C.c_uint64(B), self.stream))
+        out = []
+        for c in range(cols):
+            ct = Ciphertext(self.context, B, size, limbs, buf=_BufferWindow(buf, c * ocs, B * item))
+            ct._absorb(so)
+            out.append(ct)
+        return out
+
     # ---- plaintext operands in coefficient form (evaluator_cuda.cu:1654-1948).  plain: DeviceBuffer holding either ONE
     # plaintext (n_coeffs coefficients mod t; CKKS: [limbs][N] NTT rows) or one per batch item (per_item=True, back to back)
     def _plain_stride(self, a, n_coeffs, per_item):

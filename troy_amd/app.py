@@ -445,3 +445,129 @@ class DiagonalMatvecBSGS:
         name = ("rotateVector" if self.context.scheme == capi.CKKS else "rotateRows") + "PlainSumBsgs" + ("Grouped" if galois_keys.special_primes is not None else "")
         fn = getattr(evaluator, name)
         return fn(ct, self.baby_steps, self.giant_steps, self.plains, galois_keys, self.plain_scale)
+
+
+# ---------------------------------------------------------------- private information retrieval
+# A composition of public calls: the client sends ONE ciphertext and d RGSW ciphertexts, the server expands the first (Evaluator.expandCoefficients),
+# scans the database with it (Evaluator.multiplyPlainMatrix) and folds the columns with the RGSWs (Evaluator.cmux).  The database holds D0 * 2^d
+# records, each a plaintext polynomial of N coefficients mod t; record i = r + D0 * j lies at row r, column j.  BFV and BGV, per-prime keys.  The
+# client makes the RGSWs of the column bits itself: converting RLWE encryptions of the bits on the server is not part of this.
+def _pir_shape(context, D0, d):
+    D0, d = int(D0), int(d)
+    if context.scheme not in (capi.BFV, capi.BGV):
+        raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+    if D0 < 1 or D0 & (D0 - 1) or D0 > context.N or not 0 <= d <= 20:
+        raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: D0 is a power of two, at most N, and the database has D0 * 2^d records, d <= 20")
+    return D0, d
+
+
+def _window(ct, first, count):
+    """items first .. first + count - 1 of a dense batch, as a batch of their own (no copy)"""
+    item = ct.bstride
+    out = api.Ciphertext(ct.context, count, ct.size(), ct.limbs, ct.is_ntt_form, ct.scale, ct.correction_factor, ct.capacity,
+                         buf=api._BufferWindow(ct.buf, first * item, count * item))
+    return out
+
+
+class PIRClient:
+    def __init__(self, context, keygen, encryptor, decryptor, D0, d):
+        self.D0, self.d = _pir_shape(context, D0, d)
+        self.context, self.keygen, self.encryptor, self.decryptor = context, keygen, encryptor, decryptor
+
+    def galoisKeys(self):
+        """the keys the server's expansion needs: the elements KeyGenerator.expansionElts(D0), generated on the device"""
+        elts = self.keygen.expansionElts(self.D0)
+        return self.keygen.createGaloisKeys(elts, device=True) if elts else api.GaloisKeys(self.context)
+
+    def query(self, i):
+        """record i = r + D0 * j -> (one Ciphertext encrypting the monomial x^r, d RGSWCiphertexts of the bits of j, the highest bit first)"""
+        i = int(i)
+        if not 0 <= i < self.D0 << self.d:
+            raise capi.OutOfRange(capi.OUT_OF_RANGE, "PIR: no such record")
+        r, j = i % self.D0, i // self.D0
+        mono = np.zeros(r + 1, dtype=np.uint64)
+        mono[r] = 1
+        ct = api.Ciphertext.from_numpy(self.context, self.encryptor.encrypt(mono)[None])
+        bits = [np.array([(j >> (self.d - 1 - k)) & 1], dtype=np.uint64) for k in range(self.d)]
+        return ct, self.keygen.createRGSWBatch(bits)
+
+    def recover(self, answer):
+        """the record an answer (one ciphertext, coefficient form) encrypts: N coefficients mod t"""
+        return self.decryptor.decrypt(answer.cpu()[0], correction_factor=answer.correction_factor)
+
+    def noiseBudget(self, answer):
+        return self.decryptor.invariantNoiseBudget(answer.cpu()[0])
+
+
+class PIRServer:
+    def __init__(self, context, records, D0):
+        """records: uint64 [D0 * 2^d][N] (or fewer coefficients per record), coefficients mod t.  They are lifted and transformed ONCE, at the first data
+        level, into [D0][2^d][limbs][N] on the device"""
+        records = np.ascontiguousarray(records, dtype=np.uint64)
+        if records.ndim != 2 or records.shape[0] < 1 or records.shape[0] % int(D0) or not 1 <= records.shape[1] <= context.N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: records is [D0 * 2^d][up to N coefficients]")
+        cols = records.shape[0] // int(D0)
+        if cols & (cols - 1):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: D0 is a power of two, at most N, and the database has D0 * 2^d records, d <= 20")
+        self.D0, self.d = _pir_shape(context, D0, cols.bit_length() - 1)
+        self.context, self.cols, self.limbs = context, cols, context.first_limbs
+        self.evaluator = ev = api.Evaluator(context)
+        n = records.shape[1]
+        by_row = np.ascontiguousarray(records.reshape(cols, self.D0, n).transpose(1, 0, 2))  # record r + D0 * j -> [r][j]
+        self.plains = ev.transformPlainToNtt(api.DeviceBuffer.from_numpy(by_row), self.limbs, n_coeffs=n, count=self.D0 * cols)
+        api.synchronize()
+
+    def _scan(self, query, galois_keys):
+        """steps 1 - 4 on a batch of B queries -> ONE Ciphertext of cols * B items in coefficient form, column after column"""
+        ev = self.evaluator
+        if query.size() != 2 or query.is_ntt_form or query.limbs != self.limbs:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: a query is a fresh size-2 ciphertext in coefficient form at the first data level")
+        rows = ev.expandCoefficients(query, self.D0, galois_keys)
+        whole = api.Ciphertext(self.context, self.D0 * query.batch, 2, self.limbs, buf=rows[0].buf.owner)  # the rows are windows of one buffer, row after row
+        whole._absorb(rows[0].struct())
+        ev.transformToNttInplace(whole)
+        out = ev.multiplyPlainMatrix(whole, self.plains, self.D0, self.cols)
+        columns = api.Ciphertext(self.context, self.cols * query.batch, 2, self.limbs, buf=out[0].buf.owner)
+        columns._absorb(out[0].struct())
+        ev.transformFromNttInplace(columns)
+        return columns
+
+    def scan(self, query, galois_keys):
+        """the scan stage alone: `cols` ciphertexts, column j encrypting record r + D0 * j of the query's row r"""
+        columns = self._scan(query, galois_keys)
+        return [_window(columns, j * query.batch, query.batch) for j in range(self.cols)]
+
+    def _fold(self, columns, selectors):
+        """d rounds of cmux over the halves of the contiguous column buffer: the selector of the highest bit first"""
+        if len(selectors) != self.d:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: one selector per bit of the column index")
+        for sel in selectors:
+            half = columns.batch // 2
+            columns = self.evaluator.cmux(sel, _window(columns, 0, half), _window(columns, half, half))
+        return columns
+
+    def answer(self, query, selectors, galois_keys):
+        """one query -> one ciphertext encrypting the record"""
+        if query.batch != 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: answer takes one query; answerBatch takes several")
+        return self._fold(self._scan(query, galois_keys), selectors)
+
+    def answerBatch(self, queries, selectors, galois_keys):
+        """B clients: the expansion and the scan run once over the batch of their queries -- the database is streamed once for all of them -- and the
+        folds per client, because an RGSW multiplies every item of a batch"""
+        B = len(queries)
+        if B < 1 or len(selectors) != B or any(q.batch != 1 or q.bstride != queries[0].bstride for q in queries):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "PIR: one single query and one list of selectors per client")
+        q0 = queries[0]
+        item = q0.bstride
+        batch = api.Ciphertext(self.context, B, q0.size(), q0.limbs, q0.is_ntt_form, q0.scale, q0.correction_factor, q0.capacity)
+        for b, q in enumerate(queries):
+            batch.buf.copy_from(q.buf, item, 0, b * item)
+        columns = self._scan(batch, galois_keys)  # [cols][B]
+        out = []
+        for b in range(B):
+            mine = api.Ciphertext(self.context, self.cols, 2, self.limbs, columns.is_ntt_form, columns.scale, columns.correction_factor)
+            for j in range(self.cols):
+                mine.buf.copy_from(columns.buf, columns.bstride, (j * B + b) * columns.bstride, j * columns.bstride)
+            out.append(self._fold(mine, selectors[b]))
+        return out

@@ -66,6 +66,9 @@ SYMBOLS = [
     "troyhip_extract_lwes", "troyhip_pack_lwes", "troyhip_pack_lwes_scratch_words",
     "troyhip_expand_coefficients", "troyhip_expand_coefficients_grouped", "troyhip_expand_coefficients_scratch_words",
     "troyhip_external_product_sum", "troyhip_external_product_sum_scratch_words", "troyhip_host_rgsw", "troyhip_create_rgsw",
+    # (ctx, const troyhip_ct *in, u64 in_row_stride, int rows, const u64 *plains, u64 plain_row_stride, u64 plain_col_stride, int cols, double plain_scale,
+    #  troyhip_ct *out, u64 out_col_stride, u64 batch, stream)
+    "troyhip_multiply_plain_matrix",
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",

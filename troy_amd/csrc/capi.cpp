@@ -1044,6 +1044,18 @@ int troyhip_multiply_plain_accumulate(troyhip_context *ctx, const troyhip_ct *co
         store(o, out);
     });
 }
+/* plaintext matrix times ciphertext vector (no reference counterpart) */
+int troyhip_multiply_plain_matrix(troyhip_context *ctx, const troyhip_ct *in, uint64_t in_row_stride, int rows, const uint64_t *plains, uint64_t plain_row_stride,
+                                  uint64_t plain_col_stride, int cols, double plain_scale, troyhip_ct *out, uint64_t out_col_stride, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!in || !out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx); // the context is bound before the stream is looked at
+        const hipStream_t s = on(stream);
+        CtBatch x = view(in), o = view(out);
+        handle->ev.multiply_plain_matrix(x, in_row_stride, rows, plains, plain_row_stride, plain_col_stride, cols, plain_scale, o, out_col_stride, batch, s);
+        store(o, out);
+    });
+}
 int troyhip_multiply_sum(troyhip_context *ctx, const troyhip_ct *const *a_descs, const troyhip_ct *const *b_descs, int count, troyhip_ct *out_desc, uint64_t batch,
                          uint64_t scratch_limit_words, void *stream) {
     return guard([&] {

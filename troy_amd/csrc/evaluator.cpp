@@ -1266,6 +1266,48 @@ void Evaluator::multiply_plain_accumulate(const CtBatch *cts, const u64 *const *
     out.size = a0.size; out.limbs = a0.limbs; out.ntt = true; out.scale = new_scale; out.cf = a0.cf;
 }
 
+// Plaintext matrix times ciphertext vector (no reference counterpart): out[c] = sum_{r < rows} in[r] (x) plains[r][c] for every column in one
+// launch -- the database scan of a PIR server, the coefficient-packed linear layer.  Exact arithmetic on canonical residues: the bytes of the
+// multiply_plain_accumulate + add composition over the same operands, whatever the chunking.  No scratch; stream-ordered.
+void Evaluator::multiply_plain_matrix(const CtBatch &in, u64 in_rstride, int rows, const u64 *plains, u64 pl_rstride, u64 pl_cstride, int cols, double plain_scale, CtBatch &out,
+                                      u64 out_cstride, u64 batch, hipStream_t s) {
+    check_ct(in);
+    if (!in.ntt) throw Error(ST_INVALID_ARGUMENT, "encrypted_ntt is not in NTT form");
+    if (in.size != 2 && in.size != 3) throw Error(ST_INVALID_ARGUMENT, "encrypted size must be 2 or 3");
+    if (!plains) throw Error(ST_INVALID_ARGUMENT, "plain_ntt is not valid for encryption parameters");
+    if (rows < 1 || rows > 4096) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix takes 1 to 4096 rows");
+    if (cols < 1 || cols > (1 << 20)) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix takes 1 to 2^20 columns");
+    if (batch >> 28) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: too many items");
+    const u64 pw = poly_words(c, in.limbs), words = (u64)in.size * pw, R = (u64)rows, Cc = (u64)cols;
+    const double new_scale = in.scale * plain_scale;
+    if (c.scheme == SCHEME_CKKS && !scale_ok(new_scale, in.limbs)) throw Error(ST_INVALID_ARGUMENT, "scale out of bounds");
+    if (!out.data || out.bstride < words) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    // every extent below stays far from 2^64 BYTES: 4096 row strides and 2^20 column strides of at most 2^36 words are at most 2^56 words, and `batch` batch
+    // strides are held to 2^56 words as well -- an extent is below 2^58 words
+    const u64 max_stride = u64(1) << 36, max_bstride = std::min<u64>(max_stride, (u64(1) << 56) / std::max<u64>(batch, 1));
+    if (in_rstride > max_stride || in.bstride > max_bstride || pl_rstride > max_stride || pl_cstride > max_stride || out_cstride > max_stride || out.bstride > max_bstride)
+        throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: stride out of range");
+    if (rows > 1 && in_rstride < words) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: row stride is smaller than one ciphertext");
+    if ((rows > 1 && pl_rstride < pw) || (cols > 1 && pl_cstride < pw)) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: plaintext stride is smaller than one plaintext");
+    if (cols > 1 && out_cstride < words) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: column stride is smaller than one ciphertext");
+    if (batch) {
+        // the (column, item) results share no word: the columns lie item-major or the items column-major
+        if (cols > 1 && batch > 1 && out_cstride < (batch - 1) * out.bstride + words && out.bstride < (Cc - 1) * out_cstride + words)
+            throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: the results of the destination overlap");
+        const u64 *o0 = out.data, *o1 = o0 + (Cc - 1) * out_cstride + (batch - 1) * out.bstride + words;
+        const u64 *i0 = in.data, *i1 = i0 + (R - 1) * in_rstride + (batch - 1) * in.bstride + words;
+        const u64 *p0 = plains, *p1 = p0 + (R - 1) * pl_rstride + (Cc - 1) * pl_cstride + pw;
+        if ((o0 < i1 && i0 < o1) || (o0 < p1 && p0 < o1)) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: destination must be a distinct buffer");
+        PlainMatArgs x;
+        x.in = in.data; x.in_rstride = in_rstride; x.in_bstride = in.bstride;
+        x.plains = plains; x.pl_rstride = pl_rstride; x.pl_cstride = pl_cstride;
+        x.out = out.data; x.out_cstride = out_cstride; x.out_bstride = out.bstride;
+        x.rows = (u32)rows; x.cols = (u32)cols; x.size = (u32)in.size; x.limbs = (u32)in.limbs; x.batch = (u32)batch; x.logn = c.logn;
+        launch_plain_matrix(x, c.d_desc, c.ct_map(in.limbs), s);
+    }
+    out.size = in.size; out.limbs = in.limbs; out.ntt = true; out.scale = new_scale; out.cf = in.cf;
+}
+
 // Sum of ciphertext products, relinearized once by the caller (no reference counterpart): out = sum_r a_r (x) b_r, size 3.
 // CKKS and BGV: byte for byte what multiply per pair and add give (exact arithmetic, a linear transform).  BFV: the integer tensors of the pairs are
 // summed BEFORE the one floor and the one Shenoy-Kumaresan step (hostmath.cpp above RnsLevel::build: D = sum_r D_r, F = floor(t D / q) - alpha').

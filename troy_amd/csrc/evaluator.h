@@ -150,6 +150,10 @@ public:
     void multiply_plain_ntt(CtBatch &ct, const u64 *plain, double plain_scale, u64 batch, hipStream_t s);
     // out = sum_i cts[i] (x) plains[i]: the multiplyPlain + addInplace loop of a linear layer as one pass (NTT-form operands of one level)
     void multiply_plain_accumulate(const CtBatch *cts, const u64 *const *plains, int count, double plain_scale, CtBatch &out, u64 batch, hipStream_t s);
+    // out[c] = sum_{r < rows} in[r] (x) plains[r][c] for every column c in ONE launch: operand r, item b at in.data + r * in_rstride +
+    // b * in.bstride; plaintext (r, c), [limbs][N] in NTT form, at plains + r * pl_rstride + c * pl_cstride; result c, item b at out.data + c * out_cstride + b * out.bstride
+    void multiply_plain_matrix(const CtBatch &in, u64 in_rstride, int rows, const u64 *plains, u64 pl_rstride, u64 pl_cstride, int cols, double plain_scale, CtBatch &out,
+                               u64 out_cstride, u64 batch, hipStream_t s);
 
     // out = sum_r as[r] (x) bs[r], 1 <= count <= 16 pairs of size-2 batches of one level, size 3: lazy relinearization (and for BFV ONE floor and
     // Shenoy-Kumaresan step over the summed integer tensors).  out.data / out.bstride are the caller's (three polynomials per item, none of the

@@ -411,6 +411,11 @@ void launch_modarith_probe(int op, const u64 *a, const u64 *b, const u64 *c, u64
 struct MulPlainAccArgs { const u64 *ct[16]; u64 ct_bstride[16]; const u64 *plain[16]; int count; };
 void launch_mul_plain_acc(const MulPlainAccArgs &x, u64 *out, u64 out_bstride, const PrimeDesc *primes, const LimbMap &map, int logn, u64 limbs, u64 size, u64 batch,
                           hipStream_t s);
+// plaintext matrix times ciphertext vector in NTT form (poly.hip): out[c][b][k][l][n] = sum_{r < rows} in[r][b][k][l][n] * plains[r][c][l][n] mod p_l.
+// Operand r, item b at in + r * in_rstride + b * in_bstride, [size][limbs][N]; plaintext (r, c) at plains + r * pl_rstride + c * pl_cstride, [limbs][N]; result c,
+// item b at out + c * out_cstride + b * out_bstride.  Even strides, 16-byte aligned arrays.
+struct PlainMatArgs { const u64 *in; u64 in_rstride, in_bstride; const u64 *plains; u64 pl_rstride, pl_cstride; u64 *out; u64 out_cstride, out_bstride; u32 rows, cols, size, limbs, batch; int logn; };
+void launch_plain_matrix(const PlainMatArgs &x, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
 // sum of scalar multiples of up to 16 ciphertexts plus a constant polynomial (poly.hip):
 //   out[b][k][l][n] = sum_r scalars[r * limbs + l] * ct_r[b][k][l][n] + [k == 0] constant[l] e(n) mod p_l,  e = 1 (ntt) or [n == 0] (coefficient form).
 // Operand r of item b at ct[r] + b * ct_bstride[r], [size][ct_limbs[r]][N] with ct_limbs[r] >= limbs (its leading `limbs` rows are read); out item b at

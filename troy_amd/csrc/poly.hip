@@ -1346,6 +1346,137 @@ template <int NB, int V> __global__ __launch_bounds__(EW_THREADS) void extprod_m
         }
     }
 }
+// Plaintext matrix times ciphertext vector (no reference counterpart): at every (limb l, coefficient n) the small matrix product
+//   out[c][b][k][l][n] = sum_{r < rows} in[r][b][k][l][n] * plains[r][c][l][n] mod p_l,
+// [batch * size, rows] x [rows, cols] over Z_p.  The left rows m = b * size + k (item b, polynomial k) are tiled by Q, the columns by CT, Q * CT == 8; a thread
+// owns TWO consecutive coefficients (16-byte loads and stores, as mul_plain_acc_kernel) and so holds Q x CT x 2 = 16 MacAcc sums, four mac4 groups.  It walks r
+// inside the thread: Q + CT 16-byte loads and 16 multiply-accumulates per step; an operand word is used CT times out of registers, a plaintext word Q times.
+//   Q == 2, CT == 4: one ciphertext (its two polynomials; a size-3 one takes two tiles, the second ragged) by four columns;
+//   Q == 4, CT == 2: two items (or four of the 3 * batch polynomials) share every plaintext word -- the batched scan, the linear layer with a batch.
+// Ragged tiles recompute their last row / column and store nothing for it (no read leaves the arrays).
+// Lazy sums.  A MacAcc sum holds fewer than 64 products of operands below 2^61.  A run ends after 63 products with one Barrett step per sum; the canonical
+// word, below 2^61, becomes the START VALUE of the next run (it goes into the low accumulator word, whose carries mac4 counts like any other), so a sum
+// is at every moment below 2^61 + 63 * 2^122 < 2^128 whatever `rows` is, and barrett128 reduces any 128-bit value: exact for every rows.
+// Block order (flat grid in x, a stride loop beyond PLAINMAT_MAX_BLOCKS): item tile fastest, then column tile, then (limb, coefficient window).  The
+// workgroups in flight share a narrow window of coefficient positions: the operand words of that window (rows x batch x size x 4 KiB) are re-read by every
+// column tile out of L2 / the memory-side cache while the plaintexts stream once per item tile.  Workgroup ids are dealt to the eight XCDs in turn, each with
+// an L2 of its own, so the order is handed out in eight contiguous ranges, range (id mod 8): the workgroups ONE XCD receives are neighbours in the order (the
+// item tiles of one plaintext window meet in one L2).  Against the order as it comes: ahead by 1 - 14 % in 11 of 12 measured cells, level in one
+// (profiles/plainmat_order_ab.txt; probe builds take TROYHIP_PLAINMAT_XCDS=1 for the order as it comes).  Only locality depends on it: every block of the order is taken exactly once whatever the grid.
+constexpr u32 PLAINMAT_XCDS = 8;
+constexpr u32 PLAINMAT_RUN = 63;
+constexpr u64 PLAINMAT_MAX_BLOCKS = u64(1) << 22; // 2^22 workgroups of 256 threads: below HIP's 2^32 threads per launch
+__device__ __forceinline__ void plainmat_end_run(MacAcc (&a)[4], const Mod &m) {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const U128 v = mac_value(a[t]);
+        const u64 r = barrett128(v.lo, v.hi, m);
+        mac_zero(a[t]);
+        a[t].alo = r;
+    }
+}
+template <int Q, int CT> __global__ __launch_bounds__(EW_THREADS) void plain_matrix_kernel(PlainMatArgs x, const PrimeDesc *primes, LimbMap map, u32 windows, u32 itiles, u32 ctiles,
+                                                                                           u64 blocks, u32 xcds) {
+    static_assert(Q * CT == 8 && (Q == 2 || Q == 4), "four mac4 groups: two per coefficient of the pair");
+    const u32 N = 1u << x.logn, M = x.batch * x.size;
+    const u64 per = (blocks + xcds - 1) / xcds;
+    for (u64 slot = blockIdx.x; slot < per * xcds; slot += gridDim.x) {
+        const u64 blk = (slot % xcds) * per + slot / xcds; // range (slot mod xcds) of the order, the next block of it (xcds == 1: the order as it comes)
+        if (blk >= blocks) continue;
+        const u32 it = (u32)(blk % itiles);
+        const u64 rest = blk / itiles;
+        const u32 ct = (u32)(rest % ctiles), pos = (u32)(rest / ctiles), l = pos / windows, n = ((pos - l * windows) * EW_THREADS + threadIdx.x) * 2;
+        if (n >= N) continue;
+        const Mod m = mod_of(prime_of(primes, map, l));
+        const u64 *ip[Q], *pp[CT];
+        u64 oo[Q]; // where left row q lies in an output column
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const u32 mm = it * Q + q < M ? it * Q + q : M - 1, b = mm / x.size, k = mm - b * x.size;
+            const u64 row = (((u64)k * x.limbs + l) << x.logn) + n;
+            ip[q] = x.in + (u64)b * x.in_bstride + row;
+            oo[q] = (u64)b * x.out_bstride + row;
+        }
+#pragma unroll
+        for (int j = 0; j < CT; j++) {
+            const u32 c = ct * CT + j < x.cols ? ct * CT + j : x.cols - 1;
+            pp[j] = x.plains + (u64)c * x.pl_cstride + ((u64)l << x.logn) + n;
+        }
+        MacAcc s[2][2][4]; // [coefficient of the pair][group][entry]: entry e = q * CT + j of the tile is group e / 4, entry e % 4
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int g = 0; g < 2; g++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) mac_zero(s[h][g][t]);
+        u32 left = x.rows;
+#pragma unroll 1
+        while (true) {
+            const u32 run = left < PLAINMAT_RUN ? left : PLAINMAT_RUN;
+#pragma unroll 1
+            for (u32 r = 0; r < run; r++) {
+                ulonglong2 v[Q], w[CT];
+#pragma unroll
+                for (int q = 0; q < Q; q++) { v[q] = *reinterpret_cast<const ulonglong2 *>(ip[q]); ip[q] += x.in_rstride; }
+#pragma unroll
+                for (int j = 0; j < CT; j++) { w[j] = *reinterpret_cast<const ulonglong2 *>(pp[j]); pp[j] += x.pl_rstride; }
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+                    u64 a0[4], a1[4], k0[4], k1[4];
+#pragma unroll
+                    for (int t = 0; t < 4; t++) {
+                        const int e = g * 4 + t, q = e / CT, j = e % CT;
+                        a0[t] = v[q].x; a1[t] = v[q].y; k0[t] = w[j].x; k1[t] = w[j].y;
+                    }
+                    mac4(s[0][g], a0, k0);
+                    mac4(s[1][g], a1, k1);
+                }
+            }
+            left -= run;
+            if (!left) break;
+            plainmat_end_run(s[0][0], m); // the run ends: its canonical word starts the next one
+            plainmat_end_run(s[0][1], m);
+            plainmat_end_run(s[1][0], m);
+            plainmat_end_run(s[1][1], m);
+        }
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+#pragma unroll
+            for (int j = 0; j < CT; j++) {
+                if (it * Q + q >= M || ct * CT + j >= x.cols) continue;
+                const int e = q * CT + j;
+                const U128 v0 = mac_value(s[0][e / 4][e % 4]), v1 = mac_value(s[1][e / 4][e % 4]);
+                ulonglong2 o;
+                o.x = barrett128(v0.lo, v0.hi, m);
+                o.y = barrett128(v1.lo, v1.hi, m);
+                *reinterpret_cast<ulonglong2 *>(x.out + (u64)(ct * CT + j) * x.out_cstride + oo[q]) = o;
+            }
+        }
+    }
+}
+void launch_plain_matrix(const PlainMatArgs &x, const PrimeDesc *primes, const LimbMap &map, hipStream_t s) {
+    if (!x.batch || !x.rows || !x.cols || !x.size || !x.limbs) return;
+    if (x.logn < 1) throw Error(ST_LOGIC_ERROR, "plain_matrix: two coefficients per access");
+    // two coefficients per 16-byte access: every row, column and item starts on an even word of a 16-byte aligned array
+    if (((x.in_rstride | x.in_bstride | x.pl_rstride | x.pl_cstride | x.out_cstride | x.out_bstride) & 1) || (((uintptr_t)x.in | (uintptr_t)x.plains | (uintptr_t)x.out) & 15))
+        throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: strides must be even and the arrays 16-byte aligned");
+    if ((u64)x.batch * x.size >> 31) throw Error(ST_INVALID_ARGUMENT, "multiply_plain_matrix: too many items");
+    const u32 M = x.batch * x.size;
+    const bool wide = M >= 4; // at least one full tile of four left rows: every plaintext word serves four of them
+    const u32 Q = wide ? 4 : 2, CT = 8 / Q;
+    const u32 windows = ceil_div((u64(1) << x.logn) / 2, EW_THREADS), itiles = ceil_div(M, Q), ctiles = ceil_div(x.cols, CT);
+    const u64 blocks = (u64)itiles * ctiles * windows * x.limbs;
+    u64 cap = PLAINMAT_MAX_BLOCKS;
+    if (const char *e = probe_env("TROYHIP_PLAINMAT_MAX_BLOCKS")) cap = std::min<u64>(std::max<u64>(std::strtoull(e, nullptr, 10), 1), cap); // probe builds: the stride loop at test sizes
+    u32 xcds = PLAINMAT_XCDS;
+    if (const char *e = probe_env("TROYHIP_PLAINMAT_XCDS")) xcds = std::strtoul(e, nullptr, 10) == 1 ? 1 : PLAINMAT_XCDS; // probe builds: 1 = the order as it comes (the A/B of the hand-out)
+    const dim3 grid((unsigned)std::min<u64>((blocks + xcds - 1) / xcds * xcds, cap));
+    if (wide) TROY_LAUNCH(HIP_KERNEL_NAME(plain_matrix_kernel<4, 2>), grid, dim3(EW_THREADS), 0, s, x, primes, map, windows, itiles, ctiles, blocks, xcds);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(plain_matrix_kernel<2, 4>), grid, dim3(EW_THREADS), 0, s, x, primes, map, windows, itiles, ctiles, blocks, xcds);
+    launch_check("plain_matrix_kernel");
+    stats::counter(stats::PLAINMAT_LAUNCHES)++;
+    stats::counter(stats::PLAINMAT_WORKGROUPS) += grid.x; // the grids launched so far: a capped grid shows here
+}
 // BFV (kind 0) / BGV (kind 2) mod-down, everything in coefficient form (evaluator.cpp:2528-2648):
 //   ct[b][k][j][n] += (acc_j - [t']_{q_j} + [half]_{q_j}) * qk^-1 mod q_j, t' = (acc_last + half) mod qk       (BFV)
 //   ct[b][k][j][n] += (acc_j - [acc_last]_{q_j} - [k_t]_{q_j} * qk) * qk^-1,  k_t = -acc_last * qk^-1 mod t     (BGV)
