@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "extprod_slabs", "extprod_chunks": slabs and chunks of troyhip_external_product_sum, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "extprod_slabs", "extprod_chunks": slabs and chunks of troyhip_external_product_sum, "blindrot_slabs", "blindrot_steps": slabs and steps of troyhip_blind_rotate, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -471,6 +471,30 @@ int troyhip_host_rgsw(const troyhip_context *ctx, uint64_t seed_lo, uint64_t see
  * is byte-identical to troyhip_host_rgsw with (seed_lo + 2 i, seed_hi); m (.) sk is a dyadic product on the device.  1 <= count <= 65535. */
 int troyhip_create_rgsw(troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *const *plains, uint64_t *const *outs,
                         uint64_t count, void *stream);
+/* ---- Blind rotation: a look-up table on a batch of LWE samples (no reference counterpart).  BFV / BGV, per-prime keys, any data
+ * level.  Stream-ordered; nothing is read back and nothing synchronises inside the call. ----
+ * lwe (DEVICE): item b at lwe + b * lwe_stride, n words a_0 .. a_(n-1) and then beta; every word is taken modulo 2N.  brk (DEVICE): the bootstrapping key,
+ * a dense array [n][T] of RGSW ciphertexts ([2][K-1][2][K][N] each, as troyhip_create_rgsw writes them), shared by the batch: T == 1, brk[i][0] encrypts
+ * the digit s_i in {0, 1}; T == 2 (ternary digits), brk[i][0] encrypts [s_i = 1] and brk[i][1] encrypts [s_i = -1].  test_vector (DEVICE): [limbs][N]
+ * canonical residues, coefficient form; tv_stride == 0: one for the batch, otherwise item b's at test_vector + b * tv_stride.
+ *   acc_0 = (x^beta tv, 0);   acc_(i+1) = acc_i + sum_(t < T) brk[i][t] (.) ((x^(u_t) - 1) acc_i),  u_0 = a_i, u_1 = 2N - a_i (mod 2N);   out item b = acc_n,
+ * which decrypts to tv x^(beta + sum_i a_i s_i) plus additive noise: per step the key-switch noise of 2 T limbs digits and one rounding.  Every step is
+ * troyhip_external_product_sum over T terms with base acc_i, byte for byte, so item b equals the composition on that item alone through
+ * troyhip_negacyclic_shift, troyhip_add_sub and troyhip_external_product_sum; the limbs depend neither on the batch size nor on scratch_limit_words.
+ * out->data, ->batch_stride are INPUTS; the call sets size 2, `limbs`, coefficient form, scale 1.0, correction factor 1.  The arena request stays under
+ * scratch_limit_words (0: 2^28 words): slabs of items, each running all n steps; below one item (troyhip_blind_rotate_scratch_words(.., 1, ..)) the call is
+ * refused.  Refused: CKKS ("unsupported scheme"), a host-only context, K < 2, limbs that is no data level or >= 64, T outside {1, 2}, n == 0 or
+ * n > 65536, null pointers, lwe_stride < n + 1 (batch > 1), a destination stride below 2 limbs N, a tv_stride that is neither 0 nor >= limbs N, a
+ * destination that shares words with the test vectors.  Grouped RGSWs are out of scope.  Counters "blindrot_slabs", "blindrot_steps". */
+int troyhip_blind_rotate(troyhip_context *ctx, const uint64_t *lwe, uint64_t lwe_stride, uint64_t n, const uint64_t *brk, int T, const uint64_t *test_vector, uint64_t tv_stride,
+                         int limbs, troyhip_ct *out, uint64_t scratch_limit_words, uint64_t batch, void *stream);
+/* the arena words the call above asks for with the batch in one slab (no reference counterpart): a host-only function of (limbs, T, batch).
+ * (limbs, T, 1) is the least a call accepts as its limit. */
+int troyhip_blind_rotate_scratch_words(const troyhip_context *ctx, int limbs, int T, uint64_t batch, uint64_t *words);
+/* ONE-limb LWE samples as troyhip_extract_lwes returns them at one limb (c1 [count][batch][1][N], c0 [count][batch][1], DEVICE) switched from q_0 to 2N
+ * (no reference counterpart): out (DEVICE) [count * batch][N + 1] words round(2N x / q_0) mod 2N = floor((4N x + q_0) / (2 q_0)) mod 2N -- q_0 is odd, so
+ * there is no tie -- the N shifts first and beta last: the samples troyhip_blind_rotate reads with n = N and lwe_stride = N + 1. */
+int troyhip_lwe_mod_switch(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t count, uint64_t batch, uint64_t *out, void *stream);
 /* ---- DecryptorCuda::decrypt (src/decryptor_cuda.cu:61-330; dotProductCtSkArray + decryptScaleAndRound / decryptModt,
  * src/utils/rns_cuda.cu:510-621), SURVEY 8-f3.  secret_key: device [K][N] (NTT form, src/secretkey.h).  plain_out (device):
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */

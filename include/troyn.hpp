@@ -1006,6 +1006,35 @@ private:
     ParmsID parms_id_;
 };
 
+// The bootstrapping key of Evaluator::blindRotate (the reference has none): a dense device array [n][T] of RGSW ciphertexts, one
+// row per digit of an LWE secret of dimension n.  T == 1: row i encrypts s_i in {0, 1}; T == 2 (ternary digits): [s_i = 1] and [s_i = -1].
+class BlindRotationKey {
+public:
+    const uint64_t *device(const ParmsID &key_parms_id, size_t key_limbs, size_t poly_modulus_degree) const {
+        if (!words_ || parms_id_ != key_parms_id || key_limbs < 2 || !n_ || (T_ != 1 && T_ != 2) ||
+            words_->size() != n_ * (size_t)T_ * 2 * (key_limbs - 1) * 2 * key_limbs * poly_modulus_degree)
+            throw std::invalid_argument("blind rotation key is not valid for encryption parameters");
+        return words_->get();
+    }
+    void adopt(const ParmsID &key_parms_id, std::shared_ptr<DeviceArray> words, size_t n, int T) { parms_id_ = key_parms_id; words_ = std::move(words); n_ = n; T_ = T; }
+    std::vector<uint64_t> toHost() const {
+        std::vector<uint64_t> v(words_ ? words_->size() : 0);
+        if (!v.empty()) {
+            check(troyhip_copy_d2h(v.data(), words_->get(), v.size() * 8, nullptr));
+            check(troyhip_stream_synchronize(nullptr));
+        }
+        return v;
+    }
+    size_t dimension() const noexcept { return n_; }
+    int digitTerms() const noexcept { return T_; }
+    const ParmsID &parmsID() const noexcept { return parms_id_; }
+private:
+    std::shared_ptr<DeviceArray> words_;
+    ParmsID parms_id_;
+    size_t n_ = 0;
+    int T_ = 0;
+};
+
 // A rows x cols matrix of NTT-form plaintexts of one level and one scale in ONE device array [rows][cols][limbs][N] (the reference has none; DESIGN.md
 // section 4.21): what Evaluator::multiplyPlainMatrix streams.  Evaluator::packPlainMatrix makes one; a database that is scanned many times is packed once.
 class PlainMatrix {
@@ -1239,6 +1268,54 @@ public:
         return out;
     }
     RGSWCiphertext createRGSWOnDevice(const Plaintext &plain) const { return std::move(createRGSWOnDevice(std::vector<Plaintext>{plain})[0]); }
+    // ---- the bootstrapping key of blind rotation (troyhip_create_rgsw on the constants 0 / 1; the reference has none).
+    // lwe_secret: digits over {-1, 0, 1}; empty: the RLWE secret's own coefficients, so that the samples of extractLWEs + lweModSwitch can be used as they
+    // are.  T == 2 if any digit is -1 or `ternary` is set.  The RGSWs are generated in the order [i][t] and take two seeds each: the counter the
+    // createRGSW members share advances by 2 n T.
+    std::vector<int> secretCoefficients() const {
+        const size_t N = c_.polyModulusDegree();
+        const uint64_t p = c_.keyContextData()->parms().coeffModulus()[0].value();
+        DeviceArray d(N);
+        check(troyhip_copy_h2d(d.get(), sk_.data.data(), N * 8, nullptr));
+        check(troyhip_ntt(c_.handle(), d.get(), 1, &p, 1, 1, 1, nullptr));
+        std::vector<uint64_t> w(N);
+        check(troyhip_copy_d2h(w.data(), d.get(), N * 8, nullptr));
+        check(troyhip_stream_synchronize(nullptr));
+        std::vector<int> s(N);
+        for (size_t i = 0; i < N; i++) {
+            if (w[i] > 1 && w[i] != p - 1) throw std::logic_error("the secret key is not ternary");
+            s[i] = w[i] == p - 1 ? -1 : (int)w[i];
+        }
+        return s;
+    }
+    BlindRotationKey createBlindRotationKey(const std::vector<int> &lwe_secret = {}, bool ternary = false) const {
+        const std::vector<int> s = lwe_secret.empty() ? secretCoefficients() : lwe_secret;
+        bool neg = ternary;
+        for (int v : s) {
+            if (v < -1 || v > 1) throw std::invalid_argument("the LWE secret takes 1 to 65536 digits over {-1, 0, 1}");
+            neg = neg || v < 0;
+        }
+        if (s.size() > 65536) throw std::invalid_argument("the LWE secret takes 1 to 65536 digits over {-1, 0, 1}");
+        const size_t T = neg ? 2 : 1, total = s.size() * T, gw = 2 * ksk_words();
+        const std::shared_ptr<DeviceArray> consts[2] = {plainAtKeyLevel(Plaintext(std::vector<uint64_t>{0})), plainAtKeyLevel(Plaintext(std::vector<uint64_t>{1}))};
+        auto words = std::make_shared<DeviceArray>(total * gw);
+        for (size_t i0 = 0; i0 < total; i0 += 65535) { // troyhip_create_rgsw takes at most 65535 per call
+            const size_t cnt = std::min<size_t>(65535, total - i0);
+            std::vector<const uint64_t *> pm(cnt);
+            std::vector<uint64_t *> po(cnt);
+            for (size_t k = 0; k < cnt; k++) {
+                const size_t i = (i0 + k) / T, t = (i0 + k) % T;
+                pm[k] = consts[s[i] == (t ? -1 : 1) ? 1 : 0]->get();
+                po[k] = words->get() + (i0 + k) * gw;
+            }
+            check(troyhip_create_rgsw(c_.handle(), lo_ + kswitch_calls_, hi_, deviceSecretKey(), pm.data(), po.data(), cnt, nullptr));
+            kswitch_calls_ += 2 * cnt;
+        }
+        check(troyhip_stream_synchronize(nullptr)); // the constants are freed on return
+        BlindRotationKey key;
+        key.adopt(c_.keyParmsID(), words, s.size(), (int)T);
+        return key;
+    }
     // the ceil(log2 count) keys Evaluator::expandCoefficients(.., count, ..) needs: X -> X^((N >> j) + 1) for the layers j = 0, 1, ..
     std::vector<uint32_t> expansionElts(size_t count) const {
         const size_t N = c_.polyModulusDegree();
@@ -2975,6 +3052,46 @@ public:
         const std::vector<Ciphertext> &diff = d;
         const std::vector<const Ciphertext *> b = Ciphertext::pointers(ct0);
         return externalProductSumBatch({Ciphertext::pointers(diff)}, {&sel}, &b);
+    }
+    // Blind rotation (troyhip_blind_rotate / troyhip_lwe_mod_switch; the reference has no such call): item b of the result is
+    // test_vector x^(beta_b + sum_i a_(b, i) s_i), n CMux steps under the BlindRotationKey in ONE library call.  lwe: `batch` samples of n + 1 words
+    // (a_0 .. a_(n-1), beta), taken modulo 2N, on the device or on the host.  test_vector: limbs x N canonical residues in coefficient form shared by
+    // the batch, or batch x limbs x N.  BFV / BGV; the result has size 2, `limbs` limbs, coefficient form, scale 1 and correction factor 1.
+    std::vector<Ciphertext> blindRotateBatch(const DeviceArray &lwe, size_t batch, const BlindRotationKey &key, const std::vector<uint64_t> &test_vector, size_t limbs) const {
+        const size_t N = c_.polyModulusDegree(), n = key.dimension();
+        const uint64_t *brk = key.device(c_.keyParmsID(), c_.keyLimbs(), N);
+        if (lwe.size() != batch * (n + 1)) throw std::invalid_argument("blind_rotate: LWE samples take n + 1 words each");
+        if (!limbs || (test_vector.size() != limbs * N && test_vector.size() != batch * limbs * N)) throw std::invalid_argument("blind_rotate: a test vector takes limbs x N words");
+        if (!batch) return {};
+        DeviceArray tv(test_vector.size());
+        check(troyhip_copy_h2d(tv.get(), test_vector.data(), test_vector.size() * 8, nullptr));
+        Ciphertext like;
+        like.resize(N, limbs, 2);
+        like.bind(c_);
+        std::vector<Ciphertext> out = Ciphertext::allocateBatch(batch, like, 2, limbs);
+        troyhip_ct t = *out[0].raw();
+        check(troyhip_blind_rotate(h(), lwe.get(), n + 1, n, brk, key.digitTerms(), tv.get(), test_vector.size() == limbs * N ? 0 : limbs * N, (int)limbs, &t, 0, batch, nullptr));
+        check(troyhip_stream_synchronize(nullptr)); // the test vector is freed on return
+        for (auto &c : out) c.copyMeta(t);
+        return out;
+    }
+    std::vector<Ciphertext> blindRotateBatch(const std::vector<uint64_t> &lwe, size_t batch, const BlindRotationKey &key, const std::vector<uint64_t> &test_vector,
+                                             size_t limbs) const {
+        DeviceArray d(lwe.size());
+        if (!lwe.empty()) check(troyhip_copy_h2d(d.get(), lwe.data(), lwe.size() * 8, nullptr));
+        return blindRotateBatch(d, batch, key, test_vector, limbs); // synchronises before d goes
+    }
+    void blindRotate(const std::vector<uint64_t> &lwe, const BlindRotationKey &key, const std::vector<uint64_t> &test_vector, size_t limbs, Ciphertext &dst) const {
+        dst = std::move(blindRotateBatch(lwe, 1, key, test_vector, limbs)[0]);
+    }
+    // the ONE-limb samples of an LWEBatch switched from q_0 to 2N: [count][N + 1] words round(2N x / q_0) mod 2N on the device, the N shifts first and
+    // beta last -- what blindRotateBatch reads with a key of dimension N
+    DeviceArray lweModSwitch(const LWEBatch &lwes) const {
+        if (!lwes.count_) throw std::invalid_argument("LWE ciphertexts must not be empty.");
+        if (lwes.limbs_ != 1) throw std::invalid_argument("lwe_mod_switch takes samples of one limb");
+        DeviceArray out(lwes.count_ * (c_.polyModulusDegree() + 1));
+        check(troyhip_lwe_mod_switch(h(), lwes.c1_.get(), lwes.c0_.get(), lwes.count_, 1, out.get(), nullptr));
+        return out;
     }
 
 private:

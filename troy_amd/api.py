@@ -467,6 +467,31 @@ class RGSWCiphertext:
         return self.buf.to_numpy().reshape(2, K - 1, 2, K, N)
 
 
+class BlindRotationKey:
+    """The bootstrapping key of Evaluator.blindRotate (no reference counterpart): a dense device array [n][T] of RGSW ciphertexts
+    ([2][K-1][2][K][N] each) under the RLWE secret, one row per digit of an LWE secret of dimension n.  T == 1: row i encrypts s_i in {0, 1}; T == 2
+    (ternary digits): [s_i = 1] and [s_i = -1]."""
+
+    def __init__(self, context, buf, n, T):
+        K, N = context.key_limbs, context.N
+        n, T = int(n), int(T)
+        if not isinstance(buf, DeviceBuffer) or K < 2 or T not in (1, 2) or n < 1 or buf.words != n * T * 2 * (K - 1) * 2 * K * N:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind rotation key is not valid for encryption parameters")
+        self.context, self.buf, self.n, self.T = context, buf, n, T
+
+    @classmethod
+    def from_numpy(cls, context, host_array):
+        a = np.ascontiguousarray(host_array, dtype=np.uint64)
+        K, N = context.key_limbs, context.N
+        if a.ndim != 7 or a.shape[2:] != (2, K - 1, 2, K, N):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind rotation key is not valid for encryption parameters")
+        return cls(context, DeviceBuffer.from_numpy(a), a.shape[0], a.shape[1])
+
+    def cpu(self):
+        K, N = self.context.key_limbs, self.context.N
+        return self.buf.to_numpy().reshape(self.n, self.T, 2, K - 1, 2, K, N)
+
+
 class Evaluator:
     """EvaluatorCuda (src/evaluator_cuda.cuh:13-361) over batches."""
 
@@ -995,6 +1020,68 @@ class Evaluator:
         w = C.c_uint64(0)
         self._chk(self.lib.troyhip_external_product_sum_scratch_words(self.context.h, int(limbs), int(count), C.c_uint64(batch), C.byref(w)))
         return w.value
+
+    # -- blind rotation (troyhip_blind_rotate / troyhip_lwe_mod_switch: no reference counterpart)
+    def blindRotate(self, lwe, key, test_vector, limbs=None, scratch_limit_words=0):
+        """test_vector x^(beta + sum_i a_i s_i) for every LWE sample of the batch as ONE size-2 batch in coefficient form (BFV / BGV): n CMux steps under the
+        BlindRotationKey, enqueued on the stream with nothing read back.  lwe: a DeviceBuffer or a numpy array [batch][n + 1] of words (a_0 .. a_(n-1),
+        beta), taken modulo 2N.  test_vector: [limbs][N] canonical residues shared by the batch, or [batch][limbs][N], as numpy or a DeviceBuffer."""
+        ctx = self.context
+        if not isinstance(key, BlindRotationKey) or key.context is not ctx:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind rotation key is not valid for encryption parameters")
+        n, N = key.n, ctx.N
+        uploaded = not (isinstance(lwe, DeviceBuffer) and isinstance(test_vector, DeviceBuffer))
+        if not isinstance(lwe, DeviceBuffer):
+            a = np.ascontiguousarray(lwe, dtype=np.uint64)
+            if a.ndim != 2 or a.shape[1] != n + 1:
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind_rotate: LWE samples take n + 1 words each")
+            lwe = DeviceBuffer.from_numpy(a) if a.size else DeviceBuffer(1)
+            batch = a.shape[0]
+        else:
+            if lwe.words % (n + 1):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind_rotate: LWE samples take n + 1 words each")
+            batch = lwe.words // (n + 1)
+        if not isinstance(test_vector, DeviceBuffer):
+            tv = np.ascontiguousarray(test_vector, dtype=np.uint64)
+            if limbs is None and tv.ndim >= 2:
+                limbs = tv.shape[-2]
+            limbs = int(limbs or ctx.first_limbs)
+            if tv.shape not in ((limbs, N), (batch, limbs, N)):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind_rotate: a test vector takes limbs x N words")
+            per_item = tv.ndim == 3
+            test_vector = DeviceBuffer.from_numpy(tv)
+        else:
+            limbs = int(limbs or ctx.first_limbs)
+            if test_vector.words not in (limbs * N, batch * limbs * N):
+                raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "blind_rotate: a test vector takes limbs x N words")
+            per_item = test_vector.words != limbs * N
+        out = Ciphertext(ctx, batch, 2, limbs)
+        so = out.struct()
+        self._chk(self.lib.troyhip_blind_rotate(ctx.h, C.c_void_p(lwe.ptr), C.c_uint64(n + 1), C.c_uint64(n), C.c_void_p(key.buf.ptr), key.T, C.c_void_p(test_vector.ptr),
+                                                C.c_uint64(limbs * N if per_item else 0), limbs, C.byref(so), C.c_uint64(scratch_limit_words), C.c_uint64(batch),
+                                                self.stream))
+        out._absorb(so)
+        if uploaded:
+            synchronize(self.stream)  # the buffers uploaded here are released on return
+        return out
+
+    def blindRotateScratchWords(self, limbs, T, batch):
+        """the arena words blindRotate asks for with the batch in one slab (troyhip_blind_rotate_scratch_words)"""
+        w = C.c_uint64(0)
+        self._chk(self.lib.troyhip_blind_rotate_scratch_words(self.context.h, int(limbs), int(T), C.c_uint64(batch), C.byref(w)))
+        return w.value
+
+    def lweModSwitch(self, lwes):
+        """the one-limb samples of an LWEBatch switched from q_0 to 2N: a DeviceBuffer of [count * batch][N + 1] words round(2N x / q_0) mod 2N, the N
+        shifts first and beta last -- what blindRotate reads with a key of dimension N"""
+        if not isinstance(lwes, LWEBatch) or lwes.context is not self.context:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "lwe_mod_switch takes an LWEBatch")
+        if lwes.limbs != 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "lwe_mod_switch takes samples of one limb")
+        out = DeviceBuffer(max(lwes.count * lwes.batch * (self.context.N + 1), 1))
+        self._chk(self.lib.troyhip_lwe_mod_switch(self.context.h, C.c_void_p(lwes.c1.ptr), C.c_void_p(lwes.c0.ptr), C.c_uint64(lwes.count), C.c_uint64(lwes.batch),
+                                                  C.c_void_p(out.ptr), self.stream))
+        return out
 
     def _copy_then(self, fn, a, *args):
         r = a.copy()
@@ -1601,6 +1688,44 @@ class KeyGenerator:
         capi.check(self.lib, self.lib.troyhip_create_rgsw(ctx.h, lo, hi, C.c_void_p(self._device_sk().ptr), pm, po, C.c_uint64(len(ms)), None))
         synchronize()  # the plaintext buffers made here are released on return
         return [RGSWCiphertext(ctx, b) for b in bufs]
+
+    # ---- the bootstrapping key of blind rotation (troyhip_create_rgsw on constant plaintexts: no reference counterpart)
+    def secretCoefficients(self):
+        """the RLWE secret's coefficients over {-1, 0, 1} (the inverse transform of the key's first limb)"""
+        ctx = self.context
+        p = ctx.coeff_modulus[0]
+        buf = DeviceBuffer.from_numpy(self._sk[0])
+        ctx.ntt(buf, 1, [p], inverse=True)
+        a = buf.to_numpy().astype(object)
+        s = np.where(a > p // 2, a - p, a).astype(np.int64)
+        if np.abs(s).max(initial=0) > 1:
+            raise capi.LogicError(capi.LOGIC_ERROR, "the secret key is not ternary")
+        return s
+
+    def createBlindRotationKey(self, lwe_secret=None, ternary=None):
+        """the BlindRotationKey of an LWE secret over {-1, 0, 1} (None: the RLWE secret's own coefficients, so that the samples of extractLWEs can be used
+        as they are): RGSW ciphertexts of the constants 0 / 1 from the device generator, row i of T == 1 for s_i, of T == 2 (any digit is -1, or `ternary`)
+        for [s_i = 1] and [s_i = -1].  Every RGSW takes two of the generator's seeds, in the order [i][t]: kswitch_calls advances by 2 n T."""
+        ctx = self.context
+        K, N = ctx.key_limbs, ctx.N
+        if K < 2:
+            raise capi.LogicError(capi.LOGIC_ERROR, "keyswitching is not supported by the context")
+        s = self.secretCoefficients() if lwe_secret is None else np.asarray(lwe_secret).astype(np.int64).reshape(-1)
+        if not 1 <= s.size <= 65536 or np.abs(s).max() > 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the LWE secret takes 1 to 65536 digits over {-1, 0, 1}")
+        T = 2 if (ternary or (s < 0).any()) else 1
+        bits = np.stack([s == 1, s == -1], axis=1)[:, :T].reshape(-1)  # [n][T], the order of the seeds
+        consts = [self._rgsw_plain(np.array([v], dtype=np.uint64)) for v in (0, 1)]
+        gw = 2 * (K - 1) * 2 * K * N
+        buf = DeviceBuffer(bits.size * gw)
+        for i0 in range(0, bits.size, 65535):  # troyhip_create_rgsw takes at most 65535 per call
+            chunk = bits[i0:i0 + 65535]
+            pm = (C.c_void_p * len(chunk))(*[consts[int(v)].ptr for v in chunk])
+            po = (C.c_void_p * len(chunk))(*[buf.ptr + 8 * (i0 + i) * gw for i in range(len(chunk))])
+            lo, hi = self._rgsw_seed(len(chunk))
+            capi.check(self.lib, self.lib.troyhip_create_rgsw(ctx.h, lo, hi, C.c_void_p(self._device_sk().ptr), pm, po, C.c_uint64(len(chunk)), None))
+        synchronize()  # the plaintext buffers made here are released on return
+        return BlindRotationKey(ctx, buf, s.size, T)
 
     def automorphismElts(self):
         """X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)"""

@@ -571,3 +571,51 @@ class PIRServer:
                 mine.buf.copy_from(columns.buf, columns.bstride, (j * B + b) * columns.bstride, j * columns.bstride)
             out.append(self._fold(mine, selectors[b]))
         return out
+
+
+# ---- look-up tables on LWE samples: a composition of public calls, extract -> modulus switch -> blind rotation -> extract.
+class LookupTable:
+    """A function on Z_(2N) as a negacyclic test vector.  `f` maps a message m in [0, 2^t_bits) to a value mod t; the phases [0, N) are cut into 2^t_bits
+    equal windows, table[phi] = f(phi 2^t_bits // N), and the other half is forced: table[phi + N] = -table[phi].  The polynomial v with v_0 = table[0]
+    and v_(N - phi) = -table[phi] has table[phi] as the constant coefficient of v x^phi, which is what Evaluator.blindRotate leaves encrypted."""
+
+    def __init__(self, context, f, t_bits):
+        if context.scheme not in (capi.BFV, capi.BGV):
+            raise capi.LogicError(capi.LOGIC_ERROR, "unsupported scheme")
+        N, t = context.N, context.plain_modulus
+        t_bits = int(t_bits)
+        if not 0 <= t_bits <= N.bit_length() - 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LookupTable: 2^t_bits windows, at most N")
+        self.context, self.t_bits = context, t_bits
+        self.table = np.array([int(f((phi << t_bits) // N)) % t for phi in range(N)], dtype=np.uint64)
+        self.poly = np.zeros(N, dtype=np.uint64)
+        self.poly[0] = self.table[0]
+        self.poly[1:] = (t - self.table[:0:-1].astype(object)) % t
+
+    def value(self, phi):
+        """the constant coefficient of poly x^phi in R_t, phi in Z_(2N)"""
+        N, t = self.context.N, self.context.plain_modulus
+        phi = int(phi) % (2 * N)
+        return int(self.table[phi]) if phi < N else (t - int(self.table[phi - N])) % t
+
+    def test_vector(self, limbs):
+        """[limbs][N] canonical residues: round(q poly / t) for BFV (q the product of the level's primes), the plain lift for BGV"""
+        ctx, t = self.context, self.context.plain_modulus
+        primes = ctx.coeff_modulus[:int(limbs)]
+        q = 1
+        for p in primes:
+            q *= p
+        vals = [(q * int(v) + t // 2) // t if ctx.scheme == capi.BFV else int(v) for v in self.poly]
+        return np.array([[v % p for v in vals] for p in primes], dtype=np.uint64)
+
+    def apply(self, evaluator, ct_batch, terms, key, limbs=None, scratch_limit_words=0):
+        """the table on the coefficients `terms` of every item of a BFV / BGV batch -> (rotated, lwes): modSwitchTo one limb, extractLWEs, lweModSwitch,
+        blindRotate under `key` (createBlindRotationKey() of the ciphertexts' own secret) at `limbs` (default: the first level) and extractLWEs at term
+        0.  Sample (j, b) of `lwes` encrypts table[phi] in its constant term, phi the switched phase of coefficient terms[j] of item b;
+        Evaluator.packLWEs can follow."""
+        ev, ctx = evaluator, self.context
+        limbs = int(limbs or ctx.first_limbs)
+        low = ev.modSwitchTo(ct_batch, 1) if ct_batch.limbs > 1 else ct_batch
+        samples = ev.lweModSwitch(ev.extractLWEs(low, terms))
+        rotated = ev.blindRotate(samples, key, self.test_vector(limbs), limbs=limbs, scratch_limit_words=scratch_limit_words)
+        return rotated, ev.extractLWEs(rotated, [0])

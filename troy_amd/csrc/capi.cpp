@@ -1228,6 +1228,30 @@ int troyhip_external_product_sum_scratch_words(const troyhip_context *ctx, int l
         *words = need(ctx)->ev.external_product_sum_scratch_words(limbs, count, batch);
     }, false);
 }
+/* blind rotation (no reference counterpart) */
+int troyhip_blind_rotate(troyhip_context *ctx, const uint64_t *lwe, uint64_t lwe_stride, uint64_t n, const uint64_t *brk, int T, const uint64_t *test_vector, uint64_t tv_stride,
+                         int limbs, troyhip_ct *out, uint64_t scratch_limit_words, uint64_t batch, void *stream) {
+    return guard([&] {
+        if (!out) throw Error(ST_INVALID_ARGUMENT, "null ciphertext");
+        auto *handle = need(ctx); // the context is bound before the stream is looked at
+        const hipStream_t s = on(stream);
+        CtBatch o = view(out);
+        handle->ev.blind_rotate(lwe, lwe_stride, n, brk, T, test_vector, tv_stride, limbs, o, batch, scratch_limit_words, s);
+        store(o, out);
+    });
+}
+int troyhip_blind_rotate_scratch_words(const troyhip_context *ctx, int limbs, int T, uint64_t batch, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.blind_rotate_scratch_words(limbs, T, batch);
+    }, false);
+}
+int troyhip_lwe_mod_switch(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t count, uint64_t batch, uint64_t *out, void *stream) {
+    return guard([&] {
+        auto *handle = need(ctx);
+        handle->ev.lwe_mod_switch(c1, c0, count, batch, out, on(stream));
+    });
+}
 int troyhip_host_rgsw(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *plain_ntt_keylevel, uint64_t *out) {
     return guard([&] {
         if (!secret_key || !plain_ntt_keylevel || !out) throw Error(ST_INVALID_ARGUMENT, "null key, plaintext list or RGSW output");

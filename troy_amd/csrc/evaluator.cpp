@@ -2370,6 +2370,94 @@ void Evaluator::external_product_sum(const CtBatch *ins, const u64 *const *rgsw,
     }
 }
 
+// ---- blind rotation (no reference counterpart) ----
+// A chain of n external products on a slab of items: acc_(i+1) = acc_i + sum_t brk[i][t] (.) ((x^(u_t) - 1) acc_i).  Step i is external_product_sum over
+// T dense terms with base acc_i: the pre-kernel writes the T operand batches, ONE ks_expand_digits call reads them as T 2 nb back-to-back polynomials,
+// ONE launch_extprod_mac forms the inner product and ONE ks_acc_to_ct adds the base.  ks_acc_to_ct's destination is distinct from its base: two
+// accumulators per item take turns, and the last step writes the caller's destination.
+// Scratch in words per item: 4 pw [the two accumulators] + T 2 pw [the operands] + what extprod_words asks for T terms.
+static const u64 BLINDROT_BLOCKS = EXTPROD_BLOCKS + 3;
+static const u64 BLINDROT_MAX_N = 65536;
+static u64 blindrot_item_words(const Context &c, u64 dl, u64 T) {
+    const SlabWords sw = extprod_words(c, dl);
+    return (4 + 2 * T) * dl * c.N + sw.per_item + T * sw.per_unit_item;
+}
+static void check_blindrot_shape(const Context &c, int limbs, int T) {
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: blind rotation is defined under BFV and BGV");
+    if (c.K < 2) throw Error(ST_LOGIC_ERROR, "keyswitching is not supported by the context");
+    if (!c.is_data_level(limbs)) throw Error(ST_INVALID_ARGUMENT, "encrypted is not valid for encryption parameters");
+    if (limbs >= 64) throw Error(ST_LOGIC_ERROR, "blind_rotate: more than 63 digits");
+    if (T != 1 && T != 2) throw Error(ST_INVALID_ARGUMENT, "blind_rotate takes 1 or 2 RGSW ciphertexts per digit");
+}
+u64 Evaluator::blind_rotate_scratch_words(int limbs, int T, u64 batch) const {
+    check_blindrot_shape(c, limbs, T);
+    return std::max<u64>(batch, 1) * blindrot_item_words(c, (u64)limbs, (u64)T) + slab_slack(BLINDROT_BLOCKS);
+}
+void Evaluator::blind_rotate(const u64 *lwe, u64 lwe_stride, u64 n, const u64 *brk, int T, const u64 *tv, u64 tv_stride, int limbs, CtBatch &out, u64 batch,
+                             u64 scratch_limit_words, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    check_blindrot_shape(c, limbs, T);
+    if (!n || n > BLINDROT_MAX_N) throw Error(ST_INVALID_ARGUMENT, "blind_rotate takes 1 to 65536 LWE digits");
+    if (!lwe || !brk || !tv) throw Error(ST_INVALID_ARGUMENT, "blind_rotate: null pointer");
+    if (lwe_stride < n + 1 && batch > 1) throw Error(ST_INVALID_ARGUMENT, "blind_rotate: LWE stride is smaller than one sample");
+    const u64 N = c.N, dl = (u64)limbs, rl = dl + 1, pw = dl * N, dw = rl * dl * N, nt = (u64)T;
+    if (tv_stride && tv_stride < pw) throw Error(ST_INVALID_ARGUMENT, "blind_rotate: test vector stride is neither 0 nor at least one test vector");
+    if (!out.data || out.bstride < 2 * pw) throw Error(ST_INVALID_ARGUMENT, "destination batch stride too small for the result size");
+    // the destination is written slab by slab while later slabs still read their test vectors
+    if (batch && batches_overlap(out.data, batch, out.bstride, 2 * pw, tv, tv_stride ? batch : 1, tv_stride, pw))
+        throw Error(ST_INVALID_ARGUMENT, "blind_rotate: destination must be a distinct buffer");
+    out.size = 2; out.limbs = limbs; out.ntt = false; out.scale = 1.0; out.cf = 1;
+    const SlabPlan plan = plan_slabs(scratch_limit_words, BLINDROT_BLOCKS, blindrot_item_words(c, dl, nt), 0, std::max<u64>(batch, 1), 1,
+                                     "scratch_limit_words is too small for one ciphertext");
+    if (!batch) return;
+    const u64 bs = plan.items, gw = 2 * (c.K - 1) * 2 * c.K * N; // one RGSW
+    const u64 ls = batch > 1 ? lwe_stride : n + 1;
+    KsPlan k = ks_plan(limbs, 0);
+    const LimbMap cmap = c.ct_map(limbs);
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    u64 *A[2] = {c.arena.take(bs * 2 * pw), c.arena.take(bs * 2 * pw)};
+    u64 *ops = c.arena.take(nt * bs * 2 * pw), *D = c.arena.take(nt * bs * 2 * dw), *acc = c.arena.take(bs * 2 * rl * N);
+    const size_t mark = c.arena.mark();
+    for (u64 b0 = 0; b0 < batch; b0 += bs) {
+        const u64 nb = std::min(bs, batch - b0);
+        const u64 *lw = lwe + b0 * ls;
+        launch_blind_rotate_init(lw, ls, n, tv + b0 * tv_stride, tv_stride, A[0], 2 * pw, c.d_desc, cmap, c.logn, dl, nb, s);
+        for (u64 i = 0; i < n; i++) {
+            const u64 *cur = A[i & 1];
+            launch_blind_rotate_pre(BlindRotArgs{cur, 2 * pw, lw, ls, i, ops, nb, dl, c.logn}, T, c.d_desc, cmap, s);
+            k.a.batch = nt * 2 * nb; // [t][item][2] polynomials back to back: term t's digits at D + t nb 2 dw, item b's two sets side by side
+            ks_expand_digits(ops, pw, D, k, s);
+            ExtProdArgs h;
+            std::memset(&h, 0, sizeof(h));
+            h.terms = (u32)T;
+            for (u64 t = 0; t < nt; t++) {
+                h.D[t] = D + t * nb * 2 * dw;
+                h.d_bstride[t] = 2 * dw; h.d_hstride[t] = dw;
+                h.rgsw[t] = brk + (i * nt + t) * gw;
+            }
+            k.a.batch = nb;
+            launch_extprod_mac(acc, k.a, h, s);
+            CtBatch o;
+            if (i + 1 == n) { o.data = out.data + b0 * out.bstride; o.bstride = out.bstride; }
+            else { o.data = A[(i + 1) & 1]; o.bstride = 2 * pw; }
+            c.arena.rewind(mark);
+            ks_acc_to_ct(o, acc, k, s, KsBase{cur, 2 * pw, 2});
+            stats::counter(stats::BLINDROT_STEPS)++;
+        }
+        stats::counter(stats::BLINDROT_SLABS)++;
+    }
+}
+void Evaluator::lwe_mod_switch(const u64 *c1, const u64 *c0, u64 count, u64 batch, u64 *out, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: blind rotation is defined under BFV and BGV");
+    if (!c.is_data_level(1)) throw Error(ST_INVALID_ARGUMENT, "lwe_mod_switch: the context has no level of one limb");
+    if (count < 1) throw Error(ST_INVALID_ARGUMENT, "LWE ciphertexts must not be empty.");
+    if (!c1 || !c0 || !out) throw Error(ST_INVALID_ARGUMENT, "lwe_mod_switch: null pointer");
+    if (count > (u64(1) << 40) / std::max<u64>(batch, 1)) throw Error(ST_INVALID_ARGUMENT, "lwe_mod_switch: too many samples");
+    launch_lwe_mod_switch(c1, c0, out, c.d_desc, c.ct_map(1), c.logn, count * batch, s);
+}
+
 // ---- decryption ----
 u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
     const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;

@@ -205,6 +205,20 @@ public:
     // pairs and the base only -- not on the order of the terms, the chunks, the batch size or the limit.
     void external_product_sum(const CtBatch *ins, const u64 *const *rgsw, int count, const CtBatch *base, CtBatch &out, u64 batch, u64 scratch_limit_words, hipStream_t s);
     u64 external_product_sum_scratch_words(int limbs, int count, u64 batch) const; // what it asks of the arena with the batch in one slab, min(count, 16) terms a chunk
+    // Blind rotation (no reference counterpart): out item b = acc_n of  acc_0 = (x^beta_b tv_b, 0),
+    // acc_(i+1) = acc_i + sum_(t < T) brk[i][t] (.) ((x^(u_t) - 1) acc_i),  u_0 = a_(b, i), u_1 = 2N - a_(b, i)  (every word modulo 2N),
+    // which decrypts to tv_b x^(beta_b + sum_i a_(b, i) s_i).  lwe: DEVICE, item b at lwe + b * lwe_stride, n shifts then beta.  brk: DEVICE [n][T] RGSW
+    // ciphertexts ([2][K-1][2][K][N] each), T == 1: brk[i][0] encrypts s_i in {0, 1}; T == 2: [s_i = 1] and [s_i = -1].  tv: [limbs][N] canonical, shared
+    // (stride 0) or one per item.  BFV / BGV, per-prime keys, any data level; the result has size 2, coefficient form, scale 1, correction factor 1.
+    // A step is external_product_sum over T terms with base acc_i, byte for byte: blind_rotate_pre, ks_expand_digits, ONE launch_extprod_mac, ONE
+    // ks_acc_to_ct.  A slab of items runs all n steps before the next one starts; nothing is read back and nothing synchronises.  out.data / out.bstride
+    // are the caller's.  The arena request stays under scratch_limit_words (0: 2^28 words); the limbs do not depend on the batch size or the limit.
+    void blind_rotate(const u64 *lwe, u64 lwe_stride, u64 n, const u64 *brk, int T, const u64 *tv, u64 tv_stride, int limbs, CtBatch &out, u64 batch, u64 scratch_limit_words,
+                      hipStream_t s);
+    u64 blind_rotate_scratch_words(int limbs, int T, u64 batch) const; // what it asks of the arena with the batch in one slab
+    // one-limb LWE samples as extract_lwes returns them (c1 [count][batch][1][N], c0 [count][batch][1]) -> out [count * batch][N + 1] words
+    // round(2N x / q_0) mod 2N, the shifts first and beta last: what blind_rotate reads
+    void lwe_mod_switch(const u64 *c1, const u64 *c0, u64 count, u64 batch, u64 *out, hipStream_t s);
     // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
     // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
     static PolyPlan plan_polynomial(int degree, int baby_steps);

@@ -259,6 +259,16 @@ void launch_bsgs_base(bool ntt_form, const u64 *u, u64 u_rstride, u64 u_bstride,
 // accumulate: start from the canonical words acc holds.  One RGSW per term, shared by the batch.
 struct ExtProdArgs { const u64 *rgsw[HOIST_MAX_ROT]; const u64 *D[HOIST_MAX_ROT]; u64 d_bstride[HOIST_MAX_ROT], d_hstride[HOIST_MAX_ROT]; u32 terms, accumulate; };
 void launch_extprod_mac(u64 *acc, const KsArgs &a, const ExtProdArgs &h, hipStream_t s);
+// blind rotation, coefficient form.  LWE samples: DEVICE words, item b at lwe + b * lwe_stride, [n] shifts then beta; every
+// word is taken modulo 2N in the kernels.
+// init: out item b (at out + b * out_stride, [2][limbs][N]) = (x^beta_b tv_b, 0), tv_b at tv + b * tv_stride ([limbs][N] canonical; stride 0: shared)
+void launch_blind_rotate_init(const u64 *lwe, u64 lwe_stride, u64 n, const u64 *tv, u64 tv_stride, u64 *out, u64 out_stride, const PrimeDesc *primes, const LimbMap &map, int logn,
+                              u64 limbs, u64 batch, hipStream_t s);
+// pre: ops[t][b][2][limbs][N] = (x^(u_t) - 1) acc_b for t < terms (1 or 2), u_0 = lwe[b][step], u_1 = 2N - u_0; acc_b at acc + b * acc_stride, read only
+struct BlindRotArgs { const u64 *acc; u64 acc_stride; const u64 *lwe; u64 lwe_stride, step; u64 *ops; u64 items, limbs; int logn; };
+void launch_blind_rotate_pre(const BlindRotArgs &a, int terms, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
+// one-limb LWE samples c1 [samples][N], c0 [samples] modulo the first prime of `map` -> out [samples][N + 1] = round(2N x / q_0) mod 2N, beta last
+void launch_lwe_mod_switch(const u64 *c1, const u64 *c0, u64 *out, const PrimeDesc *primes, const LimbMap &map, int logn, u64 samples, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

@@ -673,6 +673,114 @@ void launch_expand_post(const u64 *even, u64 even_stride, u64 *odd, u64 odd_stri
     launch_check("expand_post_kernel");
 }
 
+// ---------------------------------------------------------------- blind rotation
+// Every shift is an LWE word in DEVICE memory, taken modulo 2N here (masked, never trusted); x^u moves coefficient n - u to n, so output n GATHERS input
+// m = (n - u) mod 2N: coefficient m mod N, negated where bit N of m is set (the reason for the gather form is given at galois_coeff_kernel).
+// acc_0 = (x^beta tv, 0): one thread per output word of the two polynomials; the second polynomial is zeroed.
+__global__ __launch_bounds__(EW_THREADS) void blind_rotate_init_kernel(const u64 *__restrict__ lwe, u64 lwe_stride, u64 n, const u64 *__restrict__ tv, u64 tv_stride,
+                                                                      u64 *__restrict__ out, u64 out_stride, const PrimeDesc *primes, LimbMap map, int logn, u64 limbs, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << logn, row = i >> logn, j = i & (N - 1), r = row % (2 * limbs), b = row / (2 * limbs);
+    u64 v = 0;
+    if (r < limbs) {
+        const u64 beta = lwe[b * lwe_stride + n] & (2 * N - 1), m = (j - beta) & (2 * N - 1);
+        v = tv[b * tv_stride + (r << logn) + (m & (N - 1))];
+        if (m >> logn) v = negmod(v, primes[map.id[r]].p);
+    }
+    out[b * out_stride + (r << logn) + j] = v;
+}
+void launch_blind_rotate_init(const u64 *lwe, u64 lwe_stride, u64 n, const u64 *tv, u64 tv_stride, u64 *out, u64 out_stride, const PrimeDesc *primes, const LimbMap &map, int logn,
+                              u64 limbs, u64 batch, hipStream_t s) {
+    const u64 total = (batch * 2 * limbs) << logn;
+    if (!total) return;
+    if (!lwe || !tv || !out || limbs > 64 || lwe_stride <= n || out_stride < (2 * limbs << logn) || (tv_stride && tv_stride < (limbs << logn)))
+        throw Error(ST_LOGIC_ERROR, "blind_rotate_init: operands");
+    TROY_LAUNCH(blind_rotate_init_kernel, flat_grid(total, "blind_rotate_init_kernel"), dim3(EW_THREADS), 0, s, lwe, lwe_stride, n, tv, tv_stride, out, out_stride, primes, map, logn,
+                limbs, total);
+    launch_check("blind_rotate_init_kernel");
+}
+// The operands of step `step`: for the item's word a (u_0 = a, u_1 = 2N - a) and every term t < T
+//   ops[t][b][k][l][n] = (+-acc_b[k][l][(n - u_t) mod N]) - acc_b[k][l][n] mod p_l,   canonical: (x^(u_t) - 1) acc_b,
+// laid out [t][item][2][limbs][N] so that the digit expansion reads 2 x items back-to-back polynomials per term.  A thread owns V consecutive
+// coefficients of one row: acc[n] is read once (one 16-byte load for V == 2) and serves both terms; the gathered reads are unaligned by nature and stay
+// 8-byte; every store is V words wide and a wave writes whole lines.  No LDS, no scratch, no atomics.
+template <int T, int V> __global__ __launch_bounds__(EW_THREADS) void blind_rotate_pre_kernel(BlindRotArgs a, const PrimeDesc *primes, LimbMap map, u64 total) {
+    static_assert((T == 1 || T == 2) && (V == 1 || V == 2), "one or two terms, one or two coefficients per thread");
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    constexpr int lv = V == 2 ? 1 : 0;
+    const u64 N = u64(1) << a.logn, row = i >> (a.logn - lv), j = (i & ((N >> lv) - 1)) << lv, r = row % (2 * a.limbs), b = row / (2 * a.limbs);
+    const u64 p = primes[map.id[r % a.limbs]].p;
+    const u64 w = a.lwe[b * a.lwe_stride + a.step] & (2 * N - 1);
+    const u64 *src = a.acc + b * a.acc_stride + (r << a.logn);
+    u64 x[V];
+    if (V == 2) {
+        const ulonglong2 t0 = *reinterpret_cast<const ulonglong2 *>(src + j);
+        x[0] = t0.x; x[V - 1] = t0.y;
+    } else {
+        x[0] = src[j];
+    }
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        const u64 u = t ? (2 * N - w) & (2 * N - 1) : w;
+        u64 o[V];
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+            const u64 m = (j + (u64)v - u) & (2 * N - 1);
+            u64 g = src[m & (N - 1)];
+            if (m >> a.logn) g = negmod(g, p);
+            o[v] = submod(g, x[v], p);
+        }
+        u64 *dst = a.ops + ((((u64)t * a.items + b) * 2 * a.limbs + r) << a.logn) + j;
+        if (V == 2) {
+            ulonglong2 t1;
+            t1.x = o[0]; t1.y = o[V - 1];
+            *reinterpret_cast<ulonglong2 *>(dst) = t1;
+        } else {
+            dst[0] = o[0];
+        }
+    }
+}
+void launch_blind_rotate_pre(const BlindRotArgs &a, int terms, const PrimeDesc *primes, const LimbMap &map, hipStream_t s) {
+    if (!a.items) return;
+    if (!a.acc || !a.lwe || !a.ops || !a.limbs || a.limbs > 64 || a.lwe_stride <= a.step || a.acc_stride < (2 * a.limbs << a.logn) || (terms != 1 && terms != 2))
+        throw Error(ST_LOGIC_ERROR, "blind_rotate_pre: operands");
+    // two coefficients per thread where every row starts on 16 bytes: the rows are N words apart, so the pointers and the item stride decide
+    const bool vec = a.logn >= 1 && !(((uintptr_t)a.acc | (uintptr_t)a.ops) & 15) && !(a.acc_stride & 1);
+    const u64 total = (a.items * 2 * a.limbs) << (a.logn - (vec ? 1 : 0));
+    const dim3 grid = flat_grid(total, "blind_rotate_pre_kernel");
+    if (terms == 2) {
+        if (vec) TROY_LAUNCH(HIP_KERNEL_NAME(blind_rotate_pre_kernel<2, 2>), grid, dim3(EW_THREADS), 0, s, a, primes, map, total);
+        else TROY_LAUNCH(HIP_KERNEL_NAME(blind_rotate_pre_kernel<2, 1>), grid, dim3(EW_THREADS), 0, s, a, primes, map, total);
+    } else {
+        if (vec) TROY_LAUNCH(HIP_KERNEL_NAME(blind_rotate_pre_kernel<1, 2>), grid, dim3(EW_THREADS), 0, s, a, primes, map, total);
+        else TROY_LAUNCH(HIP_KERNEL_NAME(blind_rotate_pre_kernel<1, 1>), grid, dim3(EW_THREADS), 0, s, a, primes, map, total);
+    }
+    launch_check("blind_rotate_pre_kernel");
+}
+// One-limb LWE samples from q_0 to 2N: out[r][j] = round(2N x / q_0) mod 2N = floor((4N x + q_0) / (2 q_0)) mod 2N (q_0 is odd: no tie), the N words of
+// a first and beta last.  4N x + q_0 takes more than 64 bits: the quotient by q_0 is div128's, halved.  A word at or above q_0 is reduced first.
+__global__ __launch_bounds__(EW_THREADS) void lwe_mod_switch_kernel(const u64 *__restrict__ c1, const u64 *__restrict__ c0, u64 *__restrict__ out, const PrimeDesc *primes, LimbMap map,
+                                                                   int logn, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << logn, r = i / (N + 1), j = i - r * (N + 1);
+    const Mod m = mod_of(primes[map.id[0]]);
+    const u64 x = barrett64(j < N ? c1[(r << logn) + j] : c0[r], m);
+    u64 lo = x * (4 * N), hi = mulhi64(x, 4 * N);
+    lo += m.p;
+    hi += lo < m.p;
+    out[i] = (div128(lo, hi, m) >> 1) & (2 * N - 1);
+}
+void launch_lwe_mod_switch(const u64 *c1, const u64 *c0, u64 *out, const PrimeDesc *primes, const LimbMap &map, int logn, u64 samples, hipStream_t s) {
+    const u64 total = samples * ((u64(1) << logn) + 1);
+    if (!total) return;
+    if (!c1 || !c0 || !out) throw Error(ST_LOGIC_ERROR, "lwe_mod_switch: operands");
+    TROY_LAUNCH(lwe_mod_switch_kernel, flat_grid(total, "lwe_mod_switch_kernel"), dim3(EW_THREADS), 0, s, c1, c0, out, primes, map, logn, total);
+    launch_check("lwe_mod_switch_kernel");
+}
+
 // ---------------------------------------------------------------- mod-switch / rescale (a-4 / A.10)
 // kind 0: BFV divideAndRoundqLastInplace (rns.cpp:805-830); kind 2: BGV modTAndDivideqLastInplace (rns.cpp:1097-1140).
 // in [polys][limbs][N] -> out [polys][limbs-1][N]
