@@ -113,7 +113,7 @@ int troyhip_test_modarith(int op, const uint64_t *a, const uint64_t *b, const ui
 /* per-kernel timing: while enabled every kernel launch is bracketed by HIP events on its own stream; the report is JSON text
  * [{"name", "calls", "total_us"}, ...] in first-launch order and clears the log (bench.py: roofline.per_kernel) */
 /* path counters ("ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches",
- * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "extprod_slabs", "extprod_chunks": slabs and chunks of troyhip_external_product_sum, "blindrot_slabs", "blindrot_steps": slabs and steps of troyhip_blind_rotate, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
+ * "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "ntt1_xcd_launches", "hoist_slabs": slabs of troyhip_apply_galois_hoisted, "hoist_lt_slabs": slabs of troyhip_galois_plain_sum_hoisted, "bsgs_slabs": slabs of troyhip_galois_plain_sum_bsgs, "mulsum_chunks": chunks of troyhip_multiply_sum, "poly_products", "poly_relins", "poly_scalar_sums": products, relinearizations and scalar sums of troyhip_evaluate_polynomial / troyhip_scalar_combine, "lwe_pack_key_switches", "lwe_pack_chunks": key switches and chunks of troyhip_pack_lwes, "expand_key_switches", "expand_chunks": key switches and chunks of troyhip_expand_coefficients, "extprod_slabs", "extprod_chunks": slabs and chunks of troyhip_external_product_sum, "blindrot_slabs", "blindrot_steps": slabs and steps of troyhip_blind_rotate, "lwe_ks_slabs", "lwe_ks_splits": slabs of troyhip_lwe_key_switch and the splits S of its last call, "ks_int_groups_per_wg": summed ciphertexts per workgroup of the integer key-switch accumulating launches): which kernel class (or workgroup order) the launchers chose so far in
  * this process -- the parity tests read them so that a test of the FP64 instances cannot pass on the integer kernels unnoticed.  No
  * reference counterpart (test / diagnostics support, like troyhip_ktime_*). */
 int troyhip_stat(const char *name, uint64_t *value);
@@ -495,6 +495,31 @@ int troyhip_blind_rotate_scratch_words(const troyhip_context *ctx, int limbs, in
  * (no reference counterpart): out (DEVICE) [count * batch][N + 1] words round(2N x / q_0) mod 2N = floor((4N x + q_0) / (2 q_0)) mod 2N -- q_0 is odd, so
  * there is no tie -- the N shifts first and beta last: the samples troyhip_blind_rotate reads with n = N and lwe_stride = N + 1. */
 int troyhip_lwe_mod_switch(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t count, uint64_t batch, uint64_t *out, void *stream);
+/* ---- LWE key switching to a smaller dimension (no reference counterpart).  BFV / BGV.  Stream-ordered; nothing is read back and
+ * nothing synchronises inside the call. ----
+ * c1 [samples][N], c0 [samples] (DEVICE): ONE-limb samples as troyhip_extract_lwes writes them at limbs == 1 (samples = count x batch), words taken modulo
+ * q_0 (a word at or above q_0 is reduced first).  The multiplier of word i is u_i, u_0 = s_0 and u_i = -s_(N-i): the phase is c0 + sum_i c1[i] u_i.
+ * key (DEVICE): [N][l][n + 1] words modulo q_0, l = ceil(bit_length(q_0) / base_bits); row (i, j) = (a_0 .. a_(n-1), b) has the phase
+ * b + <a, z> = u_i 2^(base_bits j) + e under the target secret z.  With the UNSIGNED digits c1[r][i] = sum_j d_(r,i,j) 2^(base_bits j), 0 <= d < 2^base_bits,
+ *   out[r][k] = ([k == n] c0_r + sum_(i < N) sum_(j < l) d_(r,i,j) key[i][j][k]) mod q_0,   canonical, at out + r * out_stride + k:
+ * the n words of a first and beta last, what troyhip_blind_rotate reads with lwe_stride = out_stride; words past n + 1 of a row are not touched.  The
+ * phase gains sum d e, at most N l (2^base_bits - 1) 21.  to_2n != 0: every word is then floor((4N x + q_0) / (2 q_0)) mod 2N, the formula of
+ * troyhip_lwe_mod_switch.  Every step is exact: the words depend neither on the batch, on the splits nor on scratch_limit_words (0: 2^28 words).  The N l
+ * rows are summed in S parts (troyhip_lwe_key_switch_scratch_words reports S, a host-only function of samples, N and n), the samples in slabs where
+ * the request [S][samples][n + 1] would pass the limit; below what ONE sample asks for the call is refused.  Refused: CKKS ("unsupported scheme"), a
+ * host-only context, null pointers, n == 0 or n > 65536, base_bits outside 1 .. 16, out_stride < n + 1, samples == 0 or more than 2^40 (or
+ * out_stride > 2^22), a destination that shares words with the operands or the key.  Counters "lwe_ks_slabs", "lwe_ks_splits". */
+int troyhip_lwe_key_switch(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t samples, const uint64_t *key, uint64_t n, int base_bits, int to_2n,
+                           uint64_t *out, uint64_t out_stride, uint64_t scratch_limit_words, void *stream);
+/* the arena words the call above asks for with the samples in one slab, and (splits != NULL) its S: host-only functions of (samples, N, n) */
+int troyhip_lwe_key_switch_scratch_words(const troyhip_context *ctx, uint64_t n, int base_bits, uint64_t samples, uint64_t *words, uint64_t *splits);
+/* N l (n + 1): the words of a key */
+int troyhip_lwe_kswitch_key_words(const troyhip_context *ctx, uint64_t n, int base_bits, uint64_t *words);
+/* the key on the HOST (works on a host-only context): secret_key [K][N] NTT form, of which the first limb is read and refused unless its inverse transform
+ * is ternary; lwe_secret: n digits over {-1, 0, 1}.  ONE ChaCha20 stream (seed_lo, seed_hi, 10 << 32), rows i-major then j: n draws uniform below q_0 for
+ * a_0 .. a_(n-1), then ONE word for e (21 - 21 coin flips);  b = u_i 2^(base_bits j) + e - sum_k a_k z_k mod q_0. */
+int troyhip_host_lwe_kswitch_key(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const int8_t *lwe_secret, uint64_t n, int base_bits,
+                                 uint64_t *out);
 /* ---- DecryptorCuda::decrypt (src/decryptor_cuda.cu:61-330; dotProductCtSkArray + decryptScaleAndRound / decryptModt,
  * src/utils/rns_cuda.cu:510-621), SURVEY 8-f3.  secret_key: device [K][N] (NTT form, src/secretkey.h).  plain_out (device):
  * BFV/BGV N coefficients mod t per item, items plain_batch_stride words apart; CKKS the RNS plaintext [limbs][N] (NTT form). */

@@ -1035,6 +1035,36 @@ private:
     int T_ = 0;
 };
 
+// The key of Evaluator::lweKeySwitch (the reference has none): a dense device array [N][l][n + 1] of words modulo q_0,
+// l = ceil(bit_length(q_0) / base_bits); row (i, j) has the phase u_i 2^(base_bits j) + e under the target secret, u the extraction secret.
+class LWESwitchKey {
+public:
+    const uint64_t *device(const ParmsID &key_parms_id, size_t expected_words) const {
+        if (!words_ || parms_id_ != key_parms_id || !n_ || base_bits_ < 1 || base_bits_ > 16 || words_->size() != expected_words)
+            throw std::invalid_argument("LWE switching key is not valid for encryption parameters");
+        return words_->get();
+    }
+    void adopt(const ParmsID &key_parms_id, std::shared_ptr<DeviceArray> words, size_t n, int base_bits) {
+        parms_id_ = key_parms_id; words_ = std::move(words); n_ = n; base_bits_ = base_bits;
+    }
+    std::vector<uint64_t> toHost() const {
+        std::vector<uint64_t> v(words_ ? words_->size() : 0);
+        if (!v.empty()) {
+            check(troyhip_copy_d2h(v.data(), words_->get(), v.size() * 8, nullptr));
+            check(troyhip_stream_synchronize(nullptr));
+        }
+        return v;
+    }
+    size_t dimension() const noexcept { return n_; }
+    int baseBits() const noexcept { return base_bits_; }
+    const ParmsID &parmsID() const noexcept { return parms_id_; }
+private:
+    std::shared_ptr<DeviceArray> words_;
+    ParmsID parms_id_;
+    size_t n_ = 0;
+    int base_bits_ = 0;
+};
+
 // A rows x cols matrix of NTT-form plaintexts of one level and one scale in ONE device array [rows][cols][limbs][N] (the reference has none; DESIGN.md
 // section 4.21): what Evaluator::multiplyPlainMatrix streams.  Evaluator::packPlainMatrix makes one; a database that is scanned many times is packed once.
 class PlainMatrix {
@@ -1314,6 +1344,37 @@ public:
         check(troyhip_stream_synchronize(nullptr)); // the constants are freed on return
         BlindRotationKey key;
         key.adopt(c_.keyParmsID(), words, s.size(), (int)T);
+        return key;
+    }
+    // ---- LWE key switching to a smaller dimension (troyhip_host_lwe_kswitch_key; the reference has none).
+    // u_0 = s_0, u_i = -s_(N-i): the multipliers of the words of a sample of extractLWEs, whose phase is c0 + sum_i c1[i] u_i.
+    // createBlindRotationKey(extractionSecret()) is the n = N key under which the samples of lweModSwitch carry the message's phase; the default
+    // createBlindRotationKey() takes digit i = s_i, the order of secretCoefficients(), which is NOT the order of an extracted sample's words.
+    std::vector<int> extractionSecret() const {
+        const std::vector<int> s = secretCoefficients();
+        std::vector<int> u(s.size());
+        for (size_t i = 0; i < s.size(); i++) u[i] = i ? -s[s.size() - i] : s[0];
+        return u;
+    }
+    // the key from the RLWE secret to lwe_secret (digits over {-1, 0, 1}) with unsigned digits of base_bits bits, made on the host and uploaded; it takes
+    // ONE seed of the counter the createRGSW members share
+    LWESwitchKey createLWESwitchKey(const std::vector<int> &lwe_secret, int base_bits = 8) const {
+        if (lwe_secret.empty() || lwe_secret.size() > 65536) throw std::invalid_argument("the LWE secret takes 1 to 65536 digits over {-1, 0, 1}");
+        std::vector<int8_t> z(lwe_secret.size());
+        for (size_t k = 0; k < z.size(); k++) {
+            if (lwe_secret[k] < -1 || lwe_secret[k] > 1) throw std::invalid_argument("the LWE secret takes 1 to 65536 digits over {-1, 0, 1}");
+            z[k] = (int8_t)lwe_secret[k];
+        }
+        uint64_t words = 0;
+        check(troyhip_lwe_kswitch_key_words(c_.handle(), z.size(), base_bits, &words));
+        std::vector<uint64_t> host(words);
+        check(troyhip_host_lwe_kswitch_key(c_.handle(), lo_ + kswitch_calls_, hi_, sk_.data.data(), z.data(), z.size(), base_bits, host.data()));
+        kswitch_calls_ += 1;
+        auto dev = std::make_shared<DeviceArray>(words);
+        check(troyhip_copy_h2d(dev->get(), host.data(), words * 8, nullptr));
+        check(troyhip_stream_synchronize(nullptr)); // the host copy goes on return
+        LWESwitchKey key;
+        key.adopt(c_.keyParmsID(), dev, z.size(), base_bits);
         return key;
     }
     // the ceil(log2 count) keys Evaluator::expandCoefficients(.., count, ..) needs: X -> X^((N >> j) + 1) for the layers j = 0, 1, ..
@@ -3091,6 +3152,21 @@ public:
         if (lwes.limbs_ != 1) throw std::invalid_argument("lwe_mod_switch takes samples of one limb");
         DeviceArray out(lwes.count_ * (c_.polyModulusDegree() + 1));
         check(troyhip_lwe_mod_switch(h(), lwes.c1_.get(), lwes.c0_.get(), lwes.count_, 1, out.get(), nullptr));
+        return out;
+    }
+    // the ONE-limb samples of an LWEBatch switched to the key's dimension n in one call (troyhip_lwe_key_switch): [count][n + 1]
+    // words on the device, the n words of a first and beta last, modulo q_0 or (to_2n) switched to 2N -- what blindRotateBatch reads with a key of
+    // dimension n.  The key carries the index map of extractLWEs: the phase of the result is the phase of the extracted coefficient plus the key's noise
+    DeviceArray lweKeySwitch(const LWEBatch &lwes, const LWESwitchKey &key, bool to_2n = true, uint64_t scratch_limit_words = 0) const {
+        if (!lwes.count_) throw std::invalid_argument("LWE ciphertexts must not be empty.");
+        if (lwes.limbs_ != 1) throw std::invalid_argument("lwe_key_switch takes samples of one limb");
+        const size_t n = key.dimension();
+        if (!n) throw std::invalid_argument("LWE switching key is not valid for encryption parameters");
+        uint64_t words = 0;
+        check(troyhip_lwe_kswitch_key_words(h(), n, key.baseBits(), &words));
+        const uint64_t *k = key.device(c_.keyParmsID(), words);
+        DeviceArray out(lwes.count_ * (n + 1));
+        check(troyhip_lwe_key_switch(h(), lwes.c1_.get(), lwes.c0_.get(), lwes.count_, k, n, key.baseBits(), to_2n ? 1 : 0, out.get(), n + 1, scratch_limit_words, nullptr));
         return out;
     }
 

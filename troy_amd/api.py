@@ -492,6 +492,35 @@ class BlindRotationKey:
         return self.buf.to_numpy().reshape(self.n, self.T, 2, K - 1, 2, K, N)
 
 
+class LWESwitchKey:
+    """The key of Evaluator.lweKeySwitch (no reference counterpart): a dense device array [N][l][n + 1] of words modulo q_0,
+    l = ceil(bit_length(q_0) / base_bits); row (i, j) = (a_0 .. a_(n-1), b) has the phase b + <a, z> = u_i 2^(base_bits j) + e under the target secret z,
+    where u_0 = s_0 and u_i = -s_(N-i) are the multipliers of the words of an extracted sample."""
+
+    def __init__(self, context, buf, n, base_bits):
+        n, base_bits = int(n), int(base_bits)
+        if not isinstance(buf, DeviceBuffer) or not 1 <= n <= 65536 or not 1 <= base_bits <= 16 or buf.words != self.shape_of(context, n, base_bits)[3]:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE switching key is not valid for encryption parameters")
+        self.context, self.buf, self.n, self.base_bits = context, buf, n, base_bits
+        self.digits = self.shape_of(context, n, base_bits)[1]
+
+    @staticmethod
+    def shape_of(context, n, base_bits):
+        """(N, l, n + 1, words)"""
+        l = -(-int(context.coeff_modulus[0]).bit_length() // int(base_bits))
+        return context.N, l, int(n) + 1, context.N * l * (int(n) + 1)
+
+    @classmethod
+    def from_numpy(cls, context, host_array, base_bits):
+        a = np.ascontiguousarray(host_array, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[2] < 2 or not 1 <= int(base_bits) <= 16 or a.shape != cls.shape_of(context, a.shape[2] - 1, base_bits)[:3]:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE switching key is not valid for encryption parameters")
+        return cls(context, DeviceBuffer.from_numpy(a), a.shape[2] - 1, base_bits)
+
+    def cpu(self):
+        return self.buf.to_numpy().reshape(self.shape_of(self.context, self.n, self.base_bits)[:3])
+
+
 class Evaluator:
     """EvaluatorCuda (src/evaluator_cuda.cuh:13-361) over batches."""
 
@@ -1082,6 +1111,31 @@ class Evaluator:
         self._chk(self.lib.troyhip_lwe_mod_switch(self.context.h, C.c_void_p(lwes.c1.ptr), C.c_void_p(lwes.c0.ptr), C.c_uint64(lwes.count), C.c_uint64(lwes.batch),
                                                   C.c_void_p(out.ptr), self.stream))
         return out
+
+    # -- LWE key switching to a smaller dimension (troyhip_lwe_key_switch: no reference counterpart)
+    def lweKeySwitch(self, lwes, key, to_2n=True, scratch_limit_words=0):
+        """the one-limb samples of an LWEBatch switched to the key's dimension n in ONE call: a DeviceBuffer of [count * batch][n + 1] words, the n words of
+        a first and beta last, modulo q_0 or (to_2n) switched to 2N -- what blindRotate reads with a key of dimension n.  The key carries the negacyclic
+        index map of extractLWEs, so the phase of the result is the phase of the extracted coefficient plus the key's noise."""
+        if not isinstance(lwes, LWEBatch) or lwes.context is not self.context:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "lwe_key_switch takes an LWEBatch")
+        if not isinstance(key, LWESwitchKey) or key.context is not self.context:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LWE switching key is not valid for encryption parameters")
+        if lwes.limbs != 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "lwe_key_switch takes samples of one limb")
+        samples = lwes.count * lwes.batch
+        out = DeviceBuffer(max(samples * (key.n + 1), 1))
+        self._chk(self.lib.troyhip_lwe_key_switch(self.context.h, C.c_void_p(lwes.c1.ptr), C.c_void_p(lwes.c0.ptr), C.c_uint64(samples), C.c_void_p(key.buf.ptr),
+                                                  C.c_uint64(key.n), key.base_bits, int(bool(to_2n)), C.c_void_p(out.ptr), C.c_uint64(key.n + 1),
+                                                  C.c_uint64(scratch_limit_words), self.stream))
+        return out
+
+    def lweKeySwitchScratchWords(self, n, base_bits, samples):
+        """(words, splits): the arena words lweKeySwitch asks for with the samples in one slab and the parts S it sums the key's rows in
+        (troyhip_lwe_key_switch_scratch_words)"""
+        w, sp = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.troyhip_lwe_key_switch_scratch_words(self.context.h, C.c_uint64(n), int(base_bits), C.c_uint64(samples), C.byref(w), C.byref(sp)))
+        return w.value, sp.value
 
     def _copy_then(self, fn, a, *args):
         r = a.copy()
@@ -1703,9 +1757,14 @@ class KeyGenerator:
         return s
 
     def createBlindRotationKey(self, lwe_secret=None, ternary=None):
-        """the BlindRotationKey of an LWE secret over {-1, 0, 1} (None: the RLWE secret's own coefficients, so that the samples of extractLWEs can be used
-        as they are): RGSW ciphertexts of the constants 0 / 1 from the device generator, row i of T == 1 for s_i, of T == 2 (any digit is -1, or `ternary`)
-        for [s_i = 1] and [s_i = -1].  Every RGSW takes two of the generator's seeds, in the order [i][t]: kswitch_calls advances by 2 n T."""
+        """the BlindRotationKey of an LWE secret over {-1, 0, 1}: RGSW ciphertexts of the constants 0 / 1 from the device generator, row i of T == 1 for
+        s_i, of T == 2 (any digit is -1, or `ternary`) for [s_i = 1] and [s_i = -1].  Every RGSW takes two of the generator's seeds, in the order [i][t]:
+        kswitch_calls advances by 2 n T.
+        None (the default) takes the RLWE secret's coefficients IN THE ORDER OF secretCoefficients(), digit i = s_i.  Under that key blindRotate turns a
+        sample into tv x^(beta + sum_i a_i s_i) -- which is NOT the phase of a sample of extractLWEs: extraction leaves c1 as a polynomial, and the phase of
+        the extracted coefficient is c0 + c1[0] s_0 - sum_(i >= 1) c1[i] s_(N-i).  For extracted samples (lweModSwitch, LookupTable.apply) pass
+        extractionSecret(): createBlindRotationKey(kg.extractionSecret()) is the n = N key under which they carry the message's phase; a smaller
+        dimension goes through createLWESwitchKey and Evaluator.lweKeySwitch."""
         ctx = self.context
         K, N = ctx.key_limbs, ctx.N
         if K < 2:
@@ -1726,6 +1785,33 @@ class KeyGenerator:
             capi.check(self.lib, self.lib.troyhip_create_rgsw(ctx.h, lo, hi, C.c_void_p(self._device_sk().ptr), pm, po, C.c_uint64(len(chunk)), None))
         synchronize()  # the plaintext buffers made here are released on return
         return BlindRotationKey(ctx, buf, s.size, T)
+
+    # ---- LWE key switching to a smaller dimension (troyhip_host_lwe_kswitch_key: no reference counterpart)
+    def extractionSecret(self):
+        """u with u_0 = s_0 and u_i = -s_(N-i) (int64, s = secretCoefficients()): the multipliers of the words of a sample of extractLWEs, whose phase is
+        c0 + sum_i c1[i] u_i.  createBlindRotationKey(extractionSecret()) is the n = N key for extracted samples."""
+        s = self.secretCoefficients()
+        u = np.empty_like(s)
+        u[0] = s[0]
+        u[1:] = -s[:0:-1]
+        return u
+
+    def createLWESwitchKey(self, lwe_secret, base_bits=8):
+        """the LWESwitchKey from the RLWE secret (in the order of extractionSecret()) to an LWE secret over {-1, 0, 1} with unsigned digits of base_bits
+        bits, made on the host and uploaded.  It takes ONE of the generator's seeds, (lo + kswitch_calls, hi): kswitch_calls advances by 1."""
+        ctx = self.context
+        z = np.asarray(lwe_secret).astype(np.int64).reshape(-1)
+        if not 1 <= z.size <= 65536 or np.abs(z).max() > 1:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "the LWE secret takes 1 to 65536 digits over {-1, 0, 1}")
+        base_bits = int(base_bits)
+        if not 1 <= base_bits <= 16:
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "lwe_key_switch takes 1 to 16 base bits")
+        z8 = np.ascontiguousarray(z, dtype=np.int8)
+        out = np.zeros(LWESwitchKey.shape_of(ctx, z.size, base_bits)[:3], dtype=np.uint64)
+        lo, hi = C.c_uint64((self.seed[0] + self.kswitch_calls) & (2**64 - 1)), C.c_uint64(self.seed[1])
+        capi.check(self.lib, self.lib.troyhip_host_lwe_kswitch_key(ctx.h, lo, hi, _u64p(self._sk), z8.ctypes.data_as(C.c_void_p), C.c_uint64(z.size), base_bits, _u64p(out)))
+        self.kswitch_calls += 1
+        return LWESwitchKey(ctx, DeviceBuffer.from_numpy(out), z.size, base_bits)
 
     def automorphismElts(self):
         """X -> X^(N / 2^k + 1) for k = 0 .. log2(N) - 1 (src/keygenerator.cpp:350-358)"""

@@ -608,14 +608,21 @@ class LookupTable:
         vals = [(q * int(v) + t // 2) // t if ctx.scheme == capi.BFV else int(v) for v in self.poly]
         return np.array([[v % p for v in vals] for p in primes], dtype=np.uint64)
 
-    def apply(self, evaluator, ct_batch, terms, key, limbs=None, scratch_limit_words=0):
-        """the table on the coefficients `terms` of every item of a BFV / BGV batch -> (rotated, lwes): modSwitchTo one limb, extractLWEs, lweModSwitch,
-        blindRotate under `key` (createBlindRotationKey() of the ciphertexts' own secret) at `limbs` (default: the first level) and extractLWEs at term
-        0.  Sample (j, b) of `lwes` encrypts table[phi] in its constant term, phi the switched phase of coefficient terms[j] of item b;
-        Evaluator.packLWEs can follow."""
+    def apply(self, evaluator, ct_batch, terms, key, limbs=None, scratch_limit_words=0, lwe_key=None):
+        """the table on the coefficients `terms` of every item of a BFV / BGV batch -> (rotated, lwes): modSwitchTo one limb, extractLWEs, the switch to
+        2N, blindRotate under `key` at `limbs` (default: the first level) and extractLWEs at term 0.  Sample (j, b) of `lwes` encrypts table[phi] in its
+        constant term, phi the phase the samples carry under `key`; Evaluator.packLWEs can follow.
+        lwe_key (an api.LWESwitchKey of createLWESwitchKey(z)): the samples go through lweKeySwitch(to_2n=True) to dimension n = lwe_key.n and `key` is
+        createBlindRotationKey(z): n CMux steps instead of N, and phi is the phase of the MESSAGE, round(2N m / t) up to the noise -- the result is f(m).
+        lwe_key=None: lweModSwitch and a key of dimension N.  phi is then beta + sum_i a_i d_i for the digits d of `key` in the order of the words: with
+        createBlindRotationKey(kg.extractionSecret()) that is the message's phase too; with the default createBlindRotationKey() (digit i = s_i) it is
+        not, because extraction leaves c1 as a polynomial whose word i multiplies -s_(N-i)."""
         ev, ctx = evaluator, self.context
         limbs = int(limbs or ctx.first_limbs)
+        if lwe_key is not None and (not isinstance(lwe_key, api.LWESwitchKey) or lwe_key.n != key.n):
+            raise capi.InvalidArgument(capi.INVALID_ARGUMENT, "LookupTable: the LWE switching key and the blind rotation key differ in dimension")
         low = ev.modSwitchTo(ct_batch, 1) if ct_batch.limbs > 1 else ct_batch
-        samples = ev.lweModSwitch(ev.extractLWEs(low, terms))
+        lwes = ev.extractLWEs(low, terms)
+        samples = ev.lweModSwitch(lwes) if lwe_key is None else ev.lweKeySwitch(lwes, lwe_key, to_2n=True, scratch_limit_words=scratch_limit_words)
         rotated = ev.blindRotate(samples, key, self.test_vector(limbs), limbs=limbs, scratch_limit_words=scratch_limit_words)
         return rotated, ev.extractLWEs(rotated, [0])

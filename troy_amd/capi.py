@@ -70,6 +70,7 @@ SYMBOLS = [
     #  troyhip_ct *out, u64 out_col_stride, u64 batch, stream)
     "troyhip_multiply_plain_matrix",
     "troyhip_blind_rotate", "troyhip_blind_rotate_scratch_words", "troyhip_lwe_mod_switch",
+    "troyhip_lwe_key_switch", "troyhip_lwe_key_switch_scratch_words", "troyhip_lwe_kswitch_key_words", "troyhip_host_lwe_kswitch_key",
     "troyhip_encrypt", "troyhip_encrypt_symmetric", "troyhip_expand_seed",
     "troyhip_host_ckks_encode", "troyhip_host_ckks_decode", "troyhip_batch_encode", "troyhip_batch_decode", "troyhip_ckks_encode", "troyhip_ckks_decode",
     "troyhip_keygen", "troyhip_create_galois_keys", "troyhip_create_relin_key", "troyhip_create_kswitch_key",

@@ -1252,6 +1252,34 @@ int troyhip_lwe_mod_switch(troyhip_context *ctx, const uint64_t *c1, const uint6
         handle->ev.lwe_mod_switch(c1, c0, count, batch, out, on(stream));
     });
 }
+/* LWE key switching to a smaller dimension (no reference counterpart) */
+int troyhip_lwe_key_switch(troyhip_context *ctx, const uint64_t *c1, const uint64_t *c0, uint64_t samples, const uint64_t *key, uint64_t n, int base_bits, int to_2n,
+                           uint64_t *out, uint64_t out_stride, uint64_t scratch_limit_words, void *stream) {
+    return guard([&] {
+        auto *handle = need(ctx); // the context is bound before the stream is looked at
+        handle->ev.lwe_key_switch(c1, c0, samples, key, n, base_bits, to_2n, out, out_stride, scratch_limit_words, on(stream));
+    });
+}
+int troyhip_lwe_key_switch_scratch_words(const troyhip_context *ctx, uint64_t n, int base_bits, uint64_t samples, uint64_t *words, uint64_t *splits) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.lwe_key_switch_scratch_words(n, base_bits, samples, splits);
+    }, false);
+}
+int troyhip_lwe_kswitch_key_words(const troyhip_context *ctx, uint64_t n, int base_bits, uint64_t *words) {
+    return guard([&] {
+        if (!words) throw Error(ST_INVALID_ARGUMENT, "null output");
+        *words = need(ctx)->ev.lwe_kswitch_key_words(n, base_bits);
+    }, false);
+}
+int troyhip_host_lwe_kswitch_key(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const int8_t *lwe_secret, uint64_t n, int base_bits,
+                                 uint64_t *out) {
+    return guard([&] {
+        if (!secret_key || !lwe_secret || !out) throw Error(ST_INVALID_ARGUMENT, "null key, LWE secret or output");
+        need(ctx)->ev.lwe_kswitch_key_words(n, base_bits); // the refusals of the shape
+        hostcrypto::keygen_lwe_kswitch(need(ctx)->ctx, seed_lo, seed_hi, secret_key, lwe_secret, n, base_bits, out);
+    }, false);
+}
 int troyhip_host_rgsw(const troyhip_context *ctx, uint64_t seed_lo, uint64_t seed_hi, const uint64_t *secret_key, const uint64_t *plain_ntt_keylevel, uint64_t *out) {
     return guard([&] {
         if (!secret_key || !plain_ntt_keylevel || !out) throw Error(ST_INVALID_ARGUMENT, "null key, plaintext list or RGSW output");

@@ -2458,6 +2458,74 @@ void Evaluator::lwe_mod_switch(const u64 *c1, const u64 *c0, u64 count, u64 batc
     launch_lwe_mod_switch(c1, c0, out, c.d_desc, c.ct_map(1), c.logn, count * batch, s);
 }
 
+// ---- LWE key switching to a smaller dimension (no reference counterpart) ----
+// The plan is a host-only function of (samples, N, n): the mac kernel's grid has ceil((n + 1) / 64) blocks of columns by the tiles of samples, one wave
+// each; below LWE_KS_WAVES waves the N coefficients are cut into S parts, a power of two, of at least LWE_KS_MIN_COEFFS coefficients (l rows each),
+// 64 parts at the most.  Scratch: the partial residues [S][samples][n + 1], one block.
+static const u64 LWE_KS_MAX_N = 65536, LWE_KS_WAVES = 1024, LWE_KS_MIN_COEFFS = 64, LWE_KS_MAX_SPLITS = 64, LWE_KS_BLOCKS = 1;
+static void check_lwe_ks_shape(const Context &c, u64 n, int base_bits) {
+    if (c.scheme == SCHEME_CKKS) throw Error(ST_LOGIC_ERROR, "unsupported scheme: LWE key switching is defined under BFV and BGV");
+    if (!n || n > LWE_KS_MAX_N) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch takes 1 to 65536 LWE digits");
+    if (base_bits < 1 || base_bits > 16) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch takes 1 to 16 base bits");
+}
+static u64 lwe_ks_digits(const Context &c, int base_bits) {
+    const u64 bits = 64 - (u64)__builtin_clzll(c.primes[0]);
+    return (bits + (u64)base_bits - 1) / (u64)base_bits;
+}
+static u64 lwe_ks_splits(const Context &c, u64 n, u64 samples) {
+    const u64 rt = lwe_ks_tile(samples), waves = ((n + 1 + LWE_KS_THREADS - 1) / LWE_KS_THREADS) * ((samples + rt - 1) / rt);
+    const u64 cap = std::min<u64>(std::max<u64>(c.N / LWE_KS_MIN_COEFFS, 1), LWE_KS_MAX_SPLITS);
+    u64 S = 1;
+    while (S < cap && S * waves < LWE_KS_WAVES) S *= 2;
+    return S;
+}
+u64 Evaluator::lwe_kswitch_key_words(u64 n, int base_bits) const {
+    check_lwe_ks_shape(c, n, base_bits);
+    return c.N * lwe_ks_digits(c, base_bits) * (n + 1);
+}
+u64 Evaluator::lwe_key_switch_scratch_words(u64 n, int base_bits, u64 samples, u64 *splits) const {
+    check_lwe_ks_shape(c, n, base_bits);
+    if (!samples || samples > (u64(1) << 40)) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: no samples, or too many");
+    const u64 S = lwe_ks_splits(c, n, samples);
+    if (splits) *splits = S;
+    return samples * S * (n + 1) + slab_slack(LWE_KS_BLOCKS);
+}
+void Evaluator::lwe_key_switch(const u64 *c1, const u64 *c0, u64 samples, const u64 *key, u64 n, int base_bits, int to_2n, u64 *out, u64 out_stride,
+                               u64 scratch_limit_words, hipStream_t s) {
+    if (!c.has_device) throw Error(ST_LOGIC_ERROR, "this context was created host-only (troyhip_context_create_host)");
+    check_lwe_ks_shape(c, n, base_bits);
+    if (!c.is_data_level(1)) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: the context has no level of one limb");
+    if (!c1 || !c0 || !key || !out) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: null pointer");
+    if (out_stride < n + 1) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: output stride is smaller than one sample");
+    // samples N, samples out_stride and S samples (n + 1) stay far below 2^64
+    if (!samples || samples > (u64(1) << 40) || out_stride > (u64(1) << 22)) throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: no samples, or too many");
+    const u64 N = c.N, n1 = n + 1, l = lwe_ks_digits(c, base_bits);
+    if (batches_overlap(out, samples, out_stride, n1, c1, 1, 0, samples * N) || batches_overlap(out, samples, out_stride, n1, c0, 1, 0, samples) ||
+        batches_overlap(out, samples, out_stride, n1, key, 1, 0, N * l * n1))
+        throw Error(ST_INVALID_ARGUMENT, "lwe_key_switch: destination must be a distinct buffer");
+    // the least limit is what ONE sample asks for (lwe_key_switch_scratch_words(.., 1, ..)); a larger batch never asks for more splits
+    const u64 limit = scratch_limit_words ? scratch_limit_words : HOIST_DEFAULT_SCRATCH_WORDS;
+    if (lwe_ks_splits(c, n, 1) * n1 + slab_slack(LWE_KS_BLOCKS) > limit) throw Error(ST_INVALID_ARGUMENT, "scratch_limit_words is too small for one sample");
+    const u64 S = lwe_ks_splits(c, n, samples);
+    const SlabPlan plan = plan_slabs(scratch_limit_words, LWE_KS_BLOCKS, S * n1, 0, samples, 1, "scratch_limit_words is too small for one sample");
+    LweKsArgs a;
+    a.key = key; a.n1 = n1; a.col_blocks = (n1 + LWE_KS_THREADS - 1) / LWE_KS_THREADS; a.splits = S; a.part_coeffs = N / S; a.digits = l;
+    a.base_bits = (u32)base_bits; a.logn = c.logn;
+    // a slab's grid (blocks of columns x splits x tiles of samples, folded into x) stays below 2^31 workgroups: at least 2^13 samples
+    const u64 bs = std::min(plan.items, ((u64(1) << 31) - 1) / (a.col_blocks * S));
+    const LimbMap map = c.ct_map(1);
+    c.arena.begin(s);
+    c.arena.reserve(plan.words);
+    a.part = c.arena.take(bs * S * n1);
+    for (u64 r0 = 0; r0 < samples; r0 += bs) {
+        a.samples = std::min(bs, samples - r0);
+        a.c1 = c1 + r0 * N;
+        launch_lwe_ks(a, c0 + r0, out + r0 * out_stride, out_stride, to_2n, c.d_desc, map, s);
+        stats::counter(stats::LWE_KS_SLABS)++;
+    }
+    stats::counter(stats::LWE_KS_SPLITS) = S;
+}
+
 // ---- decryption ----
 u64 *Evaluator::dot_ct_sk(const CtBatch &ct, const u64 *sk, u64 batch, size_t extra, DecryptArgs &a, hipStream_t s) {
     const u64 limbs = ct.limbs, pw = poly_words(c, ct.limbs), np = ct.size - 1;

@@ -219,6 +219,15 @@ public:
     // one-limb LWE samples as extract_lwes returns them (c1 [count][batch][1][N], c0 [count][batch][1]) -> out [count * batch][N + 1] words
     // round(2N x / q_0) mod 2N, the shifts first and beta last: what blind_rotate reads
     void lwe_mod_switch(const u64 *c1, const u64 *c0, u64 count, u64 batch, u64 *out, hipStream_t s);
+    // LWE key switching to dimension n (no reference counterpart): one-limb samples as extract_lwes returns them (c1 [samples][N],
+    // c0 [samples], DEVICE, words taken modulo q_0) times the key [N][l][n + 1] (DEVICE; l = ceil(bit_length(q_0) / base_bits) unsigned digits):
+    //   out[r][k] = ([k == n] c0_r + sum_(i, j) d_(r, i, j) key[i][j][k]) mod q_0,  rows out_stride apart; to_2n: switched as lwe_mod_switch does.
+    // The N l rows are split into S = lwe_ks_splits(samples, n) parts whose canonical partial residues the finish kernel adds: every step is exact, so
+    // the words depend neither on S, on the slabs nor on the limit.  The arena request stays under scratch_limit_words (0: 2^28 words).
+    void lwe_key_switch(const u64 *c1, const u64 *c0, u64 samples, const u64 *key, u64 n, int base_bits, int to_2n, u64 *out, u64 out_stride, u64 scratch_limit_words,
+                        hipStream_t s);
+    u64 lwe_key_switch_scratch_words(u64 n, int base_bits, u64 samples, u64 *splits) const; // the samples in one slab; a host-only function
+    u64 lwe_kswitch_key_words(u64 n, int base_bits) const;                                   // N l (n + 1)
     // the ONE planning function of evaluate_polynomial and of the plan query; refuses a degree outside 1 .. 255, baby steps that are no power of two in
     // 2 .. 16 (0: the smallest with k^2 >= degree + 1) and more than 17 blocks
     static PolyPlan plan_polynomial(int degree, int baby_steps);

@@ -195,6 +195,39 @@ void keygen_rgsw(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, cons
     }
     keygen_kswitch(c, r1, sk, ms.data(), out + (K - 1) * 2 * K * N);
 }
+// The LWE switching key of DESIGN.md section 4.23, words modulo q_0: row (i, j) = (a_0 .. a_(n-1), b) with b = u_i 2^(w j) + e - sum_k a_k z_k, where
+// u_0 = s_0 and u_i = -s_(N-i) are the multipliers of the words of an extracted sample (s: the RLWE secret's coefficients) and z the target secret.
+// ONE stream (seed, 10 << 32), rows i-major then j: n uniform draws for a, then ONE word for e (the 21 - 21 coin flips of sample_cbd).
+void keygen_lwe_kswitch(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, const int8_t *z, u64 n, int base_bits, u64 *out) {
+    const size_t N = c.N;
+    const u64 q = c.primes[0];
+    const Mod m = make_mod(q);
+    std::vector<u64> s(sk, sk + N);
+    ntt_inverse(s.data(), c.tables[0]);
+    for (size_t i = 0; i < N; i++)
+        if (s[i] > 1 && s[i] != q - 1) throw Error(ST_LOGIC_ERROR, "the secret key is not ternary");
+    for (u64 k = 0; k < n; k++)
+        if (z[k] < -1 || z[k] > 1) throw Error(ST_INVALID_ARGUMENT, "the LWE secret takes 1 to 65536 digits over {-1, 0, 1}");
+    const u64 bits = 64 - (u64)__builtin_clzll(q), w = (u64)base_bits, l = (bits + w - 1) / w;
+    Rng rng(seed_lo, seed_hi, (u64)10 << 32);
+    for (size_t i = 0; i < N; i++) {
+        const u64 u = i ? negmod(s[N - i], q) : s[0];
+        for (u64 j = 0; j < l; j++) {
+            u64 *row = out + (i * l + j) * (n + 1);
+            u64 dot = 0;
+            for (u64 k = 0; k < n; k++) {
+                const u64 a = row[k] = rng.uniform_below(q);
+                if (z[k] > 0) dot = addmod(dot, a, q);
+                else if (z[k] < 0) dot = submod(dot, a, q);
+            }
+            const u64 word = rng.next64();
+            const int noise = __builtin_popcountll(word & 0x1FFFFF) - __builtin_popcountll((word >> 21) & 0x1FFFFF);
+            const u64 e = noise < 0 ? q - (u64)(-noise) : (u64)noise;
+            const u64 g = (u64)(((u128)1 << (w * j)) % q); // w j < bit_length(q_0)
+            row[n] = submod(addmod(mulmod(u, g, m), e, q), dot, q);
+        }
+    }
+}
 void relin_source(const Context &c, const u64 *sk, u64 *out) { // s^2 (keygenerator.cpp:228-262)
     for (int l = 0; l < c.K; l++) {
         const Mod m = make_mod(c.primes[l]);

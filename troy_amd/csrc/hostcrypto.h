@@ -25,6 +25,9 @@ void keygen_kswitch(const Context &c, Rng &rng, const u64 *sk, const u64 *new_ke
 // RGSW ciphertext of the plaintext m ([K][N], NTT form at the key level): out [2][K-1][2][K][N], half 0 = keygen_kswitch of m from
 // the stream (seed_lo, seed_hi, 5 << 32), half 1 = keygen_kswitch of m (.) sk from (seed_lo + 1, seed_hi, 5 << 32)
 void keygen_rgsw(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, const u64 *m, u64 *out);
+// the LWE switching key of DESIGN.md section 4.23: out [N][l][n + 1] words modulo q_0, l = ceil(bit_length(q_0) / base_bits); sk: [K][N] NTT form (its first
+// limb is read; refused unless ternary); z: the target secret over {-1, 0, 1}.  One stream (seed_lo, seed_hi, 10 << 32)
+void keygen_lwe_kswitch(const Context &c, u64 seed_lo, u64 seed_hi, const u64 *sk, const int8_t *z, u64 n, int base_bits, u64 *out);
 void relin_source(const Context &c, const u64 *sk, u64 *out);
 void galois_source(const Context &c, const u64 *sk, uint32_t elt, u64 *out);
 void encrypt(const Context &c, Rng &rng, const u64 *pk, const u64 *plain, size_t n_coeffs, int limbs, u64 *ct);

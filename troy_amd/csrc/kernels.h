@@ -269,6 +269,14 @@ struct BlindRotArgs { const u64 *acc; u64 acc_stride; const u64 *lwe; u64 lwe_st
 void launch_blind_rotate_pre(const BlindRotArgs &a, int terms, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
 // one-limb LWE samples c1 [samples][N], c0 [samples] modulo the first prime of `map` -> out [samples][N + 1] = round(2N x / q_0) mod 2N, beta last
 void launch_lwe_mod_switch(const u64 *c1, const u64 *c0, u64 *out, const PrimeDesc *primes, const LimbMap &map, int logn, u64 samples, hipStream_t s);
+// LWE key switching to dimension n: one-limb samples c1 [samples][N], c0 [samples] modulo the first prime of `map`; key
+// [N][digits][n1] residues, n1 = n + 1; part [splits][samples][n1] scratch.  The mac kernel writes the partial residues of `splits` runs of part_coeffs
+// coefficients (splits * part_coeffs >= N), col_blocks = ceil(n1 / LWE_KS_THREADS) blocks of columns by splits by tiles of lwe_ks_tile(samples) samples,
+// folded into the grid's x; the finish kernel writes out[r][k] = sum of the parts + [k == n] c0_r, switched to 2N where to_2n != 0, rows out_stride apart.
+static const u32 LWE_KS_THREADS = 64;
+struct LweKsArgs { const u64 *c1, *key; u64 *part; u64 samples, n1, col_blocks, splits, part_coeffs, digits; u32 base_bits; int logn; };
+u32 lwe_ks_tile(u64 samples); // samples per thread: 1, 2, 4 or 8
+void launch_lwe_ks(const LweKsArgs &a, const u64 *c0, u64 *out, u64 out_stride, int to_2n, const PrimeDesc *primes, const LimbMap &map, hipStream_t s);
 void launch_ks_moddown(int kind, const u64 *acc, u64 *ct, u64 ct_bstride, const KsArgs &a, hipStream_t s);
 void launch_ks_bgv_share(const u64 *acc, u64 *share /* [2 batch][N][2] */, const KsArgs &a, hipStream_t s);
 void launch_ks_ckks_corr(const u64 *last, u64 *corr, const KsArgs &a, hipStream_t s);

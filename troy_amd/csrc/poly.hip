@@ -781,6 +781,137 @@ void launch_lwe_mod_switch(const u64 *c1, const u64 *c0, u64 *out, const PrimeDe
     launch_check("lwe_mod_switch_kernel");
 }
 
+// ---------------------------------------------------------------- LWE key switching to a smaller dimension
+// A matrix product: the unsigned base-2^w digits of the samples' words, [R][N l] values below 2^16, times the key [N l][n + 1] of residues modulo q_0,
+// summed lazily.  A thread owns ONE column k and RT samples: lanes run along k, so a wave reads a key row as whole lines, and every key word serves RT
+// multiply-adds from a register.  c1[r][i] is the same for every lane of a wave -- its address depends on the block and the loop counter alone -- so it
+// is a scalar load, reduced modulo q_0 and cut into its l digits with scalar shifts.  A product is 16 x 64 bits: two 32 x 32 multiply-adds, the key
+// word's halves apart, into two 64-bit sums.  A term is below 2^48, so 2^16 terms fit a sum: the sums are folded into the 128-bit total every
+// LWE_KS_FOLD coefficients (64 l <= 3904 terms).  The total stays below N l 2^16 q_0 < 2^99 and is reduced ONCE.
+// The rows of a part run as one stream, LWE_KS_ROWS at a time: the key words of the NEXT run are loaded before the current run is multiplied, so a wave
+// keeps 2 LWE_KS_ROWS loads in flight (at small batches the grid is a wave per SIMD or less and nothing else hides the latency).  A run past the end of the
+// part repeats its last row, which is in bounds, and multiplies nothing.  Part sp of S covers the coefficients [sp cp, (sp + 1) cp) and writes its
+// canonical residue to part[sp][r][k].  No LDS, no atomics, no scratch.
+static const u32 LWE_KS_FOLD = 64;
+// tot += lo + 2^32 hi
+__device__ __forceinline__ void lwe_ks_fold(U128 &tot, u64 lo, u64 hi) {
+    const u64 add = hi << 32;
+    u64 s = tot.lo + lo;
+    u64 carry = s < lo;
+    s += add;
+    carry += s < add;
+    tot.lo = s;
+    tot.hi += (hi >> 32) + carry;
+}
+static const int LWE_KS_ROWS = 8;
+template <int RT> __global__ __launch_bounds__(LWE_KS_THREADS) void lwe_ks_mac_kernel(LweKsArgs a, const PrimeDesc *primes, LimbMap map) {
+    constexpr int U = LWE_KS_ROWS;
+    const u64 blk = blockIdx.x, cb = blk % a.col_blocks, rest = blk / a.col_blocks, sp = rest % a.splits, tile = rest / a.splits;
+    const u64 k = cb * LWE_KS_THREADS + threadIdx.x;
+    if (k >= a.n1) return;
+    const Mod m = mod_of(primes[map.id[0]]);
+    const u64 N = u64(1) << a.logn, l = a.digits, i0 = sp * a.part_coeffs, i1 = i0 + a.part_coeffs < N ? i0 + a.part_coeffs : N;
+    if (i0 >= i1) return; // splits * part_coeffs >= N: the launcher gives every part a coefficient
+    const u32 w = a.base_bits, mask = (u32(1) << w) - 1;
+    const u64 *rows[RT];
+#pragma unroll
+    for (int t = 0; t < RT; t++) {
+        const u64 r = tile * RT + t;
+        rows[t] = a.c1 + ((r < a.samples ? r : a.samples - 1) << a.logn); // a ragged tile repeats the last sample and does not store it
+    }
+    U128 tot[RT];
+    u64 lo[RT], hi[RT], x[RT];
+#pragma unroll
+    for (int t = 0; t < RT; t++) {
+        tot[t] = U128{0, 0};
+        lo[t] = hi[t] = 0;
+        x[t] = barrett64(rows[t][i0], m); // wave-uniform
+    }
+    const u64 *kp = a.key + i0 * l * a.n1 + k;
+    const u64 r_end = (i1 - i0) * l; // the rows of this part
+    u64 i = i0, j = 0;
+    u32 since = 0;
+    u64 cur[U], nxt[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) cur[u] = kp[((u64)u < r_end ? (u64)u : r_end - 1) * a.n1];
+    for (u64 row = 0; row < r_end; row += U) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const u64 rr = row + U + u;
+            nxt[u] = kp[(rr < r_end ? rr : r_end - 1) * a.n1];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (row + u < r_end) { // wave-uniform
+                const u32 klo = (u32)cur[u], khi = (u32)(cur[u] >> 32);
+#pragma unroll
+                for (int t = 0; t < RT; t++) {
+                    const u32 d = (u32)x[t] & mask;
+                    x[t] >>= w;
+                    lo[t] += (u64)d * klo;
+                    hi[t] += (u64)d * khi;
+                }
+                if (++j == l) { // the next coefficient
+                    j = 0;
+                    i++;
+                    if (++since == LWE_KS_FOLD) {
+                        since = 0;
+#pragma unroll
+                        for (int t = 0; t < RT; t++) { lwe_ks_fold(tot[t], lo[t], hi[t]); lo[t] = hi[t] = 0; }
+                    }
+                    if (i < i1) {
+#pragma unroll
+                        for (int t = 0; t < RT; t++) x[t] = barrett64(rows[t][i], m);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) cur[u] = nxt[u];
+    }
+#pragma unroll
+    for (int t = 0; t < RT; t++) {
+        lwe_ks_fold(tot[t], lo[t], hi[t]);
+        const u64 r = tile * RT + t;
+        if (r < a.samples) a.part[(sp * a.samples + r) * a.n1 + k] = barrett128(tot[t].lo, tot[t].hi, m);
+    }
+}
+// out[r][k] = sum of the S partial residues + [k == n] c0_r modulo q_0, canonical; to_2n: floor((4N x + q_0) / (2 q_0)) mod 2N, the formula of
+// lwe_mod_switch_kernel.  One thread per word; the padding words of a row (out_stride > n + 1) are not touched.
+__global__ __launch_bounds__(EW_THREADS) void lwe_ks_finish_kernel(LweKsArgs a, const u64 *__restrict__ c0, u64 *__restrict__ out, u64 out_stride, int to_2n, const PrimeDesc *primes,
+                                                                  LimbMap map, u64 total) {
+    const u64 i = (u64)blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const u64 N = u64(1) << a.logn, r = i / a.n1, k = i - r * a.n1;
+    const Mod m = mod_of(primes[map.id[0]]);
+    u64 x = k + 1 == a.n1 ? barrett64(c0[r], m) : 0;
+    for (u64 sp = 0; sp < a.splits; sp++) x = addmod(x, a.part[sp * total + i], m.p);
+    if (to_2n) {
+        u64 lo = x * (4 * N), hi = mulhi64(x, 4 * N);
+        lo += m.p;
+        hi += lo < m.p;
+        x = (div128(lo, hi, m) >> 1) & (2 * N - 1);
+    }
+    out[r * out_stride + k] = x;
+}
+u32 lwe_ks_tile(u64 samples) { return samples >= 64 ? 8 : samples >= 4 ? 4 : samples >= 2 ? 2 : 1; }
+void launch_lwe_ks(const LweKsArgs &a, const u64 *c0, u64 *out, u64 out_stride, int to_2n, const PrimeDesc *primes, const LimbMap &map, hipStream_t s) {
+    if (!a.samples) return;
+    const u64 N = u64(1) << a.logn, rt = lwe_ks_tile(a.samples), tiles = (a.samples + rt - 1) / rt, blocks = a.col_blocks * a.splits * tiles;
+    if (!a.c1 || !a.key || !a.part || !c0 || !out || !a.n1 || out_stride < a.n1 || a.col_blocks != (a.n1 + LWE_KS_THREADS - 1) / LWE_KS_THREADS || !a.splits ||
+        a.splits * a.part_coeffs < N || !a.digits || a.base_bits < 1 || a.base_bits > 16 || a.digits * a.base_bits > 79 || blocks >> 31)
+        throw Error(ST_LOGIC_ERROR, "lwe_ks: operands");
+    const dim3 grid((unsigned)blocks);
+    if (rt == 8) TROY_LAUNCH(HIP_KERNEL_NAME(lwe_ks_mac_kernel<8>), grid, dim3(LWE_KS_THREADS), 0, s, a, primes, map);
+    else if (rt == 4) TROY_LAUNCH(HIP_KERNEL_NAME(lwe_ks_mac_kernel<4>), grid, dim3(LWE_KS_THREADS), 0, s, a, primes, map);
+    else if (rt == 2) TROY_LAUNCH(HIP_KERNEL_NAME(lwe_ks_mac_kernel<2>), grid, dim3(LWE_KS_THREADS), 0, s, a, primes, map);
+    else TROY_LAUNCH(HIP_KERNEL_NAME(lwe_ks_mac_kernel<1>), grid, dim3(LWE_KS_THREADS), 0, s, a, primes, map);
+    launch_check("lwe_ks_mac_kernel");
+    const u64 total = a.samples * a.n1;
+    TROY_LAUNCH(lwe_ks_finish_kernel, flat_grid(total, "lwe_ks_finish_kernel"), dim3(EW_THREADS), 0, s, a, c0, out, out_stride, to_2n, primes, map, total);
+    launch_check("lwe_ks_finish_kernel");
+}
+
 // ---------------------------------------------------------------- mod-switch / rescale (a-4 / A.10)
 // kind 0: BFV divideAndRoundqLastInplace (rns.cpp:805-830); kind 2: BGV modTAndDivideqLastInplace (rns.cpp:1097-1140).
 // in [polys][limbs][N] -> out [polys][limbs-1][N]

@@ -58,9 +58,9 @@ inline const char *probe_env(const char *name) {
 // Path counters (troyhip_stat, include/troyhip.h): which kernel class a launcher chose.  The parity tests read them so that a test of
 // the FP64 instances cannot pass on the integer kernels (or the other way round) without saying so.
 namespace stats {
-enum { KS_FP_LAUNCHES, KS_INT_LAUNCHES, NTT1_FP_LAUNCHES, NTT1_INT_LAUNCHES, NTT2_FP_LAUNCHES, NTT2_INT_LAUNCHES, BEHZ_FP_LAUNCHES, BEHZ_MFMA_LAUNCHES, BEHZ_VALU_LAUNCHES, NTT2_WIDE_LAUNCHES, ENC_TAIL_ITEMS, NTT1_XCD_LAUNCHES, KS_INT_GROUPS_PER_WG, HOIST_SLABS, HOIST_LT_SLABS, BSGS_SLABS, MULSUM_CHUNKS, POLY_PRODUCTS, POLY_RELINS, POLY_SCALAR_SUMS, LWE_PACK_KEY_SWITCHES, LWE_PACK_CHUNKS, GROUPED_KS_SLABS, GROUPED_HOIST_SLABS, GROUPED_HOIST_LT_SLABS, GROUPED_BSGS_SLABS, EXPAND_KEY_SWITCHES, EXPAND_CHUNKS, EXTPROD_SLABS, EXTPROD_CHUNKS, PLAINMAT_LAUNCHES, PLAINMAT_WORKGROUPS, BLINDROT_SLABS, BLINDROT_STEPS, COUNT };
+enum { KS_FP_LAUNCHES, KS_INT_LAUNCHES, NTT1_FP_LAUNCHES, NTT1_INT_LAUNCHES, NTT2_FP_LAUNCHES, NTT2_INT_LAUNCHES, BEHZ_FP_LAUNCHES, BEHZ_MFMA_LAUNCHES, BEHZ_VALU_LAUNCHES, NTT2_WIDE_LAUNCHES, ENC_TAIL_ITEMS, NTT1_XCD_LAUNCHES, KS_INT_GROUPS_PER_WG, HOIST_SLABS, HOIST_LT_SLABS, BSGS_SLABS, MULSUM_CHUNKS, POLY_PRODUCTS, POLY_RELINS, POLY_SCALAR_SUMS, LWE_PACK_KEY_SWITCHES, LWE_PACK_CHUNKS, GROUPED_KS_SLABS, GROUPED_HOIST_SLABS, GROUPED_HOIST_LT_SLABS, GROUPED_BSGS_SLABS, EXPAND_KEY_SWITCHES, EXPAND_CHUNKS, EXTPROD_SLABS, EXTPROD_CHUNKS, PLAINMAT_LAUNCHES, PLAINMAT_WORKGROUPS, BLINDROT_SLABS, BLINDROT_STEPS, LWE_KS_SLABS, LWE_KS_SPLITS, COUNT };
 inline std::atomic<uint64_t> &counter(int i) { static std::atomic<uint64_t> c[COUNT]; return c[i]; } // host threads launch concurrently (one context per thread)
-inline const char *name(int i) { static const char *n[COUNT] = {"ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches", "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "enc_tail_items", "ntt1_xcd_launches", "ks_int_groups_per_wg", "hoist_slabs", "hoist_lt_slabs", "bsgs_slabs", "mulsum_chunks", "poly_products", "poly_relins", "poly_scalar_sums", "lwe_pack_key_switches", "lwe_pack_chunks", "grouped_ks_slabs", "grouped_hoist_slabs", "grouped_hoist_lt_slabs", "grouped_bsgs_slabs", "expand_key_switches", "expand_chunks", "extprod_slabs", "extprod_chunks", "plainmat_launches", "plainmat_workgroups", "blindrot_slabs", "blindrot_steps"}; return n[i]; }
+inline const char *name(int i) { static const char *n[COUNT] = {"ks_fp_launches", "ks_int_launches", "ntt1_fp_launches", "ntt1_int_launches", "ntt2_fp_launches", "ntt2_int_launches", "behz_fp_launches", "behz_mfma_launches", "behz_valu_launches", "ntt2_wide_launches", "enc_tail_items", "ntt1_xcd_launches", "ks_int_groups_per_wg", "hoist_slabs", "hoist_lt_slabs", "bsgs_slabs", "mulsum_chunks", "poly_products", "poly_relins", "poly_scalar_sums", "lwe_pack_key_switches", "lwe_pack_chunks", "grouped_ks_slabs", "grouped_hoist_slabs", "grouped_hoist_lt_slabs", "grouped_bsgs_slabs", "expand_key_switches", "expand_chunks", "extprod_slabs", "extprod_chunks", "plainmat_launches", "plainmat_workgroups", "blindrot_slabs", "blindrot_steps", "lwe_ks_slabs", "lwe_ks_splits"}; return n[i]; }
 }
 
 typedef uint64_t u64;
