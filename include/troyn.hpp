@@ -2005,8 +2005,11 @@ public:
             scaled[i] = values[i] * scale;
             largest = std::max(largest, std::fabs(scaled[i]));
         }
-        // one more bit for the sign; nothing below 1.0 goes through log2 (ckks_cuda.cu:516-521)
-        const int bits = (int)std::ceil(std::log2(std::max(largest, 1.0))) + 1;
+        // one more bit for the sign; nothing below 1.0 counts (ckks_cuda.cu:516-521).  ceil(log2(.)) is taken exactly through frexp: std::log2 of
+        // 2^k (1 + 2^-52) rounds to k for k >= 4, and the reference's expression as written lets the first ulps above 2^k pass as 2^k
+        int exponent = 0;
+        const double fraction = std::frexp(std::max(largest, 1.0), &exponent);
+        const int bits = (fraction == 0.5 ? exponent - 1 : exponent) + 1;
         if (bits >= level->totalCoeffModulusBitCount()) throw std::invalid_argument("encoded values are too large");
         std::vector<uint64_t> rns(limbs * n);
         for (size_t i = 0; i < n; i++) {

@@ -109,6 +109,27 @@ static void run_ckks(size_t n, size_t B) {
         threw = std::string(e.what()) == "encoded values are too large (item 1)";
     }
     EXPECT(threw, "too large: item named");
+    // the refusal boundary, header and host form alike: 2^(total bits - 2) is taken, the next double is not (the bit count is exact, where std::log2
+    // rounds that double's logarithm down).  A constant in every slot is the constant polynomial, so the two plaintexts are the same words.
+    const int tb = context.firstContextData()->totalCoeffModulusBitCount(), first = (int)context.firstContextData()->parms().coeffModulus().size();
+    const double edge = std::ldexp(1.0, tb - 2);
+    bool boundary = true;
+    for (double v : {edge, -edge, std::nextafter(edge, INFINITY), -std::nextafter(edge, INFINITY)}) {
+        const bool refuse = std::fabs(v) > edge;
+        Plaintext p;
+        bool header_threw = false;
+        try {
+            enc.encode(v, 1.0, p);
+        } catch (const std::invalid_argument &e) {
+            header_threw = std::string(e.what()) == "encoded values are too large";
+        }
+        vector<double> flat(2 * slots, 0.0);
+        for (size_t i = 0; i < slots; i++) flat[2 * i] = v;
+        vector<uint64_t> host((size_t)first * n);
+        const int rc = troyhip_host_ckks_encode(context.handle(), flat.data(), slots, first, 1.0, host.data());
+        boundary = boundary && header_threw == refuse && (rc != 0) == refuse && (refuse || std::memcmp(host.data(), p.data(), host.size() * 8) == 0);
+    }
+    EXPECT(boundary, "refusal boundary 2^(total bits - 2): header == host form");
 }
 
 static void run_batch(SchemeType scheme, size_t n, size_t B, const char *name) {

@@ -127,9 +127,11 @@ def ckks_values(rng, batch, count, magnitude=8.0, complex_=True):
     return V
 
 
-def check_ckks(ctx, batch, count, limbs, scale, rng, complex_=True, pad=0, items=None, magnitude=8.0):
-    """device encode == host encode per item (or both refuse with the same message), device decode == host decode; returns the device plaintexts"""
-    V = ckks_values(rng, batch, count, magnitude, complex_)
+def check_ckks(ctx, batch, count, limbs, scale, rng, complex_=True, pad=0, items=None, magnitude=8.0, V=None):
+    """device encode == host encode per item (or both refuse with the same message), device decode == host decode; returns the device plaintexts.
+    V [batch][count][2]: the values to use instead of random ones"""
+    if V is None:
+        V = ckks_values(rng, batch, count, magnitude, complex_)
     rc, enc = ckks_device_encode(ctx, V, limbs, scale, pad)
     hosts = [ckks_host_encode(ctx, V[b], limbs, scale) for b in range(batch)]
     bad = [b for b in range(batch) if hosts[b][0] != capi.OK]

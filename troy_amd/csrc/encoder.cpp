@@ -128,8 +128,8 @@ void DeviceEncoder::ckks_encode(const double *values, u64 count, u64 vstride, in
     a.partial = c.arena.take(batch * a.nparts);
     a.maxbits = c.arena.take(batch);
     launch_ckks_encode(a, s);
-    // the one synchronisation of the call: "encoded values are too large" is the header's test on the host (host std::log2; the device's is not
-    // correctly rounded next to powers of two), and a refused batch launches no transform
+    // the one synchronisation of the call: "encoded values are too large" is the header's test, applied on the host to the B maxima (the bit count
+    // comes off the exponent field: encoder_math.h), and a refused batch launches no transform
     std::vector<u64> maxbits(batch);
     HIP_CHECK(hipMemcpyAsync(maxbits.data(), a.maxbits, batch * sizeof(u64), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));

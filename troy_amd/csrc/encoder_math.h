@@ -33,6 +33,15 @@ TROY_HD double bits_dbl(u64 x) { double r; __builtin_memcpy(&r, &x, 8); return r
 // |value * scale| as a bit pattern: for non-negative doubles the pattern order is the numeric order, and every infinity or NaN lies above
 // every finite value, so an integer max over the patterns is an order-free max |.| that also flags non-finite input
 constexpr u64 NONFINITE_BITS = 0x7ff0000000000000ull;
+// ceil(log2(max(x, 1))) + 1 for the finite x >= 0 with the bit pattern `bits`: the bit count of encodePolynomial's "too large" test, one more bit
+// for the sign.  Read off the exponent field, not taken with std::log2: the double logarithm of 2^k (1 + 2^-52) rounds to k for every k >= 4, so the
+// header's expression as written let the values of the first ulps above 2^k pass as if they were 2^k
+TROY_HD int ckks_value_bit_count(u64 bits) {
+    constexpr u64 ONE_BITS = 0x3ff0000000000000ull;
+    if (bits <= ONE_BITS) return 1;
+    const int E = (int)(bits >> 52) - 1023;
+    return E + ((bits & ((u64(1) << 52) - 1)) ? 1 : 0) + 1;
+}
 
 // one coefficient of encode: (re / n) * scale, rounded half away from zero (std::round); inv_n = 1 / n is a power of two, so the product equals
 // the quotient bit for bit and no division runs on the device

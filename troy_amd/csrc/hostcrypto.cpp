@@ -661,9 +661,8 @@ void ckks_check_decode(const Context &c, int limbs, double scale) {
 }
 const char *ckks_value_error(u64 largest_bits, int total_bits) {
     if (largest_bits >= NONFINITE_BITS) return "encoded values are not finite";
-    // one more bit for the sign; nothing below 1.0 goes through log2 (the header's test, host std::log2)
-    const int bits = (int)std::ceil(std::log2(std::max(bits_dbl(largest_bits), 1.0))) + 1;
-    return bits >= total_bits ? "encoded values are too large" : nullptr;
+    // one more bit for the sign; nothing below 1.0 counts (the header's test, with the logarithm taken exactly)
+    return ckks_value_bit_count(largest_bits) >= total_bits ? "encoded values are too large" : nullptr;
 }
 
 void ckks_encode(const Context &c, const double *values, size_t count, int limbs, double scale, u64 *plain) {
